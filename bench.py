@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- patches/sec of OmniTokenizer encode+decode on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
   (N > 1: launched by torch.distributed.run, one rank per GPU, RCCL)
 
 A step = one pass of the hot path over one batch already resident in HBM:
@@ -43,6 +43,27 @@ GEMM_MODES = {0: ("fp32-input MFMA", 1, PEAK_F32_TFLOPS),
               2: ("fp32 operands as 2 fp16 planes, 3 fp16-MFMA products", 3, PEAK_F16_TFLOPS)}
 
 
+# --dump-outputs: at most 2^22 pixel values (16 MB of float32) are written; ids stay far below that at every workload here
+DUMP_MAX_ELEMS = 1 << 22
+DUMP_SAMPLE_SEED = 20240611
+
+
+def dump_outputs(path, prefix, ids, rec):
+    """The last timed step's outputs as .npy files: ids as float64 (exact), pixels as float32, whole or as a fixed sample
+    (indices drawn by a seeded generator from the tensor's size alone, so equal arguments sample equal positions)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, prefix + "ids.npy"), ids.detach().cpu().numpy().astype(np.float64))
+    n = rec.numel()
+    if n <= DUMP_MAX_ELEMS:
+        np.save(os.path.join(path, prefix + "pixels.npy"), rec.detach().float().cpu().numpy())
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, DUMP_MAX_ELEMS, replace=False))
+        flat = rec.detach().reshape(-1)
+        sample = flat[torch.from_numpy(idx).to(flat.device)].float().cpu().numpy()
+        np.save(os.path.join(path, prefix + "pixels_sample.npy"), sample)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -66,7 +87,14 @@ def main():
                     help="N > 1: issue the id all-gather from C++ (ncclAllGather through libomnitok.so, include/omnitok_comm.h) "
                          "instead of torch.distributed; without the flag the native path is still probed after the timed region")
     ap.add_argument("--no-also", action="store_true", help="skip the C2 / C5 / strict-fp32 / heavy-parity extras of the default C3 line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32 / float64): "
+                         "ids.npy (encode's ids, exact in float64) and pixels.npy (decode's output), or, when the pixels exceed "
+                         f"{DUMP_MAX_ELEMS} elements, pixels_sample.npy (a fixed seeded sample of them, flat, in index order); "
+                         "N > 1: one rankR_ prefix per rank")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     from omnitokenizer_amd import launch
 
@@ -123,6 +151,8 @@ def run(a):
                                      lambda i: model.decode(i, is_image), x, a.steps, a.warmup,
                                      native_gather=a.native_gather)
     dt, ids = res.seconds, res.ids_local
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, f"rank{rank}_" if world > 1 else "", ids, res.rec_local)
     # N > 1: the C++ ncclAllGather path (omnitok_comm.h) checked against the gathered ids of the timed region and timed,
     # outside the timed region and never fatal -- so that the first multi-GPU run exercises it whichever path was timed
     native_probe = launch.probe_native_gather(info, ids, res) if world > 1 else None

@@ -8,7 +8,7 @@ lines it follows.  Only tests/ and benchmarks' cpu_baseline legs may import this
 
 Pinning: tests/golden/gpt_*.npz hold logits / greedy samples of the reference's own GPT class
 (imported unmodified by tests/golden/make_golden.py) on seeded weights; tests/test_oracle_gpt.py
-checks this file against them and, when /root/reference is present, against the live class.
+checks this file against them (and against refcheck_gpt.npz, the same class's logits and filter).
 """
 from __future__ import annotations
 

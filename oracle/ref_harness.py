@@ -4,7 +4,7 @@ vectors can be generated in the build container.
 
 /root/reference does not exist on the GPU box: nothing in `-m gpu` tests, smoke() or
 bench.py imports this module.  It is used by tests/golden/make_golden.py (fixture
-generation) and by CPU tests that are skipped when the reference is absent.
+generation); the CPU tests read the fixtures it wrote and never import the reference.
 
 Only packages that carry no arithmetic on the encode/decode path are stubbed:
 pytorch_lightning (LightningModule -> nn.Module), timm (trunc_normal_ -> torch's own),

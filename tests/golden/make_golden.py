@@ -17,6 +17,7 @@ posterior sample z = encode(x) and recon = decode(z) in the layout the reference
 
     python tests/golden/make_golden.py            # everything
     python tests/golden/make_golden.py vae        # only the vae_* fixtures
+    python tests/golden/make_golden.py refcheck   # only the refcheck_* fixtures
 """
 import os
 import sys
@@ -551,6 +552,72 @@ def make_usage_state_golden(name="usage_state_s2_sdpa_r64"):
     print(f"{name}: usage sums {[float(u.sum()) for u in usage]}, nonzero {[int((u > 0).sum()) for u in usage]}")
 
 
+# The reference next to the oracle on the CPU suite's own small cases (tests/test_oracle_vs_reference.py,
+# tests/test_oracle_gpt.py::test_gpt_oracle_matches_live_reference): the reference's path keys with their shapes / dtypes,
+# its ids and pixels, its codebook argmin on random unit latents, its GPT logits and top-k / top-p filter.
+REFCHECK_CASES = [("refcheck_s2_sdpa_r64", 2, "sdpa"), ("refcheck_s1_legacy_r64", 1, "legacy")]
+REFCHECK_OFF_PATH = ("image_discriminator", "video_discriminator", "perceptual_model")
+
+
+def make_refcheck_golden():
+    import argparse
+    import importlib
+    import zlib
+    from oracle import gpt_oracle as go
+    rh.install_stubs()
+    for name, stage, mode in REFCHECK_CASES:
+        args = make_args(stage, resolution=64)
+        cfg = OmniTokConfig.from_args(args, attention_mode=mode)
+        sd = synth.synth_state_dict(cfg, seed=3)
+        model = rh.build_reference_model(args)
+        path = {k: v for k, v in model.state_dict().items() if not k.startswith(REFCHECK_OFF_PATH)}
+        assert not model.load_state_dict(sd, strict=False).unexpected_keys
+        x = synth.synth_video(1, 9, 64, seed=5)
+        with torch.no_grad(), rh.attention_mode(mode):
+            ids = model.encode(x, False)
+            rec = model.decode(ids, False)
+        np.savez_compressed(os.path.join(OUT, name + ".npz"), stage=stage, mode=mode, weight_seed=3, x_seed=5,
+                            state_crc=np.uint32(synth.state_checksum(sd)),
+                            x_crc=np.uint32(zlib.crc32(x.contiguous().numpy().tobytes())),
+                            keys=np.array(list(path)), dtypes=np.array([str(v.dtype) for v in path.values()]),
+                            ndims=np.array([v.dim() for v in path.values()], np.int32),
+                            dims=np.array([d for v in path.values() for d in v.shape], np.int64),
+                            ids=ids.numpy().astype(np.int16), recon=rec.numpy())
+        print(f"{name}: {len(path)} path keys, ids {tuple(ids.shape)}, |recon| max {rec.abs().max().item():.3f}")
+
+    from OmniTokenizer.modules.codebook import Codebook
+    rng = np.random.default_rng(11)
+    E = rng.standard_normal((8192, 8), dtype=np.float32)
+    z = rng.standard_normal((16384, 8), dtype=np.float32)
+    z /= np.linalg.norm(z, axis=1, keepdims=True)
+    cb = Codebook(8192, 8).eval()
+    cb._need_init = False
+    cb.embeddings.data.copy_(torch.from_numpy(E))
+    zt = torch.from_numpy(z).reshape(16, 1, 32, 32, 8).permute(0, 4, 1, 2, 3).contiguous()
+    with torch.no_grad():
+        ids = cb(zt)["encodings"].reshape(-1).numpy()
+    np.savez_compressed(os.path.join(OUT, "refcheck_codebook_8192.npz"), z=z, codebook=E, ids=ids.astype(np.int16))
+    print(f"refcheck_codebook_8192: {len(np.unique(ids))} distinct ids")
+
+    gpt = importlib.import_module("OmniTokenizer.modules.gpt")
+    V, BS, L, H, C = 200, 32, 2, 4, 256
+    sd = go.synth_gpt_state(V, BS, L, H, C, seed=9)
+    m = gpt.GPT(argparse.Namespace(), V, BS, n_layer=L, n_head=H, n_embd=C).eval()
+    m.load_state_dict(sd, strict=False)
+    idx = torch.randint(0, V, (3, 12), generator=torch.Generator().manual_seed(1))
+    lg = torch.randn(3, V, generator=torch.Generator().manual_seed(2))
+    with torch.no_grad():
+        logits, _ = m(idx)
+        filtered = gpt.top_k_top_p_filtering(lg.clone(), 20, 0.8)
+    crc = 0
+    for k in sd:
+        crc = zlib.crc32(sd[k].numpy().tobytes(), crc)
+    np.savez_compressed(os.path.join(OUT, "refcheck_gpt.npz"), vocab=V, block_size=BS, n_layer=L, n_head=H, n_embd=C,
+                        weight_seed=9, state_crc=np.uint32(crc), idx=idx.numpy(), logits=logits.numpy(),
+                        filter_in=lg.numpy(), filter_top_k=20, filter_top_p=0.8, filtered=filtered.numpy())
+    print(f"refcheck_gpt: logits {tuple(logits.shape)}, {int(torch.isfinite(filtered).sum())} logits survive the filter")
+
+
 if __name__ == "__main__":
     assert rh.reference_available(), "run in the build container (needs /root/reference)"
     only = sys.argv[1] if len(sys.argv) > 1 else None
@@ -589,3 +656,5 @@ if __name__ == "__main__":
             run_case(*c, profile="heavy")
     if only in (None, "heavy", "heavy_b8"):
         run_heavy_batch_case()
+    if only in (None, "refcheck"):
+        make_refcheck_golden()

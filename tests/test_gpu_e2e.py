@@ -633,7 +633,7 @@ def test_oracle_parity_other_shapes(models):
 def test_other_architectures_vs_oracle(overrides, mode):
     """Hyper-parameters no released checkpoint uses (width, heads, depth, ff_mult, block strings,
     non-causal temporal attention / PEG, no l2 normalisation before the quantiser), straight against
-    the CPU oracle -- which tests/test_oracle_vs_reference.py pins to the live reference."""
+    the CPU oracle -- which tests/test_oracle_vs_reference.py pins to the reference's stored outputs."""
     from omnitokenizer_amd import OmniTokenizer_VQGAN, make_args, synth
     from omnitokenizer_amd.config import OmniTokConfig
     args = make_args(2, resolution=64, **overrides)

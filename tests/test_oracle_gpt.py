@@ -1,5 +1,5 @@
 """CPU: pins the LM oracle (oracle/gpt_oracle.py) against the committed outputs of the reference's
-own GPT class (tests/golden/gpt_*.npz) and, in the build container, against the live class."""
+own GPT class (tests/golden/gpt_*.npz, refcheck_gpt.npz)."""
 import os
 import zlib
 
@@ -8,7 +8,6 @@ import pytest
 import torch
 
 from oracle import gpt_oracle as go
-from oracle import ref_harness as rh
 from tests.helpers import GOLDEN
 
 GPT_CASES = ["gpt_hd64", "gpt_hd96", "gpt_hd128"]
@@ -66,22 +65,21 @@ def test_gpt_oracle_optional_inputs_match_reference_golden():
         assert np.array_equal(greedy.numpy(), g["greedy"])
 
 
-@pytest.mark.skipif(not rh.reference_available(), reason="needs /root/reference (build container only)")
 def test_gpt_oracle_matches_live_reference():
-    import argparse
-    import importlib
-    rh.install_stubs()
-    gpt = importlib.import_module("OmniTokenizer.modules.gpt")
-    V, BS, L, H, C = 200, 32, 2, 4, 256
-    sd = go.synth_gpt_state(V, BS, L, H, C, seed=9)
-    m = gpt.GPT(argparse.Namespace(), V, BS, n_layer=L, n_head=H, n_embd=C).eval()
-    m.load_state_dict(sd, strict=False)
-    idx = torch.randint(0, V, (3, 12), generator=torch.Generator().manual_seed(1))
+    """logits and the top-k / top-p filter of the reference's GPT module on the case stored in refcheck_gpt.npz"""
+    g = np.load(os.path.join(GOLDEN, "refcheck_gpt.npz"))
+    V, BS, L, H, C = (int(g[k]) for k in ("vocab", "block_size", "n_layer", "n_head", "n_embd"))
+    sd = go.synth_gpt_state(V, BS, L, H, C, seed=int(g["weight_seed"]))
+    crc = 0
+    for k in sd:
+        crc = zlib.crc32(sd[k].numpy().tobytes(), crc)
+    assert crc == int(g["state_crc"]), "synthetic GPT weights drifted from the golden fixture"
+    idx = torch.from_numpy(g["idx"])
     with torch.no_grad():
-        ref, _ = m(idx)
-        assert (go.forward(sd, idx, H) - ref).abs().max().item() < 2e-5
-        lg = torch.randn(3, V, generator=torch.Generator().manual_seed(2))
-        assert torch.equal(go.top_k_top_p_filtering(lg, 20, 0.8), gpt.top_k_top_p_filtering(lg.clone(), 20, 0.8))
+        assert (go.forward(sd, idx, H) - torch.from_numpy(g["logits"])).abs().max().item() < 2e-5
+        lg = torch.from_numpy(g["filter_in"])
+        assert torch.equal(go.top_k_top_p_filtering(lg, int(g["filter_top_k"]), float(g["filter_top_p"])),
+                           torch.from_numpy(g["filtered"]))
 
 
 def test_product_gpt_state_dict_and_cpu_refusal():
