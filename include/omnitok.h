@@ -657,6 +657,51 @@ int omnitok_engine_set_option(omnitok_engine *e, const char *name, int value);
 int omnitok_engine_set_timing(omnitok_engine *e, int enabled);
 int omnitok_engine_timing_report(omnitok_engine *e, char *buf, int buflen);
 
+/* ---- frames in, frames out (csrc/frames.hip) -------------------------------------------------------------------------
+ * uint8 video frames <-> the fp32 pixels omnitok_encode reads / omnitok_decode writes, with the arithmetic of the
+ * reference's loaders and eval scripts (INTEGRATION.md "frames in, frames out").
+ *
+ * One clip of a (possibly ragged) batch: uint8 frames with the 3 channels interleaved (pixel stride 3 bytes, channel
+ * stride 1), frame and row strides in bytes (any views of a THWC array: frame / row slices, crops).  Output frame t reads
+ * source frame frame_start + t * frame_step.  Mode NONE: the output window starts at (crop_top, crop_left) of the source.
+ * Mode BILINEAR: the frame is resized to resize_h x resize_w and the output window starts at (crop_top, crop_left) of the
+ * RESIZED frame; the caller computes the reference's sizes (data.py:320-331): short side R, long side
+ * ceil(long * (R / short)) in double precision, crop ((w - R) // 2, (h - R) // 2). */
+typedef struct omnitok_frames_desc {
+    const uint8_t *frames;   /* device pointer: byte (frame 0, row 0, column 0, channel 0) */
+    int64_t frame_stride;    /* bytes between frames */
+    int64_t row_stride;      /* bytes between rows (>= 3 * W) */
+    int F, H, W;             /* native clip size */
+    int frame_start, frame_step;
+    int crop_top, crop_left;
+    int resize_h, resize_w;  /* mode BILINEAR only */
+} omnitok_frames_desc;
+
+enum { OMNITOK_FRAMES_NONE = 0, OMNITOK_FRAMES_BILINEAR = 1 };
+/* flags of omnitok_frames_to_pixels (mode NONE only): VideoNorm's rule (video_utils.py:55-57) -- a clip none of whose
+ * cropped bytes exceeds 1 is NOT divided by 255 (pixels = u - 0.5); needs `work` */
+enum { OMNITOK_FRAMES_VIDEONORM = 1 };
+enum { OMNITOK_LAYOUT_THWC = 0, OMNITOK_LAYOUT_CTHW = 1 };
+
+/* desc[B] (HOST array, validated on the host before any launch; at most 32 clips go into one launch's kernel arguments,
+ * no copy, no synchronisation) -> pixels_out[B, 3, F_out, R_h, R_w] fp32 in [-0.5, 0.5].
+ *   NONE:     float(u) / 255 (a table of float(i) / 255.0f, the bits of torch's division) - 0.5: bit-identical to
+ *             ToTensor + Normalize(0.5, 1.0) and to VideoNorm (with OMNITOK_FRAMES_VIDEONORM).
+ *   BILINEAR: F.interpolate(u / 255, (resize_h, resize_w), 'bilinear', align_corners=False) then the crop, then - 0.5
+ *             (data.py:305-350); the fp32 arithmetic is stated in csrc/frames.hip (within 1e-6 of torch's CPU kernels,
+ *             which themselves differ by thread count; identical to them where resize size == source size).
+ * work: device buffer of >= 4 * B bytes (OMNITOK_FRAMES_VIDEONORM only; may be NULL otherwise).
+ * OMNITOK_ERR_INVALID for null pointers, a frame range past F, a crop window outside the source (NONE) or the resized
+ * frame (BILINEAR), bad sizes, modes or flags. */
+int omnitok_frames_to_pixels(const omnitok_frames_desc *desc, int B, int F_out, int R_h, int R_w, int mode, int flags,
+                             void *work, float *pixels_out, omnitok_stream_t stream);
+
+/* pixels[B, C, F, H, W] fp32 -> out uint8, u = (uint8) trunc(min(max(x + 0.5f, 0), 1) * 255.0f) with every step rounded
+ * in fp32 (vqgan_eval.py:141-148, utils.py:225-229); non-finite x give 0.  layout OMNITOK_LAYOUT_THWC: out[B, F, H, W, C]
+ * (what save_video_grid / the I3D input take); OMNITOK_LAYOUT_CTHW: out[B, C, F, H, W].  C must be 3. */
+int omnitok_pixels_to_frames(const float *pixels, int B, int C, int F, int H, int W, int layout, uint8_t *out,
+                             omnitok_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -55,6 +55,13 @@ class OmnitokPlGemm(Structure):
     ]
 
 
+class OmnitokFramesDesc(Structure):
+    """omnitok_frames_desc (include/omnitok.h): one uint8 clip of omnitok_frames_to_pixels."""
+    _fields_ = [("frames", c_void_p), ("frame_stride", c_int64), ("row_stride", c_int64),
+                ("F", c_int), ("H", c_int), ("W", c_int), ("frame_start", c_int), ("frame_step", c_int),
+                ("crop_top", c_int), ("crop_left", c_int), ("resize_h", c_int), ("resize_w", c_int)]
+
+
 class OmnitokError(RuntimeError):
     pass
 
@@ -127,6 +134,8 @@ _PROTOS = {
     "omnitok_engine_set_timing": [P, c_int],
     "omnitok_engine_set_option": [P, c_char_p, c_int],
     "omnitok_engine_timing_report": [P, c_char_p, c_int],
+    "omnitok_frames_to_pixels": [POINTER(OmnitokFramesDesc), c_int, c_int, c_int, c_int, c_int, c_int, P, P, P],
+    "omnitok_pixels_to_frames": [P, c_int, c_int, c_int, c_int, c_int, c_int, P, P],
     # include/omnitok_lm.h
     "omnitok_lm_create": [POINTER(OmnitokLmConfig), POINTER(P)],
     "omnitok_lm_destroy": [P],

@@ -20,6 +20,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from . import frames as _frames  # registers omnitok::frames_to_pixels / omnitok::pixels_to_frames
 from ._lib import OmnitokConfig, check
 from .config import OmniTokConfig
 from .synth import path_state_spec, relative_position_index
@@ -563,6 +564,36 @@ class OmniTokenizer_VQGAN(nn.Module):
                 raise IndexError(lib.omnitok_last_error().decode())
             check(rc, "check_ids")
         return out[:, :, 0] if is_image else out
+
+    @torch.no_grad()
+    @_on_own_device
+    def encode_frames(self, frames, is_image, *, resize="none", norm=None, resolution=None, crop=None, frame_start=0,
+                      sequence_length=None, sample_every_n_frames=1, include_embeddings=False, **encode_kwargs):
+        """encode() of uint8 frames as the reference's loaders hand them over: frames [B,F,H,W,3] ([B,H,W,3] with
+        is_image) on this module's GPU, or a list of per-clip tensors of different native sizes.  The frames become
+        encode()'s fp32 pixels on the device (frames.frames_to_pixels: resize "none" = crop + VideoNorm / ToTensor,
+        "bilinear" = the reference's preprocess at `resolution`, default args.resolution), in a staging tensor of
+        PyTorch's allocator; the result is exactly what encode(pixels, is_image, include_embeddings, **encode_kwargs)
+        returns (ids, or the VAE latents on a use_vae model)."""
+        for c in ([frames] if isinstance(frames, torch.Tensor) else list(frames)):
+            if isinstance(c, torch.Tensor) and c.device != self.device:
+                raise RuntimeError(f"frames on {c.device}, model on {self.device}")
+        if resize == "bilinear" and resolution is None:
+            resolution = self.resolution
+        x = _frames.frames_to_pixels(frames, is_image, resize=resize, norm=norm, resolution=resolution, crop=crop,
+                                     frame_start=frame_start, sequence_length=sequence_length,
+                                     sample_every_n_frames=sample_every_n_frames)
+        return self.encode(x, is_image, include_embeddings=include_embeddings, **encode_kwargs)
+
+    @torch.no_grad()
+    @_on_own_device
+    def decode_frames(self, encodings, is_image, layout="thwc"):
+        """decode() to uint8 frames, (clamp(x + 0.5, 0, 1) * 255).byte() of the reconstruction (vqgan_eval.py:141-148):
+        [B,F,H,W,3] / [B,H,W,3] ("thwc", what save_video_grid and the I3D input take) or [B,3,F,H,W] / [B,3,H,W]
+        ("cthw").  encodings: what decode() takes (ids, or latents on a use_vae model)."""
+        if layout not in _frames.LAYOUTS:
+            raise ValueError(f"layout must be one of {sorted(_frames.LAYOUTS)}, got {layout!r}")
+        return _frames.pixels_to_frames(self.decode(encodings, is_image), layout)
 
     def _decode_native(self, ids):
         """omnitok::vqgan_decode on CUDA tensors: ids [B, T', h, w] int64 contiguous -> pixels [B, C, F, H, W]."""
