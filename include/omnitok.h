@@ -24,6 +24,7 @@
 #define OMNITOK_H
 
 #include <stdint.h>
+#include <stddef.h>
 
 #ifdef __cplusplus
 extern "C" {
@@ -701,6 +702,43 @@ int omnitok_frames_to_pixels(const omnitok_frames_desc *desc, int B, int F_out, 
  * (what save_video_grid / the I3D input take); OMNITOK_LAYOUT_CTHW: out[B, C, F, H, W].  C must be 3. */
 int omnitok_pixels_to_frames(const float *pixels, int B, int C, int F, int H, int W, int layout, uint8_t *out,
                              omnitok_stream_t stream);
+
+/* ---- reconstruction metrics (csrc/metrics.hip) -------------------------------------------------------------------------
+ * PSNR and SSIM of every (clip, frame) of two [B, F, 3, H, W] videos in [0, 1], the arithmetic of the reference's
+ * evaluation/common_metrics_on_video_quality calculate_psnr.py (img_psnr) and calculate_ssim.py (calculate_ssim_function)
+ * (INTEGRATION.md "reconstruction metrics").
+ *
+ * One operand: a device pointer and five ELEMENT strides (clip b, frame t, channel c, row h, column w; any view, e.g. the
+ * tokenizer's [B, 3, F, H, W] pixels or the [B, F, H, W, 3] uint8 frames with stride 3 on w).  The w stride must be 1 or 3.
+ *   OMNITOK_METRICS_F32: v = x + shift, then min(max(v, 0), 1) if clamp, both in fp32 (torch.clamp(x + 0.5, 0, 1) of
+ *                        vqgan_eval.py:141-148 is shift 0.5, clamp 1; NaN stays NaN).
+ *   OMNITOK_METRICS_U8:  v = float(u) / 255.0f (the table of omnitok_frames_to_pixels); shift must be 0 and clamp 0. */
+typedef struct omnitok_metrics_operand {
+    const void *data;   /* device pointer: element (0, 0, 0, 0, 0) */
+    int64_t stride[5];  /* elements between neighbours along b, t, c, h, w (>= 0) */
+    int dtype;          /* OMNITOK_METRICS_F32 | OMNITOK_METRICS_U8 */
+    int clamp;          /* 0 | 1 */
+    float shift;
+} omnitok_metrics_operand;
+
+enum { OMNITOK_METRICS_F32 = 0, OMNITOK_METRICS_U8 = 1 };
+/* flags of omnitok_frame_metrics: the outputs to compute (at least one) */
+enum { OMNITOK_METRICS_PSNR = 1, OMNITOK_METRICS_SSIM = 2 };
+
+/* Bytes of device workspace omnitok_frame_metrics needs for this shape (-1: invalid shape). */
+int64_t omnitok_frame_metrics_workspace(int B, int F, int H, int W);
+
+/* psnr[B, F], ssim[B, F] fp64 (device; the pointer of an output not named in flags may be NULL):
+ *   PSNR: mse = sum over the 3 x H x W frame of rnd32(rnd32(a - b)^2), summed in fp64, / (3 H W);
+ *         100 if mse < 1e-10, else 20 log10(1 / sqrt(mse)) in fp64 (img_psnr).
+ *   SSIM: per channel, fp64 throughout: the 11 x 11 Gaussian window of cv2.getGaussianKernel(11, 1.5) applied separably
+ *         (11 taps along w, then 11 along h) over the valid (H - 10) x (W - 10) region, C1 = 0.01^2, C2 = 0.03^2, the map's
+ *         mean; the frame's value is ((s0 + s1) + s2) / 3.  NaN when H < 11 or W < 11 (the reference's empty crop).
+ * Every plane is cut into row strips and column tiles that depend on H and W alone; their partial sums go to `work`
+ * (>= omnitok_frame_metrics_workspace bytes) and are combined in a fixed order, so a clip's scores do not depend on
+ * the rest of the batch.  Validated on the host before any launch; no synchronisation. */
+int omnitok_frame_metrics(const omnitok_metrics_operand *a, const omnitok_metrics_operand *b, int B, int F, int H, int W,
+                          int flags, double *psnr, double *ssim, void *work, size_t work_bytes, omnitok_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -18,6 +18,9 @@ int omnitok_debug_set_gemm_trace(long long *dev_ptr);
  * `in`[4096]) to find the sustained fp32-MFMA ceiling of the chip. out[blocks*256]. */
 int omnitok_debug_mfma_peak(const float *in, float *out, int blocks, int iters, int lds_bytes,
                             long long *clk, omnitok_stream_t stream);
+/* Measurement only: 8 independent v_fma_f64 chains per lane (in[66] doubles: 64 seeds, multiplier, addend), blocks x 256
+ * threads of iters * 128 FMAs each: the sustained fp64 VALU rate. out[blocks*256]. */
+int omnitok_debug_fp64_peak(const double *in, double *out, int blocks, int iters, omnitok_stream_t stream);
 
 #ifdef __cplusplus
 }

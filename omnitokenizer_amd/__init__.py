@@ -2,10 +2,11 @@
 
     from omnitokenizer_amd import OmniTokenizer_VQGAN     # drop-in for the reference class
     from omnitokenizer_amd.gpt import GPT, sample_with_past, sample_with_past_cfg   # LM consumer
+    from omnitokenizer_amd import psnr_ssim, calculate_psnr, calculate_ssim          # reconstruction metrics
 """
 from .config import OmniTokConfig, make_args  # noqa: F401
 
-__all__ = ["OmniTokenizer_VQGAN", "GPT", "OmniTokConfig", "make_args"]
+__all__ = ["OmniTokenizer_VQGAN", "GPT", "OmniTokConfig", "make_args", "psnr_ssim", "calculate_psnr", "calculate_ssim"]
 
 
 def __getattr__(name):
@@ -15,4 +16,7 @@ def __getattr__(name):
     if name == "GPT":
         from .gpt import GPT
         return GPT
+    if name in ("psnr_ssim", "calculate_psnr", "calculate_ssim"):
+        from . import metrics
+        return getattr(metrics, name)
     raise AttributeError(name)

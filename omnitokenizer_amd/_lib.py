@@ -62,6 +62,11 @@ class OmnitokFramesDesc(Structure):
                 ("crop_top", c_int), ("crop_left", c_int), ("resize_h", c_int), ("resize_w", c_int)]
 
 
+class OmnitokMetricsOperand(Structure):
+    """omnitok_metrics_operand (include/omnitok.h): one video of omnitok_frame_metrics."""
+    _fields_ = [("data", c_void_p), ("stride", c_int64 * 5), ("dtype", c_int), ("clamp", c_int), ("shift", c_float)]
+
+
 class OmnitokError(RuntimeError):
     pass
 
@@ -136,6 +141,9 @@ _PROTOS = {
     "omnitok_engine_timing_report": [P, c_char_p, c_int],
     "omnitok_frames_to_pixels": [POINTER(OmnitokFramesDesc), c_int, c_int, c_int, c_int, c_int, c_int, P, P, P],
     "omnitok_pixels_to_frames": [P, c_int, c_int, c_int, c_int, c_int, c_int, P, P],
+    "omnitok_frame_metrics_workspace": [c_int, c_int, c_int, c_int],
+    "omnitok_frame_metrics": [POINTER(OmnitokMetricsOperand), POINTER(OmnitokMetricsOperand), c_int, c_int, c_int, c_int,
+                              c_int, P, P, P, ctypes.c_size_t, P],
     # include/omnitok_lm.h
     "omnitok_lm_create": [POINTER(OmnitokLmConfig), POINTER(P)],
     "omnitok_lm_destroy": [P],
@@ -179,6 +187,7 @@ _PROTOS = {
     "omnitok_get_option": [c_char_p, POINTER(c_int)],
     "omnitok_debug_set_gemm_trace": [P],
     "omnitok_debug_mfma_peak": [P, P, c_int, c_int, c_int, P, P],
+    "omnitok_debug_fp64_peak": [P, P, c_int, c_int, P],
     "omnitok_last_error": [],
     "omnitok_version": [],
 }
@@ -186,7 +195,8 @@ _RESTYPES = {"omnitok_last_error": c_char_p, "omnitok_version": c_char_p,
              "omnitok_engine_destroy": None, "omnitok_engine_workspace_bytes": c_int64,
              "omnitok_engine_workspace_need_encode": c_int64, "omnitok_engine_workspace_need_decode": c_int64,
              "omnitok_lm_destroy": None, "omnitok_comm_destroy": None, "omnitok_lm_cache_bytes": c_int64,
-             "omnitok_pl_planes_bytes": c_int64, "omnitok_pl_unscale": c_float}
+             "omnitok_pl_planes_bytes": c_int64, "omnitok_pl_unscale": c_float,
+             "omnitok_frame_metrics_workspace": c_int64}
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)
 

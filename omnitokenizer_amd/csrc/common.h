@@ -54,6 +54,17 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// unit[i] = float(i) / 255.0f, folded by the compiler at build time (IEEE division: the bits torch's CPU division gives).
+// The uint8 -> [0, 1] conversion of csrc/frames.hip and csrc/metrics.hip; each keeps its own __constant__ copy.
+struct U8Unit {
+    float v[256];
+};
+constexpr U8Unit make_u8_unit() {
+    U8Unit t{};
+    for (int i = 0; i < 256; ++i) t.v[i] = float(i) / 255.0f;
+    return t;
+}
+
 // ---- device helpers -----------------------------------------------------------------------
 #ifdef __HIPCC__
 

@@ -40,6 +40,24 @@ __global__ __launch_bounds__(256) void mfma_peak_kernel(const float *__restrict_
     }
 }
 
+// 8 independent v_fma_f64 chains per lane, operands from `in` (64 per lane + multiplier and addend): the sustained fp64
+// VALU rate, the roof of csrc/metrics.hip's SSIM
+__global__ __launch_bounds__(256) void fp64_peak_kernel(const double *__restrict__ in, double *__restrict__ out, int iters) {
+    const double m = in[64], c = in[65];
+    double x[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) x[i] = in[(threadIdx.x + 8 * i) & 63];
+    for (int it = 0; it < iters; ++it)
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+#pragma unroll
+            for (int i = 0; i < 8; ++i) x[i] = __builtin_fma(x[i], m, c);
+    double sum = 0.0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) sum += x[i];
+    out[(size_t)blockIdx.x * blockDim.x + threadIdx.x] = sum;
+}
+
 }  // namespace omnitok
 
 using namespace omnitok;
@@ -58,5 +76,14 @@ extern "C" int omnitok_debug_mfma_peak(const float *in, float *out, int blocks, 
     }
     hipLaunchKernelGGL(mfma_peak_kernel<4>, dim3(blocks), dim3(256), lds_bytes, stream, in, out, iters, clk);
     OT_LAUNCH_CHECK("mfma_peak");
+    return OMNITOK_OK;
+}
+
+// blocks x 256 threads, each lane iters * 128 fp64 FMAs
+extern "C" int omnitok_debug_fp64_peak(const double *in, double *out, int blocks, int iters, omnitok_stream_t stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    OT_CHECK_ARG(in && out && blocks > 0 && iters > 0, "debug_fp64_peak: bad arguments");
+    hipLaunchKernelGGL(fp64_peak_kernel, dim3(blocks), dim3(256), 0, stream, in, out, iters);
+    OT_LAUNCH_CHECK("fp64_peak");
     return OMNITOK_OK;
 }

@@ -30,14 +30,6 @@
 
 namespace omnitok {
 
-struct U8Unit {
-    float v[256];
-};
-constexpr U8Unit make_u8_unit() {
-    U8Unit t{};
-    for (int i = 0; i < 256; ++i) t.v[i] = float(i) / 255.0f;
-    return t;
-}
 __constant__ U8Unit k_u8_unit = make_u8_unit();
 
 constexpr int FR_CLIPS = 32;    // clips per launch: their descriptors travel in the kernel arguments

@@ -21,6 +21,7 @@ import torch.nn as nn
 
 from . import _lib
 from . import frames as _frames  # registers omnitok::frames_to_pixels / omnitok::pixels_to_frames
+from . import metrics as _metrics  # registers omnitok::frame_metrics
 from ._lib import OmnitokConfig, check
 from .config import OmniTokConfig
 from .synth import path_state_spec, relative_position_index
@@ -594,6 +595,18 @@ class OmniTokenizer_VQGAN(nn.Module):
         if layout not in _frames.LAYOUTS:
             raise ValueError(f"layout must be one of {sorted(_frames.LAYOUTS)}, got {layout!r}")
         return _frames.pixels_to_frames(self.decode(encodings, is_image), layout)
+
+    @torch.no_grad()
+    @_on_own_device
+    def reconstruction_metrics(self, x, x_recon, is_image):
+        """(psnr, ssim), each [B, F] float64 on this module's GPU ([B, 1] with is_image), of the pair vqgan_eval.py:141-148
+        scores: real = x + 0.5 and fake = torch.clamp(x_recon + 0.5, 0, 1), both formed in fp32 inside the metric kernel's
+        reads (no extra pass, no permute copy).  x: the fp32 [B,3,F,H,W] ([B,3,H,W]) input of encode(), x_recon: what
+        decode() returned for it.  Only reads its arguments: codebook statistics and call_cnt are untouched."""
+        for name, t in (("x", x), ("x_recon", x_recon)):
+            if isinstance(t, torch.Tensor) and t.device != self.device:
+                raise RuntimeError(f"{name} on {t.device}, model on {self.device}")
+        return _metrics.reconstruction_psnr_ssim(x, x_recon, is_image)
 
     def _decode_native(self, ids):
         """omnitok::vqgan_decode on CUDA tensors: ids [B, T', h, w] int64 contiguous -> pixels [B, C, F, H, W]."""
