@@ -91,7 +91,9 @@ const char *omnitok_version(void);
  * wrong-result ablation builds (tools/x3_ablate.py, tools/h2_bench.py).  Unknown names return OMNITOK_ERR_INVALID. */
 int omnitok_set_option(const char *name, int value);
 /* Reads the process default of a data-flow option ("gemm_mode", "attn_mode", "gemm_pl", "pl_min_tokens", "temporal_chunk",
- * "prevq_fuse"): what a clip-sharded job consults to pin ONE flow for all its ranks (omnitokenizer_amd/dist.py pin_data_flow). */
+ * "prevq_fuse", "pl_cfg", "pl_tail", "sp_small_blocks") or of a kernel choice of the LM decode step ("lm_wide_u", "lm_balance",
+ * "lm_ksliced", "lm_mfma", "lm_mfma_mult", "lm_ks_deep", "lm_attn_short", "lm_attn_waves"): what a clip-sharded job consults to
+ * pin ONE flow for all its ranks (omnitokenizer_amd/dist.py pin_data_flow), and what a test restores after an A/B arm. */
 int omnitok_get_option(const char *name, int *value);
 /* ------------------------------------------------------------------------------------------
  * Per-operator entry points (each is one HIP kernel family; the engine below chains them).

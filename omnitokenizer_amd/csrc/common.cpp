@@ -151,6 +151,15 @@ extern "C" int omnitok_get_option(const char *name, int *value) {
     else if (!strcmp(name, "prevq_fuse")) *value = omnitok::g_prevq_fuse;
     else if (!strcmp(name, "pl_cfg")) *value = omnitok::g_pl_cfg;
     else if (!strcmp(name, "pl_tail")) *value = omnitok::g_pl_tail;
+    else if (!strcmp(name, "sp_small_blocks")) *value = omnitok::g_sp_small_blocks;
+    else if (!strcmp(name, "lm_wide_u")) *value = omnitok::g_lm_wide_u;
+    else if (!strcmp(name, "lm_balance")) *value = omnitok::g_lm_balance;
+    else if (!strcmp(name, "lm_ksliced")) *value = omnitok::g_lm_ksliced;
+    else if (!strcmp(name, "lm_mfma")) *value = omnitok::g_lm_mfma;
+    else if (!strcmp(name, "lm_mfma_mult")) *value = omnitok::g_lm_mfma_mult;
+    else if (!strcmp(name, "lm_ks_deep")) *value = omnitok::g_lm_ks_deep;
+    else if (!strcmp(name, "lm_attn_short")) *value = omnitok::g_lm_attn_short;
+    else if (!strcmp(name, "lm_attn_waves")) *value = omnitok::g_lm_attn_waves;
     else {
         omnitok::set_error("get_option: %s is not a readable option", name);
         return OMNITOK_ERR_INVALID;

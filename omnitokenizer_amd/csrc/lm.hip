@@ -778,7 +778,8 @@ __global__ void lm_attn_merge_kernel(const float *__restrict__ part, const int32
     const int h = blockIdx.x, b = blockIdx.y, d = threadIdx.x;  // b: query row
     if (d >= HD) return;
     const int total = (prefill_T > 0 ? b % prefill_T : cache_len[b]) + 1;
-    const int used = (total + chunk - 1) / chunk;
+    int used = (total + chunk - 1) / chunk;
+    if (used > nchunk) used = nchunk;  // a stream stepped past max_len (flagged, clamped the same way by the attention kernel)
     const float *pp = part + ((int64_t)b * n_head + h) * nchunk * (2 + HD);
     float M = -INFINITY;
     for (int c = 0; c < used; ++c) M = fmaxf(M, pp[c * (2 + HD)]);

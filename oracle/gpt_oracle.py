@@ -32,7 +32,7 @@ def attention(sd, p, x, n_head, past_k=None, past_v=None):
         v = torch.cat((past_v, v), dim=-2)
     att = (q @ k.transpose(-2, -1)) * (1.0 / math.sqrt(hs))
     if past_k is None:
-        mask = torch.tril(torch.ones(T, T, dtype=torch.bool))
+        mask = torch.tril(torch.ones(T, T, dtype=torch.bool, device=x.device))
         att = att.masked_fill(~mask, float("-inf"))
     y = F.softmax(att, dim=-1) @ v
     y = y.transpose(1, 2).contiguous().view(B, T, C)

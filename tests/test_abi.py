@@ -278,3 +278,27 @@ def test_new_entry_points_validate_arguments_without_gpu(lib):
     assert lib.omnitok_pl_pack_weight(one, 512, 500, 512, 512, one, one, None) == -1   # N % 32
     assert lib.omnitok_pl_planes_bytes(1000, 512, 256) == 1024 * 512 * 4 and lib.omnitok_pl_planes_bytes(10, 500, 256) == -1
     assert lib.omnitok_engine_set_option(None, b"gemm_mode", 1) == -1
+
+
+# every option a test or tool sets and then has to restore: the LM decode step's kernel choices and the stats_pack form
+READABLE_OPTIONS = ("gemm_mode", "attn_mode", "gemm_pl", "pl_min_tokens", "temporal_chunk", "prevq_fuse", "pl_cfg", "pl_tail",
+                    "sp_small_blocks", "lm_wide_u", "lm_balance", "lm_ksliced", "lm_mfma", "lm_mfma_mult", "lm_ks_deep",
+                    "lm_attn_short", "lm_attn_waves")
+
+
+@pytest.mark.parametrize("name", READABLE_OPTIONS)
+def test_option_reads_back_what_was_set(lib, name):
+    """omnitok_get_option returns the value omnitok_set_option stored, for every readable option (the lm_* options and
+    sp_small_blocks could be set but not read, so tests restored hard-coded values)."""
+    from omnitokenizer_amd import _lib
+    before = _lib.get_option(name)
+    try:
+        for v in (before + 7, 0, 3, before):
+            _lib.set_option(name, v)
+            assert _lib.get_option(name) == v, (name, v)
+    finally:
+        _lib.set_option(name, before)
+    assert _lib.get_option(name) == before
+    v = ctypes.c_int(-12345)
+    assert lib.omnitok_get_option(b"lm_no_such_option", ctypes.byref(v)) == -1 and v.value == -12345
+    assert b"lm_no_such_option" in lib.omnitok_last_error()

@@ -300,15 +300,15 @@ def test_tile_schedule_does_not_show_in_the_engine_outputs(models):
     x = c.x.cuda()
 
     def run(**opts):
+        saved = {k: _lib.get_option(k) for k in opts}
         try:
             for k, v in opts.items():
                 _lib.set_option(k, v)
             ids, z = m.encode(x, c.is_image, return_latents=True)
             return ids.clone(), z.clone(), m.decode(ids, c.is_image).clone()
         finally:
-            _lib.set_option("pl_tail", 1)
-            _lib.set_option("pl_cfg", 0)
-            _lib.set_option("sp_small_blocks", 0)
+            for k, v in saved.items():
+                _lib.set_option(k, v)
     base = run()
     for opts in (dict(pl_tail=0), dict(pl_cfg=5), dict(pl_cfg=6), dict(pl_cfg=1), dict(sp_small_blocks=1)):
         got = run(**opts)

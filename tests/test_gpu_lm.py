@@ -58,30 +58,48 @@ def test_gemv(lib, B, N, K):
 
 @pytest.mark.parametrize("hd", [64, 96, 128])
 def test_attn_decode(lib, hd):
-    B, H, max_len = 3, 4, 700
+    """Flash-decode over 256-key chunks ("lm_attn_waves" 8: a wave per 32 keys, 4: per 64; both run) and the merge of the chunk
+    partials, against torch in fp32 (2e-5, as before) and in float64 (2e-5): up to 32 chunks (max_len 8192), at lengths around
+    every 256-key boundary and at max_len - 1, the last slot; the new token's K/V are appended at index cache_len, nothing else
+    changes."""
+    from omnitokenizer_amd import _lib
+    B, H = 3, 4
     C = H * hd
-    nchunk = (max_len + 255) // 256
     s = torch.cuda.current_stream().cuda_stream
-    kc = rnd(B, H, max_len, hd, seed=7).cuda()
-    vc = rnd(B, H, max_len, hd, seed=8).cuda()
-    scratch = torch.empty(B * H * nchunk * (2 + hd), device="cuda")
-    out = torch.empty(B, C, device="cuda")
-    for lens in ([0, 1, 5], [255, 256, 257], [511, 640, 699]):
-        qkv = rnd(B, 3 * C, seed=9 + lens[0])
-        cl = torch.tensor(lens, dtype=torch.int32, device="cuda")
-        kc0, vc0 = kc.clone(), vc.clone()
-        assert lib.omnitok_lm_attn_decode(_p(qkv.cuda()), _p(kc), _p(vc), _p(cl), B, H, hd, max_len, _p(scratch),
-                                          _p(out), s) == 0
-        q, kn, vn = (t.reshape(B, H, hd) for t in qkv.split(C, dim=1))
-        for b, ln in enumerate(lens):
-            k = torch.cat([kc0[b, :, :ln].cpu(), kn[b][:, None]], 1)  # H, ln+1, hd
-            v = torch.cat([vc0[b, :, :ln].cpu(), vn[b][:, None]], 1)
-            att = torch.softmax((q[b][:, None] @ k.transpose(-1, -2)) / math.sqrt(hd), -1)
-            ref = (att @ v).reshape(C)
-            assert (out[b].cpu() - ref).abs().max().item() < 2e-5, (hd, ln)
-            # the new token's K/V were appended at index ln, nothing else changed
-            assert torch.equal(kc[b, :, ln].cpu(), kn[b]) and torch.equal(vc[b, :, ln].cpu(), vn[b])
-            assert torch.equal(kc[b, :, :ln], kc0[b, :, :ln]) and torch.equal(kc[b, :, ln + 1:], kc0[b, :, ln + 1:])
+    saved = _lib.get_option("lm_attn_waves")
+    try:
+        for waves in (8, 4):
+            _lib.set_option("lm_attn_waves", waves)
+            for max_len in (700, 8192):
+                nchunk = (max_len + 255) // 256
+                kc = rnd(B, H, max_len, hd, seed=7).cuda()
+                vc = rnd(B, H, max_len, hd, seed=8).cuda()
+                kref, vref = kc.clone(), vc.clone()   # what the caches must hold after every call
+                scratch = torch.empty(B * H * nchunk * (2 + hd), device="cuda")
+                out = torch.empty(B, C, device="cuda")
+                if max_len == 700:
+                    cases = ([0, 1, 5], [255, 256, 257], [511, 640, 699])
+                else:
+                    cases = [[256 * k - 2, 256 * k - 1, 256 * k] for k in range(1, 32)] + [[1, 4100, max_len - 1]]
+                for lens in cases:
+                    qkv = rnd(B, 3 * C, seed=9 + lens[0]).cuda()
+                    cl = torch.tensor(lens, dtype=torch.int32, device="cuda")
+                    assert lib.omnitok_lm_attn_decode(_p(qkv), _p(kc), _p(vc), _p(cl), B, H, hd, max_len, _p(scratch),
+                                                      _p(out), s) == 0
+                    q, kn, vn = (t.reshape(B, H, hd) for t in qkv.split(C, dim=1))
+                    for b, ln in enumerate(lens):
+                        kref[b, :, ln] = kn[b]
+                        vref[b, :, ln] = vn[b]
+                        k, v = kref[b, :, :ln + 1], vref[b, :, :ln + 1]  # H, ln+1, hd
+                        for dt in (torch.float32, torch.float64):
+                            att = torch.softmax((q[b].to(dt)[:, None] @ k.to(dt).transpose(-1, -2)) / math.sqrt(hd), -1)
+                            ref = (att @ v.to(dt)).reshape(C)
+                            e = (out[b].to(dt) - ref).abs().max().item()
+                            assert e < 2e-5, (hd, waves, max_len, ln, dt, e)
+                    # the new tokens' K/V were appended at index cache_len[b], nothing else changed
+                    assert torch.equal(kc, kref) and torch.equal(vc, vref), (hd, waves, max_len, lens)
+    finally:
+        _lib.set_option("lm_attn_waves", saved)
 
 
 @pytest.mark.parametrize("B,N,K", [(1, 4608, 1536), (2, 1536, 6144), (1, 8192, 1536), (8, 6144, 1536), (4, 1536, 6144), (8, 1536, 1536)])
@@ -93,6 +111,7 @@ def test_gemv_forms_agree(lib, B, N, K):
     g, beta = (rnd(K, seed=5, scale=0.1) + 1.0).cuda(), rnd(K, seed=6, scale=0.1).cuda()
     s = torch.cuda.current_stream().cuda_stream
     out = {}
+    saved = {k: _lib.get_option(k) for k in ("lm_mfma", "lm_ksliced")}
     try:
         _lib.set_option("lm_mfma", 0)   # (the default; with 1, groups of >= 4 streams take the MFMA kernel whatever "lm_ksliced" says)
         for form in (2, 0):
@@ -101,7 +120,8 @@ def test_gemv_forms_agree(lib, B, N, K):
             assert lib.omnitok_lm_gemv(_p(x), _p(w), _p(bias), _p(res), _p(g), _p(beta), _p(y), B, N, K, 1, s) == 0
             out[form] = y
     finally:
-        _lib.set_option("lm_ksliced", 2)
+        for k, v in saved.items():
+            _lib.set_option(k, v)
     assert not torch.equal(out[0], out[2])  # the option is live
     assert float((out[0] - out[2]).abs().max()) < 1e-5 * math.sqrt(K / 1536)
 
@@ -122,6 +142,7 @@ def test_gemv_mfma_path_equals_valu_path(lib, B, N, K):
     refs = {"plain": F.linear(x, w, bias), "ln_gelu": F.gelu(F.linear(F.layer_norm(x, (K,), g, beta), w, bias)),
             "residual": F.linear(x, w) + res}
     outs = {}
+    saved = _lib.get_option("lm_mfma")
     try:
         for mode in (1, 0):
             _lib.set_option("lm_mfma", mode)
@@ -134,7 +155,7 @@ def test_gemv_mfma_path_equals_valu_path(lib, B, N, K):
             assert lib.omnitok_lm_gemv(_p(xd), _p(wd), None, _p(y), None, None, _p(y), B, N, K, 0, s) == 0
             outs[mode, "residual"] = y.clone()
     finally:
-        _lib.set_option("lm_mfma", 0)
+        _lib.set_option("lm_mfma", saved)
     for form, ref in refs.items():
         for mode in (1, 0):
             assert (outs[mode, form].cpu() - ref).abs().max().item() < tol, (form, mode)

@@ -45,6 +45,34 @@ def test_gpt_oracle_matches_reference_golden(name):
         assert np.array_equal(a.numpy(), g["cfg_a"]) and np.array_equal(b.numpy(), g["cfg_b"])
 
 
+def f64(sd):
+    return {k: v.double() for k, v in sd.items()}
+
+
+@pytest.mark.parametrize("name", GPT_CASES)
+def test_gpt_oracle_in_float64_matches_reference_golden(name):
+    """The oracle run in float64 (the reference of tests/test_gpu_lm_wide.py) on the fp32 weights of each golden: the
+    reference's fp32 logits within the same 2e-5, on every teacher-forced position."""
+    g, sd, (V, BS, L, H, C) = load_gpt_case(name)
+    with torch.no_grad():
+        logits = go.forward(f64(sd), torch.from_numpy(g["idx"]), H)
+    assert logits.dtype == torch.float64
+    assert (logits - torch.from_numpy(g["logits"]).double()).abs().max().item() < 2e-5
+
+
+def test_gpt_oracle_in_float64_optional_inputs_match_reference_golden():
+    g, sd, (V, BS, L, H, C) = load_gpt_case("gpt_vtok")
+    cbox = [tuple(r) for r in g["cbox"].tolist()]
+    tbox = [tuple(r) for r in g["tbox"].tolist()]
+    sd64 = f64(sd)
+    emb, idx36, idx24 = (torch.from_numpy(g[k]) for k in ("emb", "idx36", "idx24"))
+    with torch.no_grad():
+        a = go.forward(sd64, idx36, H, embeddings=emb.double(), cbox=cbox)
+        b = go.forward(sd64, idx24, H, cbox=cbox, tbox=tbox)
+    assert (a - torch.from_numpy(g["logits_emb"]).double()).abs().max().item() < 2e-5
+    assert (b - torch.from_numpy(g["logits_tbox"]).double()).abs().max().item() < 2e-5
+
+
 def test_gpt_oracle_optional_inputs_match_reference_golden():
     """explicit embeddings prepended + vtokens_pos boxes (reference gpt.py:207-258), pinned by gpt_vtok.npz."""
     g, sd, (V, BS, L, H, C) = load_gpt_case("gpt_vtok")
