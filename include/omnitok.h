@@ -742,6 +742,63 @@ int64_t omnitok_frame_metrics_workspace(int B, int F, int H, int W);
 int omnitok_frame_metrics(const omnitok_metrics_operand *a, const omnitok_metrics_operand *b, int B, int F, int H, int W,
                           int flags, double *psnr, double *ssim, void *work, size_t work_bytes, omnitok_stream_t stream);
 
+/* ---- I3D, the feature net of FVD (csrc/i3d.hip) --------------------------------------------------------------------------
+ * The layers of the reference's fvd/pytorch_i3d.py InceptionI3d (INTEGRATION.md "FVD").  Activations are fp32 and
+ * channels-last: [B, T, H, W, cs], of which a layer reads or writes the channel slice [off, off + C).  The caller (the
+ * Python InceptionI3d, omnitokenizer_amd/i3d.py) runs the ~55 launches of a forward and owns every buffer.
+ *
+ * "same" padding, per dimension of extent s, kernel k, stride st (Unit3D.compute_pad, pytorch_i3d.py:93-98):
+ *   pad = max(k - (s % st ? s % st : st), 0), front pad // 2, back pad - pad // 2, out = (s + pad - k) / st + 1
+ *   (= ceil(s / st) wherever k >= st).  omnitok_same_pad returns front and out. */
+void omnitok_same_pad(int s, int k, int stride, int *front, int *out);
+
+/* uint8 frames[B, T, H, W, 3] (dense) -> out[B, T, R_h, R_w, 4] fp32: fvd.py preprocess, F.interpolate(float(u),
+ * (R_h, R_w), 'bilinear', align_corners=False) then 2 v / 255 - 1, each step rounded in fp32; channel 3 is 0 (the first
+ * conv then reads whole 16-byte taps).  Within 1e-6 of torch's CPU result, and identical to it where R == H, W. */
+int omnitok_i3d_preprocess(const uint8_t *frames, int B, int T, int H, int W, int R_h, int R_w, float *out,
+                           omnitok_stream_t stream);
+
+/* One Unit3D: "same" pad (zeros), conv3d, + bias (the folded BatchNorm, or the conv's own), ReLU if relu.
+ * Packed weight: w[Cout][ldw], ldw = omnitok_conv3d_packed_ldw(Cin, kt, kh, kw) (a multiple of 32, 16-byte aligned), with
+ *   w[n][((dt * kh + dh) * kw + dw) * Cin + ci] = weight[n][ci][dt][dh][dw] and zeros from kt kh kw Cin up to ldw.
+ *   Cin must be a multiple of 4: a 3-channel input is zero-padded to 4 channels, and its weight with it.
+ * Output columns n < split go to y (channel y_off + n), the others to y2 (channel y2_off + n - split): split = Cout for a
+ * single output.  Each output element is one fp32 fma chain over k in a fixed order (v_mfma_f32_32x32x2_f32): the same
+ * bits for a clip alone and in any batch.  Validated on the host before any launch; no synchronisation. */
+typedef struct omnitok_conv3d {
+    const float *x;            /* input [B, T, H, W, x_cs]; channels [x_off, x_off + Cin); x + x_off 16-byte aligned */
+    int64_t x_cs;              /* multiple of 4 */
+    int x_off;                 /* multiple of 4 */
+    int B, T, H, W, Cin;
+    const float *w;            /* packed, see above */
+    const float *bias;         /* [Cout] */
+    int Cout, kt, kh, kw;      /* kernel 1..7 */
+    int st, sh, sw;            /* strides 1..4 */
+    int relu;                  /* 0 | 1 */
+    float *y;                  /* output [B, To, Ho, Wo, y_cs], channels [y_off, y_off + split) */
+    int64_t y_cs;
+    int y_off;
+    float *y2;                 /* second output [B, To, Ho, Wo, y2_cs], channels [y2_off, y2_off + Cout - split) */
+    int64_t y2_cs;
+    int y2_off;
+    int split;                 /* 1..Cout */
+} omnitok_conv3d;
+
+/* Floats per packed weight row for this kernel (-1: Cin not a positive multiple of 4, or a kernel outside 1..7). */
+int64_t omnitok_conv3d_packed_ldw(int Cin, int kt, int kh, int kw);
+int omnitok_conv3d_same(const omnitok_conv3d *conv, omnitok_stream_t stream);
+
+/* MaxPool3dSamePadding: x[B, T, H, W, C] -> y[B, To, Ho, Wo, C] (dense, C a multiple of 4, 16-byte aligned): the "same"
+ * pad with ZEROS (F.pad), then the max over the kt x kh x kw window; bit-identical to torch, NaN included. */
+int omnitok_maxpool3d_same(const float *x, int B, int T, int H, int W, int C, int kt, int kh, int kw, int st, int sh,
+                           int sw, float *y, omnitok_stream_t stream);
+
+/* The logits head: x[B, T, H, W, C] (dense, T >= 2, H, W >= 7) -> AvgPool3d([2, 7, 7], stride 1) -> the 1x1x1 logits conv
+ * (w_t[C][num_classes], the TRANSPOSED weight, + bias) -> mean over the T - 1 pooled steps -> out[B, num_classes, H - 6,
+ * W - 6].  C <= 2048, num_classes <= 1024. */
+int omnitok_i3d_head(const float *x, int B, int T, int H, int W, int C, const float *w_t, const float *bias,
+                     int num_classes, float *out, omnitok_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

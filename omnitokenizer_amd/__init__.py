@@ -3,10 +3,12 @@
     from omnitokenizer_amd import OmniTokenizer_VQGAN     # drop-in for the reference class
     from omnitokenizer_amd.gpt import GPT, sample_with_past, sample_with_past_cfg   # LM consumer
     from omnitokenizer_amd import psnr_ssim, calculate_psnr, calculate_ssim          # reconstruction metrics
+    from omnitokenizer_amd import InceptionI3d, get_fvd_logits, frechet_distance      # FVD (omnitokenizer_amd.fvd)
 """
 from .config import OmniTokConfig, make_args  # noqa: F401
 
-__all__ = ["OmniTokenizer_VQGAN", "GPT", "OmniTokConfig", "make_args", "psnr_ssim", "calculate_psnr", "calculate_ssim"]
+__all__ = ["OmniTokenizer_VQGAN", "GPT", "OmniTokConfig", "make_args", "psnr_ssim", "calculate_psnr", "calculate_ssim",
+           "InceptionI3d", "load_fvd_model", "get_fvd_logits", "frechet_distance", "compute_fvd"]
 
 
 def __getattr__(name):
@@ -19,4 +21,10 @@ def __getattr__(name):
     if name in ("psnr_ssim", "calculate_psnr", "calculate_ssim"):
         from . import metrics
         return getattr(metrics, name)
+    if name == "InceptionI3d":
+        from .i3d import InceptionI3d
+        return InceptionI3d
+    if name in ("load_fvd_model", "get_fvd_logits", "frechet_distance", "compute_fvd"):
+        from . import fvd
+        return getattr(fvd, name)
     raise AttributeError(name)

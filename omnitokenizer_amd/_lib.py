@@ -67,6 +67,15 @@ class OmnitokMetricsOperand(Structure):
     _fields_ = [("data", c_void_p), ("stride", c_int64 * 5), ("dtype", c_int), ("clamp", c_int), ("shift", c_float)]
 
 
+class OmnitokConv3d(Structure):
+    """omnitok_conv3d (include/omnitok.h): one Unit3D of the I3D net."""
+    _fields_ = [("x", c_void_p), ("x_cs", c_int64), ("x_off", c_int), ("B", c_int), ("T", c_int), ("H", c_int),
+                ("W", c_int), ("Cin", c_int), ("w", c_void_p), ("bias", c_void_p), ("Cout", c_int), ("kt", c_int),
+                ("kh", c_int), ("kw", c_int), ("st", c_int), ("sh", c_int), ("sw", c_int), ("relu", c_int),
+                ("y", c_void_p), ("y_cs", c_int64), ("y_off", c_int), ("y2", c_void_p), ("y2_cs", c_int64),
+                ("y2_off", c_int), ("split", c_int)]
+
+
 class OmnitokError(RuntimeError):
     pass
 
@@ -144,6 +153,12 @@ _PROTOS = {
     "omnitok_frame_metrics_workspace": [c_int, c_int, c_int, c_int],
     "omnitok_frame_metrics": [POINTER(OmnitokMetricsOperand), POINTER(OmnitokMetricsOperand), c_int, c_int, c_int, c_int,
                               c_int, P, P, P, ctypes.c_size_t, P],
+    "omnitok_same_pad": [c_int, c_int, c_int, POINTER(c_int), POINTER(c_int)],
+    "omnitok_i3d_preprocess": [P, c_int, c_int, c_int, c_int, c_int, c_int, P, P],
+    "omnitok_conv3d_packed_ldw": [c_int, c_int, c_int, c_int],
+    "omnitok_conv3d_same": [POINTER(OmnitokConv3d), P],
+    "omnitok_maxpool3d_same": [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P],
+    "omnitok_i3d_head": [P, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P, P],
     # include/omnitok_lm.h
     "omnitok_lm_create": [POINTER(OmnitokLmConfig), POINTER(P)],
     "omnitok_lm_destroy": [P],
@@ -196,7 +211,8 @@ _RESTYPES = {"omnitok_last_error": c_char_p, "omnitok_version": c_char_p,
              "omnitok_engine_workspace_need_encode": c_int64, "omnitok_engine_workspace_need_decode": c_int64,
              "omnitok_lm_destroy": None, "omnitok_comm_destroy": None, "omnitok_lm_cache_bytes": c_int64,
              "omnitok_pl_planes_bytes": c_int64, "omnitok_pl_unscale": c_float,
-             "omnitok_frame_metrics_workspace": c_int64}
+             "omnitok_frame_metrics_workspace": c_int64, "omnitok_same_pad": None,
+             "omnitok_conv3d_packed_ldw": c_int64}
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)
 

@@ -339,3 +339,44 @@ def synth_gpt_state(vocab_size, block_size, n_layer, n_head, n_embd, seed=0, vto
         t, r = vtokens_pos_shape
         put("vtokens_pos_emb", (1, t, r, r, C), "e")
     return sd
+
+
+def synth_i3d_state_dict(seed: int = 0, num_classes: int = 400) -> "OrderedDict[str, torch.Tensor]":
+    """Seeded weights for the reference's InceptionI3d (fvd/pytorch_i3d.py), every key of its state_dict in its order
+    (omnitokenizer_amd/i3d.py state_spec), num_batches_tracked included.  Conv weights are He-scaled normal (std
+    sqrt(2 / fan_in); the logits conv sqrt(1 / fan_in)); the BatchNorms have gamma in [0.8, 1.2], beta ~ N(0, 0.1^2),
+    running_mean ~ N(0, 0.1^2) and running_var in [0.5, 1.5], so that activations stay O(1) through the network (the
+    per-endpoint RMS is in the fixtures of tests/golden/make_golden_fvd.py).  numpy PCG64, one stream per key."""
+    from .i3d import state_spec
+    sd = OrderedDict()
+    for name, (shape, dtype) in state_spec(num_classes).items():
+        rng = np.random.Generator(np.random.PCG64(_key_seed(seed, name)))
+        if name.endswith("num_batches_tracked"):
+            v = np.array(int(rng.integers(0, 1 << 20)), dtype=np.int64)
+        elif name.endswith("conv3d.weight"):
+            fan_in = int(np.prod(shape[1:]))
+            gain = 1.0 if name.startswith("logits.") else 2.0
+            v = rng.standard_normal(shape) * np.sqrt(gain / fan_in)
+        elif name == "logits.conv3d.bias":
+            v = 0.1 * rng.standard_normal(shape)
+        elif name.endswith("bn.weight"):
+            v = rng.uniform(0.8, 1.2, shape)
+        elif name.endswith("bn.running_var"):
+            v = rng.uniform(0.5, 1.5, shape)
+        else:  # bn.bias, bn.running_mean
+            v = 0.1 * rng.standard_normal(shape)
+        sd[name] = torch.from_numpy(np.array(v, dtype=np.int64 if dtype == torch.int64 else np.float32))
+    return sd
+
+
+def synth_fvd_clips(n: int, frames: int, height: int, width: int, seed: int, noise: float = 0.0,
+                    noise_seed: int = 0) -> np.ndarray:
+    """uint8 [n, frames, height, width, 3] clips for FVD: synth_video "natural" content (a max(height, width) square, cropped),
+    plus N(0, noise^2) per-pixel noise (a lightly perturbed "reconstruction" of the same seed), quantised as
+    round((x + 0.5) * 255) clipped to 0..255"""
+    x = synth_video(n, frames, max(height, width), seed=seed, kind="natural").numpy()[:, :, :, :height, :width]
+    if noise:
+        x = x + np.float32(noise) * np.random.Generator(np.random.PCG64(noise_seed)).standard_normal(x.shape,
+                                                                                                     dtype=np.float32)
+    u = np.clip(np.rint((x + np.float32(0.5)) * np.float32(255.0)), 0, 255).astype(np.uint8)
+    return np.ascontiguousarray(u.transpose(0, 2, 3, 4, 1))
