@@ -799,6 +799,67 @@ int omnitok_maxpool3d_same(const float *x, int B, int T, int H, int W, int C, in
 int omnitok_i3d_head(const float *x, int B, int T, int H, int W, int C, const float *w_t, const float *bias,
                      int num_classes, float *out, omnitok_stream_t stream);
 
+/* ---- Inception V3, the feature net of FID (csrc/inception.hip) ---------------------------------------------------------
+ * The layers of the reference's evaluation/pytorch-fid InceptionV3 (torchvision's Inception3 with the FID patches;
+ * INTEGRATION.md "FID").  Activations are fp32 and channels-last: [N, H, W, cs], of which a layer reads or writes the
+ * channel slice [off, off + C).  The caller (the Python InceptionV3, omnitokenizer_amd/inception.py) runs the ~70 launches
+ * of a forward and owns every buffer.  Output extents are floor((s + 2 pad - k) / stride) + 1 (omnitok_conv2d_out). */
+#define OMNITOK_FID_U8_NHWC 0      /* uint8 [N, H, W, 3], rows ld bytes apart, images H * ld bytes apart */
+#define OMNITOK_FID_F32_NCHW 1     /* fp32 [N, 3, H, W] dense, values in [0, 1] (ToTensor's output) */
+#define OMNITOK_FID_RESIZE 1       /* flags: F.interpolate(x, (R_h, R_w), 'bilinear', align_corners=False) */
+#define OMNITOK_FID_NORMALIZE 2    /* flags: 2 x - 1 */
+
+/* src -> out[N, R_h, R_w, 4] fp32: u8 / 255 (ToTensor), then the resize if flags has OMNITOK_FID_RESIZE (else R == H, W),
+ * then 2 x - 1 if OMNITOK_FID_NORMALIZE, each step rounded in fp32 in that order (InceptionV3.forward); channel 3 is 0.
+ * Identical to torch where no resize happens or R == H, W; within 1e-6 of torch's CPU result elsewhere.  ld is ignored for
+ * OMNITOK_FID_F32_NCHW. */
+int omnitok_fid_preprocess(const void *src, int dtype, int64_t ld, int N, int H, int W, int R_h, int R_w, int flags,
+                           float *out, omnitok_stream_t stream);
+
+/* One BasicConv2d with its BatchNorm folded: explicit zero padding (pad_h, pad_w), conv2d, + bias, ReLU if relu.
+ * Packed weight: the conv3d layout with kt = 1, w[Cout][ldw], ldw = omnitok_conv3d_packed_ldw(Cin, 1, kh, kw), with
+ *   w[n][(dh * kw + dw) * Cin + ci] = weight[n][ci][dh][dw] and zeros from kh kw Cin up to ldw.  Cin a multiple of 4 (the
+ *   3-channel input is zero-padded to 4, and its weight with it).
+ * Output columns n < split go to y (channel y_off + n), the others to y2 (channel y2_off + n - split).  Each output element
+ * is one fp32 fma chain over k in a fixed order, the tile chosen by Cout alone: the same bits for an image alone and in
+ * any batch.  Validated on the host before any launch; no synchronisation. */
+typedef struct omnitok_conv2d_desc {
+    const float *x;            /* input [N, H, W, x_cs]; channels [x_off, x_off + Cin); x + x_off 16-byte aligned */
+    int64_t x_cs;              /* multiple of 4 */
+    int x_off;                 /* multiple of 4 */
+    int N, H, W, Cin;
+    const float *w;            /* packed, see above */
+    const float *bias;         /* [Cout] */
+    int Cout, kh, kw;          /* kernel 1..7 */
+    int sh, sw;                /* strides 1..4 */
+    int ph, pw;                /* padding 0..kernel - 1 */
+    int relu;                  /* 0 | 1 */
+    float *y;                  /* output [N, Ho, Wo, y_cs], channels [y_off, y_off + split) */
+    int64_t y_cs;
+    int y_off;
+    float *y2;                 /* second output [N, Ho, Wo, y2_cs], channels [y2_off, y2_off + Cout - split) */
+    int64_t y2_cs;
+    int y2_off;
+    int split;                 /* 1..Cout */
+} omnitok_conv2d_desc;
+
+/* floor((s + 2 pad - k) / stride) + 1, or 0 where the window does not fit */
+int omnitok_conv2d_out(int s, int k, int stride, int pad);
+int omnitok_conv2d(const omnitok_conv2d_desc *conv, omnitok_stream_t stream);
+
+/* x[N, H, W, C] (dense, C a multiple of 4) -> channels [y_off, y_off + C) of y[N, Ho, Wo, y_cs] (y_off, y_cs multiples of
+ * 4); kernel k x k, stride s, padding p <= k / 2, floor sizing.
+ * maxpool2d: max_pool2d with -inf padding; bit-identical to torch, NaN included.
+ * avgpool2d: avg_pool2d(count_include_pad=False): the fp32 sum of the in-image taps in (dy, dx) order, / their count. */
+int omnitok_maxpool2d(const float *x, int N, int H, int W, int C, int k, int s, int p, float *y, int64_t y_cs, int y_off,
+                      omnitok_stream_t stream);
+int omnitok_avgpool2d(const float *x, int N, int H, int W, int C, int k, int s, int p, float *y, int64_t y_cs, int y_off,
+                      omnitok_stream_t stream);
+
+/* adaptive_avg_pool2d(x, 1): x[N, H, W, C] (dense, C a multiple of 4) -> y[N, C], the fp32 sum over positions in (y, x)
+ * order from 0, / (H W). */
+int omnitok_spatial_mean(const float *x, int N, int H, int W, int C, float *y, omnitok_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,11 +4,18 @@
     from omnitokenizer_amd.gpt import GPT, sample_with_past, sample_with_past_cfg   # LM consumer
     from omnitokenizer_amd import psnr_ssim, calculate_psnr, calculate_ssim          # reconstruction metrics
     from omnitokenizer_amd import InceptionI3d, get_fvd_logits, frechet_distance      # FVD (omnitokenizer_amd.fvd)
+    from omnitokenizer_amd import InceptionV3, load_fid_inception, compute_fid       # FID (omnitokenizer_amd.fid)
 """
 from .config import OmniTokConfig, make_args  # noqa: F401
 
+# omnitokenizer_amd.fid's drop-ins (its Frechet distance is calculate_frechet_distance, on statistics; fvd's is
+# frechet_distance, on embeddings)
+_FID_NAMES = ("load_fid_inception", "calculate_activation_statistics", "calculate_frechet_distance",
+              "compute_statistics_of_path", "calculate_fid_given_paths", "save_fid_stats", "compute_fid")
+
 __all__ = ["OmniTokenizer_VQGAN", "GPT", "OmniTokConfig", "make_args", "psnr_ssim", "calculate_psnr", "calculate_ssim",
-           "InceptionI3d", "load_fvd_model", "get_fvd_logits", "frechet_distance", "compute_fvd"]
+           "InceptionI3d", "load_fvd_model", "get_fvd_logits", "frechet_distance", "compute_fvd",
+           "InceptionV3"] + list(_FID_NAMES)
 
 
 def __getattr__(name):
@@ -27,4 +34,10 @@ def __getattr__(name):
     if name in ("load_fvd_model", "get_fvd_logits", "frechet_distance", "compute_fvd"):
         from . import fvd
         return getattr(fvd, name)
+    if name == "InceptionV3":
+        from .inception import InceptionV3
+        return InceptionV3
+    if name in _FID_NAMES:
+        from . import fid
+        return getattr(fid, name)
     raise AttributeError(name)

@@ -76,6 +76,15 @@ class OmnitokConv3d(Structure):
                 ("y2_off", c_int), ("split", c_int)]
 
 
+class OmnitokConv2d(Structure):
+    """omnitok_conv2d_desc (include/omnitok.h): one BasicConv2d of the Inception V3 net."""
+    _fields_ = [("x", c_void_p), ("x_cs", c_int64), ("x_off", c_int), ("N", c_int), ("H", c_int), ("W", c_int),
+                ("Cin", c_int), ("w", c_void_p), ("bias", c_void_p), ("Cout", c_int), ("kh", c_int), ("kw", c_int),
+                ("sh", c_int), ("sw", c_int), ("ph", c_int), ("pw", c_int), ("relu", c_int), ("y", c_void_p),
+                ("y_cs", c_int64), ("y_off", c_int), ("y2", c_void_p), ("y2_cs", c_int64), ("y2_off", c_int),
+                ("split", c_int)]
+
+
 class OmnitokError(RuntimeError):
     pass
 
@@ -159,6 +168,12 @@ _PROTOS = {
     "omnitok_conv3d_same": [POINTER(OmnitokConv3d), P],
     "omnitok_maxpool3d_same": [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P],
     "omnitok_i3d_head": [P, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P, P],
+    "omnitok_fid_preprocess": [P, c_int, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, P, P],
+    "omnitok_conv2d_out": [c_int, c_int, c_int, c_int],
+    "omnitok_conv2d": [POINTER(OmnitokConv2d), P],
+    "omnitok_maxpool2d": [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, c_int64, c_int, P],
+    "omnitok_avgpool2d": [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, c_int64, c_int, P],
+    "omnitok_spatial_mean": [P, c_int, c_int, c_int, c_int, P, P],
     # include/omnitok_lm.h
     "omnitok_lm_create": [POINTER(OmnitokLmConfig), POINTER(P)],
     "omnitok_lm_destroy": [P],

@@ -380,3 +380,38 @@ def synth_fvd_clips(n: int, frames: int, height: int, width: int, seed: int, noi
                                                                                                      dtype=np.float32)
     u = np.clip(np.rint((x + np.float32(0.5)) * np.float32(255.0)), 0, 255).astype(np.uint8)
     return np.ascontiguousarray(u.transpose(0, 2, 3, 4, 1))
+
+
+def synth_fid_inception_state_dict(seed: int = 0) -> "OrderedDict[str, torch.Tensor]":
+    """Seeded weights with exactly the keys, shapes and dtypes of pytorch-fid's pt_inception-2015-12-05 .pth (torchvision
+    Inception3(num_classes=1008, aux_logits=False), num_batches_tracked and fc included; omnitokenizer_amd/inception.py
+    state_spec), in its order.  Conv weights are He-scaled normal (std sqrt(2 / fan_in)); the BatchNorms have gamma in
+    [0.8, 1.2], beta ~ N(0, 0.1^2), running_mean ~ N(0, 0.1^2) and running_var in [0.5, 1.5]; fc is N(0, 1 / 2048), its
+    bias N(0, 0.1^2).  So every block's RMS stays O(1) (recorded in the fixtures of tests/golden/make_golden_fid.py).
+    numpy PCG64, one stream per key."""
+    from .inception import state_spec
+    sd = OrderedDict()
+    for name, (shape, dtype) in state_spec(wrapper=False).items():
+        rng = np.random.Generator(np.random.PCG64(_key_seed(seed, name)))
+        if name.endswith("num_batches_tracked"):
+            v = np.array(int(rng.integers(0, 1 << 20)), dtype=np.int64)
+        elif name.endswith("conv.weight"):
+            v = rng.standard_normal(shape) * np.sqrt(2.0 / int(np.prod(shape[1:])))
+        elif name == "fc.weight":
+            v = rng.standard_normal(shape) * np.sqrt(1.0 / shape[1])
+        elif name == "fc.bias":
+            v = 0.1 * rng.standard_normal(shape)
+        elif name.endswith("bn.weight"):
+            v = rng.uniform(0.8, 1.2, shape)
+        elif name.endswith("bn.running_var"):
+            v = rng.uniform(0.5, 1.5, shape)
+        else:  # bn.bias, bn.running_mean
+            v = 0.1 * rng.standard_normal(shape)
+        sd[name] = torch.from_numpy(np.array(v, dtype=np.int64 if dtype == torch.int64 else np.float32))
+    return sd
+
+
+def synth_fid_images(n: int, height: int, width: int, seed: int, noise: float = 0.0, noise_seed: int = 0) -> np.ndarray:
+    """uint8 [n, height, width, 3] images for FID: one frame of synth_fvd_clips (synth_video "natural" content, plus
+    N(0, noise^2) per-pixel noise for a lightly perturbed "reconstruction" of the same seed)"""
+    return np.ascontiguousarray(synth_fvd_clips(n, 1, height, width, seed, noise, noise_seed)[:, 0])
