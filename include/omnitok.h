@@ -860,6 +860,42 @@ int omnitok_avgpool2d(const float *x, int N, int H, int W, int C, int k, int s, 
  * order from 0, / (H W). */
 int omnitok_spatial_mean(const float *x, int N, int H, int W, int C, float *y, omnitok_stream_t stream);
 
+/* ---- LPIPS, the tokenizer's perceptual model (csrc/lpips.hip) ----------------------------------------------------------
+ * The reference's OmniTokenizer/modules/lpips.py (taming's VGG16 LPIPS; INTEGRATION.md "LPIPS").  The Python LPIPS
+ * (omnitokenizer_amd/lpips.py) runs, per chunk of N pairs, one 2N-image pass: omnitok_lpips_preprocess of both operands into
+ * rows [0, N) and [N, 2N), the VGG16 trunk as 13 omnitok_conv2d (3 x 3, pad 1, bias, ReLU; the first conv's Cin 3 padded to
+ * 4) and 4 omnitok_maxpool2d (2, 2, 0), omnitok_lpips_layer on each slice output as soon as it exists, and
+ * omnitok_lpips_finalize. */
+#define OMNITOK_LPIPS_NORMALIZE 1  /* flags: 2 v - 1 (lpips' normalize=True: [0, 1] inputs) */
+#define OMNITOK_LPIPS_MIN_SIZE 16  /* H, W: the fifth slice needs four 2 x 2 pools to leave at least one pixel */
+
+/* Images i0 .. i0 + n - 1 of src (an omnitok_metrics_operand of B clips of F frames, image (b, t) = b * F + t) ->
+ * out[n, H, W, 4] fp32 channels-last, channel 3 = 0.  Each step rounded in fp32, in this order:
+ *   v = x + shift (F32) or v = float(u) / 255.0f + shift (U8: shift is allowed here, -0.5 gives the tokenizer's range);
+ *   min(max(v, 0), 1) if src->clamp; 2 v - 1 if flags has OMNITOK_LPIPS_NORMALIZE;
+ *   (v - shift[c]) / scale[c], a true division (ScalingLayer; shift, scale: host arrays of the checkpoint's buffers).
+ * Equal bits to those torch ops on the explicitly converted fp32 tensor.  Any strides >= 0; H, W >= 16; n <= 65535. */
+int omnitok_lpips_preprocess(const omnitok_metrics_operand *src, int B, int F, int H, int W, int i0, int n, int flags,
+                             const float shift[3], const float scale[3], float *out, omnitok_stream_t stream);
+
+/* Bytes of device workspace omnitok_lpips_layer needs (-1: invalid shape): N * ceil(h w / 64) doubles. */
+int64_t omnitok_lpips_workspace(int N, int h, int w);
+
+/* One slice's head: feats[2N, h, w, C] fp32 dense (image n paired with image N + n; C a multiple of 4, <= 512), lin_w[C]
+ * (NetLinLayer's 1x1 weight) -> res[n * 5 + layer] fp64, for n < N:
+ *   per pixel, fp32, channels in a fixed order (16 lanes per pixel, lane l the 16-byte groups l, l + 16, ...; their partial
+ *   sums combined by a xor butterfly): na = sqrt(sum_c a_c^2) + 1e-10, nb likewise,
+ *   v = sum_c w_c * ((a_c / na - b_c / nb)^2)   (normalize_tensor, the squared difference, the 1x1 conv; 0 for a pair
+ *   of all-zero pixels);
+ *   res = (sum of v over pixels, in fp64: strips of 64 consecutive pixels summed in order, then the strips in order)
+ *   / (h w).
+ * The partition depends on h and w alone: a pair's value does not depend on N, the chunk or the grid. */
+int omnitok_lpips_layer(const float *feats, int N, int h, int w, int C, const float *lin_w, int layer, void *work,
+                        size_t work_bytes, double *res, omnitok_stream_t stream);
+
+/* val[n] = (float)((((res[n][0] + res[n][1]) + res[n][2]) + res[n][3]) + res[n][4]) in fp64 (LPIPS.forward's val). */
+int omnitok_lpips_finalize(const double *res, int N, float *val, omnitok_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

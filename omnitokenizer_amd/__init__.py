@@ -5,6 +5,7 @@
     from omnitokenizer_amd import psnr_ssim, calculate_psnr, calculate_ssim          # reconstruction metrics
     from omnitokenizer_amd import InceptionI3d, get_fvd_logits, frechet_distance      # FVD (omnitokenizer_amd.fvd)
     from omnitokenizer_amd import InceptionV3, load_fid_inception, compute_fid       # FID (omnitokenizer_amd.fid)
+    from omnitokenizer_amd import LPIPS, load_lpips, lpips_frames                    # LPIPS (omnitokenizer_amd.lpips)
 """
 from .config import OmniTokConfig, make_args  # noqa: F401
 
@@ -15,7 +16,7 @@ _FID_NAMES = ("load_fid_inception", "calculate_activation_statistics", "calculat
 
 __all__ = ["OmniTokenizer_VQGAN", "GPT", "OmniTokConfig", "make_args", "psnr_ssim", "calculate_psnr", "calculate_ssim",
            "InceptionI3d", "load_fvd_model", "get_fvd_logits", "frechet_distance", "compute_fvd",
-           "InceptionV3"] + list(_FID_NAMES)
+           "InceptionV3"] + list(_FID_NAMES) + ["LPIPS", "load_lpips", "lpips_frames"]
 
 
 def __getattr__(name):
@@ -40,4 +41,7 @@ def __getattr__(name):
     if name in _FID_NAMES:
         from . import fid
         return getattr(fid, name)
+    if name in ("LPIPS", "load_lpips", "lpips_frames"):
+        from . import lpips
+        return getattr(lpips, name)
     raise AttributeError(name)

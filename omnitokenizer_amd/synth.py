@@ -411,6 +411,30 @@ def synth_fid_inception_state_dict(seed: int = 0) -> "OrderedDict[str, torch.Ten
     return sd
 
 
+def synth_lpips_state_dict(seed: int = 0) -> "OrderedDict[str, torch.Tensor]":
+    """Seeded weights with exactly the keys and shapes of the reference's LPIPS().state_dict() (lpips.py, use_dropout=True;
+    omnitokenizer_amd/lpips.py state_spec), in its order.  Conv weights are He-scaled normal (std sqrt(2 / fan_in)) with
+    biases N(0, 0.05^2), so every slice's RMS stays O(1) (recorded in the fixtures of tests/golden/make_golden_lpips.py);
+    the lin weights are |N(0, 1 / C)|, non-negative as trained LPIPS has them; the ScalingLayer buffers are the
+    reference's constants.  numpy PCG64, one stream per key."""
+    from .lpips import SCALING_SCALE, SCALING_SHIFT, state_spec
+    sd = OrderedDict()
+    for name, shape in state_spec().items():
+        rng = np.random.Generator(np.random.PCG64(_key_seed(seed, name)))
+        if name == "scaling_layer.shift":
+            v = np.array(SCALING_SHIFT).reshape(shape)
+        elif name == "scaling_layer.scale":
+            v = np.array(SCALING_SCALE).reshape(shape)
+        elif name.endswith(".weight") and name.startswith("net."):
+            v = rng.standard_normal(shape) * np.sqrt(2.0 / int(np.prod(shape[1:])))
+        elif name.startswith("net."):
+            v = 0.05 * rng.standard_normal(shape)
+        else:  # lin{k}.model.1.weight
+            v = np.abs(rng.standard_normal(shape)) * np.sqrt(1.0 / shape[1])
+        sd[name] = torch.from_numpy(np.array(v, dtype=np.float32))
+    return sd
+
+
 def synth_fid_images(n: int, height: int, width: int, seed: int, noise: float = 0.0, noise_seed: int = 0) -> np.ndarray:
     """uint8 [n, height, width, 3] images for FID: one frame of synth_fvd_clips (synth_video "natural" content, plus
     N(0, noise^2) per-pixel noise for a lightly perturbed "reconstruction" of the same seed)"""

@@ -608,6 +608,29 @@ class OmniTokenizer_VQGAN(nn.Module):
                 raise RuntimeError(f"{name} on {t.device}, model on {self.device}")
         return _metrics.reconstruction_psnr_ssim(x, x_recon, is_image)
 
+    @torch.no_grad()
+    @_on_own_device
+    def perceptual_distance(self, x, x_recon, is_image, lpips_model):
+        """[B, F] fp32 on this module's GPU ([B, 1] with is_image): the reference's perceptual_model(all_frames,
+        all_frames_recon) (omnitokenizer.py:403-404, 519-523) reshaped, i.e. the LPIPS of every frame pair, fed the
+        [-0.5, 0.5] values unchanged in the x.permute(0, 2, 1, 3, 4).view(-1, 3, H, W) order (read in place, no copy).
+        validation_step's val/perceptual_loss is this times perceptual_weight (its mean, for the logged scalar).
+        lpips_model: an omnitokenizer_amd.lpips.LPIPS, e.g. load_lpips(device, checkpoint) for the checkpoint's own
+        perceptual_model.* weights (load_state_dict leaves them out of this module).  Only reads its arguments: codebook
+        statistics and call_cnt are untouched."""
+        from . import lpips as _lpips
+        want = 4 if is_image else 5
+        for name, t in (("x", x), ("x_recon", x_recon)):
+            if not isinstance(t, torch.Tensor) or t.dim() != want:
+                raise ValueError(f"{name} must be [B,3,{'' if is_image else 'F,'}H,W] (is_image={is_image}), got "
+                                 f"{getattr(t, 'shape', type(t))}")
+            if t.dtype != torch.float32:
+                raise TypeError(f"{name}: dtype {t.dtype}, expected torch.float32")
+            if t.device != self.device:
+                raise RuntimeError(f"{name} on {t.device}, model on {self.device}")
+        return _lpips.lpips_frames(x, x_recon, lpips_model, layout="nchw" if is_image else "bcthw",
+                                   max_pairs=lpips_model.max_pairs)
+
     def _decode_native(self, ids):
         """omnitok::vqgan_decode on CUDA tensors: ids [B, T', h, w] int64 contiguous -> pixels [B, C, F, H, W]."""
         self._sync_engine()
