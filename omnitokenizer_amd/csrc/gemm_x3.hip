@@ -7,7 +7,8 @@
 // significand bits, truncation split: a0 = top 16 bits of a, a1 = top 16 bits of a - a0,
 // a2 = a - a0 - a1), so a*b = sum_ij a_i*b_j with every bf16 x bf16 product exact in fp32.  The six
 // products with weight >= 2^-16 are evaluated on v_mfma_f32_32x32x16_bf16 (fp32 accumulate); the three
-// dropped ones are below 2^-24 |a b|, i.e. below half an fp32 ulp of the product.  6 x 32 = 192
+// dropped ones are below 2^-21 |a b| (|a1| < 2^-7 |a|, |a2| < 2^-15 |a|: a1 b2 + a2 b1 < 2^-21; they reach
+// ~6.6 x 2^-24 on random operands, tests/test_error_bounds_cpu.py), a few fp32 ulps of the product.  6 x 32 = 192
 // matrix-pipe cycles per 32x32x16 block instead of 8 x 64 = 512: a 417 TF "fp32-equivalent" roof.
 //
 // What round 1's experiment (planes split by a separate pass, 128x128 tiles) taught: six bf16 planes
