@@ -14,7 +14,6 @@
 #include <cstdlib>
 #include <iterator>
 
-
 namespace omnitok {
 
 struct DevTensor {
@@ -149,8 +148,15 @@ namespace omnitok {
 
 constexpr int N_BOUND_LAUNCHES = 64;  // row-statistics launches with ranges per encode / decode
 
-// process defaults of the per-engine modes (omnitok_set_option; engine_run.hip)
+// every option global the engine reads (omnitok_set_option): the process defaults of the per-engine modes and the data-flow
+// switches, defined in engine_run.hip (g_vq_screen: vq.hip)
 extern int g_gemm_mode, g_attn_mode, g_attn_vpack, g_gemm_pl, g_pl_min_tokens, g_temporal_chunk, g_prevq_fuse, g_vq_screen, g_temporal_fused;
+extern int g_qkv_pl, g_attn_window_mode;
+
+// plane operands (gemm_pl.h) are stored as blocks of 64 rows x 32 k: 8 KiB each (fp16 hi|lo), k blocks of a row block adjacent
+constexpr int64_t PL_BLOCK_BYTES = 8192;
+inline int64_t pl_row_offset(int64_t row0, int K) { return (row0 / 64) * (int64_t)(K / 32) * PL_BLOCK_BYTES; }  // bytes; row0 % 64 == 0
+inline int64_t pad256(int64_t rows) { return (rows + 255) / 256 * 256; }  // plane operands are read in whole 256-row tiles
 
 Geo geometry(const omnitok_config &c);
 bool walk_enc_grid(const char *block, int *gh, int *gw, int64_t *peak);
@@ -178,12 +184,27 @@ float *next_bounds(omnitok_engine *e);
 struct VPack {  // packed-V output of the merged q|k|v launch (gemm_h2.hip): planes, first V column, sequence shape, |v| bound
     void *planes; int col0, n_tokens, heads; float bound; const float *bound_dev;
 };
-int eg_gemm(omnitok_engine *e, const float *a, int64_t lda, const float *w, int64_t ldw, const float *bias,
-            const float *residual, int64_t ldr, float *c, int64_t ldc, int64_t M, int N, int K, int flags,
-            int64_t rpg, int64_t gstride, int64_t goff, hipStream_t stream, ABound ab = ABound(),
-            const float *ln_stats = nullptr, const float *ln_g = nullptr, const float *ln_b = nullptr,
-            int ln_cols = 0, float ln_bound = 0.0f, float *c2 = nullptr, int64_t ldc2 = 0, int split_col = 0,
-            const VPack *vpk = nullptr, bool *vpacked = nullptr);
+// One nn.Linear of the engine on the GEMM kernel of its mode (fp16 split gemm_h2.hip | bf16 split gemm_x3.hip | fp32 MFMA
+// gemm.hip).  Fields are named as the omnitok_gemm* entry points name their parameters; what a call does not set is zero / null.
+struct EgGemm {
+    const float *a = nullptr, *w = nullptr, *bias = nullptr, *residual = nullptr;
+    int64_t lda = 0, ldw = 0, ldr = 0;
+    float *c = nullptr;
+    int64_t ldc = 0;
+    int64_t M = 0;
+    int N = 0, K = 0, flags = 0;
+    int64_t rpg = 0, gstride = 0, goff = 0;  // row groups of the output (patch embedding / to_pixels frame groups)
+    ABound ab;                               // range of the A operand (the fp16 split needs one)
+    const float *ln_stats = nullptr, *ln_g = nullptr, *ln_b = nullptr;  // LayerNorm applied while A is staged, columns [0, ln_cols)
+    int ln_cols = 0;
+    float ln_bound = 0.0f;
+    float *c2 = nullptr;  // columns [split_col, N) go to c2
+    int64_t ldc2 = 0;
+    int split_col = 0;
+    const VPack *vpk = nullptr;
+};
+// *vpacked is set when the launch wrote the V planes of g.vpk itself
+int eg_gemm(omnitok_engine *e, const EgGemm &g, hipStream_t stream, bool *vpacked = nullptr);
 // pre_vq fused behind the last norm_out of the encoder (omnitok_layernorm_prevq): z [L, 8] instead of LayerNorm rows in X
 struct PreVqFuse {
     const float *w, *b;

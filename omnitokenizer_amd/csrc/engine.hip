@@ -49,7 +49,7 @@ void workspace_widths(const omnitok_engine *e, int64_t (&wd)[8]) {
 int64_t workspace_bytes_for(const omnitok_engine *e, int64_t L) {
     int64_t wd[8], total = 0;
     workspace_widths(e, wd);
-    L = (L + 255) / 256 * 256;  // plane operands are read in whole 256-row tiles (gemm_pl.h)
+    L = pad256(L);  // plane operands are read in whole 256-row tiles (gemm_pl.h)
     for (int i = 0; i < 8; ++i) total += ((L * wd[i] * 4 + 255) / 256) * 256;
     return total;
 }
@@ -58,7 +58,7 @@ int ensure_workspace(omnitok_engine *e, int64_t L) {
     int64_t wd[8];
     workspace_widths(e, wd);
     const int64_t L_real = L;
-    L = (L + 255) / 256 * 256;
+    L = pad256(L);
     Buf *bufs[8] = {&e->X, &e->X2, &e->Y, &e->QKV, &e->AO, &e->HD, &e->Z, &e->ST};
     if (e->ext_ws) {  // slices of the caller's block, 256-byte aligned
         const int64_t need = workspace_bytes_for(e, L);
@@ -79,7 +79,6 @@ int ensure_workspace(omnitok_engine *e, int64_t L) {
         if (int rc = ensure(*bufs[i], L * wd[i])) return rc;
     return OMNITOK_OK;
 }
-
 
 }  // namespace omnitok
 
@@ -180,15 +179,20 @@ static int encode_tokens(omnitok_engine *e, const float *x, int B, int F, int H,
         const int64_t M = (int64_t)B * tt * S;
         const std::string n = names[i];
         const int K = e->pe_k[i], ld = e->pe_ld[i];
+        EgGemm pe;  // patches [M, ld] x pe_w^T + pe_b -> AO
+        pe.a = e->HD.p; pe.lda = ld;
+        pe.w = e->pe_w[i]; pe.ldw = ld;
+        pe.bias = e->pe_b[i];
+        pe.c = e->AO.p; pe.ldc = D;
+        pe.M = M; pe.N = D; pe.K = ld;
+        pe.flags = OMNITOK_GEMM_BIAS;
         // rows (b, t, s) of this frame group -> rows of the [B, T, S] token tensor
         const int64_t rpg = (int64_t)tt * S, gstride = (int64_t)T * S, goff = i ? S : 0;
         if (c.patch_embed_cnn) {
             // Conv3d with kernel == stride is im2col x W; eval-mode BatchNorm is folded into W, b
             OT_RUN("patchify_ln", ((double)M * K) * 8.0,
                    omnitok_patchify_ln(x, B, C, F, H, W_, f0, tt, pti, p, nullptr, nullptr, 0.0f, e->HD.p, ld, stream));
-            OT_RUN("gemm_patch", 2.0 * M * (double)K * D,
-                   eg_gemm(e, e->HD.p, ld, e->pe_w[i], ld, e->pe_b[i], nullptr, 0, e->AO.p, D, M, D, ld,
-                           OMNITOK_GEMM_BIAS, 0, 0, 0, stream));
+            OT_RUN("gemm_patch", 2.0 * M * (double)K * D, eg_gemm(e, pe, stream));
             // scatter the frame group into the token tensor (a strided row copy)
             for (int b = 0; b < B; ++b)
                 OT_HIP(hipMemcpyAsync(e->X.p + ((int64_t)b * gstride + goff) * D, e->AO.p + (int64_t)b * rpg * D,
@@ -198,9 +202,8 @@ static int encode_tokens(omnitok_engine *e, const float *x, int B, int F, int H,
         OT_RUN("patchify_ln", ((double)M * K) * 8.0,
                omnitok_patchify_ln(x, B, C, F, H, W_, f0, tt, pti, p, W(e, n + ".1.weight"), W(e, n + ".1.bias"), 1e-5f,
                                    e->HD.p, ld, stream));
-        OT_RUN("gemm_patch", 2.0 * M * (double)K * D,
-               eg_gemm(e, e->HD.p, ld, e->pe_w[i], ld, e->pe_b[i], nullptr, 0, e->AO.p, D, M, D, ld, OMNITOK_GEMM_BIAS,
-                       0, 0, 0, stream, ABound{e->pe_bound[i], nullptr, 0}));
+        pe.ab = ABound{e->pe_bound[i], nullptr, 0};
+        OT_RUN("gemm_patch", 2.0 * M * (double)K * D, eg_gemm(e, pe, stream));
         OT_RUN("layernorm", 2.0 * M * D * 4.0,
                omnitok_layernorm(e->AO.p, W(e, n + ".3.weight"), W(e, n + ".3.bias"), e->X.p, M, D, 1e-5f, rpg, gstride,
                                  goff, stream));
@@ -379,16 +382,25 @@ static int decode_latent(omnitok_engine *e, LatentKind kind, const void *latent,
         return OMNITOK_OK;
     }
     // ---- to_pixels (reference omnitokenizer.py:1006-1033, 1089-1096) -------------------------
-    OT_RUN("gemm_pixels", 2.0 * B * S * (double)K0 * D,
-           eg_gemm(e, e->X.p, D, e->px_w[0], D, e->px_b[0], nullptr, 0, e->HD.p, K0, (int64_t)B * S, K0, D,
-                   OMNITOK_GEMM_BIAS, S, (int64_t)T2 * S, 0, stream, ABound{e->dec_s.out_bound, nullptr, 0}));
+    EgGemm px;  // the first frame's tokens (rows [0, S) of every clip) x px_w[0]^T + px_b[0] -> HD
+    px.a = e->X.p; px.lda = D;
+    px.w = e->px_w[0]; px.ldw = D;
+    px.bias = e->px_b[0];
+    px.c = e->HD.p; px.ldc = K0;
+    px.M = (int64_t)B * S; px.N = K0; px.K = D;
+    px.flags = OMNITOK_GEMM_BIAS;
+    px.rpg = S; px.gstride = (int64_t)T2 * S; px.goff = 0;
+    px.ab = ABound{e->dec_s.out_bound, nullptr, 0};
+    OT_RUN("gemm_pixels", 2.0 * B * S * (double)K0 * D, eg_gemm(e, px, stream));
     OT_RUN("unpatchify", (double)B * S * K0 * 8.0,
            omnitok_unpatchify(e->HD.p, B, C, F, H, W_, 0, 1, 1, p, pixels_out, stream));
     if (T2 > 1) {
         const int64_t M1 = (int64_t)B * (T2 - 1) * S;
-        OT_RUN("gemm_pixels", 2.0 * M1 * (double)K1 * D,
-               eg_gemm(e, e->X.p, D, e->px_w[1], D, e->px_b[1], nullptr, 0, e->HD.p, K1, M1, K1, D, OMNITOK_GEMM_BIAS,
-                       (int64_t)(T2 - 1) * S, (int64_t)T2 * S, S, stream, ABound{e->dec_s.out_bound, nullptr, 0}));
+        px.w = e->px_w[1]; px.bias = e->px_b[1];  // ... and the other frames' (rows [S, T2 S)) x px_w[1]^T + px_b[1]
+        px.ldc = K1;
+        px.M = M1; px.N = K1;
+        px.rpg = (int64_t)(T2 - 1) * S; px.goff = S;
+        OT_RUN("gemm_pixels", 2.0 * M1 * (double)K1 * D, eg_gemm(e, px, stream));
         OT_RUN("unpatchify", (double)M1 * K1 * 8.0,
                omnitok_unpatchify(e->HD.p, B, C, F, H, W_, 1, T2 - 1, pt, p, pixels_out, stream));
     }
