@@ -896,6 +896,41 @@ int omnitok_lpips_layer(const float *feats, int N, int h, int w, int C, const fl
 /* val[n] = (float)((((res[n][0] + res[n][1]) + res[n][2]) + res[n][3]) + res[n][4]) in fp64 (LPIPS.forward's val). */
 int omnitok_lpips_finalize(const double *res, int N, float *val, omnitok_stream_t stream);
 
+/* ---- validation losses (csrc/losses.hip) ---------------------------------------------------------------------------------
+ * The sums behind the reference's VQGAN.forward(x) / validation_step (omnitokenizer.py:388-394, 372-377, 608-618;
+ * modules/codebook.py:93; INTEGRATION.md "validation losses").  Every summand is formed in fp32 with the reference's own
+ * sequence of roundings, widened and added in fp64; partial sums go to `work` and are combined in index order by a finalize
+ * kernel.  No atomics: for one shape on one device the result has the same bits in every call.  Operands are dense fp32;
+ * 16-byte loads are used where the base pointers are 16-byte aligned.  Validated on the host before any launch; no
+ * synchronisation. */
+enum { OMNITOK_LOSS_L1 = 1, OMNITOK_LOSS_MSE = 2, OMNITOK_LOSS_LAPLACE = 4 };
+
+/* Bytes of device workspace the three entry points below need for a batch of B items (-1: B outside [1, 65535]). */
+int64_t omnitok_losses_workspace(int B);
+
+/* x, x_recon [B][n] -> sums[B][3] fp64 (device), per item b, with d = x_recon - x:
+ *   [0] sum |d|                                              (F.l1_loss's summand)          OMNITOK_LOSS_L1
+ *   [1] sum rnd32(d * d)                                     (F.mse_loss's summand)         OMNITOK_LOSS_MSE
+ *   [2] sum |rnd32(rnd32(0.8f * rnd32(x + 0.5f)) + 0.1f) - the same of x_recon|  (logits_laplace, eps 0.1)
+ *                                                                                           OMNITOK_LOSS_LAPLACE
+ * A column not named in flags is 0.  total[3] (may be NULL): sums[0][k] + sums[1][k] + ... in index order.  Neither
+ * operand is written. */
+int omnitok_recon_losses(const float *x, const float *x_recon, int B, int64_t n, int flags, double *sums, double *total,
+                         void *work, size_t work_bytes, omnitok_stream_t stream);
+
+/* sum[0] = sum over tokens t < n_tokens and channels j < c of rnd32((z[t][j] - codebook[ids[t]][j])^2): the summand of
+ * F.mse_loss(z, embeddings) of Codebook.forward, the code row read inside the kernel (z token-major [n_tokens][c], what
+ * omnitok_encode's z_out holds; ids int64).  An id outside [0, n_codes) reads nothing and makes the sum NaN. */
+int omnitok_commitment_sum(const float *z, const int64_t *ids, const float *codebook, int64_t n_tokens, int c, int n_codes,
+                           double *sum, void *work, size_t work_bytes, omnitok_stream_t stream);
+
+/* moments [B][2][m] (item b: m means, then m log-variances; m = c T' h w of omnitok_encode_vae's moments_out) ->
+ * sums[B]: sum of rnd32(rnd32(rnd32(rnd32(mu * mu) + var) - 1.0f) - lv), lv = min(max(logvar, -30), 20), var = the
+ * correctly rounded fp32 exp(lv) (DiagonalGaussianDistribution.kl()'s summand; NaN stays NaN).  total[1] (may be NULL):
+ * the item sums added in index order. */
+int omnitok_kl_sum(const float *moments, int B, int64_t m, double *sums, double *total, void *work, size_t work_bytes,
+                   omnitok_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,6 +6,7 @@
     from omnitokenizer_amd import InceptionI3d, get_fvd_logits, frechet_distance      # FVD (omnitokenizer_amd.fvd)
     from omnitokenizer_amd import InceptionV3, load_fid_inception, compute_fid       # FID (omnitokenizer_amd.fid)
     from omnitokenizer_amd import LPIPS, load_lpips, lpips_frames                    # LPIPS (omnitokenizer_amd.lpips)
+    from omnitokenizer_amd import reconstruction_losses                              # validation losses (omnitokenizer_amd.losses)
 """
 from .config import OmniTokConfig, make_args  # noqa: F401
 
@@ -16,7 +17,7 @@ _FID_NAMES = ("load_fid_inception", "calculate_activation_statistics", "calculat
 
 __all__ = ["OmniTokenizer_VQGAN", "GPT", "OmniTokConfig", "make_args", "psnr_ssim", "calculate_psnr", "calculate_ssim",
            "InceptionI3d", "load_fvd_model", "get_fvd_logits", "frechet_distance", "compute_fvd",
-           "InceptionV3"] + list(_FID_NAMES) + ["LPIPS", "load_lpips", "lpips_frames"]
+           "InceptionV3"] + list(_FID_NAMES) + ["LPIPS", "load_lpips", "lpips_frames", "reconstruction_losses"]
 
 
 def __getattr__(name):
@@ -44,4 +45,7 @@ def __getattr__(name):
     if name in ("LPIPS", "load_lpips", "lpips_frames"):
         from . import lpips
         return getattr(lpips, name)
+    if name == "reconstruction_losses":
+        from . import losses
+        return losses.reconstruction_losses
     raise AttributeError(name)

@@ -179,6 +179,10 @@ _PROTOS = {
     "omnitok_lpips_workspace": [c_int, c_int, c_int],
     "omnitok_lpips_layer": [P, c_int, c_int, c_int, c_int, P, c_int, P, ctypes.c_size_t, P, P],
     "omnitok_lpips_finalize": [P, c_int, P, P],
+    "omnitok_losses_workspace": [c_int],
+    "omnitok_recon_losses": [P, P, c_int, I64, c_int, P, P, P, ctypes.c_size_t, P],
+    "omnitok_commitment_sum": [P, P, P, I64, c_int, c_int, P, P, ctypes.c_size_t, P],
+    "omnitok_kl_sum": [P, c_int, I64, P, P, P, ctypes.c_size_t, P],
     # include/omnitok_lm.h
     "omnitok_lm_create": [POINTER(OmnitokLmConfig), POINTER(P)],
     "omnitok_lm_destroy": [P],
@@ -232,7 +236,8 @@ _RESTYPES = {"omnitok_last_error": c_char_p, "omnitok_version": c_char_p,
              "omnitok_lm_destroy": None, "omnitok_comm_destroy": None, "omnitok_lm_cache_bytes": c_int64,
              "omnitok_pl_planes_bytes": c_int64, "omnitok_pl_unscale": c_float,
              "omnitok_frame_metrics_workspace": c_int64, "omnitok_same_pad": None,
-             "omnitok_conv3d_packed_ldw": c_int64, "omnitok_lpips_workspace": c_int64}
+             "omnitok_conv3d_packed_ldw": c_int64, "omnitok_lpips_workspace": c_int64,
+             "omnitok_losses_workspace": c_int64}
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)
 

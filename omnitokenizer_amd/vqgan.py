@@ -21,6 +21,7 @@ import torch.nn as nn
 
 from . import _lib
 from . import frames as _frames  # registers omnitok::frames_to_pixels / omnitok::pixels_to_frames
+from . import losses as _losses  # registers omnitok::recon_losses / commitment_sum / kl_sum
 from . import metrics as _metrics  # registers omnitok::frame_metrics
 from ._lib import OmnitokConfig, check
 from .config import OmniTokConfig
@@ -116,6 +117,15 @@ class OmniTokenizer_VQGAN(nn.Module):
         self.kl_weight = getattr(args, "kl_weight", 0.0)
         self.use_external_codebook = cfg.use_external_codebook
         self.l2_code = cfg.l2_code
+        # what forward(x) / validation_step weigh their terms with (reference omnitokenizer.py:86-94, 164, 199-207, 235-238)
+        self.l1_weight = getattr(args, "l1_weight", 4.0)
+        self.perceptual_weight = getattr(args, "perceptual_weight", 4.0)
+        self.logitslaplace_weight = getattr(args, "logitslaplace_weight", 0.)
+        self.recon_loss_type = getattr(args, "recon_loss_type", "l1")
+        self.apply_allframes = getattr(args, "apply_allframes", False)
+        self.gen_upscale = getattr(args, "gen_upscale", None)
+        self.resolution_scale = getattr(args, "resolution_scale", None)
+        self.perceptual_model = None   # set_perceptual_model(load_lpips(...)); not part of state_dict()
 
         for name, shape in path_state_spec(cfg).items():
             if name.endswith("relative_position_index"):
@@ -643,30 +653,25 @@ class OmniTokenizer_VQGAN(nn.Module):
                                  ctypes.c_void_p(out.data_ptr()), torch.cuda.current_stream().cuda_stream), "decode")
         return out
 
-    def forward(self, x, optimizer_idx=None, log_image=False):
-        """The inference use of reference VQGAN.forward (omnitokenizer.py:330-413,
-        `vqgan(x, log_image=True)` in vqgan_eval.py:119,187): returns
-        (frames, frames_recon, x, x_recon, vq_output) with vq_output carrying encodings/embeddings."""
+    def forward(self, x, optimizer_idx=None, log_image=False, *, noise=None, frame_idx=None):
+        """The inference uses of reference VQGAN.forward (omnitokenizer.py:330-413, 520-525):
+
+        forward(x, log_image=True)   `vqgan(x, log_image=True)` of vqgan_eval.py:119,187: returns
+            (frames, frames_recon, x, x_recon, vq_output) with vq_output carrying encodings/embeddings.
+        forward(x)                   what validation_step calls: returns (recon_loss, x_recon, vq_output, perceptual_loss),
+            see _forward_validation.  optimizer_idx 0 / 1 (the generator and discriminator steps) are training.
+
+        noise: the posterior noise of a use_vae model, as encode() takes it.  frame_idx: int64 [B], the frame of each clip the
+        perceptual loss looks at (default: drawn with torch.randint, omnitokenizer.py:401).  Both belong to the forward(x) path
+        only: with log_image=True either one raises ValueError."""
+        if log_image and (noise is not None or frame_idx is not None):
+            raise ValueError("forward: noise and frame_idx apply to forward(x) only, not to log_image=True")
         if not log_image:
-            raise NotImplementedError("training forward (losses, discriminators) is outside the built path")
+            if optimizer_idx is not None:
+                raise NotImplementedError("training forward (losses, discriminators) is outside the built path")
+            return self._forward_validation(x, noise, frame_idx)
         is_image = x.dim() == 4
-        if self.use_vae:
-            # reference omnitokenizer.py:366-370, 410-411: sample -> post_vq -> decoder, vq_output None
-            z = self.encode(x, is_image)
-            x_recon = self.decode(z if is_image else z.permute(0, 2, 3, 4, 1), is_image)
-        else:
-            stats = {}
-            if torch.cuda.is_current_stream_capturing():
-                # the statistics are part of this call's return value and advance host-side state (call_cnt): a captured graph
-                # would return nothing for them and its replays would not advance it (ADVICE r05).  encode() / decode() alone
-                # can be captured -- a replay then leaves codebook_usage where the capture found it.
-                raise RuntimeError("forward(log_image=True) returns codebook statistics and updates call_cnt on the host: it cannot "
-                                   "be recorded into a HIP graph (capture encode() / decode() instead)")
-            emb, ids = self.encode(x, is_image, include_embeddings=True, _stats_out=None if self.use_external_codebook else stats)
-            x_recon = self.decode(ids, is_image)
-            if not self.use_external_codebook and not stats:   # empty batch: no update happened, the statistics are those of no ids
-                z0 = torch.zeros(self.cfg.n_codes, device=x.device)
-                stats = dict(batch_usage=z0, perplexity=torch.ones((), device=x.device), avg_usage=self.codebook.codebook_usage.data.clone())
+        x_recon, vq_output, _ = self._reconstruct(x, is_image)
         if is_image:
             frames, frames_recon = x, x_recon
         else:
@@ -674,8 +679,33 @@ class OmniTokenizer_VQGAN(nn.Module):
             idx = torch.randint(0, T, [B], device=x.device).reshape(-1, 1, 1, 1, 1).repeat(1, C, 1, H, W)
             frames = torch.gather(x, 2, idx).squeeze(2)
             frames_recon = torch.gather(x_recon, 2, idx).squeeze(2)
+        return frames, frames_recon, x, x_recon, vq_output
+
+    _CAPTURE_MSG = ("forward(log_image=True) returns codebook statistics and updates call_cnt on the host: it cannot "
+                    "be recorded into a HIP graph (capture encode() / decode() instead)")
+
+    def _reconstruct(self, x, is_image, noise=None, want_moments=False):
+        """encoder -> quantiser (or posterior sample) -> decoder with ONE Codebook.forward's worth of state update:
+        (x_recon, vq_output, moments).  vq_output is None on a use_vae model, moments None unless asked for."""
         if self.use_vae:
-            return frames, frames_recon, x, x_recon, None
+            # reference omnitokenizer.py:366-370, 410-411: sample -> post_vq -> decoder, vq_output None
+            z = self.encode(x, is_image, noise=noise, return_moments=want_moments)
+            z, mom = z if want_moments else (z, None)
+            return self.decode(z if is_image else z.permute(0, 2, 3, 4, 1), is_image), None, mom
+        stats = {}
+        if torch.cuda.is_current_stream_capturing():
+            # the statistics are part of this call's return value and advance host-side state (call_cnt): a captured graph
+            # would return nothing for them and its replays would not advance it (ADVICE r05).  encode() / decode() alone
+            # can be captured -- a replay then leaves codebook_usage where the capture found it.
+            raise RuntimeError(self._CAPTURE_MSG)
+        if self.use_external_codebook:
+            emb, ids = self.encode(x, is_image, include_embeddings=True, _stats_out=None)
+        else:
+            emb, ids, z = self.encode(x, is_image, include_embeddings=True, return_latents=True, _stats_out=stats)
+        x_recon = self.decode(ids, is_image)
+        if not self.use_external_codebook and not stats:   # empty batch: no update happened, the statistics are those of no ids
+            z0 = torch.zeros(self.cfg.n_codes, device=x.device)
+            stats = dict(batch_usage=z0, perplexity=torch.ones((), device=x.device), avg_usage=self.codebook.codebook_usage.data.clone())
         # the statistics Codebook.forward returns next to the ids (reference codebook.py:122-143);
         # vqgan_eval.py:152,195 accumulates batch_usage
         if self.use_external_codebook:  # VectorQuantize keeps no usage state; it reports its (eval: zero) commitment loss
@@ -685,7 +715,147 @@ class OmniTokenizer_VQGAN(nn.Module):
             vq_output["perplexity"] = self._ext_perplexity(ids)
         else:
             vq_output = dict(embeddings=emb, encodings=ids, **stats)
-        return frames, frames_recon, x, x_recon, vq_output
+            # 0.25 * F.mse_loss(z, embeddings) (codebook.py:93): the fp64 sum / count rounded to fp32 once; the code rows are
+            # gathered inside the kernel
+            if z.numel():
+                total = _losses.commitment_sum(z, ids, self.codebook.embeddings.data)
+                vq_output["commitment_loss"] = _losses.mean_of(total[0], z.numel()).to(torch.float32) * 0.25
+            else:
+                vq_output["commitment_loss"] = torch.full((), float("nan"), device=x.device)
+        return x_recon, vq_output, None
+
+    def __setattr__(self, name, value):
+        if name == "perceptual_model":   # an attribute, never a submodule: off state_dict() / .to(), as load_state_dict leaves
+            object.__setattr__(self, name, value)   # perceptual_model.* out
+        else:
+            super().__setattr__(name, value)
+
+    def set_perceptual_model(self, model):
+        """The LPIPS forward(x) / validation_step score with: an omnitokenizer_amd.lpips.LPIPS, e.g.
+        load_lpips(device, checkpoint) for the checkpoint's own perceptual_model.* weights.  Returns self."""
+        from . import lpips as _lpips
+        if model is not None and not isinstance(model, _lpips.LPIPS):
+            raise TypeError(f"set_perceptual_model: expected an omnitokenizer_amd LPIPS (load_lpips), got {type(model).__name__}")
+        self.perceptual_model = model
+        return self
+
+    def _perceptual_loss(self, x, x_recon, is_image, shift=0.0, frame_idx=None):
+        """perceptual_model(frames, frames_recon) * perceptual_weight, [N, 1, 1, 1] fp32 (omnitokenizer.py:396-407, 520-523):
+        the images themselves, every frame in (b, t) order (apply_allframes), or frame frame_idx[b] of clip b (drawn with
+        torch.randint when None).  `shift` is added to both operands inside LPIPS's reads."""
+        from . import lpips as _lpips
+        model = self.perceptual_model
+        B, C = x.shape[:2]
+        T = 1 if is_image else x.shape[2]
+        if model is None:
+            N = B * T if (self.apply_allframes and not is_image) else B
+            return torch.zeros((N, 1, 1, 1), device=x.device, dtype=torch.float32)
+        if is_image:
+            d = _lpips.lpips_frames(x, x_recon, model, layout="nchw", shift=shift, max_pairs=model.max_pairs)
+        elif self.apply_allframes:
+            d = _lpips.lpips_frames(x, x_recon, model, layout="bcthw", shift=shift, max_pairs=model.max_pairs)
+        else:
+            if frame_idx is None:
+                frame_idx = torch.randint(0, T, [B], device=x.device)
+            H, W = x.shape[-2:]
+            idx = frame_idx.to(x.device).reshape(-1, 1, 1, 1, 1).repeat(1, C, 1, H, W)
+            frames = torch.gather(x, 2, idx).squeeze(2)
+            frames_recon = torch.gather(x_recon, 2, idx).squeeze(2)
+            d = _lpips.lpips_frames(frames, frames_recon, model, layout="nchw", shift=shift, max_pairs=model.max_pairs)
+        return d.reshape(-1, 1, 1, 1) * self.perceptual_weight
+
+    def _forward_validation(self, x, noise, frame_idx):
+        """reference omnitokenizer.py:357-407, 520-525, the branch validation_step runs (optimizer_idx None, log_image False):
+        (recon_loss, x_recon, vq_output, perceptual_loss).
+
+        recon_loss       0-dim fp32: l1 * l1_weight, or (recon_loss_type != 'l1') mse * l1_weight + logits_laplace *
+                         logitslaplace_weight; each mean is the fp64 sum of the fp32 summands / count, rounded to fp32 once
+        x_recon          the reconstruction; on the non-l1 path shifted by +0.5, as the reference's logits_laplace leaves it
+                         (in place there, also in the caller's x -- here x is NOT modified)
+        vq_output        forward(log_image=True)'s dict (one codebook-state update) with commitment_loss; on a use_vae model
+                         {"commitment_loss": kl_loss}, kl_loss = 0.5 * sum / B * kl_weight
+        perceptual_loss  [N, 1, 1, 1] fp32, un-reduced: perceptual_model(frames, frames_recon) * perceptual_weight over every
+                         frame in (b, t) order (apply_allframes), one drawn frame per clip, or the images themselves"""
+        from . import lpips as _lpips
+        if self.resolution_scale is not None:
+            raise NotImplementedError("resolution_scale (a random training-time resize, omnitokenizer.py:334-355) is outside "
+                                      "the built path")
+        if not isinstance(x, torch.Tensor) or x.dim() not in (4, 5):
+            raise ValueError(f"forward: x must be [B,C,H,W] or [B,C,F,H,W], got {getattr(x, 'shape', type(x))}")
+        if x.dtype != torch.float32:
+            raise TypeError(f"forward: x: dtype {x.dtype}, expected torch.float32")
+        if x.device != self.device:
+            raise RuntimeError(f"input on {x.device}, model on {self.device}")
+        model = self.perceptual_model
+        if model is None and self.perceptual_weight > 0:
+            raise RuntimeError("forward(x) needs the perceptual model (perceptual_weight > 0): assign model.perceptual_model or "
+                               "call set_perceptual_model(load_lpips(device, checkpoint)) -- load_state_dict leaves "
+                               "perceptual_model.* out")
+        if model is not None and not isinstance(model, _lpips.LPIPS):
+            raise TypeError(f"perceptual_model must be an omnitokenizer_amd LPIPS (load_lpips), got {type(model).__name__}")
+        is_image = x.dim() == 4
+        B, C = x.shape[:2]
+        T = 1 if is_image else x.shape[2]
+        if frame_idx is not None:
+            if is_image:
+                raise ValueError("forward: frame_idx applies to videos only")
+            if not isinstance(frame_idx, torch.Tensor) or frame_idx.dtype != torch.int64 or tuple(frame_idx.shape) != (B,):
+                raise ValueError(f"forward: frame_idx must be an int64 tensor [{B}]")
+        if self.device.type != "cuda":
+            raise RuntimeError(f"OmniTokenizer_VQGAN is on {self.device}: move it to the GPU (.to('cuda')). The MI355X HIP "
+                               "path is the only implementation; there is no CPU fallback.")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(self._CAPTURE_MSG)
+        with torch.no_grad(), torch.cuda.device(self.device):
+            x = x.contiguous()
+            x_recon, vq_output, mom = self._reconstruct(x, is_image, noise=noise, want_moments=self.use_vae)
+            if self.use_vae:
+                _, total = _losses.kl_sums(mom)
+                vq_output = {"commitment_loss": _losses.mean_of(0.5 * total[0], mom.shape[0]).to(torch.float32) * self.kl_weight}
+            if x.shape != x_recon.shape:   # omnitokenizer.py:379-386
+                if self.gen_upscale is None:
+                    raise ValueError(f"x {tuple(x.shape)} and its reconstruction {tuple(x_recon.shape)} differ in shape "
+                                     "without gen_upscale")
+                import torch.nn.functional as F_
+                x4 = x if is_image else x.permute(0, 2, 1, 3, 4).reshape(B * T, C, *x.shape[-2:])
+                x4 = F_.interpolate(x4, scale_factor=self.gen_upscale, mode="bilinear", align_corners=True)
+                x = x4 if is_image else x4.reshape(B, T, C, *x4.shape[-2:]).permute(0, 2, 1, 3, 4).contiguous()
+                if x.shape != x_recon.shape:
+                    raise ValueError(f"the resized x {tuple(x.shape)} and x_recon {tuple(x_recon.shape)} differ in shape")
+            n = x.numel()
+            l1_path = self.recon_loss_type == "l1"
+            _, total = _losses.recon_sums(x, x_recon, _losses.FLAG_L1 if l1_path else _losses.FLAG_MSE | _losses.FLAG_LAPLACE)
+            mean = _losses.mean_of(total, n).to(torch.float32)
+            if l1_path:
+                recon_loss = mean[0] * self.l1_weight
+                shift = 0.0
+            else:
+                recon_loss = mean[1] * self.l1_weight
+                recon_loss = recon_loss + mean[2] * self.logitslaplace_weight
+                shift = 0.5   # logits_laplace's in-place x += 0.5, x_recons += 0.5: what the reference's LPIPS then sees
+            perceptual_loss = self._perceptual_loss(x, x_recon, is_image, shift, frame_idx)
+            if not l1_path:
+                x_recon.add_(0.5)   # this call's own tensor; the caller's x stays as it was
+        return recon_loss, x_recon, vq_output, perceptual_loss
+
+    def validation_step(self, batch, batch_idx):
+        """reference omnitokenizer.py:608-618: forward(batch['video']) and the scalars it logs, returned as a dict (and
+        passed to self.log(name, value) when the instance has one): val/recon_loss, val/perceptual_loss (the mean of the
+        un-reduced tensor, what Lightning's log records) and val/perplexity, val/commitment_loss -- or val/kl_loss on a
+        use_vae model."""
+        x = batch["video"]
+        recon_loss, _, vq_output, perceptual_loss = self.forward(x)
+        out = {"val/recon_loss": recon_loss, "val/perceptual_loss": perceptual_loss.mean()}
+        if not self.use_vae:
+            out["val/perplexity"] = vq_output["perplexity"]
+            out["val/commitment_loss"] = vq_output["commitment_loss"]
+        else:
+            out["val/kl_loss"] = vq_output["commitment_loss"]
+        log = getattr(self, "log", None)
+        if callable(log):
+            for name, value in out.items():
+                log(name, value)
+        return out
 
     @staticmethod
     def _ext_perplexity(ids):
