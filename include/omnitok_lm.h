@@ -81,6 +81,34 @@ int omnitok_lm_prefill_ex(omnitok_lm *lm, const int64_t *idx, int T_tok, const f
                           const float *pos_extra, int32_t *pos, int32_t *cache_len, int B,
                           float *logits_out, omnitok_stream_t stream);
 
+/* Token cross-entropy and top-1 / top-5 hits of the reference's validation step (lm_transformer.py:308-321: F.cross_entropy and
+ * utils.accuracy(topk=(1, 5))) in ONE read of the logits (csrc/lm_loss.hip).  logits [N, V] fp32 with row stride ld >= V (rows
+ * need not be 16-byte aligned), targets int64 [N].  Per row i with t = targets[i]:
+ *   t < 0    ignored: nll[i] = 0, rank[i] = -1, counted in no sum;
+ *   t >= V   invalid: nll[i] = NaN, rank[i] = V, counted (the loss becomes NaN; nothing is read out of bounds);
+ *   else     nll[i] = (m + log s) - l_t with m = max_j l_j, s = sum_j exp(l_j - m) in fp32;
+ *            rank[i] = #{j : l_j > l_t} + #{j < t : l_j == l_t}: how many entries come before the target in a descending
+ *            order with the lowest index first among equals (omnitok_lm_select's argmax convention).
+ * sums[4] double = { sum of nll over the counted rows, counted rows, rows with rank == 0, rows with 0 <= rank < 5 }, added in
+ * fp64 in a fixed order through `work` (no atomics: two calls give equal bits).  1 <= N <= 2^31, V >= 1; the grids are sized
+ * from the CU count.  work: omnitok_lm_token_ce_workspace(N) bytes (-1 for an N outside the range), 8-byte aligned. */
+int64_t omnitok_lm_token_ce_workspace(int64_t N);
+int omnitok_lm_token_ce(const float *logits, int64_t ld, const int64_t *targets, int64_t N, int V, float *nll, int32_t *rank,
+                        double *sums, void *work, int64_t work_bytes, omnitok_stream_t stream);
+
+/* omnitok_lm_prefill_ex without the [B, T, vocab] logits tensor: the same layers, then ln_f, the head GEMM and the token
+ * cross-entropy above over blocks of R rows into a grow-only R x vocab workspace; R = option "lm_loss_chunk_rows" (default 2048:
+ * an UNMEASURED guess that keeps a block's logits inside the Infinity Cache).  With R >= B * T the head is the one GEMM call of
+ * omnitok_lm_prefill_ex and every output equals omnitok_lm_token_ce on its logits bit for bit.  targets [B, T] int64 (< 0 =
+ * ignored position); nll / rank [B, T] are optional (NULL: kept in the engine's workspace); sums [4] double as above, reduced once
+ * over all B * T rows.  A block whose rows are all ignored skips its GEMM: the targets are copied to the host first, so the call
+ * synchronises the stream once (and cannot be captured in a graph).  Fills the K/V cache like the prefill. */
+int omnitok_lm_prefill_loss(omnitok_lm *lm, const int64_t *idx, int T_tok, const float *emb, int T_emb,
+                            const float *pos_extra, const int64_t *targets, int32_t *pos, int32_t *cache_len, int B,
+                            float *nll, int32_t *rank, double *sums, omnitok_stream_t stream);
+/* bytes of the engine's loss workspace (the R x vocab logits block, per-row nll / rank, the reduction's partials) */
+int64_t omnitok_lm_loss_workspace_bytes(omnitok_lm *lm);
+
 /* Token selection of the sampling loops (gpt.py:347-357; CFG blend :428-431) for B streams, one workgroup each:
  *   v = logits / temperature,  or with logits_uncond:  v = cfg_c1 * (logits / T) - cfg_c2 * (logits_uncond / T)
  *   (cfg_c1 = 1 + t, cfg_c2 = t as fp32, the reference's roundings);

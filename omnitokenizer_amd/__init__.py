@@ -7,6 +7,7 @@
     from omnitokenizer_amd import InceptionV3, load_fid_inception, compute_fid       # FID (omnitokenizer_amd.fid)
     from omnitokenizer_amd import LPIPS, load_lpips, lpips_frames                    # LPIPS (omnitokenizer_amd.lpips)
     from omnitokenizer_amd import reconstruction_losses                              # validation losses (omnitokenizer_amd.losses)
+    from omnitokenizer_amd import token_cross_entropy                                # LM validation (omnitokenizer_amd.lm_losses)
 """
 from .config import OmniTokConfig, make_args  # noqa: F401
 
@@ -17,7 +18,8 @@ _FID_NAMES = ("load_fid_inception", "calculate_activation_statistics", "calculat
 
 __all__ = ["OmniTokenizer_VQGAN", "GPT", "OmniTokConfig", "make_args", "psnr_ssim", "calculate_psnr", "calculate_ssim",
            "InceptionI3d", "load_fvd_model", "get_fvd_logits", "frechet_distance", "compute_fvd",
-           "InceptionV3"] + list(_FID_NAMES) + ["LPIPS", "load_lpips", "lpips_frames", "reconstruction_losses"]
+           "InceptionV3"] + list(_FID_NAMES) + ["LPIPS", "load_lpips", "lpips_frames", "reconstruction_losses",
+                                           "token_cross_entropy"]
 
 
 def __getattr__(name):
@@ -48,4 +50,7 @@ def __getattr__(name):
     if name == "reconstruction_losses":
         from . import losses
         return losses.reconstruction_losses
+    if name == "token_cross_entropy":
+        from . import lm_losses
+        return lm_losses.token_cross_entropy
     raise AttributeError(name)

@@ -195,6 +195,10 @@ _PROTOS = {
     "omnitok_lm_prefill": [P, P, P, P, c_int, c_int, P, P],
     "omnitok_lm_step_ex": [P, P, P, P, P, P, c_int, P, c_int, P],
     "omnitok_lm_prefill_ex": [P, P, c_int, P, c_int, P, P, P, c_int, P, P],
+    "omnitok_lm_token_ce_workspace": [I64],
+    "omnitok_lm_token_ce": [P, I64, P, I64, c_int, P, P, P, P, I64, P],
+    "omnitok_lm_prefill_loss": [P, P, c_int, P, c_int, P, P, P, P, c_int, P, P, P, P],
+    "omnitok_lm_loss_workspace_bytes": [P],
     "omnitok_lm_select": [P, P, c_int, c_int, c_float, c_float, c_float, c_int, c_float, c_int, P, P, P, P, P],
     "omnitok_lm_gemv": [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P],
     "omnitok_lm_attn_decode": [P, P, P, P, c_int, c_int, c_int, c_int, P, P, P],
@@ -237,7 +241,8 @@ _RESTYPES = {"omnitok_last_error": c_char_p, "omnitok_version": c_char_p,
              "omnitok_pl_planes_bytes": c_int64, "omnitok_pl_unscale": c_float,
              "omnitok_frame_metrics_workspace": c_int64, "omnitok_same_pad": None,
              "omnitok_conv3d_packed_ldw": c_int64, "omnitok_lpips_workspace": c_int64,
-             "omnitok_losses_workspace": c_int64}
+             "omnitok_losses_workspace": c_int64, "omnitok_lm_token_ce_workspace": c_int64,
+             "omnitok_lm_loss_workspace_bytes": c_int64}
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)
 

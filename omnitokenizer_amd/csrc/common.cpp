@@ -91,6 +91,7 @@ extern int g_lm_mfma_mult;
 extern int g_lm_ks_deep;
 extern int g_lm_attn_short;
 extern int g_lm_attn_waves;
+extern int g_lm_loss_chunk_rows;
 }  // namespace omnitok
 
 extern "C" int omnitok_set_option(const char *name, int value) {
@@ -129,6 +130,10 @@ extern "C" int omnitok_set_option(const char *name, int value) {
     else if (!strcmp(name, "lm_ks_deep")) omnitok::g_lm_ks_deep = value;
     else if (!strcmp(name, "lm_attn_short")) omnitok::g_lm_attn_short = value;
     else if (!strcmp(name, "lm_attn_waves")) omnitok::g_lm_attn_waves = value;
+    else if (!strcmp(name, "lm_loss_chunk_rows")) {
+        OT_CHECK_ARG(value >= 1, "set_option: lm_loss_chunk_rows %d, expected at least 1", value);
+        omnitok::g_lm_loss_chunk_rows = value;
+    }
     else if (!strcmp(name, "h2_dbg")) omnitok::g_h2_dbg = value;
     else if (!strcmp(name, "h2_tile")) omnitok::g_h2_tile = value;
     else if (!strcmp(name, "x3_dbg")) omnitok::g_x3_dbg = value;
@@ -160,6 +165,7 @@ extern "C" int omnitok_get_option(const char *name, int *value) {
     else if (!strcmp(name, "lm_ks_deep")) *value = omnitok::g_lm_ks_deep;
     else if (!strcmp(name, "lm_attn_short")) *value = omnitok::g_lm_attn_short;
     else if (!strcmp(name, "lm_attn_waves")) *value = omnitok::g_lm_attn_waves;
+    else if (!strcmp(name, "lm_loss_chunk_rows")) *value = omnitok::g_lm_loss_chunk_rows;
     else {
         omnitok::set_error("get_option: %s is not a readable option", name);
         return OMNITOK_ERR_INVALID;

@@ -49,6 +49,13 @@ int current_device_cus(int *n_cu);
 // replays (ROCm 7.2, tests/test_gpu_e2e.py::test_hip_graph_capture_and_side_stream), kernel nodes do not.
 int device_fill_u32(void *ptr, unsigned value, int64_t n_words, hipStream_t stream);
 
+// csrc/lm_loss.hip, the two halves of omnitok_lm_token_ce as omnitok_lm_prefill_loss chains them: per-row nll / rank of a block of
+// rows, and the ordered reduction of all rows to sums[4] (work: omnitok_lm_token_ce_workspace bytes)
+int lm_token_ce_rows(const float *logits, int64_t ld, const int64_t *targets, int64_t N, int V, float *nll, int32_t *rank,
+                     hipStream_t stream);
+int lm_token_ce_reduce(const float *nll, const int32_t *rank, int64_t N, int V, double *sums, void *work, int64_t work_bytes,
+                       hipStream_t stream);
+
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 

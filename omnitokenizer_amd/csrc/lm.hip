@@ -19,6 +19,7 @@
 #include "gemm_x_common.h"  // gelu_erf, x3_rsrc
 #include "../../include/omnitok_lm.h"
 
+#include <algorithm>
 #include <map>
 #include <string>
 #include <vector>
@@ -1093,6 +1094,7 @@ int g_lm_attn_waves = 8;  // "lm_attn_waves": 8 = a wave owns 32 keys of the 256
 int g_lm_attn_short = 1;  // "lm_attn_short": 1 = 128-key attention chunks for caches of up to 4096 tokens (read at omnitok_lm_alloc_cache) | 0 = 256
 int g_lm_ks_deep = 0;   // "lm_ks_deep": weights in flight per wave of the K-sliced GEMV: 1 = 16 KiB | 0 = 8 KiB
 int g_lm_ksliced = 2;  // "lm_ksliced": 2 = lm_gemv_ks_kernel for K in {1536, 2048, 6144, 8192} | 1 = only for B <= 2 | 0 = lm_gemv_kernel
+int g_lm_loss_chunk_rows = 2048;  // "lm_loss_chunk_rows": rows per head-GEMM block of omnitok_lm_prefill_loss (a guess, not measured)
 int g_lm_balance = 1;  // "lm_balance": 1 = waves per workgroup and rows per wave chosen so that every CU gets the same number of
                        // workgroups | 0 = 4 waves, 1 row (N <= 2048) or 2 rows per wave
 
@@ -1340,6 +1342,11 @@ struct omnitok_lm {
     // grow-only prefill workspace (rows = B * T)
     float *pf = nullptr;
     int64_t pf_floats = 0;
+    // grow-only workspace of omnitok_lm_prefill_loss: a block of logits rows; nll [rows] | rank [rows] | reduction partials
+    float *lg = nullptr;
+    int64_t lg_floats = 0;
+    float *ce = nullptr;
+    int64_t ce_rows = 0, ce_bytes = 0;
 };
 
 static const float *LW(omnitok_lm *lm, const std::string &k) {
@@ -1386,8 +1393,8 @@ extern "C" int omnitok_lm_create(const omnitok_lm_config *cfg, omnitok_lm **out)
 }
 
 static void lm_free_cache(omnitok_lm *lm) {
-    lm->pf_floats = 0;
-    for (float **p : {&lm->kv, &lm->x, &lm->qkv, &lm->att, &lm->hid, &lm->part, &lm->pf})
+    lm->pf_floats = lm->lg_floats = lm->ce_rows = lm->ce_bytes = 0;
+    for (float **p : {&lm->kv, &lm->x, &lm->qkv, &lm->att, &lm->hid, &lm->part, &lm->pf, &lm->lg, &lm->ce})
         if (*p) {
             (void)hipFree(*p);
             *p = nullptr;
@@ -1592,14 +1599,13 @@ extern "C" int omnitok_lm_prefill(omnitok_lm *lm, const int64_t *idx, int32_t *p
     return omnitok_lm_prefill_ex(lm, idx, T, nullptr, 0, nullptr, pos, cache_len, B, logits_out, stream_);
 }
 
-extern "C" int omnitok_lm_prefill_ex(omnitok_lm *lm, const int64_t *idx, int T_tok, const float *emb, int T_emb,
-                                     const float *pos_extra, int32_t *pos, int32_t *cache_len, int B,
-                                     float *logits_out, omnitok_stream_t stream_) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    OT_CHECK_ARG(lm, "lm_prefill: null engine");
-    OT_CHECK_ARG(T_tok >= 0 && T_emb >= 0, "lm_prefill: negative length");
+// Embedding and the n_layer blocks of a batched prefill, shared by omnitok_lm_prefill_ex and omnitok_lm_prefill_loss: checks the
+// arguments, grows the workspace, fills the K/V cache; *x_out [M, C] is the residual stream after the last block, *xn_out [M, C]
+// scratch for its ln_f.  B * T > 0.
+static int lm_prefill_layers(omnitok_lm *lm, const int64_t *idx, int T_tok, const float *emb, int T_emb,
+                             const float *pos_extra, int32_t *pos, int32_t *cache_len, int B, hipStream_t stream,
+                             float **x_out, float **xn_out) {
     const int T = T_tok + T_emb;
-    if (B == 0 || T == 0) return OMNITOK_OK;
     OT_CHECK_ARG((idx || T_tok == 0) && (emb || T_emb == 0) && pos && cache_len, "lm_prefill: null pointer");
     if (!lm->finalized) {
         set_error("lm_prefill: engine not finalised (load the weights first)");
@@ -1657,15 +1663,94 @@ extern "C" int omnitok_lm_prefill_ex(omnitok_lm *lm, const int64_t *idx, int T_t
         OT_LAUNCH_CHECK("lm_gelu");
         if (int rc = omnitok_gemm(hid, 4 * C, L.w2, 4 * C, L.b2, x, C, x, C, M, C, 4 * C, BR, 0, 0, 0, stream)) return rc;
     }
-    if (logits_out) {
-        hipLaunchKernelGGL(lm_layernorm_rows_kernel, ln_grid, dim3(256), 0, stream, x, LW(lm, "ln_f.weight"),
-                           LW(lm, "ln_f.bias"), xn, M, C);
-        OT_LAUNCH_CHECK("lm_layernorm_rows");
-        if (int rc = omnitok_gemm(xn, C, LW(lm, "head.weight"), C, nullptr, nullptr, 0, logits_out, V, M, V, C, 0, 0, 0, 0,
-                                  stream))
-            return rc;
-    }
+    *x_out = x;
+    *xn_out = xn;
+    return OMNITOK_OK;
+}
+
+// logits [rows, V] = head(ln_f(x [rows, C])); xn: scratch [rows, C]
+static int lm_head_rows(omnitok_lm *lm, const float *x, float *xn, int64_t rows, float *logits, hipStream_t stream) {
+    const int C = lm->cfg.n_embd, V = lm->cfg.vocab_size;
+    hipLaunchKernelGGL(lm_layernorm_rows_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, x,
+                       LW(lm, "ln_f.weight"), LW(lm, "ln_f.bias"), xn, rows, C);
+    OT_LAUNCH_CHECK("lm_layernorm_rows");
+    return omnitok_gemm(xn, C, LW(lm, "head.weight"), C, nullptr, nullptr, 0, logits, V, rows, V, C, 0, 0, 0, 0, stream);
+}
+
+extern "C" int omnitok_lm_prefill_ex(omnitok_lm *lm, const int64_t *idx, int T_tok, const float *emb, int T_emb,
+                                     const float *pos_extra, int32_t *pos, int32_t *cache_len, int B,
+                                     float *logits_out, omnitok_stream_t stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    OT_CHECK_ARG(lm, "lm_prefill: null engine");
+    OT_CHECK_ARG(T_tok >= 0 && T_emb >= 0, "lm_prefill: negative length");
+    const int T = T_tok + T_emb;
+    if (B == 0 || T == 0) return OMNITOK_OK;
+    float *x = nullptr, *xn = nullptr;
+    if (int rc = lm_prefill_layers(lm, idx, T_tok, emb, T_emb, pos_extra, pos, cache_len, B, stream, &x, &xn)) return rc;
+    if (logits_out)
+        if (int rc = lm_head_rows(lm, x, xn, (int64_t)B * T, logits_out, stream)) return rc;
     hipLaunchKernelGGL(lm_set_len_kernel, dim3(1), dim3(64), 0, stream, pos, cache_len, B, T);
     OT_LAUNCH_CHECK("lm_set_len");
     return OMNITOK_OK;
+}
+
+extern "C" int omnitok_lm_prefill_loss(omnitok_lm *lm, const int64_t *idx, int T_tok, const float *emb, int T_emb,
+                                       const float *pos_extra, const int64_t *targets, int32_t *pos, int32_t *cache_len,
+                                       int B, float *nll, int32_t *rank, double *sums, omnitok_stream_t stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    OT_CHECK_ARG(lm, "lm_prefill_loss: null engine");
+    OT_CHECK_ARG(T_tok >= 0 && T_emb >= 0 && B >= 0, "lm_prefill_loss: negative length");
+    OT_CHECK_ARG(targets && sums, "lm_prefill_loss: null pointer (targets / sums)");
+    OT_CHECK_ARG((reinterpret_cast<uintptr_t>(targets) & 7) == 0 && (reinterpret_cast<uintptr_t>(sums) & 7) == 0,
+                 "lm_prefill_loss: targets / sums are not 8-byte aligned");
+    const int T = T_tok + T_emb;
+    OT_CHECK_ARG(B > 0 && T > 0, "lm_prefill_loss: no rows (B %d, T %d)", B, T);
+    const int64_t M = (int64_t)B * T, V = lm->cfg.vocab_size, C = lm->cfg.n_embd;
+    OT_CHECK_ARG(M <= 65535, "lm_prefill_loss: B * T = %lld rows (max 65535)", (long long)M);
+    OT_CHECK_ARG(g_lm_loss_chunk_rows >= 1, "lm_prefill_loss: option lm_loss_chunk_rows = %d", g_lm_loss_chunk_rows);
+    const int64_t R = std::min<int64_t>(g_lm_loss_chunk_rows, M);
+    float *x = nullptr, *xn = nullptr;
+    if (int rc = lm_prefill_layers(lm, idx, T_tok, emb, T_emb, pos_extra, pos, cache_len, B, stream, &x, &xn)) return rc;
+    // workspaces (grow-only)
+    if (lm->lg_floats < R * V) {
+        if (lm->lg) OT_HIP(hipFree(lm->lg));
+        lm->lg = nullptr;
+        lm->lg_floats = 0;
+        OT_HIP(hipMalloc(reinterpret_cast<void **>(&lm->lg), (size_t)(R * V) * 4));
+        lm->lg_floats = R * V;
+    }
+    const int64_t red_bytes = omnitok_lm_token_ce_workspace(M);
+    if (lm->ce_rows < M) {
+        if (lm->ce) OT_HIP(hipFree(lm->ce));
+        lm->ce = nullptr;
+        lm->ce_rows = lm->ce_bytes = 0;
+        const int64_t rows8 = (M + 1) & ~(int64_t)1;  // keeps the partials 8-byte aligned
+        OT_HIP(hipMalloc(reinterpret_cast<void **>(&lm->ce), (size_t)(rows8 * 8 + red_bytes)));
+        lm->ce_rows = rows8;
+        lm->ce_bytes = rows8 * 8 + red_bytes;
+    }
+    float *nll_w = nll ? nll : lm->ce;
+    int32_t *rank_w = rank ? rank : reinterpret_cast<int32_t *>(lm->ce + lm->ce_rows);
+    void *red = lm->ce + 2 * lm->ce_rows;
+    // which blocks have a row that counts
+    std::vector<int64_t> tg((size_t)M);
+    OT_HIP(hipMemcpyAsync(tg.data(), targets, (size_t)M * 8, hipMemcpyDeviceToHost, stream));
+    OT_HIP(hipStreamSynchronize(stream));
+    for (int64_t r0 = 0; r0 < M; r0 += R) {
+        const int64_t rows = std::min(R, M - r0);
+        bool any = false;
+        for (int64_t i = r0; i < r0 + rows && !any; ++i) any = tg[(size_t)i] >= 0;
+        if (any)
+            if (int rc = lm_head_rows(lm, x + r0 * C, xn + r0 * C, rows, lm->lg, stream)) return rc;
+        // an all-ignored block: the kernel writes nll 0 / rank -1 from the targets alone and reads no logits
+        if (int rc = lm_token_ce_rows(lm->lg, V, targets + r0, rows, (int)V, nll_w + r0, rank_w + r0, stream)) return rc;
+    }
+    if (int rc = lm_token_ce_reduce(nll_w, rank_w, M, (int)V, sums, red, red_bytes, stream)) return rc;
+    hipLaunchKernelGGL(lm_set_len_kernel, dim3(1), dim3(64), 0, stream, pos, cache_len, B, T);
+    OT_LAUNCH_CHECK("lm_set_len");
+    return OMNITOK_OK;
+}
+
+extern "C" int64_t omnitok_lm_loss_workspace_bytes(omnitok_lm *lm) {
+    return lm ? lm->lg_floats * 4 + lm->ce_bytes : 0;
 }

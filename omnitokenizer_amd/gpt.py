@@ -340,6 +340,48 @@ class GPT(nn.Module):
         return out, loss
 
     @torch.no_grad()
+    def token_losses(self, idx, targets, embeddings=None, cbox=None, tbox=None):
+        """The validation numbers of forward(idx, embeddings, cbox=, tbox=) against targets [B, T] int64 (T = the sequence
+        with the embeddings prepended; a target < 0 is an ignored position) WITHOUT the [B, T, V] logits: the prefill's
+        layers, then ln_f, the head GEMM and the token cross-entropy over blocks of `lm_loss_chunk_rows` rows
+        (include/omnitok_lm.h omnitok_lm_prefill_loss).  Returns lm_losses.token_cross_entropy's dict
+        {"loss", "acc1", "acc5", "nll", "rank", "count"} with nll / rank [B, T].  One host synchronisation."""
+        from . import lm_losses
+        B, Tt = idx.shape
+        Te = 0 if embeddings is None else embeddings.shape[1]
+        T = Te + Tt
+        assert T <= self.block_size, "Cannot forward, model block size is exhausted."
+        if not isinstance(targets, torch.Tensor) or targets.dtype != torch.int64:
+            raise TypeError(f"token_losses: targets must be an int64 tensor, got {getattr(targets, 'dtype', type(targets).__name__)}")
+        if tuple(targets.shape) != (B, T):
+            raise ValueError(f"token_losses: targets must be [B, T] = {(B, T)}, got {tuple(targets.shape)}")
+        if B * T > 65535:
+            raise ValueError(f"token_losses: B * T = {B * T} rows, at most 65535 per call (the batched prefill's limit): "
+                             "split the batch")
+        if B * T == 0:
+            raise ValueError("token_losses: an empty sequence")
+        self._sync_engine()
+        emb = None if embeddings is None else self._f32(embeddings, (B, Te, self.n_embd), "embeddings")
+        extra = self.vtokens_position_embeddings(cbox, tbox)
+        if extra is not None:
+            extra = self._f32(extra, (B, T, self.n_embd), "vtokens position embeddings (cbox / tbox)")
+        self.reset_streams(B, T)
+        idx = idx.to(self.device).long().contiguous()
+        targets = targets.to(self.device).contiguous()
+        nll = torch.empty(B, T, device=self.device, dtype=torch.float32)
+        rank = torch.empty(B, T, device=self.device, dtype=torch.int32)
+        sums = torch.empty(4, device=self.device, dtype=torch.float64)
+        check(_lib.load().omnitok_lm_prefill_loss(self._engine, self._fp(idx), Tt, self._fp(emb), Te, self._fp(extra),
+                                                  self._fp(targets), ctypes.c_void_p(self._pos.data_ptr()),
+                                                  ctypes.c_void_p(self._len.data_ptr()), B, self._fp(nll), self._fp(rank),
+                                                  self._fp(sums), torch.cuda.current_stream().cuda_stream), "lm_prefill_loss")
+        return lm_losses.results(nll, rank, sums)
+
+    def loss_workspace_bytes(self) -> int:
+        """bytes of the engine's loss workspace (the block of logits rows of token_losses and its per-row buffers)"""
+        return 0 if self._engine is None else int(_lib.load().omnitok_lm_loss_workspace_bytes(self._engine))
+
+    @torch.no_grad()
     def forward_with_past(self, idx, embeddings=None, targets=None, past=None, past_length=None, cbox=None,
                           forward_uncond=False):
         """reference gpt.py:236-275.  past=None: idx [B, T] starts new streams (positions 0..T-1).

@@ -2,7 +2,8 @@
 object `transformer_eval.py` drives: a first-stage tokenizer (OmniTokenizer_VQGAN), a conditioning stage
 (Labelator / SOSProvider / Identity / a second tokenizer) and the GPT, with the reference's attribute names
 (`transformer`, `first_stage_model`, `cond_stage_model`, `first_stage_vocab_size`, `cond_stage_vocab_size`,
-`starts_with_sos`, `class_first`) and methods (`forward`, `encode_to_z`, `encode_to_c`, `sample`, `get_xc`).
+`starts_with_sos`, `class_first`) and methods (`forward`, `encode_to_z`, `encode_to_c`, `sample`, `get_xc`, `shared_step`,
+`validation_step`).
 
 All arithmetic runs in libomnitok.so through the two drop-in classes; this file is index bookkeeping (token
 offsets, sos / class prefixes) exactly as the reference does it.  Training-only members (optimizers, pkeep
@@ -167,10 +168,10 @@ class Net2NetTransformer(nn.Module):
             indices = indices.view(c.shape[0], -1)
         return quant_c, indices
 
-    @torch.no_grad()
-    def forward(self, x, c, cbox=None):
-        """reference lm_transformer.py:136-192 at inference (no pkeep corruption, no condition drop-out):
-        teacher-forced logits of the latent tokens and their targets."""
+    def _teacher_forced_sequence(self, x, c):
+        """reference lm_transformer.py:137-181 at inference (no pkeep corruption, no condition drop-out):
+        (cz_indices [B, prefix + 1 + n], z_indices [B, n] with the vocabulary offset, prefix_len) -- output i + prefix_len of
+        the transformer on cz_indices[:, :-1] predicts z_indices[:, i]."""
         is_image = x.ndim == 4
         _, z_indices = self.encode_to_z(x, is_image)
         _, c_indices = self.encode_to_c(c, is_image)
@@ -185,10 +186,43 @@ class Net2NetTransformer(nn.Module):
             z_indices = z_indices + self.cond_stage_vocab_size
             cz = torch.cat((c_indices, z_indices), 1)
             prefix_len = c_indices.shape[1] - 1
+        return cz, z_indices, prefix_len
+
+    @torch.no_grad()
+    def forward(self, x, c, cbox=None):
+        """reference lm_transformer.py:136-192 at inference (no pkeep corruption, no condition drop-out):
+        teacher-forced logits of the latent tokens and their targets."""
+        cz, z_indices, prefix_len = self._teacher_forced_sequence(x, c)
         logits, _ = self.transformer(cz[:, :-1], cbox=cbox)
         logits = logits[:, prefix_len:]
         assert logits.shape[1] == z_indices.shape[1]
         return logits, z_indices
+
+    @torch.no_grad()
+    def shared_step(self, batch, batch_idx):
+        """reference lm_transformer.py:308-321: (loss, acc1, acc5) of one batch -- F.cross_entropy and
+        accuracy(topk=(1, 5)) of forward's logits against its targets -- without the logits tensor: the conditioning
+        positions enter GPT.token_losses as ignored targets (-1)."""
+        x, c = self.get_xc(batch)
+        cbox = batch["cbox"] if _get(self.args, "vtokens_pos", False) else None
+        cz, z_indices, prefix_len = self._teacher_forced_sequence(x, c)
+        pad = torch.full((z_indices.shape[0], prefix_len), -1, dtype=torch.int64, device=z_indices.device)
+        targets = torch.cat((pad, z_indices.long()), 1)
+        assert targets.shape[1] == cz.shape[1] - 1
+        out = self.transformer.token_losses(cz[:, :-1], targets, cbox=cbox)
+        return out["loss"], out["acc1"], out["acc5"]
+
+    @torch.no_grad()
+    def validation_step(self, batch, batch_idx):
+        """reference lm_transformer.py:347-352: {"val/loss", "val/acc1", "val/acc5"}, each passed to self.log(name, value)
+        when the instance has one (a Lightning wrapper); the reference returns the loss alone and only logs the rest."""
+        loss, acc1, acc5 = self.shared_step(batch, batch_idx)
+        out = {"val/loss": loss, "val/acc1": acc1, "val/acc5": acc5}
+        log = getattr(self, "log", None)
+        if callable(log):
+            for k, v in out.items():
+                log(k, v)
+        return out
 
     @torch.no_grad()
     def sample(self, x, c, steps, temperature=1.0, sample=False, top_k=None, callback=lambda k: None):
