@@ -88,8 +88,7 @@ const char *omnitok_version(void);
  * 256-key attention chunk; "lm_attn_short" 1 (default, read by omnitok_lm_alloc_cache) 128-key chunks for caches of up to 4096
  * tokens | 0 always 256; "lm_ks_deep" 0 (default) 8 KiB | 1 16 KiB of weights in flight per wave of the K-sliced GEMV; "lm_mfma" 0 (default) | 1 groups of
  * 4 .. 8 streams on the fp32-MFMA GEMV (measured slower, profiles/r06_lm_mfma.txt); "lm_loss_chunk_rows" (default 2048, at least 1) rows per head-GEMM block of
- * omnitok_lm_prefill_loss; "x3_dbg" / "h2_dbg" select
- * wrong-result ablation builds (tools/x3_ablate.py, tools/h2_bench.py).  Unknown names return OMNITOK_ERR_INVALID. */
+ * omnitok_lm_prefill_loss.  Unknown names return OMNITOK_ERR_INVALID. */
 int omnitok_set_option(const char *name, int value);
 /* Reads the process default of a data-flow option ("gemm_mode", "attn_mode", "gemm_pl", "pl_min_tokens", "temporal_chunk",
  * "prevq_fuse", "pl_cfg", "pl_tail", "sp_small_blocks") or of a kernel choice of the LM decode step ("lm_wide_u", "lm_balance",

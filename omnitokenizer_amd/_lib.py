@@ -10,7 +10,7 @@ import os
 from ctypes import POINTER, Structure, c_char, c_char_p, c_float, c_int, c_int64, c_void_p
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-# OMNITOK_LIB: another build of the same library (measurement builds of tools/: ablation arms compiled with extra -D flags)
+# OMNITOK_LIB: another build of the same library (an experiment build compiled with extra flags, tools/ab_bench.sh)
 LIB_PATH = os.environ.get("OMNITOK_LIB") or os.path.join(HERE, "lib", "libomnitok.so")
 
 

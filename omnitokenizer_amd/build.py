@@ -43,8 +43,8 @@ NO_PACKED_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 # Its packed ops are plain pairs -- no op_sel / op_sel_hi broadcast, the only form that ever failed (variant E of the r05 table:
 # hand-written plain v_pk_fma_f32 chains, 90 / 90 launches right) -- and the scan below enforces exactly that for this file.
 PACKED_PLAIN_OK = {"peg.hip"}
-# measurement builds only (e.g. OMNITOK_EXTRA_FLAGS=-DOMNITOK_PL_MEASUREMENT_BUILDS for tools/pl_bench's ablation arms);
-# they are ADDED to the flags above, the ISA scan below stays on
+# OMNITOK_EXTRA_FLAGS: extra compiler flags for an experiment build (e.g. a -D of a local patch); they are ADDED to the flags
+# above, the ISA scan below stays on
 FLAGS += os.environ.get("OMNITOK_EXTRA_FLAGS", "").split()
 ISA_FORBIDDEN = re.compile(r"^\s*(v_pk_(?:fma|mul|add)_f32)\b", re.M)
 ISA_FORBIDDEN_OPSEL = re.compile(r"^\s*v_pk_(?:fma|mul|add)_f32\b[^\n]*\bop_sel", re.M)

@@ -551,9 +551,7 @@ __global__ __launch_bounds__(256, 2) void attn_spatial_h2p_kernel(AttnH2Params p
 //     LDS per workgroup and <= 168 registers: three workgroups per CU, so that a SIMD has three waves in different phases
 //     (one in its MFMA chain, the others in softmax / waiting on the barrier).
 // -------------------------------------------------------------------------------------------
-// DBG (measurement builds behind "attn_h2_dbg", wrong results): 1 no softmax arithmetic (P = S), 2 no S^T MFMAs, 4 no P.V MFMAs,
-// 8 no barrier / DMA wait in the tile loop, 16 no DMA in the tile loop, 32 no P split (lo = hi)
-template <bool HAS_BIAS, int SUBS, int DBG = 0, int MINB = (SUBS == 1 ? 3 : 2)>
+template <bool HAS_BIAS, int SUBS, int MINB = (SUBS == 1 ? 3 : 2)>
 __global__ __launch_bounds__(256, MINB) void attn_spatial_h2x_kernel(AttnH2Params p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_h2[];
     constexpr int TILE = SUBS * 16384;  // K (SUBS blocks of 8 KiB) | V (SUBS blocks)
@@ -615,7 +613,7 @@ __global__ __launch_bounds__(256, MINB) void attn_spatial_h2x_kernel(AttnH2Param
 
     for (int t = 0; t < ntiles; ++t) {
         const int buf = t & 1;
-        if ((DBG & 16) == 0 && t + 1 < ntiles) dma(t + 1, buf ^ 1);
+        if (t + 1 < ntiles) dma(t + 1, buf ^ 1);
         const unsigned char *Ks = smem_h2 + buf * TILE + hi * 512 + r32 * 16;
         const unsigned char *Vs = Ks + SUBS * 8192;
 
@@ -632,11 +630,6 @@ __global__ __launch_bounds__(256, MINB) void attn_spatial_h2x_kernel(AttnH2Param
             f32x16 st;
 #pragma unroll
             for (int r = 0; r < 16; ++r) st[r] = 0.0f;
-            if constexpr (DBG & 2) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) st[r] = __builtin_bit_cast(float, kf[r & 7][r >> 3] ^ qf[0][r & 3][r >> 2]) * 1e-30f;
-                return st;
-            }
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) {
                 const f16x8 kh = __builtin_bit_cast(f16x8, kf[ks]), kl = __builtin_bit_cast(f16x8, kf[4 + ks]);
@@ -657,26 +650,22 @@ __global__ __launch_bounds__(256, MINB) void attn_spatial_h2x_kernel(AttnH2Param
         };
         auto softmax = [&](f32x16 &st, f16x8 (&ph)[2], f16x8 (&pl)[2]) {
             float alpha = 1.0f;
-            if constexpr ((DBG & 1) == 0) {
-                float mx = fmaxf(fmaxf(st[0], st[1]), st[2]);
+            float mx = fmaxf(fmaxf(st[0], st[1]), st[2]);
 #pragma unroll
-                for (int r = 3; r < 15; r += 2) mx = fmaxf(fmaxf(mx, st[r]), st[r + 1]);
-                mx = halves_max(fmaxf(mx, st[15]));
-                const float m_new = fmaxf(m_run, mx);
-                const float mc = fmaf(m_new, cs, -P_SHIFT);
-                float ps = 0.0f;
+            for (int r = 3; r < 15; r += 2) mx = fmaxf(fmaxf(mx, st[r]), st[r + 1]);
+            mx = halves_max(fmaxf(mx, st[15]));
+            const float m_new = fmaxf(m_run, mx);
+            const float mc = fmaf(m_new, cs, -P_SHIFT);
+            float ps = 0.0f;
 #pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    st[r] = __builtin_amdgcn_exp2f(fmaf(st[r], cs, -mc));
-                    ps += st[r];
-                }
-                ps = halves_sum(ps);
-                alpha = __builtin_amdgcn_exp2f((m_run - m_new) * cs);
-                l_run = fmaf(l_run, alpha, ps);
-                m_run = m_new;
-            } else {
-                l_run += st[0];
+            for (int r = 0; r < 16; ++r) {
+                st[r] = __builtin_amdgcn_exp2f(fmaf(st[r], cs, -mc));
+                ps += st[r];
             }
+            ps = halves_sum(ps);
+            alpha = __builtin_amdgcn_exp2f((m_run - m_new) * cs);
+            l_run = fmaf(l_run, alpha, ps);
+            m_run = m_new;
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 f32x4 pa, pb;
@@ -687,18 +676,13 @@ __global__ __launch_bounds__(256, MINB) void attn_spatial_h2x_kernel(AttnH2Param
                 }
                 const f16x4 ha = __builtin_convertvector(pa, f16x4), hb = __builtin_convertvector(pb, f16x4);
                 ph[j] = __builtin_shufflevector(ha, hb, 0, 1, 2, 3, 4, 5, 6, 7);
-                if constexpr (DBG & 32) {
-                    pl[j] = ph[j];
-                } else {
-                    const f16x4 la = __builtin_convertvector(pa - __builtin_convertvector(ha, f32x4), f16x4);
-                    const f16x4 lb = __builtin_convertvector(pb - __builtin_convertvector(hb, f32x4), f16x4);
-                    pl[j] = __builtin_shufflevector(la, lb, 0, 1, 2, 3, 4, 5, 6, 7);
-                }
+                const f16x4 la = __builtin_convertvector(pa - __builtin_convertvector(ha, f32x4), f16x4);
+                const f16x4 lb = __builtin_convertvector(pb - __builtin_convertvector(hb, f32x4), f16x4);
+                pl[j] = __builtin_shufflevector(la, lb, 0, 1, 2, 3, 4, 5, 6, 7);
             }
             return alpha;
         };
         auto rescale = [&](float alpha) {
-            if constexpr (DBG & 1) return;
             if (__any(alpha != 1.0f)) {
 #pragma unroll
                 for (int d = 0; d < 2; ++d)
@@ -707,14 +691,6 @@ __global__ __launch_bounds__(256, MINB) void attn_spatial_h2x_kernel(AttnH2Param
             }
         };
         auto pv = [&](const u32x4 (&vf)[8], const f16x8 (&ph)[2], const f16x8 (&pl)[2]) {
-            if constexpr (DBG & 4) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    ot[0][r] += __builtin_bit_cast(float, vf[r & 7][r >> 3]) * (float)ph[0][r & 7];
-                    ot[1][r] += __builtin_bit_cast(float, vf[(r + 1) & 7][r >> 3]) * (float)pl[1][r & 7];
-                }
-                return;
-            }
 #pragma unroll
             for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -760,10 +736,8 @@ __global__ __launch_bounds__(256, MINB) void attn_spatial_h2x_kernel(AttnH2Param
             rescale(alpha_a);
             pv(va, pha, pla);
         }
-        if constexpr ((DBG & 8) == 0) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
     }
 
     if (!wave_active) return;
@@ -1213,7 +1187,6 @@ __global__ __launch_bounds__(256, 2) void attn_window_h2_kernel(WinH2Params p, i
     }
 }
 
-int g_attn_h2_dbg = 0;  // "attn_h2_dbg": measurement builds of variant 3 (OMNITOK_ATTN_MEASUREMENT_BUILDS only)
 // "attn_h2_variant": 6 (default) 64 queries per wave, deferred rescale, v_fma_mix split | 5 64 queries per wave, softmax of
 // variants 1 - 3 | 4 = 5 with sched_group_barrier pipelines | 3 32 queries per wave, hoisted fragment reads, 32-key tiles, three
 // workgroups per CU (also what the legacy-bias path runs) | 2 the same with 64-key tiles | 1 the r02 / r03 pipelined + LDS-DMA kernel
@@ -1343,21 +1316,6 @@ extern "C" int omnitok_attn_spatial_h2_planes(const void *qp, const void *kp, co
         const bool v3 = variant == 3;
         const int lds = v3 ? 2 * 16384 : 2 * 32768;
         if (v3) {
-#ifdef OMNITOK_ATTN_MEASUREMENT_BUILDS  // wrong-result ablation arms (profiles/r04_attn_ablation.txt)
-#define OT_ATTN_DBG(D) case D: hipLaunchKernelGGL((attn_spatial_h2x_kernel<false, 1, D>), grid, dim3(256), lds, stream, p); break;
-            if (g_attn_h2_dbg > 0 && !bias_table) {
-                switch (g_attn_h2_dbg) {
-                    OT_ATTN_DBG(1) OT_ATTN_DBG(2) OT_ATTN_DBG(4) OT_ATTN_DBG(6) OT_ATTN_DBG(7) OT_ATTN_DBG(8) OT_ATTN_DBG(24) OT_ATTN_DBG(32)
-                    OT_ATTN_DBG(33)
-                    case 100: hipLaunchKernelGGL((attn_spatial_h2x_kernel<false, 1, 0, 4>), grid, dim3(256), lds, stream, p); break;
-                    case 101: hipLaunchKernelGGL((attn_spatial_h2x_kernel<false, 1, 0, 2>), grid, dim3(256), lds, stream, p); break;
-                    case 102: hipLaunchKernelGGL((attn_spatial_h2x_kernel<false, 1, 0, 1>), grid, dim3(256), lds, stream, p); break;
-                    default: set_error("attn_h2_dbg %d not built", g_attn_h2_dbg); return OMNITOK_ERR_INVALID;
-                }
-                OT_LAUNCH_CHECK("attn_spatial_h2 (measurement build)");
-                return OMNITOK_OK;
-            }
-#endif
             if (bias_table)
                 hipLaunchKernelGGL((attn_spatial_h2x_kernel<true, 1>), grid, dim3(256), lds, stream, p);
             else

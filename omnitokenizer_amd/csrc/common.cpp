@@ -1,6 +1,7 @@
 // Error reporting shared by all C-ABI entry points.
 #include "common.h"
 #include "../../include/omnitok_debug.h"
+#include <limits.h>
 #include <string.h>
 
 namespace omnitok {
@@ -50,126 +51,91 @@ int current_device_cus(int *n_cu) {
 }
 }  // namespace omnitok
 
+// Process options, one row each: X(name, readable through omnitok_get_option, smallest value accepted).  The variable is
+// omnitok::g_<name>, defined next to the code that reads it.  omnitok_set_option and omnitok_get_option both walk this table.
+#define OT_OPTIONS(X)                   \
+    X(gemm_variant, false, INT_MIN)     \
+    X(gemm_lds_pad_kb, false, INT_MIN)  \
+    X(gemm_gn, false, INT_MIN)          \
+    X(gemm_small, false, INT_MIN)       \
+    X(vq_split, false, INT_MIN)         \
+    X(vq_variant, false, INT_MIN)       \
+    X(vq_screen, false, INT_MIN)        \
+    X(vq_screen_split, false, INT_MIN)  \
+    X(x3_tile, false, INT_MIN)          \
+    X(h2_tile, false, INT_MIN)          \
+    X(peg_variant, false, INT_MIN)      \
+    X(gemm_mode, true, INT_MIN)         \
+    X(attn_mode, true, INT_MIN)         \
+    X(attn_h2_variant, false, INT_MIN)  \
+    X(attn_vpack, false, INT_MIN)       \
+    X(attn_window_mode, false, INT_MIN) \
+    X(gemm_pl, true, INT_MIN)           \
+    X(qkv_pl, false, INT_MIN)           \
+    X(pl_min_tokens, true, INT_MIN)     \
+    X(pl_cfg, true, INT_MIN)            \
+    X(pl_tail, true, INT_MIN)           \
+    X(pl_stagger, false, INT_MIN)       \
+    X(sp_small_blocks, true, INT_MIN)   \
+    X(temporal_chunk, true, INT_MIN)    \
+    X(temporal_fused, false, INT_MIN)   \
+    X(temporal_kernel, false, INT_MIN)  \
+    X(prevq_fuse, true, INT_MIN)        \
+    X(lm_wide_u, true, INT_MIN)         \
+    X(lm_balance, true, INT_MIN)        \
+    X(lm_ksliced, true, INT_MIN)        \
+    X(lm_mfma, true, INT_MIN)           \
+    X(lm_mfma_mult, true, INT_MIN)      \
+    X(lm_ks_deep, true, INT_MIN)        \
+    X(lm_attn_short, true, INT_MIN)     \
+    X(lm_attn_waves, true, INT_MIN)     \
+    X(lm_loss_chunk_rows, true, 1)
+
 namespace omnitok {
-extern int g_gemm_variant;
-extern int g_gemm_lds_pad_kb;
-extern int g_gemm_small;
-extern int g_gemm_gn;
-extern int g_vq_split;
 extern long long *g_gemm_trace;
 void lm_trace_reset();
-extern int g_peg_variant;
-extern int g_x3_tile;
-extern int g_x3_dbg;
-extern int g_h2_tile;
-extern int g_h2_dbg;
-extern int g_gemm_mode;
-extern int g_attn_mode;
-extern int g_attn_h2_variant;
-extern int g_attn_h2_dbg;
-extern int g_attn_vpack;
-extern int g_gemm_pl;
-extern int g_pl_min_tokens;
-extern int g_temporal_chunk;
-extern int g_prevq_fuse;
-extern int g_temporal_fused;
-extern int g_temporal_kernel;
-extern int g_qkv_pl;
-extern int g_attn_window_mode;
-extern int g_pl_cfg;
-extern int g_sp_small_blocks;
-extern int g_pl_tail;
-extern int g_pl_stagger;
-extern int g_vq_variant;
-extern int g_vq_screen;
-extern int g_vq_screen_split;
-extern int g_lm_wide_u;
-extern int g_lm_balance;
-extern int g_lm_ksliced;
-extern int g_lm_mfma;
-extern int g_lm_mfma_mult;
-extern int g_lm_ks_deep;
-extern int g_lm_attn_short;
-extern int g_lm_attn_waves;
-extern int g_lm_loss_chunk_rows;
+#define OT_OPTION_DECL(name, readable, min) extern int g_##name;
+OT_OPTIONS(OT_OPTION_DECL)
+#undef OT_OPTION_DECL
+
+struct Option {
+    const char *name;
+    int *value;
+    bool readable;
+    int min;
+};
+#define OT_OPTION_ROW(name, readable, min) {#name, &g_##name, readable, min},
+static const Option g_options[] = {OT_OPTIONS(OT_OPTION_ROW)};
+#undef OT_OPTION_ROW
+
+static const Option *find_option(const char *name) {
+    for (const Option &o : g_options)
+        if (!strcmp(name, o.name)) return &o;
+    return nullptr;
+}
 }  // namespace omnitok
 
 extern "C" int omnitok_set_option(const char *name, int value) {
     if (!name) return OMNITOK_ERR_INVALID;
-    if (!strcmp(name, "gemm_variant")) omnitok::g_gemm_variant = value;
-    else if (!strcmp(name, "gemm_lds_pad_kb")) omnitok::g_gemm_lds_pad_kb = value;
-    else if (!strcmp(name, "gemm_gn")) omnitok::g_gemm_gn = value;
-    else if (!strcmp(name, "gemm_small")) omnitok::g_gemm_small = value;
-    else if (!strcmp(name, "vq_split")) omnitok::g_vq_split = value;
-    else if (!strcmp(name, "vq_variant")) omnitok::g_vq_variant = value;
-    else if (!strcmp(name, "vq_screen")) omnitok::g_vq_screen = value;
-    else if (!strcmp(name, "vq_screen_split")) omnitok::g_vq_screen_split = value;
-    else if (!strcmp(name, "x3_tile")) omnitok::g_x3_tile = value;
-    else if (!strcmp(name, "gemm_mode")) omnitok::g_gemm_mode = value;
-    else if (!strcmp(name, "attn_mode")) omnitok::g_attn_mode = value;
-    else if (!strcmp(name, "attn_h2_variant")) omnitok::g_attn_h2_variant = value;
-    else if (!strcmp(name, "attn_h2_dbg")) omnitok::g_attn_h2_dbg = value;
-    else if (!strcmp(name, "attn_vpack")) omnitok::g_attn_vpack = value;
-    else if (!strcmp(name, "gemm_pl")) omnitok::g_gemm_pl = value;
-    else if (!strcmp(name, "pl_min_tokens")) omnitok::g_pl_min_tokens = value;
-    else if (!strcmp(name, "temporal_chunk")) omnitok::g_temporal_chunk = value;
-    else if (!strcmp(name, "prevq_fuse")) omnitok::g_prevq_fuse = value;
-    else if (!strcmp(name, "temporal_fused")) omnitok::g_temporal_fused = value;
-    else if (!strcmp(name, "temporal_kernel")) omnitok::g_temporal_kernel = value;
-    else if (!strcmp(name, "pl_cfg")) omnitok::g_pl_cfg = value;
-    else if (!strcmp(name, "pl_tail")) omnitok::g_pl_tail = value;
-    else if (!strcmp(name, "sp_small_blocks")) omnitok::g_sp_small_blocks = value;
-    else if (!strcmp(name, "pl_stagger")) omnitok::g_pl_stagger = value;
-    else if (!strcmp(name, "qkv_pl")) omnitok::g_qkv_pl = value;
-    else if (!strcmp(name, "attn_window_mode")) omnitok::g_attn_window_mode = value;
-    else if (!strcmp(name, "lm_wide_u")) omnitok::g_lm_wide_u = value;
-    else if (!strcmp(name, "lm_balance")) omnitok::g_lm_balance = value;
-    else if (!strcmp(name, "lm_ksliced")) omnitok::g_lm_ksliced = value;
-    else if (!strcmp(name, "lm_mfma")) omnitok::g_lm_mfma = value;
-    else if (!strcmp(name, "lm_mfma_mult")) omnitok::g_lm_mfma_mult = value;
-    else if (!strcmp(name, "lm_ks_deep")) omnitok::g_lm_ks_deep = value;
-    else if (!strcmp(name, "lm_attn_short")) omnitok::g_lm_attn_short = value;
-    else if (!strcmp(name, "lm_attn_waves")) omnitok::g_lm_attn_waves = value;
-    else if (!strcmp(name, "lm_loss_chunk_rows")) {
-        OT_CHECK_ARG(value >= 1, "set_option: lm_loss_chunk_rows %d, expected at least 1", value);
-        omnitok::g_lm_loss_chunk_rows = value;
-    }
-    else if (!strcmp(name, "h2_dbg")) omnitok::g_h2_dbg = value;
-    else if (!strcmp(name, "h2_tile")) omnitok::g_h2_tile = value;
-    else if (!strcmp(name, "x3_dbg")) omnitok::g_x3_dbg = value;
-    else if (!strcmp(name, "peg_variant")) omnitok::g_peg_variant = value;
-    else {
+    const omnitok::Option *o = omnitok::find_option(name);
+    if (!o) {
         omnitok::set_error("set_option: unknown option %s", name);
         return OMNITOK_ERR_INVALID;
     }
+    OT_CHECK_ARG(value >= o->min, "set_option: %s %d, expected at least %d", name, value, o->min);
+    *o->value = value;
     return OMNITOK_OK;
 }
 
 // current process default of a data-flow option (what an engine follows unless omnitok_engine_set_option pinned its own)
 extern "C" int omnitok_get_option(const char *name, int *value) {
     if (!name || !value) return OMNITOK_ERR_INVALID;
-    if (!strcmp(name, "gemm_mode")) *value = omnitok::g_gemm_mode;
-    else if (!strcmp(name, "attn_mode")) *value = omnitok::g_attn_mode;
-    else if (!strcmp(name, "gemm_pl")) *value = omnitok::g_gemm_pl;
-    else if (!strcmp(name, "pl_min_tokens")) *value = omnitok::g_pl_min_tokens;
-    else if (!strcmp(name, "temporal_chunk")) *value = omnitok::g_temporal_chunk;
-    else if (!strcmp(name, "prevq_fuse")) *value = omnitok::g_prevq_fuse;
-    else if (!strcmp(name, "pl_cfg")) *value = omnitok::g_pl_cfg;
-    else if (!strcmp(name, "pl_tail")) *value = omnitok::g_pl_tail;
-    else if (!strcmp(name, "sp_small_blocks")) *value = omnitok::g_sp_small_blocks;
-    else if (!strcmp(name, "lm_wide_u")) *value = omnitok::g_lm_wide_u;
-    else if (!strcmp(name, "lm_balance")) *value = omnitok::g_lm_balance;
-    else if (!strcmp(name, "lm_ksliced")) *value = omnitok::g_lm_ksliced;
-    else if (!strcmp(name, "lm_mfma")) *value = omnitok::g_lm_mfma;
-    else if (!strcmp(name, "lm_mfma_mult")) *value = omnitok::g_lm_mfma_mult;
-    else if (!strcmp(name, "lm_ks_deep")) *value = omnitok::g_lm_ks_deep;
-    else if (!strcmp(name, "lm_attn_short")) *value = omnitok::g_lm_attn_short;
-    else if (!strcmp(name, "lm_attn_waves")) *value = omnitok::g_lm_attn_waves;
-    else if (!strcmp(name, "lm_loss_chunk_rows")) *value = omnitok::g_lm_loss_chunk_rows;
-    else {
+    const omnitok::Option *o = omnitok::find_option(name);
+    if (!o || !o->readable) {
         omnitok::set_error("get_option: %s is not a readable option", name);
         return OMNITOK_ERR_INVALID;
     }
+    *value = *o->value;
     return OMNITOK_OK;
 }
 

@@ -77,9 +77,7 @@ struct H2Cfg {
     static_assert(TM % RPP == 0 && TN % RPP == 0, "loader passes");
 };
 
-// DBG (measurement builds only, wrong results): 1 skip the split arithmetic, 2 skip the LDS stores of the
-// K loop, 4 skip the global loads of the K loop, 8 skip the per-step barrier
-template <int FLAGS, typename C, bool LN, int DBG = 0>
+template <int FLAGS, typename C, bool LN>
 __global__ __launch_bounds__(C::NT, 2) void gemm_h2_kernel(H2Params hp) {
     constexpr int MI = C::MI, NI = C::NI, NA = C::NA, NB = C::NB, NP = C::NP;
     constexpr int TM = C::TM, TN = C::TN, RPP = C::RPP, SBK = 16;
@@ -155,9 +153,7 @@ __global__ __launch_bounds__(C::NT, 2) void gemm_h2_kernel(H2Params hp) {
     int st_tab[2];
     bool st_ln[2];
     float st_sraw[2];
-    auto gload = [&](int set, int k0, bool in_loop = true) {
-        if constexpr ((DBG & 4) != 0)
-            if (in_loop) return;
+    auto gload = [&](int set, int k0) {
 #pragma unroll
         for (int i = 0; i < NA; ++i) ga[set][i] = *reinterpret_cast<const f32x4 *>(ap[i] + k0);
 #pragma unroll
@@ -179,9 +175,7 @@ __global__ __launch_bounds__(C::NT, 2) void gemm_h2_kernel(H2Params hp) {
     };
     const int st_a = (lq >> 1) * C::SUBA + lrow * 16 + (lq & 1) * 8;
     const int st_b = 2 * C::PLA + (lq & 1) * C::PLB + (lq >> 1) * C::SUBB + lrow * 16;
-    auto sstore_a = [&](int set, int i, int stage, bool in_loop = true) {
-        if constexpr ((DBG & 2) != 0)
-            if (in_loop) return;
+    auto sstore_a = [&](int set, int i, int stage) {
         f32x4 v = ga[set][i];
         float s = st_sraw[set];
         if constexpr (LN) {
@@ -202,16 +196,12 @@ __global__ __launch_bounds__(C::NT, 2) void gemm_h2_kernel(H2Params hp) {
         }
         v *= s;  // exact (power of two)
         const f16x4 h = __builtin_convertvector(v, f16x4);                                // round to nearest
-        f16x4 l = h;
-        if constexpr ((DBG & 1) == 0)
-            l = __builtin_convertvector(v - __builtin_convertvector(h, f32x4), f16x4);  // exact difference
+        const f16x4 l = __builtin_convertvector(v - __builtin_convertvector(h, f32x4), f16x4);  // exact difference
         char *base = smem_c + stage * C::STAGE + st_a + i * RPP * 16;
         *reinterpret_cast<u32x2 *>(base) = __builtin_bit_cast(u32x2, h);
         *reinterpret_cast<u32x2 *>(base + C::PLA) = __builtin_bit_cast(u32x2, l);
     };
-    auto sstore_w = [&](int set, int i, int stage, bool in_loop = true) {
-        if constexpr ((DBG & 2) != 0)
-            if (in_loop) return;
+    auto sstore_w = [&](int set, int i, int stage) {
         *reinterpret_cast<u32x4 *>(smem_c + stage * C::STAGE + st_b + i * RPP * 16) = gw[set][i];
     };
 
@@ -267,7 +257,7 @@ __global__ __launch_bounds__(C::NT, 2) void gemm_h2_kernel(H2Params hp) {
 #pragma unroll
         for (int i = 0; i < NB; ++i) sstore_w(PAR ^ 1, i, PAR ^ 1);
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr ((DBG & 8) == 0) lds_barrier();
+        lds_barrier();
         mfma_group(fay, 0);
 #pragma unroll
         for (int mi = 0; mi < MI; ++mi) lda(fax, PAR ^ 1, 0, mi);
@@ -279,13 +269,13 @@ __global__ __launch_bounds__(C::NT, 2) void gemm_h2_kernel(H2Params hp) {
     using P1 = std::integral_constant<int, 1>;
 
     set_ptrs(0);
-    gload(0, 0, false);
-    gload(1, SBK, false);
+    gload(0, 0);
+    gload(1, SBK);
     if constexpr (LN) __syncthreads();
 #pragma unroll
-    for (int i = 0; i < NA; ++i) sstore_a(0, i, 0, false);
+    for (int i = 0; i < NA; ++i) sstore_a(0, i, 0);
 #pragma unroll
-    for (int i = 0; i < NB; ++i) sstore_w(0, i, 0, false);
+    for (int i = 0; i < NB; ++i) sstore_w(0, i, 0);
     lds_barrier();
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi) lda(fax, 0, 0, mi);
@@ -408,13 +398,11 @@ __global__ __launch_bounds__(256) void h2_pack_weight_kernel(const float *__rest
     }
 }
 
-int g_h2_dbg = 0;  // "h2_dbg": ablation build of the plain 256x256 kernel (measurement only)
-
-template <int FLAGS, typename C, bool LN, int DBG = 0>
+template <int FLAGS, typename C, bool LN>
 static int launch_h2_cfg(H2Params hp, int n_cu, hipStream_t stream) {
     GemmParams &p = hp.g;
     const int lds = 2 * C::STAGE + (LN ? C::LN_TAB : 0);
-    if (int rc = set_max_dynamic_lds(reinterpret_cast<const void *>(gemm_h2_kernel<FLAGS, C, LN, DBG>), lds)) return rc;
+    if (int rc = set_max_dynamic_lds(reinterpret_cast<const void *>(gemm_h2_kernel<FLAGS, C, LN>), lds)) return rc;
     const int64_t nbm = (p.M + C::TM - 1) / C::TM;
     const int nbn = (p.N + C::TN - 1) / C::TN;
     const int64_t nt = nbm * nbn;
@@ -428,7 +416,7 @@ static int launch_h2_cfg(H2Params hp, int n_cu, hipStream_t stream) {
     if (wg_per_cu < 1) wg_per_cu = 1;
     const int64_t cap = (int64_t)n_cu * wg_per_cu;
     const int grid = (int)(nt < cap ? nt : cap);
-    hipLaunchKernelGGL((gemm_h2_kernel<FLAGS, C, LN, DBG>), dim3(grid), dim3(C::NT), lds, stream, hp);
+    hipLaunchKernelGGL((gemm_h2_kernel<FLAGS, C, LN>), dim3(grid), dim3(C::NT), lds, stream, hp);
     OT_LAUNCH_CHECK("gemm_h2");
     return OMNITOK_OK;
 }
@@ -462,20 +450,6 @@ static int launch_h2(H2Params hp, hipStream_t stream) {
     // (measured at C3: 0.429 -> 0.380 ms; profiles/r02_h2_tile_experiment.txt)
     if (g_h2_tile == 0 && t == 1 && (FLAGS & OMNITOK_GEMM_RESIDUAL) && !LN && p.K <= 512 && rpc % 128 == 0) t = 6;
     constexpr bool GEGLU = (FLAGS & OMNITOK_GEMM_GEGLU) != 0;
-    if constexpr (FLAGS == 0 && !LN) {
-        if (t == 1 && g_h2_dbg) {
-            using C1 = H2Cfg<2, 4, 4, 2>;
-            switch (g_h2_dbg) {
-                case 1: return launch_h2_cfg<0, C1, false, 1>(hp, n_cu, stream);
-                case 2: return launch_h2_cfg<0, C1, false, 2>(hp, n_cu, stream);
-                case 4: return launch_h2_cfg<0, C1, false, 4>(hp, n_cu, stream);
-                case 6: return launch_h2_cfg<0, C1, false, 6>(hp, n_cu, stream);
-                case 8: return launch_h2_cfg<0, C1, false, 8>(hp, n_cu, stream);
-                case 14: return launch_h2_cfg<0, C1, false, 14>(hp, n_cu, stream);
-                default: break;
-            }
-        }
-    }
     switch (t) {
         case 1: return launch_h2_cfg<FLAGS, H2Cfg<2, 4, 4, 2>, LN>(hp, n_cu, stream);
         case 3: return launch_h2_cfg<FLAGS, H2Cfg<2, 2, 2, 2>, LN>(hp, n_cu, stream);

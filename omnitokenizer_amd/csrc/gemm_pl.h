@@ -37,7 +37,7 @@ enum PlEpi {
     PL_UNPATCH = 5,     // fp32 (+ bias) scattered as pixels: the un-patchify Rearrange of to_pixels fused into the store
     // The temporal stage without its q|k|v round trip (T' == 5; reference attention.py:402-486, is_spatial = False): rows ordered
     // [tile of 64 sequences][32-sequence half][time step][sequence], so that the five time steps of a sequence are the five row
-    // blocks of ONE lane pair of a wave (PlCfg<2, 2, R, D, 0, 2, 5>: 320 x 128 tiles, wave tile 2 x 5 accumulator blocks = 160
+    // blocks of ONE lane pair of a wave (PlCfg<2, 2, R, D, 2, 5>: 320 x 128 tiles, wave tile 2 x 5 accumulator blocks = 160
     // registers, one wave per SIMD, 7 DMA pieces per wave and K step)
     PL_TSCORE = 6,      // tile = one head [q_h | k_h]: LayerNorm fold, l2norm, scales; k to the q wave through LDS; causal scores, softmax -> P
     PL_TPV = 7,         // tile = V of two heads: o_t = sum_s P[t][s] v_s in-lane -> the out-projection's operand planes (token order)
@@ -137,29 +137,13 @@ __device__ __forceinline__ void pl_wait_steps(int ahead) {
     }
 }
 
-// D = how many K steps the DMA cursor runs ahead (D < R).  DBG (measurement builds, wrong results): 1 no vmcnt wait in
-// front of the barrier, 2 no barrier, 4 no DMA in the K loop, 8 no epilogue, 16 no fp32 stores, 32 no store drain at the tile end
+// D = how many K steps the DMA cursor runs ahead (D < R).
 // Wave tile = NI x MI accumulator blocks of 32 x 32 (n x m): 2 x 4 at two waves per SIMD (256 registers), 4 x 4 at one
 // wave per SIMD (512 registers; a third fewer fragment bytes read from LDS per MFMA -- the kernel is power-bound, so
 // bytes moved per flop, not stalls, set its rate: profiles/r03_pl_ablation.txt).
-// LOOP_ = 1 (r06, thin wave tiles, ONE tile per workgroup): a K loop built for a wave tile with 2-MFMA groups.  Ablation of the
-// default loop on the 128 x 64 tile (profiles/r06_pl_small_tiles.txt): 930 cycles per K step, of which MFMAs + fragment reads alone
-// are 570 (192 cycles of matrix issue + two exposed LDS round trips: the default loop hides them behind 8-MFMA groups), the DMA
-// issue 220, waits and barrier the rest.  Here step s + 1's fragments are ALL read right behind the barrier, under step s's MFMAs
-// (two register sets, loop unrolled by two), and the DMA of step s + R -- into the stage step s just vacated, so the ring runs
-// R - 1 steps ahead with the same LDS -- is spread over the MFMA gaps.  Same products in the same order per accumulator.
-// LOOP_ = 3 (r06, thin tiles, one tile per workgroup): the operands travel global -> REGISTERS -> LDS instead of by LDS-DMA.  Every
-// restructuring of the LDS-DMA loop measured the same ~900 cycles per K step for a lone thin workgroup, whatever the ring depth: a
-// wave keeps only a few global_load_lds in flight (6 pieces = 6 KiB per wave at two steps of prefetch; issuing more steps ahead did
-// not raise it), so one CU fetches ~24 KiB per memory round trip (~25 - 30 GB/s) and the K loop waits for memory.  Plain
-// global_load_dwordx4 into registers has the full vmcnt depth: D steps (D x PPW x 16 B per lane) are in flight per wave, written to
-// a two-stage LDS ring one step ahead of their use.  Same pieces, same LDS image, same fragment reads, same MFMA order: same bits.
-template <int WN_, int WM_, int R_, int D_ = 2, int DBG_ = 0, int NI_ = 2, int MI_ = 4, int LOOP_ = 0>
+template <int WN_, int WM_, int R_, int D_ = 2, int NI_ = 2, int MI_ = 4>
 struct PlCfg {
-    static constexpr int WN = WN_, WM = WM_, R = R_, D = D_, DBG = DBG_, NI = NI_, MI = MI_, LOOP = LOOP_;
-    static_assert(LOOP_ == 0 || LOOP_ == 3 || (DBG_ == 0 && NI_ * MI_ <= 4 && R_ >= 3), "the pipelined loop is for thin wave tiles (fragment double buffer: registers)");
-    static_assert(LOOP_ != 3 || (DBG_ == 0 && NI_ * MI_ <= 4), "the register-staged loop is for thin wave tiles");
-    static_assert(LOOP_ != 2 || R_ >= 5, "LOOP 2 (one barrier per two steps) needs R >= 5: R - 4 steps stay in flight across a barrier");
+    static constexpr int WN = WN_, WM = WM_, R = R_, D = D_, NI = NI_, MI = MI_;
     static constexpr int NW = WN * WM, NT = 64 * NW;
     static constexpr int TN = 32 * NI * WN, TM = 32 * MI * WM;
     static constexpr int WPS = NW > 4 ? 2 : 1;  // waves per SIMD of one workgroup
@@ -174,7 +158,7 @@ struct PlCfg {
     static constexpr bool EPI_T = NW == 8;  // fp32 epilogues go through a 4 KiB LDS block per wave (row-major global accesses)
     static_assert((TM % 64 == 0 || TM == 32) && TN % 64 == 0, "tile shape");
     static_assert((D_ - 1) * PPW < 48, "vmcnt bookkeeping: vmcnt < 64");
-    static_assert(LOOP_ == 3 ? (D_ >= 2 && R_ == 2) : (D_ >= 2 && D_ < R_), "prefetch distance (LOOP 3: D register slots, two LDS stages)");
+    static_assert(D_ >= 2 && D_ < R_, "prefetch distance");
     // PL_ROWLN, thin tiles (r06): the row-major epilogue block of the 8 waves (32 KiB) lives in the ONE ring stage the DMA cursor
     // does not own during an epilogue (R - D == 1: the stage of the last K step, all of whose fragment reads are behind that
     // step's barrier) instead of behind the ring -- what lets a 4-stage ring of 34 / 36 KiB stages fit the CU's 160 KiB
@@ -208,7 +192,7 @@ __device__ __forceinline__ float lane_bcast(float v, int src_bytes) {
 
 template <int EPI, bool SWAP, typename C>
 __global__ __launch_bounds__(C::NT, (C::NI * C::MI > 8) ? 1 : 2) void gemm_pl_kernel(PlParams p) {
-    constexpr int TN = C::TN, TM = C::TM, R = C::R, PPW = C::PPW, NW = C::NW, D = C::D, DBG = C::DBG;
+    constexpr int TN = C::TN, TM = C::TM, R = C::R, PPW = C::PPW, NW = C::NW, D = C::D;
     constexpr int NI = C::NI, MI = C::MI;
     extern __shared__ __attribute__((aligned(16))) unsigned char pl_smem[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -331,45 +315,15 @@ __global__ __launch_bounds__(C::NT, (C::NI * C::MI > 8) ? 1 : 2) void gemm_pl_ke
 
     // ---- prologue ----------------------------------------------------------------------------------------------
     d_set_tile(0);
-    // LOOP 3: register staging -- slot u of stg holds the pieces of step (u mod D); the cursor (d_k) is the next step to load
-    u32x4 stg[C::LOOP == 3 ? D : 1][PPW];
-    auto ld_step = [&](int slot) {   // (slot is a constant after unrolling)
-        const unsigned koff = (unsigned)(d_k >> 1) * 8192u + (unsigned)(d_k & 1) * 2048u;
-#pragma unroll
-        for (int j = 0; j < PPW; ++j)
-            if (piece_live(j)) stg[slot][j] = *reinterpret_cast<const u32x4 *>((p_is_w[j] ? d_w : d_a) + koff + pv_off[j]);
-        ++d_k;
-    };
-    auto st_step = [&](int slot, int stage) {
-#pragma unroll
-        for (int j = 0; j < PPW; ++j)
-            if (piece_live(j)) *reinterpret_cast<u32x4 *>(pl_smem + stage * C::STAGE + pl_dst[j] + lane * 16) = stg[slot][j];
-    };
     int st = 0;  // stage of the current step
-    if constexpr (C::LOOP == 3) {
+    dma_step();
 #pragma unroll
-        for (int u = 0; u < D; ++u)
-            if (u < total) ld_step(u);
-        PL_WAIT_VM(0);
-        st_step(0, 0);
-        if (D < total) ld_step(0);
-        lds_barrier();
-    } else {
-        dma_step();
-#pragma unroll
-        for (int d = 1; d < (C::LOOP == 1 ? R : (C::LOOP == 2 ? R - 1 : D)); ++d)   // LOOP 1: every stage is filled, the cursor then runs R steps ahead (LOOP 2: R - 1)
-            if (total > d) dma_step();
-        PL_WAIT_VM(0);
-        __builtin_amdgcn_s_barrier();
-    }
+    for (int d = 1; d < D; ++d)
+        if (total > d) dma_step();
+    PL_WAIT_VM(0);
+    __builtin_amdgcn_s_barrier();
     rdA(X, 0, 0);
     rdW(Pl, 0, 1);
-    // LOOP == 1: second fragment set (the loop alternates between the two) and the rest of step 0's fragments
-    u32x4 X2[MI], Y2[MI], Ph2[NI], Pl2[NI];
-    if constexpr (C::LOOP >= 1) {
-        rdW(Ph, 0, 0);
-        rdA(Y, 0, 1);
-    }
 
     for (int ti = 0; ti < my_tiles; ++ti) {
         // PL_GEGLU: the tile's per-row operand scales and the wave's 64 weight-row scales (one per lane) are requested HERE,
@@ -438,126 +392,9 @@ __global__ __launch_bounds__(C::NT, (C::NI * C::MI > 8) ? 1 : 2) void gemm_pl_ke
                 for (int q = 0; q < 10; ++q) pt_p[q] = *reinterpret_cast<const f32x4 *>(pp + q * 4);
             }
         }
-        if constexpr (C::LOOP == 3) {
-            // register-staged loop (single tile: total == nk).  At the top of step s the registers of step s + 1 have landed: they go
-            // to the stage step s - 1 was read from (every wave finished with it before barrier(s - 1)) and the loads of step
-            // s + 1 + D take their place; then the plain loop's three groups with its fragment timing.
-            for (int k0 = 0; k0 < nk; k0 += D) {
-#pragma unroll
-                for (int u = 0; u < D; ++u) {
-                    const int s = k0 + u;
-                    if (s < nk) {   // wave-uniform
-                        const int st1 = st ^ 1;
-                        if (s + 1 < total) {
-                            const int ahead = total - 2 - s;   // steps s + 2 .. min(s + D, total - 1) stay in flight
-                            if (full)
-                                pl_wait_steps<PPW, D - 1>(ahead);
-                            else
-                                pl_wait_steps<(PPW > 1 ? PPW - 1 : 0), D - 1>(ahead);
-                            st_step((u + 1) % D, st1);
-                            if (s + 1 + D < total) ld_step((u + 1) % D);
-                        }
-                        __builtin_amdgcn_sched_barrier(0);
-                        group(Pl, X, [&](int i) {
-                            if (i == 0) {
-                                rdW(Ph, st, 0);
-                                rdA(Y, st, 1);
-                                __builtin_amdgcn_sched_barrier(0);
-                            }
-                        });
-                        group(Ph, X, nohook);
-                        lds_barrier();
-                        if (s + 1 < total) {
-                            rdA(X, st1, 0);
-                            rdW(Pl, st1, 1);
-                        }
-                        __builtin_amdgcn_sched_barrier(0);
-                        group(Ph, Y, nohook);
-                        st = st1;
-                    }
-                }
-            }
-        } else if constexpr (C::LOOP >= 1) {
-            // pipelined loop: [step s + 1 landed: vmcnt, barrier] [read ALL fragments of s + 1] [MFMAs of s, the DMA pieces of step
-            // s + R (into the stage s came from) in their gaps]
-            // LOOP 2: ONE wait + barrier per TWO steps (even steps only; a tile's step count is even or its last step syncs alone).
-            // At the barrier of even step s the steps s + 1 and s + 2 have landed and every wave is done reading the stages of steps
-            // <= s; step s then issues step s - 1 + R (into the stage of s - 1), step s + 1 issues s + R: the cursor runs R - 1 ahead.
-            auto kstep = [&](u32x4 (&cX)[MI], u32x4 (&cY)[MI], u32x4 (&cPh)[NI], u32x4 (&cPl)[NI], u32x4 (&nX)[MI], u32x4 (&nY)[MI],
-                             u32x4 (&nPh)[NI], u32x4 (&nPl)[NI], int s, bool sync) {
-                const int st1 = st + 1 == R ? 0 : st + 1;
-                if (C::LOOP == 1 || sync) {
-                    if constexpr (C::LOOP == 1) {   // steps s + 2 .. min(s + R - 1, total - 1) may stay in flight
-                        const int ahead = total - 2 - s;
-                        if (full)
-                            pl_wait_steps<PPW, R - 2>(ahead);
-                        else
-                            pl_wait_steps<(PPW > 1 ? PPW - 1 : 0), R - 2>(ahead);
-                    } else {                        // steps s + 3 .. min(s - 2 + R, total - 1) may stay in flight
-                        const int ahead = total - 3 - s;
-                        if (full)
-                            pl_wait_steps<PPW, (R > 4 ? R - 4 : 0)>(ahead);
-                        else
-                            pl_wait_steps<(PPW > 1 ? PPW - 1 : 0), (R > 4 ? R - 4 : 0)>(ahead);
-                    }
-                    lds_barrier();
-                }
-                if (s + 1 < total) {
-                    rdA(nX, st1, 0);
-                    rdW(nPl, st1, 1);
-                    rdW(nPh, st1, 0);
-                    rdA(nY, st1, 1);
-                }
-                // wave-uniform; the cursor stands on step s + R (stage == st) or, LOOP 2, s - 1 + R (the stage before st)
-                const bool more = C::LOOP == 1 ? s + R < total : s - 1 + R < total;
-                unsigned koff = 0;
-                const unsigned char *ca = d_a, *cw = d_w;
-                const int cst = d_stage;
-                if (more) koff = (unsigned)(d_k >> 1) * 8192u + (unsigned)(d_k & 1) * 2048u;
-                constexpr int HOOKS = 3 * SLOTS, PPH = (PPW + HOOKS - 1) / HOOKS;
-                auto dma_hook = [&](int h) {
-#pragma unroll
-                    for (int u = 0; u < PPH; ++u) {
-                        const int j = PPH * h + u;
-                        if (more && j < PPW && piece_live(j)) {
-                            const unsigned char *src = (p_is_w[j] ? cw : ca) + koff + pv_off[j];
-                            __builtin_amdgcn_global_load_lds((pl_glob_t *)src, (pl_lds_t *)(pl_smem + cst * C::STAGE + pl_dst[j]), 16, 0, 0);
-                        }
-                    }
-                };
-                __builtin_amdgcn_sched_barrier(0);
-                group(cPl, cX, [&](int i) { dma_hook(i); });               // W lo . A hi
-                group(cPh, cX, [&](int i) { dma_hook(SLOTS + i); });       // W hi . A hi
-                group(cPh, cY, [&](int i) { dma_hook(2 * SLOTS + i); });   // W hi . A lo
-                __builtin_amdgcn_sched_barrier(0);
-                if (more) {
-                    d_stage = d_stage + 1 == R ? 0 : d_stage + 1;
-                    if (++d_k == nk && d_tile + 1 < my_tiles) d_set_tile(d_tile + 1);
-                }
-                st = st1;
-            };
-            int k = 0;
-            for (; k + 1 < nk; k += 2) {
-                kstep(X, Y, Ph, Pl, X2, Y2, Ph2, Pl2, ti * nk + k, true);
-                kstep(X2, Y2, Ph2, Pl2, X, Y, Ph, Pl, ti * nk + k + 1, false);
-            }
-            if (k < nk) {   // odd step count: the next tile starts from the first set again
-                kstep(X, Y, Ph, Pl, X2, Y2, Ph2, Pl2, ti * nk + k, true);
-#pragma unroll
-                for (int mi = 0; mi < MI; ++mi) {
-                    X[mi] = X2[mi];
-                    Y[mi] = Y2[mi];
-                }
-#pragma unroll
-                for (int ni = 0; ni < NI; ++ni) {
-                    Ph[ni] = Ph2[ni];
-                    Pl[ni] = Pl2[ni];
-                }
-            }
-        } else
         for (int k = 0; k < nk; ++k) {
             const int s = ti * nk + k;
-            const bool more = (DBG & 4) ? false : s + D < total;  // wave-uniform
+            const bool more = s + D < total;  // wave-uniform
             const int st1 = st + 1 == R ? 0 : st + 1;
             // the cursor state is advanced by whichever group issues; pieces are spread over the MFMA gaps
             unsigned koff = 0;
@@ -596,14 +433,12 @@ __global__ __launch_bounds__(C::NT, (C::NI * C::MI > 8) ? 1 : 2) void gemm_pl_ke
             }
             // this wave's share of step s + 1 has landed: everything but the pieces of steps s + 2 .. s + D
             // (steps s + 2 .. min(s + D, total - 1) may stay in flight: min(D - 1, total - 2 - s) of them)
-            if constexpr ((DBG & 1) == 0) {
-                const int ahead = total - 2 - s;
-                if (full)
-                    pl_wait_steps<PPW, D - 1>(ahead);
-                else
-                    pl_wait_steps<(PPW > 1 ? PPW - 1 : 0), D - 1>(ahead);
-            }
-            if constexpr ((DBG & 2) == 0) lds_barrier();
+            const int ahead = total - 2 - s;
+            if (full)
+                pl_wait_steps<PPW, D - 1>(ahead);
+            else
+                pl_wait_steps<(PPW > 1 ? PPW - 1 : 0), D - 1>(ahead);
+            lds_barrier();
             // G3: W hi . A lo   | reads A hi, W lo of the next step
             if (s + 1 < total) {
                 rdA(X, st1, 0);
@@ -630,17 +465,7 @@ __global__ __launch_bounds__(C::NT, (C::NI * C::MI > 8) ? 1 : 2) void gemm_pl_ke
             const float ascl_c = second ? p.a2_scale_const : p.a_scale_const;
             const int n_w0 = bn * TN + wn * (32 * NI);      // first column of this wave
             const int64_t m_w0 = bm * TM + wm * (32 * MI);  // first row of this wave
-            if constexpr (DBG & 8) {
-                // measurement build: no epilogue (the accumulators stay live through a store that never happens)
-                float t = 0.0f;
-#pragma unroll
-                for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-                    for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-                        for (int e = 0; e < 16; ++e) t += acc[ni][mi][e];
-                if (t == 12345.678f) p.c[lane] = t;
-            } else if constexpr (!SWAP) {
+            if constexpr (!SWAP) {
                 // lane = row m_w0 + mi * 32 + r32; run c of block ni: columns n_w0 + ni * 32 + c * 16 + hi * 8 + 0..7
                 // per-row activation scales.  The load is unconditional and branch-free (a dummy address and an
                 // arithmetic select when there is no per-row array): a load on one side of a branch stays "pending" on
@@ -802,9 +627,7 @@ __global__ __launch_bounds__(C::NT, (C::NI * C::MI > 8) ? 1 : 2) void gemm_pl_ke
                                     }
                                     if (ni * MI + mi + 1 < NI * MI)
                                         res[i] = __builtin_amdgcn_raw_buffer_load_b128(r_rs, vo_r, so(ni * MI + mi + 1, i, (int)p.ldr), 0);
-                                    if constexpr (DBG & 16) {
-                                        if (v[0] == 12345.678f) p.c[lane] = v[1];  // measurement build: no stores
-                                    } else if constexpr (EPI == PL_UNPATCH) {
+                                    if constexpr (EPI == PL_UNPATCH) {
                                         // element (m, n) of the token x feature result is pixel  up_rowb[mi] + (i 8 + rrow) 8  +  up_colb[ni]
                                         // + (rch / 2) W + (rch % 2) 4: the lane's 4 columns are 16 contiguous bytes, the 8 lanes of a row cover 4
                                         // pixel rows of the patch and neighbouring rows (gx, gx + 1) continue them (256-byte runs)
@@ -950,6 +773,10 @@ __global__ __launch_bounds__(C::NT, (C::NI * C::MI > 8) ? 1 : 2) void gemm_pl_ke
                     // residual in and fp32 out both go row-major through the wave's LDS block (see PL_F32): the residual is
                     // loaded as full lines, re-read in the accumulator layout, and the sum (kept in the accumulators for
                     // the statistics) takes the same way back out
+                    // SCR_IN_RING pins R - D == 1: d_stage is then the one stage the cursor has not filled for the next tile, and this
+                    // wave's DMA does not resume before the next K loop.  A faster wave's does -- its first next-tile step lands in this very
+                    // stage -- and what keeps it off the scratch of a slower wave are the two lds_barrier() calls of the row statistics below:
+                    // every wave is past its last scratch access ((c) of the last block) before any wave leaves the epilogue.
                     unsigned char *scr = C::SCR_IN_RING ? pl_smem + d_stage * C::STAGE + wave * 4096
                                                         : pl_smem + C::LDS + 2 * C::WN * TM * 4 + wave * 4096;
                     const int rrow = hi * 4 + (r32 >> 3), rch = r32 & 7;
@@ -1359,7 +1186,7 @@ __global__ __launch_bounds__(C::NT, (C::NI * C::MI > 8) ? 1 : 2) void gemm_pl_ke
                     // bank conflicts.  Before: every lane fetched its own 8-byte pieces from the [n_tokens][32] tables in
                     // global memory, 128 uncoalesced loads per lane and tile, four waves the same rows -- 0.13 ms of the
                     // 0.66 ms launch.  All waves take part (and meet at the two barriers) whether their columns exist or not.
-                    static_assert(EPI != PL_QKPACK || (C::STAGE >= TM * 128 && (C::LOOP == 3 ? R >= 2 : R - D >= 2) && TM % (8 * NW) == 0),
+                    static_assert(EPI != PL_QKPACK || (C::STAGE >= TM * 128 && R - D >= 2 && TM % (8 * NW) == 0),
                                   "RoPE rows of a tile fit the two free ring stages");
                     // per-column constants by lane (column n_w0 + lane of the wave's 64), requested before the RoPE rows so that
                     // one memory round trip per tile covers both; chunks fetch theirs with ds_bpermute in one batch
@@ -1581,7 +1408,7 @@ __global__ __launch_bounds__(C::NT, (C::NI * C::MI > 8) ? 1 : 2) void gemm_pl_ke
         // waitcnt pass still sees "pending" on some path (e.g. one issued inside a wave-uniform branch) would otherwise
         // make it drain vmcnt -- and with it the LDS-DMA ring -- in front of the fragment reads of EVERY K step.  The wait
         // costs the store latency once per tile; the kernel is power-bound, not stall-bound (profiles/r03_gemm_limiter_probe.txt).
-        if constexpr ((DBG & 32) == 0) PL_WAIT_VM(0);
+        PL_WAIT_VM(0);
         zero_acc();
     }
     if (p.cycles && blockIdx.x == 0 && tid == 0) {

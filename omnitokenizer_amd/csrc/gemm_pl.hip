@@ -117,7 +117,7 @@ static int launch_pl_cfg(PlParams p, hipStream_t stream) {
     if (wg_per_cu < 1) wg_per_cu = 1;
     // two small workgroups per CU: one tile each (the hardware dispatcher overlaps one's epilogue with the other's K loop);
     // one big workgroup per CU: persistent
-    const int64_t cap = (wg_per_cu > 1 || C::LOOP >= 1) ? nt : (int64_t)n_cu;   // (the pipelined loop is a one-tile-per-workgroup loop)
+    const int64_t cap = wg_per_cu > 1 ? nt : (int64_t)n_cu;
     const int grid = (int)(nt < cap ? nt : cap);
     hipLaunchKernelGGL((gemm_pl_kernel<EPI, SWAP, C>), dim3(grid), dim3(C::NT), LDS, stream, p);
     OT_LAUNCH_CHECK("gemm_pl");
@@ -141,29 +141,17 @@ using PlBig = PlCfg<4, 2, 4>;
 // other's barrier and fragment-read bubbles.  Deeper rings (DMA 4 / 6 steps ahead, 96 KiB, one workgroup per CU) measured SLOWER
 // at every size from 5120 rows up and equal at 1024 (profiles/r06_pl_small_tiles.txt): a thin wave tile has 2 MFMAs per
 // group to cover an LDS round trip with, co-resident workgroups are what hides it, not prefetch distance.
-using PlMid = PlCfg<2, 2, 4, 2, 0, 2, 2>;      // 128 x 128
-using PlSmall = PlCfg<2, 2, 4, 2, 0, 2, 1>;    // 128 x  64
-// Closed by measurement this round (profiles/r06_pl_small_tiles.txt; the arms stay in measurement builds, -DOMNITOK_PL_MEASUREMENT_BUILDS):
-// a lone 128 x 64 workgroup runs its K loop at ~900 cycles per 16-k step for 192 cycles of MFMA issue (ablation: MFMAs + fragment reads
-// alone 570, DMA issue 220, waits + barrier the rest).  FIVE restructurings, all bit-identical to the shipped tiles, all within 5 % of
-// the same time at 1024 rows:  deeper rings (DMA 4 / 6 steps ahead: arms 9 / 8);  a loop that reads all of step s + 1's fragments under
-// step s's MFMAs and spreads the DMA of step s + R over their gaps (PlCfg LOOP_ = 1: 35 / 36);  one barrier per TWO steps (LOOP_ = 2:
-// 37 / 38);  operands through registers instead of LDS-DMA, 4 / 6 steps in flight per wave (LOOP_ = 3: 39 / 40 / 41);  tiles small
-// enough that every CU gets one (128 x 32, 64 x 32: 10 / 11).  So it is neither LDS latency, nor barrier count, nor memory-level
-// parallelism, nor fetch rate per CU alone; what does help a thin tile is a second / third workgroup on its CU.
-#ifdef OMNITOK_PL_MEASUREMENT_BUILDS
-using PlMidD = PlCfg<2, 2, 6, 4, 0, 2, 2, 1>;
-using PlSmallD = PlCfg<2, 2, 8, 6, 0, 2, 1, 1>;
-using PlMid1 = PlCfg<2, 2, 4, 2, 0, 2, 2, 1>;
-using PlSmall1 = PlCfg<2, 2, 4, 2, 0, 2, 1, 1>;
-using PlSmall3 = PlCfg<2, 2, 2, 4, 0, 2, 1, 3>;   // 128 x 64, operands through registers, 4 steps in flight (arm 39); 40: 6 steps; 41: 128 x 128
-using PlSmall3b = PlCfg<2, 2, 2, 6, 0, 2, 1, 3>;
-using PlMid3 = PlCfg<2, 2, 2, 3, 0, 2, 2, 3>;
-using PlSmall2 = PlCfg<2, 2, 8, 2, 0, 2, 1, 2>;   // 128 x 64, ring of 8, one barrier per two K steps (arm 37); 38: ring of 6
-using PlSmall2b = PlCfg<2, 2, 6, 2, 0, 2, 1, 2>;
-using PlTiny = PlCfg<2, 1, 4, 2, 0, 2, 1>;     // 128 x 32, two waves
-using PlTiny64 = PlCfg<1, 1, 4, 2, 0, 2, 1>;   //  64 x 32, one wave
-#endif
+using PlMid = PlCfg<2, 2, 4, 2, 2, 2>;      // 128 x 128
+using PlSmall = PlCfg<2, 2, 4, 2, 2, 1>;    // 128 x  64
+// Closed by measurement in r06 (profiles/r06_pl_small_tiles.txt): a lone 128 x 64 workgroup runs its K loop at ~900 cycles per 16-k
+// step for 192 cycles of MFMA issue (ablation: MFMAs + fragment reads alone 570, DMA issue 220, waits + barrier the rest).  FIVE
+// restructurings, all bit-identical to the shipped tiles, all within 5 % of the same time at 1024 rows:  deeper rings (DMA 4 / 6
+// steps ahead);  a loop that reads all of step s + 1's fragments under step s's MFMAs and spreads the DMA of step s + R over their
+// gaps;  one barrier per TWO steps;  operands through registers instead of LDS-DMA, 4 / 6 steps in flight per wave;  tiles small
+// enough that every CU gets one (128 x 32, 64 x 32).  So it is neither LDS latency, nor barrier count, nor memory-level
+// parallelism, nor fetch rate per CU alone; what does help a thin tile is a second / third workgroup on its CU.  That is why
+// gemm_pl_kernel has ONE K loop.  The other loops and the wrong-result ablation builds behind the r03 / r06 profiles are gone from
+// the source; the last tree that has them (measurement builds, pl_cfg arms 3 .. 41) is commit a53abed.
 
 // Which configuration(s) a launch takes (results do not depend on it).  From the sweeps in profiles/r06_pl_small_tiles.txt:
 //  * 256 x 256 tiles win once they fill >= 3/4 of the CUs; below that 128 x 128 while there are >= n_cu of those, else 128 x 64
@@ -187,7 +175,7 @@ static int pl_thin_cfg(int epi, int64_t M, int N, int n_cu) {
     return tiles(128, 128) >= n_cu ? 5 : 6;
 }
 
-static PlPlan pl_auto_plan(int epi, int64_t M, int N, int64_t row_align) {
+static PlPlan pl_auto_plan(int epi, int64_t M, int N) {
     int n_cu = 0;
     if (current_device_cus(&n_cu) != OMNITOK_OK || n_cu <= 0) n_cu = 256;
     const int tm = epi == PL_ROWLN ? 128 : 256, tn = epi == PL_ROWLN ? 512 : 256;
@@ -198,10 +186,8 @@ static PlPlan pl_auto_plan(int epi, int64_t M, int N, int64_t row_align) {
     if (!enough) return PlPlan{pl_thin_cfg(epi, M, N, n_cu), 0, 0};
     const int64_t r = t / n_cu, rem = t % n_cu;
     if (g_pl_tail && r >= 1 && rem > 0 && (n_cu - rem) * 20 >= (int64_t)n_cu * (r + 1)) {
-        // rows of the full rounds: whole row tiles, and whole units of `row_align` rows (sequences / clips / videos an epilogue
-        // addresses by division: a launch boundary inside one is fine for the arithmetic but keeps the checks simple)
-        int64_t rows_main = (r * n_cu / nbn) * tm;
-        if (row_align > 1) rows_main -= rows_main % row_align;
+        // rows of the full rounds: whole row tiles
+        const int64_t rows_main = (r * n_cu / nbn) * tm;
         if (rows_main >= tm && rows_main % tm == 0 && rows_main < M)
             return PlPlan{1, rows_main, pl_thin_cfg(epi, M - rows_main, N, n_cu)};
     }
@@ -224,7 +210,7 @@ static int launch_pl(const PlParams &p, int cfg, hipStream_t stream) {
         }
     } else if constexpr (EPI == PL_UNPATCH) {
         switch (cfg) {
-            case 6: return launch_pl_cfg<EPI, false, PlCfg<4, 2, 3, 2, 0, 2, 1>>(p, stream);
+            case 6: return launch_pl_cfg<EPI, false, PlCfg<4, 2, 3, 2, 2, 1>>(p, stream);
             default: return launch_pl_cfg<EPI, false, PlBig>(p, stream);
         }
     } else if constexpr (EPI == PL_TSCORE || EPI == PL_TPV) {
@@ -235,11 +221,11 @@ static int launch_pl(const PlParams &p, int cfg, hipStream_t stream) {
         // (more than ~400 clips of 17 x 256 x 256 in one call) take the first form below
         const bool fits32 = (int64_t)p.M * (EPI == PL_TPV ? p.cp_kblocks * 32 : 0) * 4 < (1ll << 32) && (int64_t)p.t_nseq * p.t_heads * 160 < (1ll << 32);
         if (g_temporal_kernel >= 1 && fits32) return EPI == PL_TSCORE ? launch_plt_tscore(p, stream) : launch_plt_tpv(p, stream);
-        return launch_pl_cfg<EPI, false, PlCfg<2, 2, 4, 2, 0, 2, 5>>(p, stream);
+        return launch_pl_cfg<EPI, false, PlCfg<2, 2, 4, 2, 2, 5>>(p, stream);
     } else if constexpr (EPI == PL_ROWLN) {
         switch (cfg) {  // 512 (= N) columns: a workgroup owns whole rows
-            case 6: return launch_pl_cfg<EPI, false, PlCfg<8, 1, 4, 3, 0, 2, 2>>(p, stream);  // 64 rows
-            case 7: return launch_pl_cfg<EPI, false, PlCfg<8, 1, 4, 3, 0, 2, 1>>(p, stream);  // 32 rows
+            case 6: return launch_pl_cfg<EPI, false, PlCfg<8, 1, 4, 3, 2, 2>>(p, stream);  // 64 rows
+            case 7: return launch_pl_cfg<EPI, false, PlCfg<8, 1, 4, 3, 2, 1>>(p, stream);  // 32 rows
             default: return launch_pl_cfg<EPI, false, PlCfg<8, 1, 3>>(p, stream);             // 128 rows
         }
     } else {
@@ -247,35 +233,6 @@ static int launch_pl(const PlParams &p, int cfg, hipStream_t stream) {
             case 2: return launch_pl_cfg<EPI, false, PlCfg<2, 2, 3>>(p, stream);
             case 5: return launch_pl_cfg<EPI, false, PlMid>(p, stream);
             case 6: return launch_pl_cfg<EPI, false, PlSmall>(p, stream);
-#ifdef OMNITOK_PL_MEASUREMENT_BUILDS
-            case 10: return launch_pl_cfg<EPI, false, PlTiny>(p, stream);
-            case 11: return launch_pl_cfg<EPI, false, PlTiny64>(p, stream);
-            case 8: return launch_pl_cfg<EPI, false, PlSmallD>(p, stream);
-            case 9: return launch_pl_cfg<EPI, false, PlMidD>(p, stream);
-            case 35: return launch_pl_cfg<EPI, false, PlMid1>(p, stream);
-            case 36: return launch_pl_cfg<EPI, false, PlSmall1>(p, stream);
-            case 39: return launch_pl_cfg<EPI, false, PlSmall3>(p, stream);
-            case 40: return launch_pl_cfg<EPI, false, PlSmall3b>(p, stream);
-            case 41: return launch_pl_cfg<EPI, false, PlMid3>(p, stream);
-            case 37: return launch_pl_cfg<EPI, false, PlSmall2>(p, stream);
-            case 38: return launch_pl_cfg<EPI, false, PlSmall2b>(p, stream);
-            case 21: return launch_pl_cfg<EPI, false, PlCfg<2, 2, 4, 2, 1, 2, 1>>(p, stream);   // 128 x 64: no vmcnt wait
-            case 22: return launch_pl_cfg<EPI, false, PlCfg<2, 2, 4, 2, 2, 2, 1>>(p, stream);   // no barrier
-            case 23: return launch_pl_cfg<EPI, false, PlCfg<2, 2, 4, 2, 3, 2, 1>>(p, stream);   // neither
-            case 24: return launch_pl_cfg<EPI, false, PlCfg<2, 2, 4, 2, 4, 2, 1>>(p, stream);   // no DMA in the K loop
-            case 27: return launch_pl_cfg<EPI, false, PlCfg<2, 2, 4, 2, 7, 2, 1>>(p, stream);   // MFMAs + fragment reads only
-            case 28: return launch_pl_cfg<EPI, false, PlCfg<2, 2, 4, 2, 8, 2, 1>>(p, stream);   // no epilogue  // wrong-result ablation builds of profiles/r03_gemm_limiter_probe.txt
-            case 3: return launch_pl_cfg<EPI, false, PlCfg<4, 2, 4, 3>>(p, stream);
-            case 4: return launch_pl_cfg<EPI, false, PlCfg<2, 2, 4, 2, 0, 4, 4>>(p, stream);
-            case 31: return launch_pl_cfg<EPI, false, PlCfg<4, 2, 4, 3, 1>>(p, stream);
-            case 13: return launch_pl_cfg<EPI, false, PlCfg<4, 2, 4, 3, 3>>(p, stream);
-            case 14: return launch_pl_cfg<EPI, false, PlCfg<2, 2, 4, 2, 4, 4, 4>>(p, stream);
-            case 33: return launch_pl_cfg<EPI, false, PlCfg<4, 2, 4, 3, 5>>(p, stream);
-            case 17: return launch_pl_cfg<EPI, false, PlCfg<4, 2, 4, 3, 7>>(p, stream);
-            case 18: return launch_pl_cfg<EPI, false, PlCfg<4, 2, 4, 2, 8>>(p, stream);
-            case 19: return launch_pl_cfg<EPI, false, PlCfg<4, 2, 4, 2, 16>>(p, stream);
-            case 20: return launch_pl_cfg<EPI, false, PlCfg<4, 2, 4, 2, 32>>(p, stream);
-#endif
             default: return launch_pl_cfg<EPI, false, PlBig>(p, stream);
         }
     }
@@ -285,7 +242,7 @@ static int launch_pl(const PlParams &p, int cfg, hipStream_t stream) {
 template <int EPI>
 static int pl_run(const PlParams &p, int forced_cfg, hipStream_t stream) {
     if (forced_cfg > 0) return launch_pl<EPI>(p, forced_cfg, stream);
-    const PlPlan plan = pl_auto_plan(EPI, p.M, p.N, 1);
+    const PlPlan plan = pl_auto_plan(EPI, p.M, p.N);
     if (plan.split == 0) return launch_pl<EPI>(p, plan.cfg, stream);
     PlParams a = p, b = p;
     a.row_begin = 0;

@@ -1,6 +1,6 @@
 // The fused temporal stage's own GEMM kernel (T' == 5; reference attention.py:402-486 with is_spatial = False): the same
 // plane x plane products and the same two epilogues as gemm_pl.h's PL_TSCORE / PL_TPV, in a K loop built for TWO waves per
-// SIMD.  The first fused form ran its 320 x 128 tiles on PlCfg<2, 2, 4, 2, 0, 2, 5> -- one wave per SIMD, 4 x 28 KiB ring --
+// SIMD.  The first fused form ran its 320 x 128 tiles on PlCfg<2, 2, 4, 2, 2, 5> -- one wave per SIMD, 4 x 28 KiB ring --
 // and the matrix pipe sat at 42 / 37 % busy: with 10 MFMAs per product group nothing fills the barrier and fragment-read
 // bubbles of a single wave (profiles/r05_temporal_fused.txt).  Here
 //   * a workgroup is still 4 waves x (2 x 5 accumulator blocks) on a 320 x 128 tile, but TWO workgroups share a CU:

@@ -94,9 +94,7 @@ __device__ __forceinline__ void split3x4(const f32x4 v, u32x2 &p0, u32x2 &p1, u3
     p2[1] = __builtin_amdgcn_perm(b2[3], b2[2], 0x07060302u);
 }
 
-// DBG (measurement builds only, wrong results): 1 skip the split arithmetic, 2 skip the LDS stores of the
-// K loop, 4 skip the global loads of the K loop, 8 skip the per-step barrier
-template <int FLAGS, typename C, bool LN, int DBG = 0>
+template <int FLAGS, typename C, bool LN>
 __global__ __launch_bounds__(C::NT, 2) void gemm_x3_kernel(X3Params xp) {
     constexpr int MI = C::MI, NI = C::NI, NA = C::NA, NB = C::NB, NP = C::NP;
     constexpr int TM = C::TM, TN = C::TN, RPP = C::RPP, SBK = 16;
@@ -111,11 +109,6 @@ __global__ __launch_bounds__(C::NT, 2) void gemm_x3_kernel(X3Params xp) {
     if ((int)blockIdx.x >= p.ntiles) return;
     const int my_tiles = (p.ntiles - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
     const int nbm = (int)((p.M + TM - 1) / TM), nbn = (p.N + TN - 1) / TN;
-    long long dbg_c0 = 0, dbg_w0 = 0;
-    if constexpr ((DBG & 16) != 0) {  // shader-clock / 100 MHz wall-clock stamps -> effective clock
-        dbg_c0 = clock64();
-        dbg_w0 = wall_clock64();
-    }
 
     // LayerNorm table in LDS (after the two stages): gamma|beta pairs
     float *ln_tab = reinterpret_cast<float *>(smem_c + 2 * C::STAGE);
@@ -180,9 +173,7 @@ __global__ __launch_bounds__(C::NT, 2) void gemm_x3_kernel(X3Params xp) {
     };
     const int st_a = (lq >> 1) * C::SUBA + lrow * 16 + (lq & 1) * 8;
     const int st_b = 3 * C::PLA + (lq >> 1) * C::SUBB + lrow * 16 + (lq & 1) * 8;
-    auto sstore = [&](int set, int piece, int stage, bool in_loop = true) {
-        if constexpr ((DBG & 2) != 0)
-            if (in_loop) return;
+    auto sstore = [&](int set, int piece, int stage) {
         f32x4 v = gs[set][piece];
         if constexpr (LN) {
             if (piece < NA) {
@@ -200,14 +191,7 @@ __global__ __launch_bounds__(C::NT, 2) void gemm_x3_kernel(X3Params xp) {
             }
         }
         u32x2 p0, p1, p2;
-        if constexpr ((DBG & 1) != 0) {
-            p0[0] = __builtin_amdgcn_perm(__float_as_uint(v[1]), __float_as_uint(v[0]), 0x07060302u);
-            p0[1] = __builtin_amdgcn_perm(__float_as_uint(v[3]), __float_as_uint(v[2]), 0x07060302u);
-            p1 = p0;
-            p2 = p0;
-        } else {
-            split3x4(v, p0, p1, p2);
-        }
+        split3x4(v, p0, p1, p2);
         char *base = smem_c + stage * C::STAGE +
                      (piece < NA ? st_a + piece * RPP * 16 : st_b + (piece - NA) * RPP * 16);
         const int pl = piece < NA ? C::PLA : C::PLB;
@@ -265,10 +249,8 @@ __global__ __launch_bounds__(C::NT, 2) void gemm_x3_kernel(X3Params xp) {
         constexpr int SS = C::ONE ? 0 : (PAR ^ 1);  // register set that is split + stored in this step
         // global loads first (ONE: K-step g+1, consumed in the second half of this step; else K-step
         // g+2, a whole K-step of latency cover)
-        if constexpr ((DBG & 4) == 0) {
 #pragma unroll
-            for (int pc = 0; pc < NP; ++pc) gload(LS, pc, k0);
-        }
+        for (int pc = 0; pc < NP; ++pc) gload(LS, pc, k0);
         gload_meta(LS, k0);
 #pragma unroll
         for (int ni = 0; ni < NI; ++ni) ldb(PAR, 1, ni);
@@ -299,7 +281,7 @@ __global__ __launch_bounds__(C::NT, 2) void gemm_x3_kernel(X3Params xp) {
 #pragma unroll
         for (int pc = S3; pc < NP; ++pc) sstore(SS, pc, PAR ^ 1);
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr ((DBG & 8) == 0) lds_barrier();
+        lds_barrier();
         mfma_group(X, 0);
 #pragma unroll
         for (int mi = 0; mi < MI; ++mi) lda(Y, PAR ^ 1, 0, mi);
@@ -322,7 +304,7 @@ __global__ __launch_bounds__(C::NT, 2) void gemm_x3_kernel(X3Params xp) {
     }
     if constexpr (LN) __syncthreads();  // the table
 #pragma unroll
-    for (int pc = 0; pc < NP; ++pc) sstore(0, pc, 0, false);
+    for (int pc = 0; pc < NP; ++pc) sstore(0, pc, 0);
     lds_barrier();
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi) lda(fax, 0, 0, mi);
@@ -369,22 +351,13 @@ __global__ __launch_bounds__(C::NT, 2) void gemm_x3_kernel(X3Params xp) {
         }
         zero_acc();
     }
-    if constexpr ((DBG & 16) != 0) {
-        if (p.trace && tid == 0 && blockIdx.x < 256) {
-            p.trace[2 * blockIdx.x] = clock64() - dbg_c0;
-            p.trace[2 * blockIdx.x + 1] = wall_clock64() - dbg_w0;
-        }
-    }
 }
 
-extern long long *g_gemm_trace;
-int g_x3_dbg = 0;  // "x3_dbg": ablation build of the plain 256x256 kernel (measurement only)
-
-template <int FLAGS, typename C, bool LN, int DBG = 0>
+template <int FLAGS, typename C, bool LN>
 static int launch_x3_cfg(X3Params xp, int n_cu, hipStream_t stream) {
     GemmParams &p = xp.g;
     const int lds = 2 * C::STAGE + (LN ? C::LN_TAB : 0);
-    if (int rc = set_max_dynamic_lds(reinterpret_cast<const void *>(gemm_x3_kernel<FLAGS, C, LN, DBG>), lds)) return rc;
+    if (int rc = set_max_dynamic_lds(reinterpret_cast<const void *>(gemm_x3_kernel<FLAGS, C, LN>), lds)) return rc;
     const int64_t nbm = (p.M + C::TM - 1) / C::TM;
     const int nbn = (p.N + C::TN - 1) / C::TN;
     const int64_t nt = nbm * nbn;
@@ -398,7 +371,7 @@ static int launch_x3_cfg(X3Params xp, int n_cu, hipStream_t stream) {
     if (wg_per_cu < 1) wg_per_cu = 1;
     const int64_t cap = (int64_t)n_cu * wg_per_cu;
     const int grid = (int)(nt < cap ? nt : cap);
-    hipLaunchKernelGGL((gemm_x3_kernel<FLAGS, C, LN, DBG>), dim3(grid), dim3(C::NT), lds, stream, xp);
+    hipLaunchKernelGGL((gemm_x3_kernel<FLAGS, C, LN>), dim3(grid), dim3(C::NT), lds, stream, xp);
     OT_LAUNCH_CHECK("gemm_x3");
     return OMNITOK_OK;
 }
@@ -418,22 +391,6 @@ static int launch_x3(X3Params xp, hipStream_t stream) {
         else t = 4;
     }
     constexpr bool GEGLU = (FLAGS & OMNITOK_GEMM_GEGLU) != 0;
-    if constexpr (FLAGS == 0 && !LN) {
-        if (t == 1 && g_x3_dbg) {
-            using C1 = X3Cfg<2, 4, 4, 2>;
-            switch (g_x3_dbg) {
-                case 1: return launch_x3_cfg<0, C1, false, 1>(xp, n_cu, stream);
-                case 2: return launch_x3_cfg<0, C1, false, 2>(xp, n_cu, stream);
-                case 4: return launch_x3_cfg<0, C1, false, 4>(xp, n_cu, stream);
-                case 6: return launch_x3_cfg<0, C1, false, 6>(xp, n_cu, stream);
-                case 8: return launch_x3_cfg<0, C1, false, 8>(xp, n_cu, stream);
-                case 14: return launch_x3_cfg<0, C1, false, 14>(xp, n_cu, stream);
-                case 16: return launch_x3_cfg<0, C1, false, 16>(xp, n_cu, stream);
-                case 30: return launch_x3_cfg<0, C1, false, 30>(xp, n_cu, stream);
-                default: break;
-            }
-        }
-    }
     switch (t) {
         case 1: return launch_x3_cfg<FLAGS, X3Cfg<2, 4, 4, 2>, LN>(xp, n_cu, stream);
         case 2: return launch_x3_cfg<FLAGS, X3Cfg<4, 2, 2, 2>, LN>(xp, n_cu, stream);
@@ -478,7 +435,7 @@ extern "C" int omnitok_gemm_x3(const float *a, int64_t lda, const float *w, int6
     p.M = M; p.N = N; p.K = K;
     p.a_rpg = a_rows_per_group; p.a_stride = a_group_stride; p.a_off = a_group_offset;
     p.gn = 8;
-    p.trace = g_gemm_trace;
+    p.trace = nullptr;
     xp.ln_stats = ln_stats; xp.ln_gamma = ln_gamma; xp.ln_beta = ln_beta; xp.ln_cols = ln ? ln_cols : 0;
     xp.c2 = c2; xp.ldc2 = ldc2; xp.split_col = split_col;
 #define X3_CASE(F)                                                    \

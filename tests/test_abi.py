@@ -302,3 +302,36 @@ def test_option_reads_back_what_was_set(lib, name):
     v = ctypes.c_int(-12345)
     assert lib.omnitok_get_option(b"lm_no_such_option", ctypes.byref(v)) == -1 and v.value == -12345
     assert b"lm_no_such_option" in lib.omnitok_last_error()
+
+
+def test_option_table_settable_readable_and_retired_names(lib):
+    """The one option table behind omnitok_set_option / omnitok_get_option: every readable option round-trips, the minimum of
+    lm_loss_chunk_rows holds, the retired ablation switches are unknown names, and a settable option outside the readable subset
+    still cannot be read."""
+    readable = ["gemm_mode", "attn_mode", "gemm_pl", "pl_min_tokens", "temporal_chunk", "prevq_fuse", "pl_cfg", "pl_tail",
+                "sp_small_blocks", "lm_wide_u", "lm_balance", "lm_ksliced", "lm_mfma", "lm_mfma_mult", "lm_ks_deep",
+                "lm_attn_short", "lm_attn_waves", "lm_loss_chunk_rows"]
+    for name in readable:
+        before, v = ctypes.c_int(), ctypes.c_int()
+        assert lib.omnitok_get_option(name.encode(), ctypes.byref(before)) == 0, name
+        try:
+            assert lib.omnitok_set_option(name.encode(), before.value + 5) == 0, name
+            assert lib.omnitok_get_option(name.encode(), ctypes.byref(v)) == 0 and v.value == before.value + 5, name
+        finally:
+            assert lib.omnitok_set_option(name.encode(), before.value) == 0
+        assert lib.omnitok_get_option(name.encode(), ctypes.byref(v)) == 0 and v.value == before.value, name
+
+    rows = ctypes.c_int()
+    assert lib.omnitok_get_option(b"lm_loss_chunk_rows", ctypes.byref(rows)) == 0 and rows.value >= 1
+    assert lib.omnitok_set_option(b"lm_loss_chunk_rows", 0) == -1
+    assert b"lm_loss_chunk_rows 0, expected at least 1" in lib.omnitok_last_error()
+    v = ctypes.c_int()
+    assert lib.omnitok_get_option(b"lm_loss_chunk_rows", ctypes.byref(v)) == 0 and v.value == rows.value
+
+    for name in b"h2_dbg x3_dbg attn_h2_dbg no_such_option".split():   # the three retired switches and a made-up name
+        assert lib.omnitok_set_option(name, 1) == -1, name
+        assert b"unknown option " + name in lib.omnitok_last_error(), name
+
+    v = ctypes.c_int(-12345)   # settable, but outside the readable subset (not set here: its value could not be restored)
+    assert lib.omnitok_get_option(b"gemm_variant", ctypes.byref(v)) == -1 and v.value == -12345
+    assert b"gemm_variant is not a readable option" in lib.omnitok_last_error()

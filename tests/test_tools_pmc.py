@@ -18,8 +18,8 @@ def _csv(path, header, rows):
 
 
 def test_family_means_units_and_stamp(tmp_path):
-    ff = '"void omnitok::gemm_pl_kernel<1, false, omnitok::PlCfg<4, 2, 4, 2, 0, 2, 4> >(omnitok::PlParams)"'
-    f32 = '"void omnitok::gemm_pl_kernel<0, false, omnitok::PlCfg<4, 2, 4, 2, 0, 2, 4> >(omnitok::PlParams)"'
+    ff = '"void omnitok::gemm_pl_kernel<1, false, omnitok::PlCfg<4, 2, 4, 2, 2, 4> >(omnitok::PlParams)"'
+    f32 = '"void omnitok::gemm_pl_kernel<0, false, omnitok::PlCfg<4, 2, 4, 2, 2, 4> >(omnitok::PlParams)"'
     fetch, write, mfma = tmp_path / "f.csv", tmp_path / "w.csv", tmp_path / "m.csv"
     _csv(fetch, ["kernel", "dispatches", "mean_us_under_pmc", "mean_FETCH_SIZE"], [[ff, 16, 1300.0, 1000.0], [f32, 26, 700.0, 500.0],
                                                                                    ["other_kernel", 3, 1.0, 7.0]])

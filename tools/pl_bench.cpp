@@ -53,14 +53,13 @@ struct Shape { const char *name; int N, K; bool geglu, residual; bool rowln = fa
 int main(int argc, char **argv) {
     int iters = 10;
     bool check = false;
-    std::string only, cfgs = "1,2", h2dbg;
+    std::string only, cfgs = "1,2";
     int64_t L = 32 * 5120;
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "--iters")) iters = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--shape")) only = argv[++i];
         else if (!strcmp(argv[i], "--cfg")) cfgs = argv[++i];
         else if (!strcmp(argv[i], "--check")) check = true;
-        else if (!strcmp(argv[i], "--h2dbg")) h2dbg = argv[++i];  // ablation builds of the h2 kernel (plain shapes only)
         else if (!strcmp(argv[i], "--rows")) L = atoll(argv[++i]);
         else if (!strcmp(argv[i], "--opt")) {  // --opt name value: omnitok_set_option
             const char *n = argv[++i];
@@ -146,17 +145,6 @@ int main(int argc, char **argv) {
         {
             const float ms = time_it(run_h2);
             printf("   h2 (fp32 A, in-loop split)     %.4f ms  %6.1f TF\n", ms, flops / ms / 1e9);
-        }
-        if (!sh.geglu && !sh.residual && !sh.rowln) {
-            for (size_t pos = 0; pos < h2dbg.size();) {
-                const int dbg = atoi(h2dbg.c_str() + pos);
-                size_t nx = h2dbg.find(',', pos);
-                pos = nx == std::string::npos ? h2dbg.size() : nx + 1;
-                OK(omnitok_set_option("h2_dbg", dbg));
-                const float ms = time_it(run_h2);
-                OK(omnitok_set_option("h2_dbg", 0));
-                printf("   h2 ablation build dbg=%-2d        %.4f ms  %6.1f TF\n", dbg, ms, flops / ms / 1e9);
-            }
         }
         for (size_t pos = 0; pos < cfgs.size();) {
             const int cfg = atoi(cfgs.c_str() + pos);
