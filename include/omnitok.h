@@ -121,81 +121,91 @@ int omnitok_layernorm_prevq(const float *x, const float *gamma, const float *bet
                             float *z, int64_t n, int a, int c, int dim, float eps, int transpose, int l2,
                             omnitok_stream_t stream);
 
-/* Epilogue flags of omnitok_gemm */
+/* Epilogue flags of omnitok_row_gemm */
 #define OMNITOK_GEMM_BIAS 1      /* + bias[n]                                               */
 #define OMNITOK_GEMM_RESIDUAL 2  /* + residual[m, n] (may alias c)                           */
 #define OMNITOK_GEMM_GEGLU 4     /* c[m, j] = gelu(acc[m, gate j]) * acc[m, value j]; weight  */
                                  /* rows pre-interleaved by omnitok_pack_geglu_weight         */
 #define OMNITOK_GEMM_LEAKY 8     /* leaky_relu(., 0.1) after bias                              */
 
-/* c[M,N] = a[M,K] . w[N,K]^T (+epilogue), fp32 in / fp32 accumulate on v_mfma_f32_32x32x2_f32.
- * This is nn.Linear (y = x W^T + b) as used by every projection on the path
- * (attention.py:164,167,271,287,386-393; omnitokenizer.py:146,158,810,819,1007,1013).
- * K % 32 == 0; lda, ldw % 4 == 0; pointers 16-byte aligned. With GEGLU, N is the packed width
- * (2 * padded inner) and c has N/2 columns.
- * a_row(m) = (m / a_rows_per_group) * a_group_stride + a_group_offset + m % a_rows_per_group
- * (0 = identity) lets the A operand be read from a strided group of token rows. */
-int omnitok_gemm(const float *a, int64_t lda, const float *w, int64_t ldw, const float *bias,
-                 const float *residual, int64_t ldr, float *c, int64_t ldc,
-                 int64_t M, int N, int K, int flags,
-                 int64_t a_rows_per_group, int64_t a_group_stride, int64_t a_group_offset,
-                 omnitok_stream_t stream);
-
-/* --- fp32 GEMM on the bf16 matrix cores, operands split in-kernel (csrc/gemm_x3.hip) ----------------
- * Same contract as omnitok_gemm (c = a . w^T + epilogue, fp32 operands in HBM, fp32 result) but each
- * fp32 operand element is split exactly into three bf16 numbers while it is staged to LDS and six
- * v_mfma_f32_32x32x16_bf16 products per element pair are accumulated in fp32 (the three dropped
- * products are < 2^-24 |a b|).  K % 32 == 0, N % 32 == 0.  The per-element arithmetic does not depend
- * on M, N or the tile shape, so results are independent of the batch size.
- * Optional fused LayerNorm of the A operand (reference attention.py:73-80,163: the norm that precedes
- * to_q / qkv / the FeedForward's first Linear): ln_stats[rows][2] = (mean, rstd) per PHYSICAL a row
- * (omnitok_row_stats), ln_gamma[K], ln_beta[K] (NULL = 0), K <= 512; output columns [0, ln_cols) are
- * computed from LN(a), columns [ln_cols, N) from a itself (Q from LN(x), K/V from x in one launch,
- * attention.py:404-412).  ln_stats == NULL: no LayerNorm.
- * split_col > 0 (a multiple of 256, plain / bias epilogues only): output columns [split_col, N) are written
- * to c2 (row stride ldc2) instead of c, so that one launch produces Q and K|V as two dense tensors. */
-int omnitok_gemm_x3(const float *a, int64_t lda, const float *w, int64_t ldw, const float *bias,
-                    const float *residual, int64_t ldr, float *c, int64_t ldc,
-                    int64_t M, int N, int K, int flags,
-                    int64_t a_rows_per_group, int64_t a_group_stride, int64_t a_group_offset,
-                    const float *ln_stats, const float *ln_gamma, const float *ln_beta, int ln_cols,
-                    float *c2, int64_t ldc2, int split_col, omnitok_stream_t stream);
-/* --- fp32 GEMM on the fp16 matrix cores, 2-way split operands (csrc/gemm_h2.hip) ---------------------
- * c = a . w^T (+epilogue as omnitok_gemm) with each operand element a' = hi + lo (two fp16 numbers, 22
- * significand bits) and three v_mfma_f32_32x32x16_f16 products per element pair, fp32 accumulation.
- * The weight is packed once by omnitok_h2_pack_weight (row-scaled by a power of two, split, in blocks of 64
- * rows x 32 k: planes[ceil(N/64)][K/32][hi|lo][4][64][8] fp16 = 4 bytes per element, scale[N]).  fp16 has 5 exponent bits, so the caller
- * states an UPPER BOUND of |a|: a_bound (> 0), multiplied by a_bound_dev[a_bound_stride * (m /
- * a_rows_per_clip)] for row m when that device pointer is given (bounds produced by an earlier kernel, e.g.
- * omnitok_row_stats; a_rows_per_clip <= 0: one value for all rows); the kernel scales the rows of a clip by
- * one power of two so that |a'| <= 2^15 (tiles never straddle clips: a_rows_per_clip % 64 == 0).  A wrong (too small) bound overflows to inf; elements more than
- * 2^18 below the bound lose relative precision (absolute error <= 2^-40 of the bound).
- * Fused LayerNorm as omnitok_gemm_x3, with ln_bound >= max |LN(a)| (sqrt(K) max|gamma| + max|beta|).
- * K % 32 == 0, N % 32 == 0.  Results are independent of M and of the tile shape. */
+/* --- nn.Linear on fp32 rows: c[M,N] = a[M,K] . w[N,K]^T (+epilogue), three kernels behind one descriptor -----------
+ * (y = x W^T + b as used by every projection on the path: attention.py:164,167,271,287,386-393;
+ * omnitokenizer.py:146,158,810,819,1007,1013).  The entry point names the kernel:
+ *   omnitok_gemm     fp32 in / fp32 accumulate on v_mfma_f32_32x32x2_f32 (csrc/gemm.hip).  K % 32 == 0.
+ *   omnitok_gemm_x3  each fp32 operand element is split exactly into three bf16 numbers while it is staged to LDS and six
+ *                    v_mfma_f32_32x32x16_bf16 products per element pair are accumulated in fp32 (the three dropped products
+ *                    are < 2^-24 |a b|; csrc/gemm_x3.hip).  K % 32 == 0, N % 32 == 0.
+ *   omnitok_gemm_h2  each operand element a' = hi + lo (two fp16 numbers, 22 significand bits), three
+ *                    v_mfma_f32_32x32x16_f16 products per element pair, fp32 accumulation (csrc/gemm_h2.hip).  The weight
+ *                    is packed once by omnitok_h2_pack_weight (row-scaled by a power of two, split, in blocks of 64 rows x
+ *                    32 k: planes[ceil(N/64)][K/32][hi|lo][4][64][8] fp16 = 4 bytes per element, scale[N]).
+ *                    K % 32 == 0, N % 32 == 0.
+ * The per-element arithmetic of x3 and h2 does not depend on M, N or the tile shape: results are independent of the batch
+ * size.  A zero-initialised descriptor means "nothing optional".  A field that selects something the called kernel does
+ * not implement (w_planes outside h2, w for h2, ln_stats / split_col for omnitok_gemm, v_planes outside h2) is refused
+ * with OMNITOK_ERR_INVALID; the range statements (a_bound*, a_rows_per_clip, ln_bound) are ignored by the kernels that need
+ * no range, and the operands of an option that is off (ln_* without ln_stats, c2 without split_col, v_* without v_planes)
+ * are not looked at. */
+typedef struct omnitok_row_gemm {
+    const float *a;             /* [M, lda] fp32 rows; 16-byte aligned, lda % 4 == 0                              */
+    int64_t lda;
+    const float *w;             /* gemm, x3: weight [N, ldw] fp32; 16-byte aligned, ldw % 4 == 0.  h2: NULL        */
+    int64_t ldw;
+    const void *w_planes;       /* h2: planes and scale[N] of omnitok_h2_pack_weight (ld = K).  gemm, x3: NULL     */
+    const float *w_scale;
+    const float *bias;          /* [N], with OMNITOK_GEMM_BIAS                                                    */
+    const float *residual;      /* [M, ldr], with OMNITOK_GEMM_RESIDUAL (may alias c)                             */
+    int64_t ldr;
+    float *c;                   /* [M, ldc]; with GEGLU, N is the packed width (2 * padded inner) and c has N / 2  */
+    int64_t ldc;                /* columns                                                                        */
+    int64_t M;
+    int N, K;
+    int flags;                  /* OMNITOK_GEMM_*; LEAKY only for omnitok_gemm                                    */
+    /* a_row(m) = (m / a_rows_per_group) * a_group_stride + a_group_offset + m % a_rows_per_group (0 = identity): the A
+     * operand read from a strided group of token rows */
+    int64_t a_rows_per_group, a_group_stride, a_group_offset;
+    /* h2: fp16 has 5 exponent bits, so the caller states an UPPER BOUND of |a|: a_bound (> 0), multiplied by
+     * a_bound_dev[a_bound_stride * (m / a_rows_per_clip)] for row m when that device pointer is given (bounds produced by an
+     * earlier kernel, e.g. omnitok_row_stats; a_rows_per_clip <= 0: one value for all rows; stride 0 = 1); the kernel
+     * scales the rows of a clip by one power of two so that |a'| <= 2^15 (tiles never straddle clips:
+     * a_rows_per_clip % 64 == 0).  A wrong (too small) bound overflows to inf; elements more than 2^18 below the bound
+     * lose relative precision (absolute error <= 2^-40 of the bound). */
+    float a_bound;
+    const float *a_bound_dev;
+    int a_bound_stride;
+    int64_t a_rows_per_clip;
+    /* x3, h2: LayerNorm of the A operand fused into its staging (reference attention.py:73-80,163: the norm that precedes
+     * to_q / qkv / the FeedForward's first Linear).  ln_stats[rows][2] = (mean, rstd) per PHYSICAL a row
+     * (omnitok_row_stats) or NULL = no LayerNorm; ln_gamma[K], ln_beta[K] (NULL = 0), K <= 512; output columns
+     * [0, ln_cols) are computed from LN(a), columns [ln_cols, N) from a itself (Q from LN(x), K/V from x in one launch,
+     * attention.py:404-412); h2: ln_bound >= max |LN(a)| (sqrt(K) max|gamma| + max|beta|). */
+    const float *ln_stats;
+    const float *ln_gamma;
+    const float *ln_beta;
+    int ln_cols;
+    float ln_bound;
+    /* x3, h2: split_col > 0 (a multiple of 256, plain / bias epilogues only): output columns [split_col, N) are written to
+     * c2 (row stride ldc2) instead of c, so that one launch produces Q and K|V as two dense tensors */
+    float *c2;
+    int64_t ldc2;
+    int split_col;
+    /* h2: v_planes != NULL -- columns [v_col0, N), the V projection of a merged to_q | to_kv launch (reference
+     * attention.py:404-412), are not stored as fp32 but written straight into the packed fp16 hi|lo V planes of
+     * omnitok_attn_spatial_h2 (the 32x32 MFMA accumulator layout is that layout), bit-identical to storing them and running
+     * omnitok_attn_pack on the result.  Needs flags == 0, the fused LayerNorm, v_col0 % 256 == 0, N - v_col0 == heads * 64,
+     * M a whole number of n_tokens-row sequences (n_tokens % 32 == 0) and a_rows_per_clip % 128 == 0; v_bound (times
+     * v_bound_dev[v_bound_stride * clip], stride 0 = 1) >= max|v|. */
+    void *v_planes;
+    int v_col0, n_tokens, heads;
+    float v_bound;
+    const float *v_bound_dev;
+    int v_bound_stride;
+} omnitok_row_gemm;
+int omnitok_gemm(const omnitok_row_gemm *g, omnitok_stream_t stream);
+int omnitok_gemm_x3(const omnitok_row_gemm *g, omnitok_stream_t stream);
 int omnitok_h2_pack_weight(const float *w, int64_t ldw, int N, int K, void *planes, float *scale,
                            omnitok_stream_t stream);
-int omnitok_gemm_h2(const float *a, int64_t lda, const void *w_planes, const float *w_scale,
-                    const float *bias, const float *residual, int64_t ldr, float *c, int64_t ldc,
-                    int64_t M, int N, int K, int flags,
-                    int64_t a_rows_per_group, int64_t a_group_stride, int64_t a_group_offset,
-                    float a_bound, const float *a_bound_dev, int a_bound_stride, int64_t a_rows_per_clip,
-                    const float *ln_stats, const float *ln_gamma, const float *ln_beta, int ln_cols,
-                    float ln_bound, float *c2, int64_t ldc2, int split_col, omnitok_stream_t stream);
-/* omnitok_gemm_h2 whose columns [v_col0, N) -- the V projection of a merged to_q | to_kv launch (reference
- * attention.py:404-412) -- are not stored as fp32 but written straight into the packed fp16 hi|lo V planes of
- * omnitok_attn_spatial_h2 (the 32x32 MFMA accumulator layout is that layout), bit-identical to storing them and
- * running omnitok_attn_pack on the result.  v_planes NULL: plain omnitok_gemm_h2.  Needs flags == 0, the fused
- * LayerNorm, v_col0 % 256 == 0, N - v_col0 == heads * 64, M a whole number of n_tokens-row sequences
- * (n_tokens % 32 == 0) and a_rows_per_clip % 128 == 0; v_bound (times v_bound_dev[v_bound_stride * clip]) >= max|v|. */
-int omnitok_gemm_h2_vpack(const float *a, int64_t lda, const void *w_planes, const float *w_scale,
-                          const float *bias, const float *residual, int64_t ldr, float *c, int64_t ldc,
-                          int64_t M, int N, int K, int flags,
-                          int64_t a_rows_per_group, int64_t a_group_stride, int64_t a_group_offset,
-                          float a_bound, const float *a_bound_dev, int a_bound_stride, int64_t a_rows_per_clip,
-                          const float *ln_stats, const float *ln_gamma, const float *ln_beta, int ln_cols,
-                          float ln_bound, float *c2, int64_t ldc2, int split_col, void *v_planes, int v_col0,
-                          int n_tokens, int heads, float v_bound, const float *v_bound_dev, int v_bound_stride,
-                          omnitok_stream_t stream);
+int omnitok_gemm_h2(const omnitok_row_gemm *g, omnitok_stream_t stream);
 /* --- plane x plane GEMM (csrc/gemm_pl.h, gemm_pl.hip) --------------------------------------------------------
  * The arithmetic of omnitok_gemm_h2 with BOTH operands already stored as fp16 hi|lo planes in blocks of 64 rows
  * x 32 k ([rows/64][K/32][hi|lo][4 k groups][64 rows][8] fp16, 8 KiB per block): the K loop is LDS-DMA + ds_read +
@@ -402,7 +412,7 @@ int omnitok_attn_spatial(const float *q, int64_t ldq, const float *k, const floa
  *     hi|lo planes in MFMA-fragment order: qp / kp / vp are rows*heads*64*4 bytes each (blocks of 32 tokens of
  *     one head, 8 KiB).  q_bound >= max|q| (= scale * max|q_scale|), k_bound >= max|k| (= max|k_scale|);
  *     v_bound (times v_bound_dev[v_bound_stride * clip] if given, clip = row / rows_per_clip) >= max|v| of the
- *     rows of a clip.  n_tokens % 32 == 0.  v == vp == NULL: only q and k (V written by omnitok_gemm_h2_vpack).
+ *     rows of a clip.  n_tokens % 32 == 0.  v == vp == NULL: only q and k (V written by omnitok_gemm_h2 with v_planes).
  *   omnitok_attn_spatial_h2: out[Bn*N, heads*64] = softmax(q k^T [+ bias]) v from the packed operands; the same
  *     bounds must be passed (they define the power-of-two operand scales); seq_per_clip = sequences per clip
  *     for v_bound_dev.  N % 64 == 0. */

@@ -55,6 +55,21 @@ class OmnitokPlGemm(Structure):
     ]
 
 
+class OmnitokRowGemm(Structure):
+    """omnitok_row_gemm (include/omnitok.h): arguments of omnitok_gemm / omnitok_gemm_x3 / omnitok_gemm_h2."""
+    _fields_ = [
+        ("a", c_void_p), ("lda", c_int64), ("w", c_void_p), ("ldw", c_int64), ("w_planes", c_void_p), ("w_scale", c_void_p),
+        ("bias", c_void_p), ("residual", c_void_p), ("ldr", c_int64), ("c", c_void_p), ("ldc", c_int64),
+        ("M", c_int64), ("N", c_int), ("K", c_int), ("flags", c_int),
+        ("a_rows_per_group", c_int64), ("a_group_stride", c_int64), ("a_group_offset", c_int64),
+        ("a_bound", c_float), ("a_bound_dev", c_void_p), ("a_bound_stride", c_int), ("a_rows_per_clip", c_int64),
+        ("ln_stats", c_void_p), ("ln_gamma", c_void_p), ("ln_beta", c_void_p), ("ln_cols", c_int), ("ln_bound", c_float),
+        ("c2", c_void_p), ("ldc2", c_int64), ("split_col", c_int),
+        ("v_planes", c_void_p), ("v_col0", c_int), ("n_tokens", c_int), ("heads", c_int), ("v_bound", c_float),
+        ("v_bound_dev", c_void_p), ("v_bound_stride", c_int),
+    ]
+
+
 class OmnitokFramesDesc(Structure):
     """omnitok_frames_desc (include/omnitok.h): one uint8 clip of omnitok_frames_to_pixels."""
     _fields_ = [("frames", c_void_p), ("frame_stride", c_int64), ("row_stride", c_int64),
@@ -95,14 +110,10 @@ I64 = c_int64
 # name -> argtypes (restype is int unless listed in _RESTYPES); mirrors include/omnitok.h
 _PROTOS = {
     "omnitok_layernorm": [P, P, P, P, I64, c_int, c_float, I64, I64, I64, P],
-    "omnitok_gemm": [P, I64, P, I64, P, P, I64, P, I64, I64, c_int, c_int, c_int, I64, I64, I64, P],
-    "omnitok_gemm_x3": [P, I64, P, I64, P, P, I64, P, I64, I64, c_int, c_int, c_int, I64, I64, I64, P, P, P, c_int, P, I64,
-                        c_int, P],
+    "omnitok_gemm": [POINTER(OmnitokRowGemm), P],
+    "omnitok_gemm_x3": [POINTER(OmnitokRowGemm), P],
     "omnitok_h2_pack_weight": [P, I64, c_int, c_int, P, P, P],
-    "omnitok_gemm_h2": [P, I64, P, P, P, P, I64, P, I64, I64, c_int, c_int, c_int, I64, I64, I64, c_float, P, c_int,
-                        I64, P, P, P, c_int, c_float, P, I64, c_int, P],
-    "omnitok_gemm_h2_vpack": [P, I64, P, P, P, P, I64, P, I64, I64, c_int, c_int, c_int, I64, I64, I64, c_float, P, c_int,
-                              I64, P, P, P, c_int, c_float, P, I64, c_int, P, c_int, c_int, c_int, c_float, P, c_int, P],
+    "omnitok_gemm_h2": [POINTER(OmnitokRowGemm), P],
     "omnitok_row_stats": [P, I64, c_int, c_float, P, P, I64, P],
     "omnitok_weight_range": [P, I64, c_int, c_int, P, P],
     "omnitok_pack_geglu_weight": [P, c_int, c_int, c_int, P, P],

@@ -99,7 +99,7 @@ __global__ __launch_bounds__(256) void attn_pack_kernel(PackParams p) {
         }
     }
     // ---- V: lane = channel d, each wave takes two key quads (j, ii, h): four keys 16 j + 8 ii + 4 h + r --------
-    //      (skipped when the q|k|v GEMM already wrote the V planes from its epilogue: omnitok_gemm_h2_vpack)
+    //      (skipped when the q|k|v GEMM already wrote the V planes from its epilogue: omnitok_gemm_h2 with v_planes)
     if (p.vp) {
         const int lane = tid & 63, wave = tid >> 6;
         const int mt = lane >> 5, dd = lane & 31;

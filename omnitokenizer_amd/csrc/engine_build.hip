@@ -579,16 +579,18 @@ int get_bias_table(omnitok_engine *e, const std::string &prefix, int gh, int gw,
                            W(e, prefix + ".net.0.0.weight"), c.dim, 2, 32, w0p);
         OT_LAUNCH_CHECK("pad_cols");
     }
-    const int BL = OMNITOK_GEMM_BIAS | OMNITOK_GEMM_LEAKY;
-    if (int rc = omnitok_gemm(dfeat, 32, w0p, 32, W(e, prefix + ".net.0.0.bias"), nullptr, 0, h0, c.dim, P, c.dim, 32,
-                              BL, 0, 0, 0, stream))
-        return rc;
-    if (int rc = omnitok_gemm(h0, c.dim, W(e, prefix + ".net.1.0.weight"), c.dim, W(e, prefix + ".net.1.0.bias"),
-                              nullptr, 0, h1, c.dim, P, c.dim, c.dim, BL, 0, 0, 0, stream))
-        return rc;
-    if (int rc = omnitok_gemm(h1, c.dim, W(e, prefix + ".net.2.weight"), c.dim, W(e, prefix + ".net.2.bias"), nullptr,
-                              0, tab, c.heads, P, c.heads, c.dim, OMNITOK_GEMM_BIAS, 0, 0, 0, stream))
-        return rc;
+    // the three Linear layers of the MLP, leaky_relu(0.1) after the first two
+    auto linear = [&](const float *a, int K, const float *w, const float *bias, float *out, int N, bool leaky) {
+        omnitok_row_gemm g = {};
+        g.a = a; g.lda = K; g.w = w; g.ldw = K;
+        g.bias = bias; g.c = out; g.ldc = N;
+        g.M = P; g.N = N; g.K = K;
+        g.flags = OMNITOK_GEMM_BIAS | (leaky ? OMNITOK_GEMM_LEAKY : 0);
+        return omnitok_gemm(&g, stream);
+    };
+    if (int rc = linear(dfeat, 32, w0p, W(e, prefix + ".net.0.0.bias"), h0, c.dim, true)) return rc;
+    if (int rc = linear(h0, c.dim, W(e, prefix + ".net.1.0.weight"), W(e, prefix + ".net.1.0.bias"), h1, c.dim, true)) return rc;
+    if (int rc = linear(h1, c.dim, W(e, prefix + ".net.2.weight"), W(e, prefix + ".net.2.bias"), tab, c.heads, false)) return rc;
     e->bias_tables[key] = tab;
     *out = tab;
     return OMNITOK_OK;

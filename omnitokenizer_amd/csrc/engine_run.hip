@@ -90,32 +90,33 @@ float *next_bounds(omnitok_engine *e) {  // [n_clips][2] slots of one row-statis
 }
 
 int eg_gemm(omnitok_engine *e, const EgGemm &g, hipStream_t stream, bool *vpacked) {
+    omnitok_row_gemm d = {};
+    d.a = g.a; d.lda = g.lda; d.w = g.w; d.ldw = g.ldw;
+    d.bias = g.bias; d.residual = g.residual; d.ldr = g.ldr; d.c = g.c; d.ldc = g.ldc;
+    d.M = g.M; d.N = g.N; d.K = g.K; d.flags = g.flags;
+    d.a_rows_per_group = g.rpg; d.a_group_stride = g.gstride; d.a_group_offset = g.goff;
+    d.a_bound = g.ab.stat; d.a_bound_dev = g.ab.dev; d.a_bound_stride = 2; d.a_rows_per_clip = g.ab.rpc;
+    d.ln_stats = g.ln_stats; d.ln_gamma = g.ln_g; d.ln_beta = g.ln_b; d.ln_cols = g.ln_cols; d.ln_bound = g.ln_bound;
+    d.c2 = g.c2; d.ldc2 = g.ldc2; d.split_col = g.split_col;
     if (gemm_mode_of(e) == 2 && g.ab.stat > 0.0f && x3_ok(e, g.N, g.K, g.flags) && (!g.ln_stats || g.ln_bound > 0.0f) &&
         (!g.ab.dev || (g.ab.rpc > 0 && g.ab.rpc % 64 == 0 && g.rpg == 0))) {
         auto it = e->h2w.find(g.w);
         if (it != e->h2w.end() && g.ldw == g.K) {
+            d.w = nullptr; d.ldw = 0; d.w_planes = it->second.pl; d.w_scale = it->second.sc;
             if (g.vpk && g.ab.dev && g.ab.rpc % 128 == 0) {  // V columns straight into the attention kernel's fp16 planes
                 *vpacked = true;
-                return omnitok_gemm_h2_vpack(g.a, g.lda, it->second.pl, it->second.sc, g.bias, g.residual, g.ldr, g.c, g.ldc, g.M,
-                                             g.N, g.K, g.flags, g.rpg, g.gstride, g.goff, g.ab.stat, g.ab.dev, 2, g.ab.rpc,
-                                             g.ln_stats, g.ln_g, g.ln_b, g.ln_cols, g.ln_bound, g.c2, g.ldc2, g.split_col,
-                                             g.vpk->planes, g.vpk->col0, g.vpk->n_tokens, g.vpk->heads, g.vpk->bound,
-                                             g.vpk->bound_dev, 2, stream);
+                d.v_planes = g.vpk->planes; d.v_col0 = g.vpk->col0; d.n_tokens = g.vpk->n_tokens; d.heads = g.vpk->heads;
+                d.v_bound = g.vpk->bound; d.v_bound_dev = g.vpk->bound_dev; d.v_bound_stride = 2;
             }
-            return omnitok_gemm_h2(g.a, g.lda, it->second.pl, it->second.sc, g.bias, g.residual, g.ldr, g.c, g.ldc, g.M, g.N, g.K,
-                                   g.flags, g.rpg, g.gstride, g.goff, g.ab.stat, g.ab.dev, 2, g.ab.rpc, g.ln_stats, g.ln_g, g.ln_b,
-                                   g.ln_cols, g.ln_bound, g.c2, g.ldc2, g.split_col, stream);
+            return omnitok_gemm_h2(&d, stream);
         }
     }
-    if (x3_ok(e, g.N, g.K, g.flags))
-        return omnitok_gemm_x3(g.a, g.lda, g.w, g.ldw, g.bias, g.residual, g.ldr, g.c, g.ldc, g.M, g.N, g.K, g.flags, g.rpg,
-                               g.gstride, g.goff, g.ln_stats, g.ln_g, g.ln_b, g.ln_cols, g.c2, g.ldc2, g.split_col, stream);
+    if (x3_ok(e, g.N, g.K, g.flags)) return omnitok_gemm_x3(&d, stream);
     if (g.ln_stats) {
         set_error("eg_gemm: fused LayerNorm needs the x3 / h2 kernel");
         return OMNITOK_ERR_STATE;
     }
-    return omnitok_gemm(g.a, g.lda, g.w, g.ldw, g.bias, g.residual, g.ldr, g.c, g.ldc, g.M, g.N, g.K, g.flags, g.rpg, g.gstride,
-                        g.goff, stream);
+    return omnitok_gemm(&d, stream);
 }
 
 // plane x plane GEMM of the engine: the weight is looked up by its fp32 pointer

@@ -16,7 +16,7 @@
 //  * epilogues (bias, residual add, GEGLU, leaky-relu) are fused on the accumulator registers.
 // fp32 MFMA is bitwise a k-ordered fmaf chain, so the result differs from the reference's MKL
 // GEMM only by summation order (~1e-7 relative).
-#include "gemm_common.h"
+#include "gemm_row_host.h"
 
 namespace omnitok {
 
@@ -539,27 +539,21 @@ __global__ void pack_geglu_kernel(const float *w1, int inner, int K, int inner_p
 
 using namespace omnitok;
 
-extern "C" int omnitok_gemm(const float *a, int64_t lda, const float *w, int64_t ldw, const float *bias,
-                            const float *residual, int64_t ldr, float *c, int64_t ldc, int64_t M, int N,
-                            int K, int flags, int64_t a_rows_per_group, int64_t a_group_stride,
-                            int64_t a_group_offset, omnitok_stream_t stream_) {
+extern "C" int omnitok_gemm(const omnitok_row_gemm *d, omnitok_stream_t stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    OT_CHECK_ARG(a && w && c, "gemm: null pointer");
-    OT_CHECK_ARG(M >= 0 && N > 0 && K > 0, "gemm: bad sizes M=%lld N=%d K=%d", (long long)M, N, K);
-    if (M == 0) return OMNITOK_OK;
-    OT_CHECK_ARG(K % BK == 0, "gemm: K=%d must be a multiple of %d (pad the weight)", K, BK);
-    OT_CHECK_ARG(lda % 4 == 0 && ldw % 4 == 0 && aligned16(a) && aligned16(w),
-                 "gemm: operands must be 16-byte aligned with ld %% 4 == 0");
-    OT_CHECK_ARG(!(flags & OMNITOK_GEMM_BIAS) || bias, "gemm: BIAS flag without bias");
-    OT_CHECK_ARG(!(flags & OMNITOK_GEMM_RESIDUAL) || residual, "gemm: RESIDUAL flag without residual");
-    GemmParams p;
-    p.a = a; p.w = w; p.bias = bias; p.residual = residual; p.c = c;
-    p.lda = lda; p.ldw = ldw; p.ldr = ldr; p.ldc = ldc;
-    p.M = M; p.N = N; p.K = K;
-    p.nbn = (N + BN - 1) / BN;
-    p.a_rpg = a_rows_per_group; p.a_stride = a_group_stride; p.a_off = a_group_offset;
-    p.gn = g_gemm_gn > 0 ? g_gemm_gn : 8;
-    switch (flags) {
+    OT_CHECK_ARG(d, "gemm: null descriptor");
+    OT_ROW_GEMM_REFUSE("gemm", d, w_planes);
+    OT_ROW_GEMM_REFUSE("gemm", d, ln_stats);
+    OT_ROW_GEMM_REFUSE("gemm", d, split_col);
+    OT_ROW_GEMM_REFUSE("gemm", d, v_planes);
+    if (int rc = row_gemm_check_shape("gemm", *d, d->w != nullptr)) return rc;
+    if (d->M == 0) return OMNITOK_OK;
+    static_assert(BK == 32, "row_gemm_check_w_rows states the K granularity");
+    if (int rc = row_gemm_check_w_rows("gemm", *d, 1)) return rc;
+    if (int rc = row_gemm_check_options("gemm", *d, false)) return rc;
+    GemmParams p = row_gemm_params(*d, g_gemm_gn > 0 ? g_gemm_gn : 8);
+    p.nbn = (d->N + BN - 1) / BN;
+    switch (d->flags) {
         case 0: return launch_gemm<0>(p, stream);
         case OMNITOK_GEMM_BIAS: return launch_gemm<OMNITOK_GEMM_BIAS>(p, stream);
         case OMNITOK_GEMM_RESIDUAL: return launch_gemm<OMNITOK_GEMM_RESIDUAL>(p, stream);
@@ -568,10 +562,10 @@ extern "C" int omnitok_gemm(const float *a, int64_t lda, const float *w, int64_t
         case OMNITOK_GEMM_BIAS | OMNITOK_GEMM_LEAKY:
             return launch_gemm<OMNITOK_GEMM_BIAS | OMNITOK_GEMM_LEAKY>(p, stream);
         case OMNITOK_GEMM_GEGLU:
-            OT_CHECK_ARG(N % BN == 0, "gemm: GEGLU packed width %d must be a multiple of %d", N, BN);
+            OT_CHECK_ARG(d->N % BN == 0, "gemm: GEGLU packed width %d must be a multiple of %d", d->N, BN);
             return launch_gemm<OMNITOK_GEMM_GEGLU>(p, stream);
         default:
-            set_error("gemm: unsupported epilogue flags %d", flags);
+            set_error("gemm: unsupported epilogue flags %d", d->flags);
             return OMNITOK_ERR_INVALID;
     }
 }

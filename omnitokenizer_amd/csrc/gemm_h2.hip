@@ -23,6 +23,7 @@
 // barrier per K-step, operands split while staged) with two planes per operand; the weight planes are
 // pre-split / pre-scaled once (omnitok_h2_pack_weight: [N][K/8][hi|lo][8] fp16, the same 4 B per
 // element as the fp32 weight) so only the A operand costs VALU work in the loop.
+#include "gemm_row_host.h"
 #include "gemm_x_common.h"
 #include "h2_common.h"
 
@@ -398,41 +399,12 @@ __global__ __launch_bounds__(256) void h2_pack_weight_kernel(const float *__rest
     }
 }
 
-template <int FLAGS, typename C, bool LN>
-static int launch_h2_cfg(H2Params hp, int n_cu, hipStream_t stream) {
-    GemmParams &p = hp.g;
-    const int lds = 2 * C::STAGE + (LN ? C::LN_TAB : 0);
-    if (int rc = set_max_dynamic_lds(reinterpret_cast<const void *>(gemm_h2_kernel<FLAGS, C, LN>), lds)) return rc;
-    const int64_t nbm = (p.M + C::TM - 1) / C::TM;
-    const int nbn = (p.N + C::TN - 1) / C::TN;
-    const int64_t nt = nbm * nbn;
-    OT_CHECK_ARG(nt < (1ll << 31), "gemm_h2: grid too large");
-    p.nbm = (int)nbm;
-    p.nbn = nbn;
-    p.ntiles = (int)nt;
-    int wg_per_cu = (160 * 1024) / lds;
-    const int by_waves = 8 / (C::NT / 64);
-    if (wg_per_cu > by_waves) wg_per_cu = by_waves;
-    if (wg_per_cu < 1) wg_per_cu = 1;
-    const int64_t cap = (int64_t)n_cu * wg_per_cu;
-    const int grid = (int)(nt < cap ? nt : cap);
-    hipLaunchKernelGGL((gemm_h2_kernel<FLAGS, C, LN>), dim3(grid), dim3(C::NT), lds, stream, hp);
-    OT_LAUNCH_CHECK("gemm_h2");
-    return OMNITOK_OK;
-}
-
 template <int FLAGS, bool LN>
 static int launch_h2(H2Params hp, hipStream_t stream) {
     int n_cu = 0;
     if (int rc = current_device_cus(&n_cu)) return rc;
     const GemmParams &p = hp.g;
-    auto tiles = [&](int tm, int tn) { return ((p.M + tm - 1) / tm) * (int64_t)((p.N + tn - 1) / tn); };
-    int t = g_h2_tile;
-    if (t == 0) {
-        if (tiles(256, 256) >= 2 * n_cu) t = 1;
-        else if (tiles(128, 128) >= n_cu) t = 3;
-        else t = 4;
-    }
+    int t = g_h2_tile ? g_h2_tile : split_auto_tile(p, n_cu);
     // a tile must lie inside one clip (one A scale per tile)
     const int64_t rpc = (hp.a_bound_dev && hp.a_rpc > 0) ? hp.a_rpc : 256;
     if ((t == 1 || t == 5) && rpc % 256) t = 3;
@@ -450,14 +422,17 @@ static int launch_h2(H2Params hp, hipStream_t stream) {
     // (measured at C3: 0.429 -> 0.380 ms; profiles/r02_h2_tile_experiment.txt)
     if (g_h2_tile == 0 && t == 1 && (FLAGS & OMNITOK_GEMM_RESIDUAL) && !LN && p.K <= 512 && rpc % 128 == 0) t = 6;
     constexpr bool GEGLU = (FLAGS & OMNITOK_GEMM_GEGLU) != 0;
+    auto go = [&](auto cfg) {
+        return launch_split_cfg<gemm_h2_kernel<FLAGS, decltype(cfg), LN>, decltype(cfg), LN>("gemm_h2", hp, n_cu, stream);
+    };
     switch (t) {
-        case 1: return launch_h2_cfg<FLAGS, H2Cfg<2, 4, 4, 2>, LN>(hp, n_cu, stream);
-        case 3: return launch_h2_cfg<FLAGS, H2Cfg<2, 2, 2, 2>, LN>(hp, n_cu, stream);
-        case 5: return launch_h2_cfg<FLAGS, H2Cfg<2, 2, 4, 2>, LN>(hp, n_cu, stream);  // 256x128, 2 WGs per CU
-        case 6: return launch_h2_cfg<FLAGS, H2Cfg<2, 2, 2, 4>, LN>(hp, n_cu, stream);  // 128x256, 2 WGs per CU
+        case 1: return go(H2Cfg<2, 4, 4, 2>{});
+        case 3: return go(H2Cfg<2, 2, 2, 2>{});
+        case 5: return go(H2Cfg<2, 2, 4, 2>{});  // 256x128, 2 WGs per CU
+        case 6: return go(H2Cfg<2, 2, 2, 4>{});  // 128x256, 2 WGs per CU
         default:
-            if constexpr (GEGLU) return launch_h2_cfg<FLAGS, H2Cfg<2, 2, 1, 2>, LN>(hp, n_cu, stream);
-            else return launch_h2_cfg<FLAGS, H2Cfg<2, 2, 1, 1>, LN>(hp, n_cu, stream);
+            if constexpr (GEGLU) return go(H2Cfg<2, 2, 1, 2>{});
+            else return go(H2Cfg<2, 2, 1, 1>{});
     }
 }
 
@@ -476,80 +451,33 @@ extern "C" int omnitok_h2_pack_weight(const float *w, int64_t ldw, int N, int K,
     return OMNITOK_OK;
 }
 
-extern "C" int omnitok_gemm_h2(const float *a, int64_t lda, const void *w_planes, const float *w_scale,
-                               const float *bias, const float *residual, int64_t ldr, float *c, int64_t ldc,
-                               int64_t M, int N, int K, int flags, int64_t a_rows_per_group, int64_t a_group_stride,
-                               int64_t a_group_offset, float a_bound, const float *a_bound_dev, int a_bound_stride,
-                               int64_t a_rows_per_clip, const float *ln_stats, const float *ln_gamma, const float *ln_beta, int ln_cols,
-                               float ln_bound, float *c2, int64_t ldc2, int split_col, omnitok_stream_t stream_) {
-    return omnitok_gemm_h2_vpack(a, lda, w_planes, w_scale, bias, residual, ldr, c, ldc, M, N, K, flags, a_rows_per_group,
-                                 a_group_stride, a_group_offset, a_bound, a_bound_dev, a_bound_stride, a_rows_per_clip,
-                                 ln_stats, ln_gamma, ln_beta, ln_cols, ln_bound, c2, ldc2, split_col, nullptr, 0, 0, 0, 0.0f,
-                                 nullptr, 1, stream_);
-}
-
-extern "C" int omnitok_gemm_h2_vpack(const float *a, int64_t lda, const void *w_planes, const float *w_scale,
-                                     const float *bias, const float *residual, int64_t ldr, float *c, int64_t ldc,
-                                     int64_t M, int N, int K, int flags, int64_t a_rows_per_group, int64_t a_group_stride,
-                                     int64_t a_group_offset, float a_bound, const float *a_bound_dev, int a_bound_stride,
-                                     int64_t a_rows_per_clip, const float *ln_stats, const float *ln_gamma,
-                                     const float *ln_beta, int ln_cols, float ln_bound, float *c2, int64_t ldc2,
-                                     int split_col, void *v_planes, int v_col0, int n_tokens, int heads, float v_bound,
-                                     const float *v_bound_dev, int v_bound_stride, omnitok_stream_t stream_) {
+extern "C" int omnitok_gemm_h2(const omnitok_row_gemm *d, omnitok_stream_t stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    OT_CHECK_ARG(!v_planes || (flags == 0 && ln_stats && v_col0 > 0 && v_col0 % 256 == 0 && v_col0 < N &&
-                               (N - v_col0) == heads * 64 && n_tokens > 0 && n_tokens % 32 == 0 && M % n_tokens == 0 &&
-                               v_bound > 0.0f && aligned16(v_planes) && a_rows_per_group == 0 &&
-                               (!v_bound_dev || a_rows_per_clip > 0)),
+    OT_CHECK_ARG(d, "gemm_h2: null descriptor");
+    OT_ROW_GEMM_REFUSE("gemm_h2", d, w);
+    OT_CHECK_ARG(!d->v_planes || (d->flags == 0 && d->ln_stats && d->v_col0 > 0 && d->v_col0 % 256 == 0 && d->v_col0 < d->N &&
+                                  (d->N - d->v_col0) == d->heads * 64 && d->n_tokens > 0 && d->n_tokens % 32 == 0 &&
+                                  d->M % d->n_tokens == 0 && d->v_bound > 0.0f && aligned16(d->v_planes) &&
+                                  d->a_rows_per_group == 0 && (!d->v_bound_dev || d->a_rows_per_clip > 0)),
                  "gemm_h2: packed-V output needs the fused-LN plain epilogue, v_col0 %% 256 == 0, N - v_col0 == heads * 64, "
                  "whole sequences of n_tokens %% 32 == 0 rows and a positive bound");
-    OT_CHECK_ARG(a && w_planes && w_scale && c, "gemm_h2: null pointer");
-    OT_CHECK_ARG(split_col == 0 || (c2 && split_col % 256 == 0 && split_col < N && !(flags & (OMNITOK_GEMM_GEGLU | OMNITOK_GEMM_RESIDUAL))),
-                 "gemm_h2: split output needs c2, split_col %% 256 == 0 and no GEGLU / residual epilogue");
-    OT_CHECK_ARG(M >= 0 && N > 0 && K > 0, "gemm_h2: bad sizes M=%lld N=%d K=%d", (long long)M, N, K);
-    if (M == 0) return OMNITOK_OK;
-    OT_CHECK_ARG(K % 32 == 0 && N % 32 == 0, "gemm_h2: K=%d and N=%d must be multiples of 32", K, N);
-    OT_CHECK_ARG(lda % 4 == 0 && aligned16(a) && aligned16(w_planes), "gemm_h2: operands must be 16-byte aligned");
-    OT_CHECK_ARG(a_bound > 0.0f, "gemm_h2: an upper bound of |a| is required (fp16 range)");
-    OT_CHECK_ARG(!a_bound_dev || a_rows_per_clip <= 0 || (a_rows_per_clip % 64 == 0 && a_rows_per_group == 0),
+    if (int rc = row_gemm_check_shape("gemm_h2", *d, d->w_planes && d->w_scale)) return rc;
+    if (d->M == 0) return OMNITOK_OK;
+    OT_CHECK_ARG(d->K % 32 == 0 && d->N % 32 == 0, "gemm_h2: K=%d and N=%d must be multiples of 32", d->K, d->N);
+    OT_CHECK_ARG(d->lda % 4 == 0 && aligned16(d->a) && aligned16(d->w_planes), "gemm_h2: operands must be 16-byte aligned");
+    OT_CHECK_ARG(d->a_bound > 0.0f, "gemm_h2: an upper bound of |a| is required (fp16 range)");
+    OT_CHECK_ARG(!d->a_bound_dev || d->a_rows_per_clip <= 0 || (d->a_rows_per_clip % 64 == 0 && d->a_rows_per_group == 0),
                  "gemm_h2: rows per clip (%lld) must be a multiple of 64 (tiles may not straddle clips)",
-                 (long long)a_rows_per_clip);
-    OT_CHECK_ARG(!(flags & OMNITOK_GEMM_BIAS) || bias, "gemm_h2: BIAS flag without bias");
-    OT_CHECK_ARG(!(flags & OMNITOK_GEMM_RESIDUAL) || residual, "gemm_h2: RESIDUAL flag without residual");
-    const bool ln = ln_stats != nullptr;
-    OT_CHECK_ARG(!ln || (ln_gamma && K <= 512 && ln_cols > 0 && ln_bound > 0.0f && (ln_cols >= N || ln_cols % 256 == 0)),
-                 "gemm_h2: fused LayerNorm needs gamma, a bound, K <= 512 and ln_cols a multiple of 256 (or >= N)");
+                 (long long)d->a_rows_per_clip);
+    if (int rc = row_gemm_check_options("gemm_h2", *d, true)) return rc;
     H2Params hp;
-    GemmParams &p = hp.g;
-    p.a = a; p.w = nullptr; p.bias = bias; p.residual = residual; p.c = c;
-    p.lda = lda; p.ldw = K; p.ldr = ldr; p.ldc = ldc;
-    p.M = M; p.N = N; p.K = K;
-    p.a_rpg = a_rows_per_group; p.a_stride = a_group_stride; p.a_off = a_group_offset;
-    p.gn = g_gemm_gn > 0 ? g_gemm_gn : 8;
-    p.trace = nullptr;
-    hp.wpl = w_planes; hp.wscale = w_scale; hp.a_bound = a_bound; hp.a_bound_dev = a_bound_dev;
-    hp.a_bound_stride = a_bound_stride > 0 ? a_bound_stride : 1; hp.a_rpc = a_rows_per_clip;
-    hp.ln_stats = ln_stats; hp.ln_gamma = ln_gamma; hp.ln_beta = ln_beta; hp.ln_cols = ln ? ln_cols : 0;
-    hp.ln_bound = ln_bound;
-    hp.c2 = c2; hp.ldc2 = ldc2; hp.split_col = split_col;
-    hp.vp = static_cast<unsigned char *>(v_planes); hp.v_col0 = v_col0; hp.v_ntok = n_tokens; hp.v_heads = heads;
-    hp.v_bound = v_bound; hp.v_bound_dev = v_bound_dev; hp.v_bound_stride = v_bound_stride > 0 ? v_bound_stride : 1;
-    hp.v_rpc = a_rows_per_clip;
-#define H2_CASE(F)                                                    \
-    case F:                                                           \
-        return ln ? launch_h2<F, true>(hp, stream) : launch_h2<F, false>(hp, stream);
-    switch (flags) {
-        H2_CASE(0)
-        H2_CASE(OMNITOK_GEMM_BIAS)
-        H2_CASE(OMNITOK_GEMM_RESIDUAL)
-        H2_CASE(OMNITOK_GEMM_BIAS | OMNITOK_GEMM_RESIDUAL)
-        case OMNITOK_GEMM_GEGLU:
-            OT_CHECK_ARG(N % 64 == 0, "gemm_h2: GEGLU packed width %d must be a multiple of 64", N);
-            return ln ? launch_h2<OMNITOK_GEMM_GEGLU, true>(hp, stream)
-                      : launch_h2<OMNITOK_GEMM_GEGLU, false>(hp, stream);
-        default:
-            set_error("gemm_h2: unsupported epilogue flags %d", flags);
-            return OMNITOK_ERR_INVALID;
-    }
-#undef H2_CASE
+    row_gemm_fill_split(hp, *d, g_gemm_gn > 0 ? g_gemm_gn : 8);
+    hp.g.ldw = d->K;  // the packed weight's
+    hp.wpl = d->w_planes; hp.wscale = d->w_scale; hp.a_bound = d->a_bound; hp.a_bound_dev = d->a_bound_dev;
+    hp.a_bound_stride = d->a_bound_stride > 0 ? d->a_bound_stride : 1; hp.a_rpc = d->a_rows_per_clip;
+    hp.ln_bound = d->ln_bound;
+    hp.vp = static_cast<unsigned char *>(d->v_planes); hp.v_col0 = d->v_col0; hp.v_ntok = d->n_tokens; hp.v_heads = d->heads;
+    hp.v_bound = d->v_bound; hp.v_bound_dev = d->v_bound_dev; hp.v_bound_stride = d->v_bound_stride > 0 ? d->v_bound_stride : 1;
+    hp.v_rpc = d->a_rows_per_clip;
+    OT_SPLIT_DISPATCH("gemm_h2", launch_h2, hp, d, d->ln_stats != nullptr, stream)
 }

@@ -32,6 +32,7 @@
 //  * optional LayerNorm fused into the A staging (mean / rstd per row from a stats pass, gamma/beta
 //    from an LDS table): the LN output never exists in HBM, and a column range [0, ln_cols) of one
 //    launch can take LN(x) while the rest takes x (Q from LN(x), K/V from x: attention.py:404-412).
+#include "gemm_row_host.h"
 #include "gemm_x_common.h"
 
 #include <type_traits>
@@ -353,54 +354,25 @@ __global__ __launch_bounds__(C::NT, 2) void gemm_x3_kernel(X3Params xp) {
     }
 }
 
-template <int FLAGS, typename C, bool LN>
-static int launch_x3_cfg(X3Params xp, int n_cu, hipStream_t stream) {
-    GemmParams &p = xp.g;
-    const int lds = 2 * C::STAGE + (LN ? C::LN_TAB : 0);
-    if (int rc = set_max_dynamic_lds(reinterpret_cast<const void *>(gemm_x3_kernel<FLAGS, C, LN>), lds)) return rc;
-    const int64_t nbm = (p.M + C::TM - 1) / C::TM;
-    const int nbn = (p.N + C::TN - 1) / C::TN;
-    const int64_t nt = nbm * nbn;
-    OT_CHECK_ARG(nt < (1ll << 31), "gemm_x3: grid too large");
-    p.nbm = (int)nbm;
-    p.nbn = nbn;
-    p.ntiles = (int)nt;
-    int wg_per_cu = (160 * 1024) / lds;
-    const int by_waves = 8 / (C::NT / 64);  // at most two waves per SIMD (register budget of the kernel)
-    if (wg_per_cu > by_waves) wg_per_cu = by_waves;
-    if (wg_per_cu < 1) wg_per_cu = 1;
-    const int64_t cap = (int64_t)n_cu * wg_per_cu;
-    const int grid = (int)(nt < cap ? nt : cap);
-    hipLaunchKernelGGL((gemm_x3_kernel<FLAGS, C, LN>), dim3(grid), dim3(C::NT), lds, stream, xp);
-    OT_LAUNCH_CHECK("gemm_x3");
-    return OMNITOK_OK;
-}
-
 template <int FLAGS, bool LN>
 static int launch_x3(X3Params xp, hipStream_t stream) {
     int n_cu = 0;
     if (int rc = current_device_cus(&n_cu)) return rc;
-    const GemmParams &p = xp.g;
-    // tile choice by how many tiles the problem offers per CU (every tile shape performs the same
-    // per-element arithmetic, so the choice never changes a result)
-    auto tiles = [&](int tm, int tn) { return ((p.M + tm - 1) / tm) * (int64_t)((p.N + tn - 1) / tn); };
-    int t = g_x3_tile;
-    if (t == 0) {
-        if (tiles(256, 256) >= 2 * n_cu) t = 1;
-        else if (tiles(128, 128) >= n_cu) t = 3;
-        else t = 4;
-    }
+    const int t = g_x3_tile ? g_x3_tile : split_auto_tile(xp.g, n_cu);
     constexpr bool GEGLU = (FLAGS & OMNITOK_GEMM_GEGLU) != 0;
+    auto go = [&](auto cfg) {
+        return launch_split_cfg<gemm_x3_kernel<FLAGS, decltype(cfg), LN>, decltype(cfg), LN>("gemm_x3", xp, n_cu, stream);
+    };
     switch (t) {
-        case 1: return launch_x3_cfg<FLAGS, X3Cfg<2, 4, 4, 2>, LN>(xp, n_cu, stream);
-        case 2: return launch_x3_cfg<FLAGS, X3Cfg<4, 2, 2, 2>, LN>(xp, n_cu, stream);
-        case 3: return launch_x3_cfg<FLAGS, X3Cfg<2, 2, 2, 2>, LN>(xp, n_cu, stream);
-        case 5: return launch_x3_cfg<FLAGS, X3Cfg<2, 2, 4, 2, true>, LN>(xp, n_cu, stream);
-        case 6: return launch_x3_cfg<FLAGS, X3Cfg<2, 2, 2, 4, true>, LN>(xp, n_cu, stream);
-        case 7: return launch_x3_cfg<FLAGS, X3Cfg<2, 4, 4, 2, true>, LN>(xp, n_cu, stream);
+        case 1: return go(X3Cfg<2, 4, 4, 2>{});
+        case 2: return go(X3Cfg<4, 2, 2, 2>{});
+        case 3: return go(X3Cfg<2, 2, 2, 2>{});
+        case 5: return go(X3Cfg<2, 2, 4, 2, true>{});
+        case 6: return go(X3Cfg<2, 2, 2, 4, true>{});
+        case 7: return go(X3Cfg<2, 4, 4, 2, true>{});
         default:
-            if constexpr (GEGLU) return launch_x3_cfg<FLAGS, X3Cfg<2, 2, 1, 2>, LN>(xp, n_cu, stream);
-            else return launch_x3_cfg<FLAGS, X3Cfg<2, 2, 1, 1>, LN>(xp, n_cu, stream);
+            if constexpr (GEGLU) return go(X3Cfg<2, 2, 1, 2>{});
+            else return go(X3Cfg<2, 2, 1, 1>{});
     }
 }
 
@@ -408,51 +380,16 @@ static int launch_x3(X3Params xp, hipStream_t stream) {
 
 using namespace omnitok;
 
-extern "C" int omnitok_gemm_x3(const float *a, int64_t lda, const float *w, int64_t ldw, const float *bias,
-                               const float *residual, int64_t ldr, float *c, int64_t ldc, int64_t M, int N, int K,
-                               int flags, int64_t a_rows_per_group, int64_t a_group_stride, int64_t a_group_offset,
-                               const float *ln_stats, const float *ln_gamma, const float *ln_beta, int ln_cols,
-                               float *c2, int64_t ldc2, int split_col, omnitok_stream_t stream_) {
+extern "C" int omnitok_gemm_x3(const omnitok_row_gemm *d, omnitok_stream_t stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    OT_CHECK_ARG(a && w && c, "gemm_x3: null pointer");
-    OT_CHECK_ARG(split_col == 0 || (c2 && split_col % 256 == 0 && split_col < N && !(flags & (OMNITOK_GEMM_GEGLU | OMNITOK_GEMM_RESIDUAL))),
-                 "gemm_x3: split output needs c2, split_col %% 256 == 0 and no GEGLU / residual epilogue");
-    OT_CHECK_ARG(M >= 0 && N > 0 && K > 0, "gemm_x3: bad sizes M=%lld N=%d K=%d", (long long)M, N, K);
-    if (M == 0) return OMNITOK_OK;
-    OT_CHECK_ARG(K % 32 == 0, "gemm_x3: K=%d must be a multiple of 32 (pad the weight)", K);
-    OT_CHECK_ARG(N % 32 == 0, "gemm_x3: N=%d must be a multiple of 32", N);
-    OT_CHECK_ARG(lda % 4 == 0 && ldw % 4 == 0 && aligned16(a) && aligned16(w),
-                 "gemm_x3: operands must be 16-byte aligned with ld %% 4 == 0");
-    OT_CHECK_ARG(!(flags & OMNITOK_GEMM_BIAS) || bias, "gemm_x3: BIAS flag without bias");
-    OT_CHECK_ARG(!(flags & OMNITOK_GEMM_RESIDUAL) || residual, "gemm_x3: RESIDUAL flag without residual");
-    const bool ln = ln_stats != nullptr;
-    OT_CHECK_ARG(!ln || (ln_gamma && K <= 512 && ln_cols > 0 && (ln_cols >= N || ln_cols % 256 == 0)),
-                 "gemm_x3: fused LayerNorm needs gamma, K <= 512 and ln_cols a multiple of 256 (or >= N)");
+    OT_CHECK_ARG(d, "gemm_x3: null descriptor");
+    OT_ROW_GEMM_REFUSE("gemm_x3", d, w_planes);
+    OT_ROW_GEMM_REFUSE("gemm_x3", d, v_planes);
+    if (int rc = row_gemm_check_shape("gemm_x3", *d, d->w != nullptr)) return rc;
+    if (d->M == 0) return OMNITOK_OK;
+    if (int rc = row_gemm_check_w_rows("gemm_x3", *d, 32)) return rc;
+    if (int rc = row_gemm_check_options("gemm_x3", *d, false)) return rc;
     X3Params xp;
-    GemmParams &p = xp.g;
-    p.a = a; p.w = w; p.bias = bias; p.residual = residual; p.c = c;
-    p.lda = lda; p.ldw = ldw; p.ldr = ldr; p.ldc = ldc;
-    p.M = M; p.N = N; p.K = K;
-    p.a_rpg = a_rows_per_group; p.a_stride = a_group_stride; p.a_off = a_group_offset;
-    p.gn = 8;
-    p.trace = nullptr;
-    xp.ln_stats = ln_stats; xp.ln_gamma = ln_gamma; xp.ln_beta = ln_beta; xp.ln_cols = ln ? ln_cols : 0;
-    xp.c2 = c2; xp.ldc2 = ldc2; xp.split_col = split_col;
-#define X3_CASE(F)                                                    \
-    case F:                                                           \
-        return ln ? launch_x3<F, true>(xp, stream) : launch_x3<F, false>(xp, stream);
-    switch (flags) {
-        X3_CASE(0)
-        X3_CASE(OMNITOK_GEMM_BIAS)
-        X3_CASE(OMNITOK_GEMM_RESIDUAL)
-        X3_CASE(OMNITOK_GEMM_BIAS | OMNITOK_GEMM_RESIDUAL)
-        case OMNITOK_GEMM_GEGLU:
-            OT_CHECK_ARG(N % 64 == 0, "gemm_x3: GEGLU packed width %d must be a multiple of 64", N);
-            return ln ? launch_x3<OMNITOK_GEMM_GEGLU, true>(xp, stream)
-                      : launch_x3<OMNITOK_GEMM_GEGLU, false>(xp, stream);
-        default:
-            set_error("gemm_x3: unsupported epilogue flags %d", flags);
-            return OMNITOK_ERR_INVALID;
-    }
-#undef X3_CASE
+    row_gemm_fill_split(xp, *d, 8);  // the "gemm_gn" option is not read here
+    OT_SPLIT_DISPATCH("gemm_x3", launch_x3, xp, d, d->ln_stats != nullptr, stream)
 }

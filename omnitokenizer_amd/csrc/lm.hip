@@ -1599,6 +1599,17 @@ extern "C" int omnitok_lm_prefill(omnitok_lm *lm, const int64_t *idx, int32_t *p
     return omnitok_lm_prefill_ex(lm, idx, T, nullptr, 0, nullptr, pos, cache_len, B, logits_out, stream_);
 }
 
+// nn.Linear of the prefill on the fp32-MFMA GEMM: y [M, N] = x [M, K] . w [N, K]^T (+ bias) (+ residual [M, N], may be y), dense rows
+static int lm_linear(const float *x, const float *w, const float *bias, const float *residual, float *y, int64_t M, int N,
+                     int K, hipStream_t stream) {
+    omnitok_row_gemm g = {};
+    g.a = x; g.lda = K; g.w = w; g.ldw = K;
+    g.bias = bias; g.residual = residual; g.ldr = N; g.c = y; g.ldc = N;
+    g.M = M; g.N = N; g.K = K;
+    g.flags = (bias ? OMNITOK_GEMM_BIAS : 0) | (residual ? OMNITOK_GEMM_RESIDUAL : 0);
+    return omnitok_gemm(&g, stream);
+}
+
 // Embedding and the n_layer blocks of a batched prefill, shared by omnitok_lm_prefill_ex and omnitok_lm_prefill_loss: checks the
 // arguments, grows the workspace, fills the K/V cache; *x_out [M, C] is the residual stream after the last block, *xn_out [M, C]
 // scratch for its ln_f.  B * T > 0.
@@ -1637,15 +1648,12 @@ static int lm_prefill_layers(omnitok_lm *lm, const int64_t *idx, int T_tok, cons
     hipLaunchKernelGGL(lm_embed_seq_kernel, dim3((unsigned)M), dim3(256), 0, stream, idx, LW(lm, "tok_emb.weight"),
                        LW(lm, "pos_emb"), emb, T_emb, pos_extra, x, T, C, V);
     OT_LAUNCH_CHECK("lm_embed_seq");
-    const int BR = OMNITOK_GEMM_BIAS | OMNITOK_GEMM_RESIDUAL;
     for (int i = 0; i < c.n_layer; ++i) {
         const LmLayer &L = lm->layers[i];
         float *kc = lm->kv + (int64_t)(2 * i) * per_layer, *vc = kc + per_layer;
         hipLaunchKernelGGL(lm_layernorm_rows_kernel, ln_grid, dim3(256), 0, stream, x, L.ln1w, L.ln1b, xn, M, C);
         OT_LAUNCH_CHECK("lm_layernorm_rows");
-        if (int rc = omnitok_gemm(xn, C, L.wqkv, C, L.bqkv, nullptr, 0, qkv, 3 * C, M, 3 * C, C, OMNITOK_GEMM_BIAS, 0, 0,
-                                  0, stream))
-            return rc;
+        if (int rc = lm_linear(xn, L.wqkv, L.bqkv, nullptr, qkv, M, 3 * C, C, stream)) return rc;
         hipLaunchKernelGGL(lm_kv_scatter_kernel, dim3((unsigned)M), dim3(256), 0, stream, qkv, kc, vc, T, c.n_head, hd,
                            lm->max_len);
         OT_LAUNCH_CHECK("lm_kv_scatter");
@@ -1653,15 +1661,13 @@ static int lm_prefill_layers(omnitok_lm *lm, const int64_t *idx, int T_tok, cons
         hipLaunchKernelGGL(lm_attn_merge_kernel, dim3(c.n_head, (unsigned)M), dim3(128), 0, stream, part, nullptr,
                            c.n_head, hd, nchunk, T, att, LM_CHUNK);
         OT_LAUNCH_CHECK("lm_attn_merge");
-        if (int rc = omnitok_gemm(att, C, L.wproj, C, L.bproj, x, C, x, C, M, C, C, BR, 0, 0, 0, stream)) return rc;
+        if (int rc = lm_linear(att, L.wproj, L.bproj, x, x, M, C, C, stream)) return rc;
         hipLaunchKernelGGL(lm_layernorm_rows_kernel, ln_grid, dim3(256), 0, stream, x, L.ln2w, L.ln2b, xn, M, C);
         OT_LAUNCH_CHECK("lm_layernorm_rows");
-        if (int rc = omnitok_gemm(xn, C, L.w1, C, L.b1, nullptr, 0, hid, 4 * C, M, 4 * C, C, OMNITOK_GEMM_BIAS, 0, 0, 0,
-                                  stream))
-            return rc;
+        if (int rc = lm_linear(xn, L.w1, L.b1, nullptr, hid, M, 4 * C, C, stream)) return rc;
         hipLaunchKernelGGL(lm_gelu_kernel, dim3((unsigned)((M * C + 255) / 256)), dim3(256), 0, stream, hid, M * C);
         OT_LAUNCH_CHECK("lm_gelu");
-        if (int rc = omnitok_gemm(hid, 4 * C, L.w2, 4 * C, L.b2, x, C, x, C, M, C, 4 * C, BR, 0, 0, 0, stream)) return rc;
+        if (int rc = lm_linear(hid, L.w2, L.b2, x, x, M, C, 4 * C, stream)) return rc;
     }
     *x_out = x;
     *xn_out = xn;
@@ -1674,7 +1680,7 @@ static int lm_head_rows(omnitok_lm *lm, const float *x, float *xn, int64_t rows,
     hipLaunchKernelGGL(lm_layernorm_rows_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, x,
                        LW(lm, "ln_f.weight"), LW(lm, "ln_f.bias"), xn, rows, C);
     OT_LAUNCH_CHECK("lm_layernorm_rows");
-    return omnitok_gemm(xn, C, LW(lm, "head.weight"), C, nullptr, nullptr, 0, logits, V, rows, V, C, 0, 0, 0, 0, stream);
+    return lm_linear(xn, LW(lm, "head.weight"), nullptr, nullptr, logits, rows, V, C, stream);
 }
 
 extern "C" int omnitok_lm_prefill_ex(omnitok_lm *lm, const int64_t *idx, int T_tok, const float *emb, int T_emb,

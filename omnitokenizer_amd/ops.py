@@ -57,6 +57,25 @@ def _opt(t: Optional[torch.Tensor], name: str, numel: Optional[int] = None, dtyp
     return t
 
 
+def _row_gemm(x, out, M, N, K, ldc, flags, **fields):
+    """omnitok_row_gemm of dense rows x [M, K] -> out [M, ldc]; a tensor among `fields` is passed as its device pointer."""
+    g = _lib.OmnitokRowGemm()
+    g.a, g.lda, g.c, g.ldc, g.M, g.N, g.K, g.flags = x.data_ptr(), K, out.data_ptr(), ldc, M, N, K, flags
+    for name, v in fields.items():
+        setattr(g, name, v.data_ptr() if isinstance(v, torch.Tensor) else v)
+    return g
+
+
+def _ln_fields(ln, K, ln_cols):
+    """ln = (stats, gamma, beta|None) or None -> the fused-LayerNorm fields of omnitok_row_gemm."""
+    st, g, b = ln if ln is not None else (None, None, None)
+    if ln is not None:
+        _req(st, "ln stats")
+        _req(g, "ln gamma")
+        _opt(b, "ln beta", K)
+    return dict(ln_stats=st, ln_gamma=g, ln_beta=b, ln_cols=int(ln_cols))
+
+
 def layernorm(x, gamma, beta=None, eps=1e-5):
     x = _req(x, "x")
     rows, dim = x.numel() // x.shape[-1], x.shape[-1]
@@ -104,8 +123,8 @@ def linear(x, weight, bias=None, residual=None, leaky=False):
     _opt(residual, "residual", M * N)
     flags = (GEMM_BIAS if bias is not None else 0) | (GEMM_RESIDUAL if residual is not None else 0) \
         | (GEMM_LEAKY if leaky else 0)
-    check(_lib.load().omnitok_gemm(_p(x), K, _p(weight), weight.shape[1], _p(bias), _p(residual), N, _p(out), N,
-                                   M, N, K, flags, 0, 0, 0, _stream()), "gemm")
+    g = _row_gemm(x, out, M, N, K, N, flags, w=weight, ldw=weight.shape[1], bias=bias, residual=residual, ldr=N)
+    check(_lib.load().omnitok_gemm(ctypes.byref(g), _stream()), "gemm")
     return out
 
 
@@ -138,15 +157,9 @@ def linear_x3(x, weight, bias=None, residual=None, geglu=False, ln=None, ln_cols
     _opt(residual, "residual", M * ncol)
     flags = GEMM_GEGLU if geglu else ((GEMM_BIAS if bias is not None else 0) |
                                       (GEMM_RESIDUAL if residual is not None else 0))
-    st = g = b = None
-    if ln is not None:
-        st, g, b = ln
-        _req(st, "ln stats")
-        _req(g, "ln gamma")
-        _opt(b, "ln beta", K)
-    check(_lib.load().omnitok_gemm_x3(_p(x), K, _p(weight), weight.shape[1], _p(bias), _p(residual), ncol, _p(out),
-                                      ncol, M, N, K, flags, 0, 0, 0, _p(st), _p(g), _p(b),
-                                      int(ln_cols if ln_cols is not None else N), None, 0, 0, _stream()), "gemm_x3")
+    d = _row_gemm(x, out, M, N, K, ncol, flags, w=weight, ldw=weight.shape[1], bias=bias, residual=residual, ldr=ncol,
+                  **_ln_fields(ln, K, ln_cols if ln_cols is not None else N))
+    check(_lib.load().omnitok_gemm_x3(ctypes.byref(d), _stream()), "gemm_x3")
     return out
 
 
@@ -179,24 +192,18 @@ def linear_h2(x, packed, a_bound, bias=None, residual=None, geglu=False, a_bound
     _opt(a_bound_dev, "a_bound_dev")
     flags = GEMM_GEGLU if geglu else ((GEMM_BIAS if bias is not None else 0) |
                                       (GEMM_RESIDUAL if residual is not None else 0))
-    st = g = b = None
-    if ln is not None:
-        st, g, b = ln
-        _req(st, "ln stats")
-        _req(g, "ln gamma")
-        _opt(b, "ln beta", K)
-    check(_lib.load().omnitok_gemm_h2(_p(x), K, _p(planes), _p(scale), _p(bias), _p(residual), ncol, _p(out), ncol,
-                                      M, N, K, flags, 0, 0, 0, float(a_bound), _p(a_bound_dev), int(a_bound_stride),
-                                      int(rows_per_clip), _p(st), _p(g), _p(b),
-                                      int(ln_cols if ln_cols is not None else N), float(ln_bound), None, 0, 0,
-                                      _stream()), "gemm_h2")
+    d = _row_gemm(x, out, M, N, K, ncol, flags, w_planes=planes, w_scale=scale, bias=bias, residual=residual, ldr=ncol,
+                  a_bound=float(a_bound), a_bound_dev=a_bound_dev, a_bound_stride=int(a_bound_stride),
+                  a_rows_per_clip=int(rows_per_clip), ln_bound=float(ln_bound),
+                  **_ln_fields(ln, K, ln_cols if ln_cols is not None else N))
+    check(_lib.load().omnitok_gemm_h2(ctypes.byref(d), _stream()), "gemm_h2")
     return out
 
 
 def linear_h2_vpack(x, packed, a_bound, ln, ln_cols, ln_bound, v_col0, n_tokens, heads, v_bound, a_bound_dev=None,
                     a_bound_stride=1, rows_per_clip=0, v_bound_dev=None, v_bound_stride=1):
     """linear_h2 (fused LayerNorm on the first ln_cols columns) whose columns [v_col0, N) go straight into the packed
-    fp16 hi|lo V planes of attn_spatial_h2 (omnitok_gemm_h2_vpack).  Returns (out[M, v_col0], v_planes)."""
+    fp16 hi|lo V planes of attn_spatial_h2 (omnitok_gemm_h2 with v_planes).  Returns (out[M, v_col0], v_planes)."""
     x = _req(x, "x")
     planes, scale = packed
     K = x.shape[-1]
@@ -204,17 +211,14 @@ def linear_h2_vpack(x, packed, a_bound, ln, ln_cols, ln_bound, v_col0, n_tokens,
     N = scale.shape[0]
     out = torch.empty(M, v_col0, device=x.device, dtype=torch.float32)
     vp = torch.empty(M * heads * 64, device=x.device, dtype=torch.int32)
-    st, g, b = ln
-    _req(st, "ln stats")
-    _req(g, "ln gamma")
-    _opt(b, "ln beta", K)
     _opt(a_bound_dev, "a_bound_dev")
     _opt(v_bound_dev, "v_bound_dev")
-    check(_lib.load().omnitok_gemm_h2_vpack(_p(x), K, _p(planes), _p(scale), None, None, 0, _p(out), v_col0, M, N, K, 0, 0,
-                                            0, 0, float(a_bound), _p(a_bound_dev), int(a_bound_stride),
-                                            int(rows_per_clip), _p(st), _p(g), _p(b), int(ln_cols), float(ln_bound), None,
-                                            0, 0, _p(vp), int(v_col0), int(n_tokens), int(heads), float(v_bound),
-                                            _p(v_bound_dev), int(v_bound_stride), _stream()), "gemm_h2_vpack")
+    d = _row_gemm(x, out, M, N, K, v_col0, 0, w_planes=planes, w_scale=scale,
+                  a_bound=float(a_bound), a_bound_dev=a_bound_dev, a_bound_stride=int(a_bound_stride),
+                  a_rows_per_clip=int(rows_per_clip), ln_bound=float(ln_bound), **_ln_fields(ln, K, ln_cols),
+                  v_planes=vp, v_col0=int(v_col0), n_tokens=int(n_tokens), heads=int(heads), v_bound=float(v_bound),
+                  v_bound_dev=v_bound_dev, v_bound_stride=int(v_bound_stride))
+    check(_lib.load().omnitok_gemm_h2(ctypes.byref(d), _stream()), "gemm_h2_vpack")
     return out, vp
 
 
@@ -506,8 +510,8 @@ def linear_geglu(x, w1_packed):
     M = x.numel() // K
     Np = w1_packed.shape[0]
     out = torch.empty(*x.shape[:-1], Np // 2, device=x.device, dtype=torch.float32)
-    check(_lib.load().omnitok_gemm(_p(x), K, _p(_req(w1_packed, "w1_packed")), K, None, None, 0, _p(out), Np // 2,
-                                   M, Np, K, GEMM_GEGLU, 0, 0, 0, _stream()), "gemm_geglu")
+    g = _row_gemm(x, out, M, Np, K, Np // 2, GEMM_GEGLU, w=_req(w1_packed, "w1_packed"), ldw=K)
+    check(_lib.load().omnitok_gemm(ctypes.byref(g), _stream()), "gemm_geglu")
     return out
 
 

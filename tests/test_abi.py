@@ -33,7 +33,8 @@ def test_header_symbols_exported(lib):
 def test_version_and_argument_errors_without_gpu(lib):
     assert b"gfx950" in lib.omnitok_version()
     # argument validation happens before any HIP call, so it is testable on the CPU
-    rc = lib.omnitok_gemm(None, 0, None, 0, None, None, 0, None, 0, 1, 1, 1, 0, 0, 0, 0, None)
+    from omnitokenizer_amd._lib import OmnitokRowGemm
+    rc = lib.omnitok_gemm(ctypes.byref(OmnitokRowGemm(M=1, N=1, K=1)), None)
     assert rc == -1 and b"null" in lib.omnitok_last_error()
     rc = lib.omnitok_rope_table(0, 64, 10000.0, None, None)
     assert rc == -1
@@ -278,6 +279,60 @@ def test_new_entry_points_validate_arguments_without_gpu(lib):
     assert lib.omnitok_pl_pack_weight(one, 512, 500, 512, 512, one, one, None) == -1   # N % 32
     assert lib.omnitok_pl_planes_bytes(1000, 512, 256) == 1024 * 512 * 4 and lib.omnitok_pl_planes_bytes(10, 500, 256) == -1
     assert lib.omnitok_engine_set_option(None, b"gemm_mode", 1) == -1
+
+
+ROW_GEMMS = ("omnitok_gemm", "omnitok_gemm_x3", "omnitok_gemm_h2")
+
+
+def _row_gemm(name, **fields):
+    """A descriptor whose required pointers are a non-null, 16-byte aligned dummy: every check fires before a dereference."""
+    from omnitokenizer_amd._lib import OmnitokRowGemm
+    weight = dict(w_planes=256, w_scale=256) if name == "omnitok_gemm_h2" else dict(w=256)
+    return OmnitokRowGemm(**{**dict(a=256, c=256, M=64, N=64, K=64, a_bound=1.0), **weight, **fields})
+
+
+@pytest.mark.parametrize("name", ROW_GEMMS)
+def test_row_gemm_descriptor_layout_and_null_checks(lib, name):
+    """omnitok_row_gemm through ctypes: the size fields land where the C struct has them (the message echoes them), and a NULL
+    descriptor or NULL operand is refused -- all before the first HIP call."""
+    fn = getattr(lib, name)
+    assert fn(ctypes.byref(_row_gemm(name, M=7, N=5, K=-3)), None) == -1
+    assert b"M=7 N=5 K=-3" in lib.omnitok_last_error()
+    assert fn(None, None) == -1
+    assert fn(ctypes.byref(_row_gemm(name, a=None)), None) == -1 and b"null pointer" in lib.omnitok_last_error()
+
+
+def test_row_gemm_h2_fields_echoed(lib):
+    """Fields behind the sizes: a_rows_per_clip (int64 after a float, a pointer and an int) and N under the GEGLU flag."""
+    one = ctypes.c_float(1.0)
+    g = _row_gemm("omnitok_gemm_h2", a_bound_dev=ctypes.addressof(one), a_rows_per_clip=100)
+    assert lib.omnitok_gemm_h2(ctypes.byref(g), None) == -1 and b"(100)" in lib.omnitok_last_error()
+    g = _row_gemm("omnitok_gemm_h2", flags=4, N=96)
+    assert lib.omnitok_gemm_h2(ctypes.byref(g), None) == -1 and b"96" in lib.omnitok_last_error()
+
+
+@pytest.mark.parametrize("name,field", [("omnitok_gemm", "w_planes"), ("omnitok_gemm", "ln_stats"), ("omnitok_gemm", "split_col"),
+                                        ("omnitok_gemm", "v_planes"), ("omnitok_gemm_x3", "w_planes"),
+                                        ("omnitok_gemm_x3", "v_planes"), ("omnitok_gemm_h2", "w")])
+def test_row_gemm_refuses_fields_the_kernel_does_not_implement(lib, name, field):
+    g = _row_gemm(name, **{field: 256})
+    assert getattr(lib, name)(ctypes.byref(g), None) == -1
+    err = lib.omnitok_last_error()
+    assert field.encode() in err and name[len("omnitok_"):].encode() + b":" in err, err
+
+
+def test_row_gemm_vpack_entry_point_is_gone(lib):
+    """The packed-V epilogue is omnitok_gemm_h2 with v_planes set; header, library and binding agree on the symbol set."""
+    from omnitokenizer_amd import _lib
+    assert "omnitok_gemm_h2_vpack" not in _lib.EXPORTED_SYMBOLS
+    assert not hasattr(ctypes.CDLL(_lib.LIB_PATH), "omnitok_gemm_h2_vpack")
+    hdr = open(os.path.join(ROOT, "include", "omnitok.h")).read()
+    assert "omnitok_gemm_h2_vpack" not in hdr
+    declared = set(re.findall(r"\b(omnitok_gemm[a-z0-9_]*)\s*\(", hdr))
+    assert declared == {n for n in _lib.EXPORTED_SYMBOLS if n.startswith("omnitok_gemm")}
+    # v_planes under a precondition the packed-V epilogue does not meet (a flag set) is refused, as before
+    g = _row_gemm("omnitok_gemm_h2", v_planes=256, flags=1, bias=256)
+    assert lib.omnitok_gemm_h2(ctypes.byref(g), None) == -1 and b"packed-V" in lib.omnitok_last_error()
 
 
 # every option a test or tool sets and then has to restore: the LM decode step's kernel choices and the stats_pack form

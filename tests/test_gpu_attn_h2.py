@@ -248,7 +248,7 @@ def test_engine_attn_modes_vs_golden(mode, name):
 
 @pytest.mark.parametrize("M,N_tok,rpc", [(256, 64, 0), (1024, 256, 256), (49152, 1024, 12288), (640, 64, 128)])
 def test_qkv_gemm_writes_v_planes(ops, M, N_tok, rpc):
-    """omnitok_gemm_h2_vpack: the V columns of the merged to_q | to_kv launch land in the packed fp16 planes bit for bit
+    """omnitok_gemm_h2 with v_planes: the V columns of the merged to_q | to_kv launch land in the packed fp16 planes bit for bit
     as if they had been stored as fp32 and packed by omnitok_attn_pack; the q | k columns are those of the plain launch."""
     D, h = 256, 4
     x = rnd(M, D, seed=171, scale=2.0)

@@ -215,20 +215,22 @@ def test_split_gemm_row_map(ops):
     from omnitokenizer_amd import _lib
     lib = _lib.load()
     s = torch.cuda.current_stream().cuda_stream
-    p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    p = lambda t: t.data_ptr()  # noqa: E731
     K, N = 512, 192
     big, w = rnd(4 * 160, K, seed=9), rnd(N, K, seed=2) * 0.05
     bd, wd = dev(big), dev(w)
     rows = torch.tensor([(m // 64) * 160 + 32 + m % 64 for m in range(256)])
     ref = big[rows].double() @ w.double().t()
     out = torch.empty(256, N, device="cuda")
-    assert lib.omnitok_gemm_x3(p(bd), K, p(wd), K, None, None, 0, p(out), N, 256, N, K, 0, 64, 160, 32, None, None,
-                               None, 0, None, 0, 0, s) == 0
+    rowmap = dict(lda=K, ldc=N, M=256, N=N, K=K, a_rows_per_group=64, a_group_stride=160, a_group_offset=32)
+    g = _lib.OmnitokRowGemm(a=p(bd), w=p(wd), ldw=K, c=p(out), **rowmap)
+    assert lib.omnitok_gemm_x3(ctypes.byref(g), s) == 0
     assert maxerr(out, ref) < 1e-5
     planes, scale = ops.h2_pack_weight(wd)
     out2 = torch.empty(256, N, device="cuda")
-    assert lib.omnitok_gemm_h2(p(bd), K, p(planes), p(scale), None, None, 0, p(out2), N, 256, N, K, 0, 64, 160, 32,
-                               float(big.abs().max()), None, 1, 0, None, None, None, 0, 0.0, None, 0, 0, s) == 0
+    g = _lib.OmnitokRowGemm(a=p(bd), w_planes=p(planes), w_scale=p(scale), c=p(out2), a_bound=float(big.abs().max()),
+                            a_bound_stride=1, **rowmap)
+    assert lib.omnitok_gemm_h2(ctypes.byref(g), s) == 0
     assert maxerr(out2, ref) < 1e-5
 
 
@@ -238,20 +240,22 @@ def test_split_gemm_two_output_tensors(ops, tile, kind):
     from omnitokenizer_amd import _lib
     lib = _lib.load()
     s = torch.cuda.current_stream().cuda_stream
-    p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    p = lambda t: t.data_ptr()  # noqa: E731
     M, K, N = 1000, 512, 1536
     x, w = dev(rnd(M, K, seed=71)), dev(rnd(N, K, seed=72) * 0.05)
     q = torch.full((M, 512), float("nan"), device="cuda")
     kv = torch.full((M, 1024), float("nan"), device="cuda")
     if kind == "x3":
         whole = ops.linear_x3(x, w)
-        assert lib.omnitok_gemm_x3(p(x), K, p(w), K, None, None, 0, p(q), 512, M, N, K, 0, 0, 0, 0, None, None, None, 0,
-                                   p(kv), 1024, 512, s) == 0
+        g = _lib.OmnitokRowGemm(a=p(x), lda=K, w=p(w), ldw=K, c=p(q), ldc=512, M=M, N=N, K=K,
+                                c2=p(kv), ldc2=1024, split_col=512)
+        assert lib.omnitok_gemm_x3(ctypes.byref(g), s) == 0
     else:
         planes, scale = ops.h2_pack_weight(w)
         whole = ops.linear_h2(x, (planes, scale), 6.0)
-        assert lib.omnitok_gemm_h2(p(x), K, p(planes), p(scale), None, None, 0, p(q), 512, M, N, K, 0, 0, 0, 0, 6.0, None,
-                                   1, 0, None, None, None, 0, 0.0, p(kv), 1024, 512, s) == 0
+        g = _lib.OmnitokRowGemm(a=p(x), lda=K, w_planes=p(planes), w_scale=p(scale), c=p(q), ldc=512, M=M, N=N, K=K,
+                                a_bound=6.0, a_bound_stride=1, c2=p(kv), ldc2=1024, split_col=512)
+        assert lib.omnitok_gemm_h2(ctypes.byref(g), s) == 0
     assert torch.equal(q, whole[:, :512]) and torch.equal(kv, whole[:, 512:])
 
 

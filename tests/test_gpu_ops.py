@@ -86,15 +86,18 @@ def test_gemm_inplace_residual_and_row_map(ops, gemm_variant):
     xd = dev(x)
     lib = _lib.load()
     s = torch.cuda.current_stream().cuda_stream
-    p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    p = lambda t: t.data_ptr()  # noqa: E731
     ad, wd = dev(a), dev(w)
-    assert lib.omnitok_gemm(p(ad), K, p(wd), K, None, p(xd), N, p(xd), N, M, N, K, 2, 0, 0, 0, s) == 0
+    g = _lib.OmnitokRowGemm(a=p(ad), lda=K, w=p(wd), ldw=K, residual=p(xd), ldr=N, c=p(xd), ldc=N, M=M, N=N, K=K, flags=2)
+    assert lib.omnitok_gemm(ctypes.byref(g), s) == 0
     assert maxerr(xd, a.double() @ w.double().t() + x.double()) < 1e-5
     # A rows gathered as groups: m -> (m // 64) * 160 + 32 + m % 64  (frame-0 / rest-frames selection)
     big = rnd(4 * 160, K, seed=9)
     out = torch.empty(256, N, device="cuda")
     bd = dev(big)
-    assert lib.omnitok_gemm(p(bd), K, p(wd), K, None, None, 0, p(out), N, 256, N, K, 0, 64, 160, 32, s) == 0
+    g = _lib.OmnitokRowGemm(a=p(bd), lda=K, w=p(wd), ldw=K, c=p(out), ldc=N, M=256, N=N, K=K,
+                            a_rows_per_group=64, a_group_stride=160, a_group_offset=32)
+    assert lib.omnitok_gemm(ctypes.byref(g), s) == 0
     rows = torch.tensor([(m // 64) * 160 + 32 + m % 64 for m in range(256)])
     assert maxerr(out, big[rows].double() @ w.double().t()) < 1e-5
 

@@ -126,9 +126,14 @@ int main(int argc, char **argv) {
             OK(omnitok_gemm_pl(&g, st));
         };
         auto run_h2 = [&]() {
-            OK(omnitok_gemm_h2(x, K, wp_h2, wsc_h2, nullptr, sh.residual ? res : nullptr, 512, c_h2, Nout, L, N, K,
-                               sh.geglu ? OMNITOK_GEMM_GEGLU : (sh.residual ? OMNITOK_GEMM_RESIDUAL : 0), 0, 0, 0, 8.0f, nullptr, 1, 0,
-                               nullptr, nullptr, nullptr, 0, 0.0f, nullptr, 0, 0, st));
+            omnitok_row_gemm h;
+            memset(&h, 0, sizeof(h));
+            h.a = x; h.lda = K; h.w_planes = wp_h2; h.w_scale = wsc_h2;
+            h.residual = sh.residual ? res : nullptr; h.ldr = 512; h.c = c_h2; h.ldc = Nout;
+            h.M = L; h.N = N; h.K = K;
+            h.flags = sh.geglu ? OMNITOK_GEMM_GEGLU : (sh.residual ? OMNITOK_GEMM_RESIDUAL : 0);
+            h.a_bound = 8.0f;
+            OK(omnitok_gemm_h2(&h, st));
         };
         auto time_it = [&](auto &&fn) {
             for (int i = 0; i < 3; ++i) fn();
