@@ -687,7 +687,7 @@ typedef struct omnitok_frames_desc {
     int F, H, W;             /* native clip size */
     int frame_start, frame_step;
     int crop_top, crop_left;
-    int resize_h, resize_w;  /* mode BILINEAR only */
+    int resize_h, resize_w;  /* mode BILINEAR and omnitok_frames_resize_pil only */
 } omnitok_frames_desc;
 
 enum { OMNITOK_FRAMES_NONE = 0, OMNITOK_FRAMES_BILINEAR = 1 };
@@ -714,6 +714,45 @@ int omnitok_frames_to_pixels(const omnitok_frames_desc *desc, int B, int F_out, 
  * (what save_video_grid / the I3D input take); OMNITOK_LAYOUT_CTHW: out[B, C, F, H, W].  C must be 3. */
 int omnitok_pixels_to_frames(const float *pixels, int B, int C, int F, int H, int W, int layout, uint8_t *out,
                              omnitok_stream_t stream);
+
+/* ---- Pillow-exact image resize (csrc/resize_pil.hip) ------------------------------------------------------------------
+ * Image.resize((resize_w, resize_h), BICUBIC | BILINEAR | BOX) of 8-bit RGB frames, Pillow's antialiased two-pass resampler
+ * (whole-image box, reducing_gap=None): what torchvision's Resize does to a PIL image (the reference's ImageDataset,
+ * data.py:83-99) and what the DiT / Latte loaders' center_crop_arr is made of.  The result is Pillow's byte for byte; the
+ * arithmetic (22-bit fixed-point coefficients from double precision, int32 accumulation, the horizontal pass first into a
+ * uint8 intermediate, a pass whose size does not change skipped) is stated in csrc/resize_pil.hip.  Lanczos is not covered:
+ * its coefficients need the host libm's sin.
+ *
+ * The clips are the omnitok_frames_desc of omnitok_frames_to_pixels: frame t of the output reads source frame frame_start + t * frame_step, the
+ * frame is resized to resize_h x resize_w and the output window starts at (crop_top, crop_left) of the RESIZED frame.
+ * A filter with more than OMNITOK_RESIZE_MAX_TAPS taps per output sample is refused: ksize = ceil(S * in / out) * 2 + 1 with
+ * S = 2 (bicubic), 1 (bilinear), 0.5 (box), i.e. a bicubic downscale up to in / out = 511. */
+enum { OMNITOK_RESIZE_BICUBIC = 0, OMNITOK_RESIZE_BILINEAR = 1, OMNITOK_RESIZE_BOX = 2 };
+enum { OMNITOK_RESIZE_OUT_PIXELS = 0, OMNITOK_RESIZE_OUT_U8 = 1 };
+#define OMNITOK_RESIZE_MAX_TAPS 2048
+
+/* Bytes of workspace omnitok_frames_resize_pil needs for desc[B] (HOST array) at any output window: the coefficient tables
+ * of both axes and the uint8 intermediate of every clip.  Host only; OMNITOK_ERR_INVALID (< 0) with a message for bad
+ * descriptors (the checks of omnitok_frames_resize_pil that need no output size). */
+int64_t omnitok_frames_resize_pil_workspace(const omnitok_frames_desc *desc, int B, int F_out, int filter);
+
+/* desc[B] (HOST array, validated on the host before any launch; at most 32 clips go into one launch's kernel arguments, no
+ * copy, no synchronisation: the call can be captured in a graph) -> out,
+ *   OMNITOK_RESIZE_OUT_PIXELS: fp32 [B, 3, F_out, R_h, R_w] = float(u) / 255 - 0.5 (the table of omnitok_frames_to_pixels:
+ *                              bit-identical to ToTensor + Normalize(0.5, 1.0) of Pillow's bytes)
+ *   OMNITOK_RESIZE_OUT_U8:     uint8 [B, F_out, R_h, R_w, 3], Pillow's bytes.
+ * work: device buffer, 16-byte aligned, of work_bytes >= omnitok_frames_resize_pil_workspace(desc, B, F_out, filter); it
+ * receives the coefficient tables (a small prologue kernel computes them on the device) and the intermediate.
+ * OMNITOK_ERR_INVALID, naming the clip, for null pointers, a bad filter or out kind, a frame range past F, resize_h /
+ * resize_w < 1, a crop window outside the resized frame, strides too small, a workspace too small, a tap count above
+ * OMNITOK_RESIZE_MAX_TAPS. */
+int omnitok_frames_resize_pil(const omnitok_frames_desc *desc, int B, int F_out, int R_h, int R_w, int filter, int out_kind,
+                              void *work, int64_t work_bytes, void *out, omnitok_stream_t stream);
+
+/* Host only, for tests and non-GPU callers: the coefficient table of one axis, computed by the text the device runs.
+ * *ksize out; k[out_size * ksize] (zero past a row's taps), bounds[out_size * 2] = (first tap, number of taps) per output
+ * sample.  k == NULL: only *ksize is written. */
+int omnitok_pil_resize_coeffs(int in_size, int out_size, int filter, int *ksize, int32_t *k, int32_t *bounds);
 
 /* ---- reconstruction metrics (csrc/metrics.hip) -------------------------------------------------------------------------
  * PSNR and SSIM of every (clip, frame) of two [B, F, 3, H, W] videos in [0, 1], the arithmetic of the reference's

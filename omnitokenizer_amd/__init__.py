@@ -8,6 +8,7 @@
     from omnitokenizer_amd import LPIPS, load_lpips, lpips_frames                    # LPIPS (omnitokenizer_amd.lpips)
     from omnitokenizer_amd import reconstruction_losses                              # validation losses (omnitokenizer_amd.losses)
     from omnitokenizer_amd import token_cross_entropy                                # LM validation (omnitokenizer_amd.lm_losses)
+    from omnitokenizer_amd import resize_frames, images_to_pixels, center_crop_arr   # Pillow-exact resize (omnitokenizer_amd.frames)
 """
 from .config import OmniTokConfig, make_args  # noqa: F401
 
@@ -19,7 +20,7 @@ _FID_NAMES = ("load_fid_inception", "calculate_activation_statistics", "calculat
 __all__ = ["OmniTokenizer_VQGAN", "GPT", "OmniTokConfig", "make_args", "psnr_ssim", "calculate_psnr", "calculate_ssim",
            "InceptionI3d", "load_fvd_model", "get_fvd_logits", "frechet_distance", "compute_fvd",
            "InceptionV3"] + list(_FID_NAMES) + ["LPIPS", "load_lpips", "lpips_frames", "reconstruction_losses",
-                                           "token_cross_entropy"]
+                                           "token_cross_entropy", "resize_frames", "images_to_pixels", "center_crop_arr"]
 
 
 def __getattr__(name):
@@ -53,4 +54,7 @@ def __getattr__(name):
     if name == "token_cross_entropy":
         from . import lm_losses
         return lm_losses.token_cross_entropy
+    if name in ("resize_frames", "images_to_pixels", "center_crop_arr"):
+        from . import frames
+        return getattr(frames, name)
     raise AttributeError(name)

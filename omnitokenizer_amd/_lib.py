@@ -170,6 +170,9 @@ _PROTOS = {
     "omnitok_engine_timing_report": [P, c_char_p, c_int],
     "omnitok_frames_to_pixels": [POINTER(OmnitokFramesDesc), c_int, c_int, c_int, c_int, c_int, c_int, P, P, P],
     "omnitok_pixels_to_frames": [P, c_int, c_int, c_int, c_int, c_int, c_int, P, P],
+    "omnitok_frames_resize_pil_workspace": [POINTER(OmnitokFramesDesc), c_int, c_int, c_int],
+    "omnitok_frames_resize_pil": [POINTER(OmnitokFramesDesc), c_int, c_int, c_int, c_int, c_int, c_int, P, I64, P, P],
+    "omnitok_pil_resize_coeffs": [c_int, c_int, c_int, POINTER(c_int), P, P],
     "omnitok_frame_metrics_workspace": [c_int, c_int, c_int, c_int],
     "omnitok_frame_metrics": [POINTER(OmnitokMetricsOperand), POINTER(OmnitokMetricsOperand), c_int, c_int, c_int, c_int,
                               c_int, P, P, P, ctypes.c_size_t, P],
@@ -250,7 +253,8 @@ _RESTYPES = {"omnitok_last_error": c_char_p, "omnitok_version": c_char_p,
              "omnitok_engine_workspace_need_encode": c_int64, "omnitok_engine_workspace_need_decode": c_int64,
              "omnitok_lm_destroy": None, "omnitok_comm_destroy": None, "omnitok_lm_cache_bytes": c_int64,
              "omnitok_pl_planes_bytes": c_int64, "omnitok_pl_unscale": c_float,
-             "omnitok_frame_metrics_workspace": c_int64, "omnitok_same_pad": None,
+             "omnitok_frame_metrics_workspace": c_int64, "omnitok_frames_resize_pil_workspace": c_int64,
+             "omnitok_same_pad": None,
              "omnitok_conv3d_packed_ldw": c_int64, "omnitok_lpips_workspace": c_int64,
              "omnitok_losses_workspace": c_int64, "omnitok_lm_token_ce_workspace": c_int64,
              "omnitok_lm_loss_workspace_bytes": c_int64}

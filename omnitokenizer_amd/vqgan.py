@@ -598,6 +598,21 @@ class OmniTokenizer_VQGAN(nn.Module):
 
     @torch.no_grad()
     @_on_own_device
+    def encode_images(self, images, *, interpolation="bicubic", resize_to=None, crop=None, include_embeddings=False,
+                      **encode_kwargs):
+        """encode() of uint8 images of any native size as the reference's ImageDataset hands them over (data.py:83-99):
+        images [B,H,W,3] on this module's GPU, or a list of [H,W,3] tensors of different sizes.  They go through Pillow's
+        resize to args.resolution on the device (frames.images_to_pixels: bit-identical to Resize + ToTensor + Normalize on
+        PIL images; resize_to / crop: the train-time resizecrop) and the result is exactly what
+        encode(images_to_pixels(images, self.resolution, ...), True, include_embeddings, **encode_kwargs) returns."""
+        for c in ([images] if isinstance(images, torch.Tensor) else list(images)):
+            if isinstance(c, torch.Tensor) and c.device != self.device:
+                raise RuntimeError(f"images on {c.device}, model on {self.device}")
+        x = _frames.images_to_pixels(images, self.resolution, interpolation=interpolation, resize_to=resize_to, crop=crop)
+        return self.encode(x, True, include_embeddings=include_embeddings, **encode_kwargs)
+
+    @torch.no_grad()
+    @_on_own_device
     def decode_frames(self, encodings, is_image, layout="thwc"):
         """decode() to uint8 frames, (clamp(x + 0.5, 0, 1) * 255).byte() of the reconstruction (vqgan_eval.py:141-148):
         [B,F,H,W,3] / [B,H,W,3] ("thwc", what save_video_grid and the I3D input take) or [B,3,F,H,W] / [B,3,H,W]
