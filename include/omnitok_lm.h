@@ -39,6 +39,33 @@ void omnitok_lm_destroy(omnitok_lm *lm);
 int omnitok_lm_set_weight(omnitok_lm *lm, const char *name, const void *dev_ptr,
                           const int64_t *shape, int ndim, omnitok_stream_t stream);
 int omnitok_lm_finalize(omnitok_lm *lm, omnitok_stream_t stream);
+/* Format of the weight matrices a decode step streams -- per engine, default OMNITOK_LM_W_FP32 (nothing below applies then).  The
+ * reference trains this model under Lightning's precision="bf16" / 16 (transformer_train.py:63-66): every nn.Linear sees 16-bit
+ * weights there.  A 16-bit engine rounds ONLY the matrices; activations, accumulation, LayerNorm, attention and the K/V cache stay
+ * fp32, and the decode step -- bound by the bytes of exactly these matrices -- streams half of them.
+ *   Which tensors: wqkv (query | key | value, concatenated at finalize), attn.proj.weight, mlp.0.weight, mlp.2.weight of every
+ *     block and head.weight.  Biases, LayerNorm parameters, tok_emb, pos_emb and the K/V cache stay fp32 (gathers, or a few KB
+ *     per step).
+ *   Rounding: on the device, inside omnitok_lm_finalize, round to nearest even -- the bits of tensor.to(torch.bfloat16) /
+ *     .to(torch.float16), fp16 subnormals included.
+ *   Two images of each matrix: the packed 16-bit one, which the decode GEMVs read and widen to fp32 in registers (exact), and the
+ *     fp32 one OVERWRITTEN IN PLACE with the rounded values, which omnitok_lm_prefill* and omnitok_lm_prefill_loss keep using
+ *     unchanged -- prefill and stepping compute on the same weight values ("same arithmetic as T decode steps" below holds).
+ *     Weight memory is 1.5 x the fp32 engine's.
+ *   fp16 range: if an element of one of these matrices rounds to +-inf in fp16, omnitok_lm_finalize fails with
+ *     OMNITOK_ERR_INVALID and names the tensor in omnitok_last_error(); the engine stays unfinalized and, its images being
+ *     half-rounded by then, accepts a finalize only after ALL weights were set again.  bf16 has fp32's range.
+ *   omnitok_lm_set_weight_format clears `finalized` (-1: null engine / unknown format).  As after any finalize the q/k/v
+ *     sources are gone: set ALL weights again, then finalize. */
+#define OMNITOK_LM_W_FP32 0
+#define OMNITOK_LM_W_BF16 1
+#define OMNITOK_LM_W_FP16 2
+int omnitok_lm_set_weight_format(omnitok_lm *lm, int fmt);
+int omnitok_lm_weight_format(omnitok_lm *lm); /* -1: null engine */
+/* bytes of matrices one decode step WITH logits streams in the engine's format:
+ * (12 * n_embd^2 * n_layer + vocab_size * n_embd) * sizeof(element).  Needs no GPU; 0 for a null engine. */
+int64_t omnitok_lm_step_weight_bytes(omnitok_lm *lm);
+
 /* K/V cache [n_layer][2][max_batch][n_head][max_len][head_dim] fp32 + step workspaces. */
 int omnitok_lm_alloc_cache(omnitok_lm *lm, int max_batch, int max_len);
 int64_t omnitok_lm_cache_bytes(omnitok_lm *lm);
@@ -130,6 +157,12 @@ int omnitok_lm_select(const float *logits, const float *logits_uncond, int B, in
 int omnitok_lm_gemv(const float *x, const float *w, const float *bias, const float *residual,
                     const float *ln_gamma, const float *ln_beta, float *y, int B, int N, int K,
                     int act, omnitok_stream_t stream);
+/* omnitok_lm_gemv over a packed 16-bit weight matrix w16 [N, K] (fmt = OMNITOK_LM_W_BF16 | OMNITOK_LM_W_FP16, 16-byte aligned;
+ * anything else returns -1): each weight is widened to fp32 in registers, then the same fmaf chains into fp32 accumulators.
+ * Same contract otherwise. */
+int omnitok_lm_gemv_w16(const float *x, const void *w16, int fmt, const float *bias, const float *residual,
+                        const float *ln_gamma, const float *ln_beta, float *y, int B, int N, int K, int act,
+                        omnitok_stream_t stream);
 /* Decode attention for one layer: qkv[B, 3*C] = (query | key | value) of the new token; K/V cache of
  * this layer kc / vc [max_batch][n_head][max_len][head_dim]; out[B, C].  scratch: float
  * [B * n_head * ceil(max_len/256) * (2 + head_dim)]. */

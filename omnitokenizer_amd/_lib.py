@@ -202,6 +202,9 @@ _PROTOS = {
     "omnitok_lm_destroy": [P],
     "omnitok_lm_set_weight": [P, c_char_p, P, POINTER(I64), c_int, P],
     "omnitok_lm_finalize": [P, P],
+    "omnitok_lm_set_weight_format": [P, c_int],
+    "omnitok_lm_weight_format": [P],
+    "omnitok_lm_step_weight_bytes": [P],
     "omnitok_lm_alloc_cache": [P, c_int, c_int],
     "omnitok_lm_cache_bytes": [P],
     "omnitok_lm_overflowed": [P, P],
@@ -215,6 +218,7 @@ _PROTOS = {
     "omnitok_lm_loss_workspace_bytes": [P],
     "omnitok_lm_select": [P, P, c_int, c_int, c_float, c_float, c_float, c_int, c_float, c_int, P, P, P, P, P],
     "omnitok_lm_gemv": [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P],
+    "omnitok_lm_gemv_w16": [P, P, c_int, P, P, P, P, P, c_int, c_int, c_int, c_int, P],
     "omnitok_lm_attn_decode": [P, P, P, P, c_int, c_int, c_int, c_int, P, P, P],
     "omnitok_pl_planes_bytes": [I64, c_int, c_int],
     "omnitok_pl_unscale": [c_float],
@@ -257,7 +261,7 @@ _RESTYPES = {"omnitok_last_error": c_char_p, "omnitok_version": c_char_p,
              "omnitok_same_pad": None,
              "omnitok_conv3d_packed_ldw": c_int64, "omnitok_lpips_workspace": c_int64,
              "omnitok_losses_workspace": c_int64, "omnitok_lm_token_ce_workspace": c_int64,
-             "omnitok_lm_loss_workspace_bytes": c_int64}
+             "omnitok_lm_loss_workspace_bytes": c_int64, "omnitok_lm_step_weight_bytes": c_int64}
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)
 

@@ -5,7 +5,7 @@
 
 namespace omnitok {
 
-__device__ __forceinline__ auto x3_rsrc(const float *ptr, int bytes) {
+__device__ __forceinline__ auto x3_rsrc(const void *ptr, int bytes) {
     const unsigned long long u = reinterpret_cast<unsigned long long>(ptr);
     const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u);
     const unsigned hi32 = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));

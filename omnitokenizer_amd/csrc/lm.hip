@@ -1,9 +1,9 @@
 // LM consumer of the token path: KV-cached decode step of the reference's minGPT
 // (OmniTokenizer/modules/gpt.py:74-275) for sample_with_past (gpt.py:327-359).
 //
-// One token per stream per step, so every matrix product is a GEMV over fp32 weights: the step is
-// HBM-bound (24 layers x 12 C^2 x 4 B = 2.7 GB of weights at C = 1536, plus the K/V cache), not
-// MFMA-bound.  Kernels:
+// One token per stream per step, so every matrix product is a GEMV over the weights: the step is
+// HBM-bound (24 layers x 12 C^2 x 4 B = 2.7 GB of fp32 weights at C = 1536, half of that in a 16-bit
+// weight format -- omnitok_lm_set_weight_format -- plus the K/V cache), not MFMA-bound.  Kernels:
 //   lm_embed_kernel        x = tok_emb[idx] + pos_emb[pos]
 //   lm_gemv_kernel         y = act(LN(x) W^T + b) (+ residual): one wave streams ROWS weight rows with
 //                          16-byte loads (each row read exactly once for up to 8 batch rows), LayerNorm
@@ -70,6 +70,45 @@ constexpr int LM_KP = 2048;        // K panel staged in LDS (BQ * LM_KP * 4 B <=
 constexpr int LM_MAX_CHUNKS = 32;  // attention chunks per sequence: max_len <= 8192
 constexpr int LM_MAX_HEADS = 32;   // (bounds the merge-weight table in LDS: B * heads * chunks floats)
 
+// Weight element types of the decode GEMVs (omnitok_lm_set_weight_format).  Both kernels below take the element type WT as a template
+// parameter; a lane's share of a 256-column chunk is always the same 4 consecutive weights -- 16 bytes of fp32, 8 bytes of a 16-bit
+// format -- widened to fp32 in registers (exact) in front of the same fmaf chain.  WT = float compiles to the code it was before.
+struct lm_bf16 { unsigned short bits; };
+struct lm_fp16 { unsigned short bits; };
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+template <typename WT> struct LmW;
+template <> struct LmW<float> {
+    typedef f32x4 quad;  // 4 consecutive weights as loaded
+    static __device__ __forceinline__ f32x4 widen(const f32x4 &q) { return q; }
+    static __device__ __forceinline__ quad load(__amdgpu_buffer_rsrc_t rs, int byte_off) {
+        return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, byte_off, 0, 2));
+    }
+};
+template <> struct LmW<lm_bf16> {
+    typedef u32x2 quad;
+    static __device__ __forceinline__ f32x4 widen(const u32x2 &q) {  // bf16 is the high half of the fp32 pattern: a shift or a mask per element
+        return f32x4{__builtin_bit_cast(float, q[0] << 16), __builtin_bit_cast(float, q[0] & 0xffff0000u),
+                     __builtin_bit_cast(float, q[1] << 16), __builtin_bit_cast(float, q[1] & 0xffff0000u)};
+    }
+    static __device__ __forceinline__ quad load(__amdgpu_buffer_rsrc_t rs, int byte_off) {
+        return __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(rs, byte_off, 0, 2));
+    }
+};
+template <> struct LmW<lm_fp16> {
+    typedef u32x2 quad;
+    // fp16 -> fp32 of each half, subnormals included (exact).  The compiler folds the conversion into the multiply-add
+    // (v_fma_mix_f32 reads an fp16 half as a source operand): no VALU instruction of its own.  The quad is reinterpreted as a whole:
+    // __builtin_bit_cast of ONE ELEMENT of an ext_vector (q[1]) reads element 0 with this compiler.
+    static __device__ __forceinline__ f32x4 widen(const u32x2 &q) {
+        const f16x4 h = __builtin_bit_cast(f16x4, q);
+        return f32x4{(float)h[0], (float)h[1], (float)h[2], (float)h[3]};
+    }
+    static __device__ __forceinline__ quad load(__amdgpu_buffer_rsrc_t rs, int byte_off) {
+        return __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(rs, byte_off, 0, 2));
+    }
+};
+
 struct LmMerge {
     const float *part;         // [B][n_head][nchunk][2 + hd]
     const int32_t *cache_len;  // [B]
@@ -78,8 +117,8 @@ struct LmMerge {
     float *merged = nullptr;   // [B][n_head * hd] scratch: where the multi-stream MFMA path materialises the merged attention output
 };
 
-template <int BQ, int ROWS, int U, int ACT, bool LN, bool XM, int NW>
-__global__ __launch_bounds__(NW * 64) void lm_gemv_kernel(const float *__restrict__ x, const float *__restrict__ w,
+template <typename WT, int BQ, int ROWS, int U, int ACT, bool LN, bool XM, int NW>
+__global__ __launch_bounds__(NW * 64) void lm_gemv_kernel(const float *__restrict__ x, const WT *__restrict__ w,
                                                       const float *__restrict__ bias, const float *residual,
                                                       const float *__restrict__ g, const float *__restrict__ beta,
                                                       float *y, int N, int K, LmMerge mg) {
@@ -91,20 +130,21 @@ __global__ __launch_bounds__(NW * 64) void lm_gemv_kernel(const float *__restric
     const int row0 = (blockIdx.x * NW + wave) * ROWS;
     const int kp = K < LM_KP ? K : LM_KP;
     const int nch = K >> 8;  // 256-float chunks
-    const float *wr[ROWS];
+    typedef typename LmW<WT>::quad wquad;
+    const WT *wr[ROWS];
 #pragma unroll
     for (int r = 0; r < ROWS; ++r) wr[r] = w + (int64_t)(row0 + r < N ? row0 + r : N - 1) * K + lane * 4;
-    auto load_w = [&](f32x4 (&dst)[ROWS][U], int c0) {
+    auto load_w = [&](wquad (&dst)[ROWS][U], int c0) {
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             if (c0 + u < nch) {  // uniform; chunks past the row are neither loaded nor consumed
 #pragma unroll
                 for (int r = 0; r < ROWS; ++r)
-                    dst[r][u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(wr[r] + (c0 + u) * 256));
+                    dst[r][u] = __builtin_nontemporal_load(reinterpret_cast<const wquad *>(wr[r] + (c0 + u) * 256));
             }
         }
     };
-    f32x4 wa[ROWS][U], wb[ROWS][U];
+    wquad wa[ROWS][U], wb[ROWS][U];
     load_w(wa, 0);  // in flight while the LayerNorm statistics / merge weights are computed
     // LayerNorm with the whole row in one LDS panel (K <= LM_KP, every GPT block): x, gamma and beta are requested
     // together at kernel start (one memory round trip instead of three dependent ones), the two-pass statistics are
@@ -202,20 +242,23 @@ __global__ __launch_bounds__(NW * 64) void lm_gemv_kernel(const float *__restric
 #pragma unroll
         for (int b = 0; b < BQ; ++b) acc[r][b] = 0.0f;
 
-    auto consume = [&](const f32x4 (&wv)[ROWS][U], int c0, int cbase) {
+    auto consume = [&](const wquad (&wv)[ROWS][U], int c0, int cbase) {
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             if (c0 + u < nch) {
                 const int off = (c0 + u - cbase) * 256 + lane * 4;
+                f32x4 wf[ROWS];  // widened once, used by every stream
+#pragma unroll
+                for (int r = 0; r < ROWS; ++r) wf[r] = LmW<WT>::widen(wv[r][u]);
 #pragma unroll
                 for (int b = 0; b < BQ; ++b) {
                     const f32x4 xv = *reinterpret_cast<const f32x4 *>(xs + b * kp + off);
 #pragma unroll
                     for (int r = 0; r < ROWS; ++r) {
-                        acc[r][b] = fmaf(wv[r][u][0], xv[0], acc[r][b]);
-                        acc[r][b] = fmaf(wv[r][u][1], xv[1], acc[r][b]);
-                        acc[r][b] = fmaf(wv[r][u][2], xv[2], acc[r][b]);
-                        acc[r][b] = fmaf(wv[r][u][3], xv[3], acc[r][b]);
+                        acc[r][b] = fmaf(wf[r][0], xv[0], acc[r][b]);
+                        acc[r][b] = fmaf(wf[r][1], xv[1], acc[r][b]);
+                        acc[r][b] = fmaf(wf[r][2], xv[2], acc[r][b]);
+                        acc[r][b] = fmaf(wf[r][3], xv[3], acc[r][b]);
                     }
                 }
             }
@@ -372,8 +415,8 @@ __device__ __forceinline__ void wave_transpose_sum(float (&a)[N], int lane) {
 #ifndef LM_TRACE
 #define LM_TRACE 0  // 1: s_memrealtime stamps per workgroup (tools/r05/lm_timeline.py; build with OMNITOK_EXTRA_FLAGS=-DLM_TRACE=1)
 #endif
-template <int BQ, int CW, int RG, int ACT, bool LN, bool XM, int NW>
-__global__ __launch_bounds__(NW * 64) void lm_gemv_ks_kernel(const float *__restrict__ x, const float *__restrict__ w,
+template <typename WT, int BQ, int CW, int RG, int ACT, bool LN, bool XM, int NW>
+__global__ __launch_bounds__(NW * 64) void lm_gemv_ks_kernel(const float *__restrict__ x, const WT *__restrict__ w,
                                                              const float *__restrict__ bias, const float *residual,
                                                              const float *__restrict__ g, const float *__restrict__ beta,
                                                              float *y, int N, int K, LmMerge mg, long long *trace) {
@@ -389,22 +432,25 @@ __global__ __launch_bounds__(NW * 64) void lm_gemv_ks_kernel(const float *__rest
     const int col0 = wave * CW * 256 + lane * 4;  // + cw * 256
     // the workgroup's rows through a buffer descriptor that ends with them: a request past the last row (short last group, the
     // prefetch of the groups after the last) returns zeros without touching memory -- no branch, no wasted traffic.  aux = 2: nt
-    const auto w_rs = x3_rsrc(w + (int64_t)r_begin * K, nrows * K * 4);
-    const int w_vo = col0 * 4;
-    auto load_w = [&](f32x4 (&dst)[RG][CW], int grp) {
+    typedef typename LmW<WT>::quad wquad;
+    constexpr int ES = (int)sizeof(WT);  // bytes per weight
+    const auto w_rs = x3_rsrc(w + (int64_t)r_begin * K, nrows * K * ES);
+    const int w_vo = col0 * ES;
+    auto load_w = [&](wquad (&dst)[RG][CW], int grp) {
 #pragma unroll
         for (int r = 0; r < RG; ++r)
 #pragma unroll
             for (int cw = 0; cw < CW; ++cw)
                 // the row offset rides in the VECTOR offset: that operand (+ the instruction offset) is what the descriptor's range
                 // check covers on every generation; an soffset is documented as outside it on some
-                dst[r][cw] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(w_rs, w_vo + ((grp * RG + r) * K + cw * 256) * 4, 0, 2));
+                dst[r][cw] = LmW<WT>::load(w_rs, w_vo + ((grp * RG + r) * K + cw * 256) * ES);
     };
-    f32x4 wa[RG][CW], wb[RG][CW];
+    wquad wa[RG][CW], wb[RG][CW];
     f32x4 xr[BQ][CW];
     // the finishing thread of output (row r, stream b) is thread r * BQ + b; every thread loads from a clamped index
     const int fr = tid / BQ < nrows ? tid / BQ : nrows - 1, fb = tid % BQ, fn = r_begin + fr;
-    const float *bias_p = bias ? bias + fn : w, *res_p = residual ? residual + (int64_t)fb * N + fn : w;
+    const float *w_any = reinterpret_cast<const float *>(w);  // (a valid address for the loads whose value is not used)
+    const float *bias_p = bias ? bias + fn : w_any, *res_p = residual ? residual + (int64_t)fb * N + fn : w_any;
     float e_bias, e_res;
     // ---- this wave's slice of the activations -> registers, then the weights of the first two row groups ----
     if constexpr (XM) {
@@ -577,22 +623,26 @@ __global__ __launch_bounds__(NW * 64) void lm_gemv_ks_kernel(const float *__rest
     }
     stamp(1);
     // ---- rows, RG at a time, two groups of weights in flight ----
-    auto consume = [&](const f32x4 (&wv)[RG][CW], int grp) {
+    auto consume = [&](const wquad (&wv)[RG][CW], int grp) {
         float acc[RG * BQ];
 #pragma unroll
-        for (int r = 0; r < RG; ++r)
+        for (int r = 0; r < RG; ++r) {
+            f32x4 wf[CW];  // widened once, used by every stream
+#pragma unroll
+            for (int cw = 0; cw < CW; ++cw) wf[cw] = LmW<WT>::widen(wv[r][cw]);
 #pragma unroll
             for (int b = 0; b < BQ; ++b) {
                 float a = 0.0f;
 #pragma unroll
                 for (int cw = 0; cw < CW; ++cw) {
-                    a = fmaf(wv[r][cw][0], xr[b][cw][0], a);
-                    a = fmaf(wv[r][cw][1], xr[b][cw][1], a);
-                    a = fmaf(wv[r][cw][2], xr[b][cw][2], a);
-                    a = fmaf(wv[r][cw][3], xr[b][cw][3], a);
+                    a = fmaf(wf[cw][0], xr[b][cw][0], a);
+                    a = fmaf(wf[cw][1], xr[b][cw][1], a);
+                    a = fmaf(wf[cw][2], xr[b][cw][2], a);
+                    a = fmaf(wf[cw][3], xr[b][cw][3], a);
                 }
                 acc[r * BQ + b] = a;
             }
+        }
         wave_transpose_sum<RG * BQ>(acc, lane);  // lane l: the wave's sum for (row, stream) number l / (64 / (RG BQ))
         constexpr int LPV = 64 / (RG * BQ);      // lanes per value
         const int id = lane / LPV, r = id / BQ;
@@ -893,6 +943,37 @@ __global__ void lm_concat3_kernel(const float *a, const float *b, const float *c
     out[i] = i < n ? a[i] : (i < 2 * n ? b[i - n] : c[i - 2 * n]);
 }
 
+// omnitok_lm_set_weight_format: rounds a matrix to bf16 / fp16 (round to nearest even: the bits of tensor.to(torch.bfloat16) /
+// .to(torch.float16), fp16 subnormals included), writes the packed image for the decode GEMVs and puts the rounded values back into
+// the fp32 image in place (what the prefill GEMMs read).  An fp16 result of +-inf sets flags[element / seg]: one flag per source
+// tensor of a concatenated matrix.  n % 4 == 0.
+template <int FMT>
+__global__ __launch_bounds__(256) void lm_round_w16_kernel(float *__restrict__ w, unsigned short *__restrict__ out, int64_t n4,
+                                                           int64_t seg, int *__restrict__ flags) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n4) return;
+    f32x4 v = reinterpret_cast<const f32x4 *>(w)[i];
+    unsigned short h[4];
+    bool inf = false;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const float f = v[e];  // (a scalar copy: __builtin_bit_cast of a vector ELEMENT reads element 0 with this compiler)
+        if constexpr (FMT == OMNITOK_LM_W_BF16) {
+            const unsigned u = __builtin_bit_cast(unsigned, f);
+            h[e] = f != f ? (unsigned short)0x7FC0 : (unsigned short)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
+            v[e] = __builtin_bit_cast(float, (unsigned)h[e] << 16);
+        } else {
+            const _Float16 r = (_Float16)f;  // v_cvt_f16_f32: round to nearest even, subnormal results kept
+            h[e] = __builtin_bit_cast(unsigned short, r);
+            v[e] = (float)r;
+            inf = inf || (h[e] & 0x7FFF) == 0x7C00;
+        }
+    }
+    reinterpret_cast<f32x4 *>(w)[i] = v;
+    reinterpret_cast<u32x2 *>(out)[i] = u32x2{(unsigned)h[0] | ((unsigned)h[1] << 16), (unsigned)h[2] | ((unsigned)h[3] << 16)};
+    if (inf) flags[(i * 4) / seg] = 1;
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // Multi-stream decode GEMV on the matrix cores (r06): y[b][n] = act(LN(x_b) . w_n + bias_n) (+ residual) for 4 .. 8 streams in ONE
 // pass over the weights.  The K-sliced VALU kernel above spends, per weight float4, 4 FMAs per stream plus a cross-lane
@@ -1098,14 +1179,14 @@ int g_lm_loss_chunk_rows = 2048;  // "lm_loss_chunk_rows": rows per head-GEMM bl
 int g_lm_balance = 1;  // "lm_balance": 1 = waves per workgroup and rows per wave chosen so that every CU gets the same number of
                        // workgroups | 0 = 4 waves, 1 row (N <= 2048) or 2 rows per wave
 
-template <int BQ, int ROWS, int U, int ACT, bool LN, bool XM, int NW>
-static void launch_gemv_cfg(const float *x, const float *w, const float *bias, const float *residual, const float *g,
+template <typename WT, int BQ, int ROWS, int U, int ACT, bool LN, bool XM, int NW>
+static void launch_gemv_cfg(const float *x, const WT *w, const float *bias, const float *residual, const float *g,
                             const float *beta, float *y, int N, int K, const LmMerge &mg, hipStream_t stream) {
     const int kp = K < LM_KP ? K : LM_KP;
     const int lds = BQ * kp * 4;
     const int rows_per_wg = NW * ROWS;
-    if (lds > 65536) (void)set_max_dynamic_lds(reinterpret_cast<const void *>(lm_gemv_kernel<BQ, ROWS, U, ACT, LN, XM, NW>), lds);
-    hipLaunchKernelGGL((lm_gemv_kernel<BQ, ROWS, U, ACT, LN, XM, NW>), dim3((N + rows_per_wg - 1) / rows_per_wg), dim3(NW * 64),
+    if (lds > 65536) (void)set_max_dynamic_lds(reinterpret_cast<const void *>(lm_gemv_kernel<WT, BQ, ROWS, U, ACT, LN, XM, NW>), lds);
+    hipLaunchKernelGGL((lm_gemv_kernel<WT, BQ, ROWS, U, ACT, LN, XM, NW>), dim3((N + rows_per_wg - 1) / rows_per_wg), dim3(NW * 64),
                        lds, stream, x, w, bias, residual, g, beta, y, N, K, mg);
 }
 
@@ -1117,10 +1198,16 @@ static long long *lm_trace_slot(int grid) {  // 8 stamps per workgroup, 1024 wor
     return g_gemm_trace + (int64_t)(g_lm_trace_launch++) * 1024 * 8;
 }
 
-template <int BQ, int ACT, bool LN, bool XM>
-static void launch_gemv_rows(const float *x, const float *w, const float *bias, const float *residual, const float *g,
+// 16-bit weights in the K-sliced kernel keep the fp32 form's rows per group: 4 KiB of weights in flight per wave.  Doubling the rows
+// per group (8 KiB, the fp32 form's bytes) measured SLOWER at every batch size -- bf16 decode step at 1 / 2 / 4 / 8 streams
+// 0.737 / 0.856 / 0.972 / 1.311 ms against 0.708 / 0.792 / 0.855 / 1.160 ms, fp32 0.849 / 0.918 / 1.010 / 1.268 ms in the same session
+// (the A/B lines of profiles/lm_w16_bench.json): the transpose-sum of 64 accumulators per group outweighs the deeper queue.
+template <typename WT, int BQ, int ACT, bool LN, bool XM>
+static void launch_gemv_rows(const float *x, const WT *w, const float *bias, const float *residual, const float *g,
                              const float *beta, float *y, int N, int K, const LmMerge &mg, hipStream_t stream) {
-    // ROWS weight rows x U chunks (x2 register buffers) per wave = 8 KiB of weights in flight per wave.
+    // ROWS weight rows x U chunks (x2 register buffers) per wave = 8 KiB of fp32 weights in flight per wave.  The 16-bit
+    // instantiations keep ROWS and U (4 KiB in flight): the row kernel serves no GEMV of the reference's LM, it was taken as it is
+    // and not A/B'd -- the rows-per-group A/B above is about the K-sliced kernel only.
     // Narrow outputs (N <= 2048: the C x C and C x 4C projections) take one row per wave so that the
     // launch still covers every CU.  Wide outputs: 2 rows x 2 chunks x 2 buffers per wave, i.e. a whole K = 1536 row pair is
     // requested before the LayerNorm prologue finishes (the matrix streams from HBM while x is normalised).
@@ -1138,12 +1225,13 @@ static void launch_gemv_rows(const float *x, const float *w, const float *bias, 
         const int max_rows = (N + grid - 1) / grid + 1;
         if (N >= grid && max_rows * BQ <= 6 * 64) {
             const int lds = max_rows * BQ * 8 * 4;
+            constexpr bool W16 = sizeof(WT) == 2;
 #define OT_KS(CW_, RG_, NW_)                                                                                                         \
-    hipLaunchKernelGGL((lm_gemv_ks_kernel<BQ, CW_, RG_, ACT, LN, XM, NW_>), dim3(grid), dim3(NW_ * 64), lds, stream, x, w, bias, residual, g, \
+    hipLaunchKernelGGL((lm_gemv_ks_kernel<WT, BQ, CW_, RG_, ACT, LN, XM, NW_>), dim3(grid), dim3(NW_ * 64), lds, stream, x, w, bias, residual, g, \
                        beta, y, N, K, mg, lm_trace_slot(grid))
             // rows per group: 2 groups in flight per wave = 8 KiB ("lm_ks_deep" 1: 16 KiB, measured slower: profiles/r05_lm_timeline.txt)
-            constexpr int DEEP = BQ <= 2 ? 2 : 1;  // (the deep variants exist for B <= 2 only)
-            const bool deep = g_lm_ks_deep == 1 && BQ <= 2;
+            constexpr int DEEP = BQ <= 2 && !W16 ? 2 : 1;  // (the deep variants exist for B <= 2 and fp32 weights only)
+            const bool deep = g_lm_ks_deep == 1 && BQ <= 2 && !W16;
             if (K == 6 * 256) {
                 if (deep) OT_KS(1, 4 * DEEP, 6);
                 else OT_KS(1, 4, 6);
@@ -1176,42 +1264,57 @@ static void launch_gemv_rows(const float *x, const float *w, const float *bias, 
     };
     const bool six = g_lm_balance && BQ <= 2 && K % 256 == 0;
     if (N <= 2048) {
-        if (six && waste(6) + 0.05 < waste(4)) launch_gemv_cfg<BQ, 1, 4, ACT, LN, XM, 6>(x, w, bias, residual, g, beta, y, N, K, mg, stream);
-        else launch_gemv_cfg<BQ, 1, 4, ACT, LN, XM, 4>(x, w, bias, residual, g, beta, y, N, K, mg, stream);
+        if (six && waste(6) + 0.05 < waste(4)) launch_gemv_cfg<WT, BQ, 1, 4, ACT, LN, XM, 6>(x, w, bias, residual, g, beta, y, N, K, mg, stream);
+        else launch_gemv_cfg<WT, BQ, 1, 4, ACT, LN, XM, 4>(x, w, bias, residual, g, beta, y, N, K, mg, stream);
     } else if (six && waste(6) + 0.05 < waste(8)) {
-        launch_gemv_cfg<BQ, 1, 4, ACT, LN, XM, 6>(x, w, bias, residual, g, beta, y, N, K, mg, stream);
+        launch_gemv_cfg<WT, BQ, 1, 4, ACT, LN, XM, 6>(x, w, bias, residual, g, beta, y, N, K, mg, stream);
     } else if (g_lm_wide_u == 2) {
-        launch_gemv_cfg<BQ, 2, 2, ACT, LN, XM, 4>(x, w, bias, residual, g, beta, y, N, K, mg, stream);
+        launch_gemv_cfg<WT, BQ, 2, 2, ACT, LN, XM, 4>(x, w, bias, residual, g, beta, y, N, K, mg, stream);
     } else {
-        launch_gemv_cfg<BQ, 2, 4, ACT, LN, XM, 4>(x, w, bias, residual, g, beta, y, N, K, mg, stream);
+        launch_gemv_cfg<WT, BQ, 2, 4, ACT, LN, XM, 4>(x, w, bias, residual, g, beta, y, N, K, mg, stream);
     }
 }
 
-template <int BQ>
-static void launch_gemv_bq(const float *x, const float *w, const float *bias, const float *residual, const float *g,
+template <typename WT, int BQ>
+static void launch_gemv_bq(const float *x, const WT *w, const float *bias, const float *residual, const float *g,
                            const float *beta, float *y, int N, int K, int act, const LmMerge *mg, hipStream_t stream) {
     const LmMerge none{nullptr, nullptr, 0, 0, 0, LM_CHUNK};
     if (mg) {
-        launch_gemv_rows<BQ, 0, false, true>(x, w, bias, residual, g, beta, y, N, K, *mg, stream);
+        launch_gemv_rows<WT, BQ, 0, false, true>(x, w, bias, residual, g, beta, y, N, K, *mg, stream);
     } else if (g) {
-        if (act) launch_gemv_rows<BQ, 1, true, false>(x, w, bias, residual, g, beta, y, N, K, none, stream);
-        else launch_gemv_rows<BQ, 0, true, false>(x, w, bias, residual, g, beta, y, N, K, none, stream);
+        if (act) launch_gemv_rows<WT, BQ, 1, true, false>(x, w, bias, residual, g, beta, y, N, K, none, stream);
+        else launch_gemv_rows<WT, BQ, 0, true, false>(x, w, bias, residual, g, beta, y, N, K, none, stream);
     } else {
-        if (act) launch_gemv_rows<BQ, 1, false, false>(x, w, bias, residual, g, beta, y, N, K, none, stream);
-        else launch_gemv_rows<BQ, 0, false, false>(x, w, bias, residual, g, beta, y, N, K, none, stream);
+        if (act) launch_gemv_rows<WT, BQ, 1, false, false>(x, w, bias, residual, g, beta, y, N, K, none, stream);
+        else launch_gemv_rows<WT, BQ, 0, false, false>(x, w, bias, residual, g, beta, y, N, K, none, stream);
+    }
+}
+
+template <typename WT>
+static void launch_gemv_group(int bq, const float *x, const WT *w, const float *bias, const float *residual, const float *g,
+                              const float *beta, float *y, int N, int K, int act, const LmMerge *mg, hipStream_t stream) {
+    switch (bq) {
+        case 8: launch_gemv_bq<WT, 8>(x, w, bias, residual, g, beta, y, N, K, act, mg, stream); break;
+        case 4: launch_gemv_bq<WT, 4>(x, w, bias, residual, g, beta, y, N, K, act, mg, stream); break;
+        case 2: launch_gemv_bq<WT, 2>(x, w, bias, residual, g, beta, y, N, K, act, mg, stream); break;
+        default: launch_gemv_bq<WT, 1>(x, w, bias, residual, g, beta, y, N, K, act, mg, stream); break;
     }
 }
 
 // y = act(LN(x) W^T + b) (+ residual) for B rows, in groups of up to 8 rows per pass over the weights.
 // mg != nullptr: the activations are the merged attention partials (x unused).
-static int lm_gemv_any(const float *x, const float *w, const float *bias, const float *residual, const float *g,
-                       const float *beta, float *y, int B, int N, int K, int act, const LmMerge *mg, hipStream_t stream) {
+// w: the fp32 matrix | w16 != nullptr: its packed image in format fmt (OMNITOK_LM_W_BF16 / _FP16), which every group of streams then
+// takes: the 16-bit kernels measured faster than the fp32 ones over the rounded fp32 image at 1, 2, 4 and 8 streams,
+// so no group is routed back.
+static int lm_gemv_any(const float *x, const float *w, const void *w16, int fmt, const float *bias, const float *residual,
+                       const float *g, const float *beta, float *y, int B, int N, int K, int act, const LmMerge *mg,
+                       hipStream_t stream) {
     for (int b0 = 0; b0 < B;) {
         const int left = B - b0;
         const float *xb = x ? x + (int64_t)b0 * K : nullptr, *rb = residual ? residual + (int64_t)b0 * N : nullptr;
         float *yb = y + (int64_t)b0 * N;
         const bool mfma_k = K == 1536 || K == 2048 || (!g && (K == 6144 || K == 8192));
-        if (g_lm_mfma && left >= 4 && mfma_k && N >= 16 && (int64_t)N * K < (1ll << 29) && (!mg || mg->merged)) {
+        if (g_lm_mfma && !w16 && left >= 4 && mfma_k && N >= 16 && (int64_t)N * K < (1ll << 29) && (!mg || mg->merged)) {
             // 4 .. 8 streams in one pass over the weights on the matrix cores (lm_gemm4_kernel)
             const int bq = left > 8 ? 8 : left;
             if (mg) {   // the merged attention output as a tensor first (the VALU path merges inside its prologue)
@@ -1239,11 +1342,11 @@ static int lm_gemv_any(const float *x, const float *w, const float *bias, const 
             m2.cache_len += b0;
         }
         const LmMerge *mp = mg ? &m2 : nullptr;
-        switch (bq) {
-            case 8: launch_gemv_bq<8>(xb, w, bias, rb, g, beta, yb, N, K, act, mp, stream); break;
-            case 4: launch_gemv_bq<4>(xb, w, bias, rb, g, beta, yb, N, K, act, mp, stream); break;
-            case 2: launch_gemv_bq<2>(xb, w, bias, rb, g, beta, yb, N, K, act, mp, stream); break;
-            default: launch_gemv_bq<1>(xb, w, bias, rb, g, beta, yb, N, K, act, mp, stream); break;
+        if (w16) {
+            if (fmt == OMNITOK_LM_W_BF16) launch_gemv_group(bq, xb, static_cast<const lm_bf16 *>(w16), bias, rb, g, beta, yb, N, K, act, mp, stream);
+            else launch_gemv_group(bq, xb, static_cast<const lm_fp16 *>(w16), bias, rb, g, beta, yb, N, K, act, mp, stream);
+        } else {
+            launch_gemv_group(bq, xb, w, bias, rb, g, beta, yb, N, K, act, mp, stream);
         }
         OT_LAUNCH_CHECK("lm_gemv");
         b0 += bq;
@@ -1265,7 +1368,21 @@ extern "C" int omnitok_lm_gemv(const float *x, const float *w, const float *bias
     OT_CHECK_ARG((ln_gamma != nullptr) == (ln_beta != nullptr), "lm_gemv: ln_gamma / ln_beta must come together");
     OT_CHECK_ARG(act == 0 || act == 1, "lm_gemv: act %d", act);
     OT_CHECK_ARG(aligned16(x) && aligned16(w), "lm_gemv: unaligned");
-    return lm_gemv_any(x, w, bias, residual, ln_gamma, ln_beta, y, B, N, K, act, nullptr, stream);
+    return lm_gemv_any(x, w, nullptr, OMNITOK_LM_W_FP32, bias, residual, ln_gamma, ln_beta, y, B, N, K, act, nullptr, stream);
+}
+
+extern "C" int omnitok_lm_gemv_w16(const float *x, const void *w16, int fmt, const float *bias, const float *residual,
+                                   const float *ln_gamma, const float *ln_beta, float *y, int B, int N, int K, int act,
+                                   omnitok_stream_t stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    OT_CHECK_ARG(fmt == OMNITOK_LM_W_BF16 || fmt == OMNITOK_LM_W_FP16, "lm_gemv_w16: fmt %d (OMNITOK_LM_W_BF16 | OMNITOK_LM_W_FP16)", fmt);
+    OT_CHECK_ARG(x && w16 && y, "lm_gemv_w16: null pointer");
+    if (B == 0) return OMNITOK_OK;
+    OT_CHECK_ARG(B > 0 && B <= 16 && N > 0 && K > 0 && K % 256 == 0, "lm_gemv_w16: bad sizes B=%d N=%d K=%d", B, N, K);
+    OT_CHECK_ARG((ln_gamma != nullptr) == (ln_beta != nullptr), "lm_gemv_w16: ln_gamma / ln_beta must come together");
+    OT_CHECK_ARG(act == 0 || act == 1, "lm_gemv_w16: act %d", act);
+    OT_CHECK_ARG(aligned16(x) && aligned16(w16), "lm_gemv_w16: unaligned");
+    return lm_gemv_any(x, nullptr, w16, fmt, bias, residual, ln_gamma, ln_beta, y, B, N, K, act, nullptr, stream);
 }
 
 // chunk partials only (the engine merges them inside the proj GEMV)
@@ -1323,6 +1440,7 @@ struct LmLayer {
     const float *ln1w, *ln1b, *ln2w, *ln2b;
     float *wqkv, *bqkv;  // (query | key | value) concatenated at finalize
     const float *wproj, *bproj, *w1, *b1, *w2, *b2;
+    const void *wqkv16 = nullptr, *wproj16 = nullptr, *w116 = nullptr, *w216 = nullptr;  // packed 16-bit images (weight_format != FP32)
 };
 
 struct omnitok_lm {
@@ -1332,6 +1450,8 @@ struct omnitok_lm {
     std::vector<void *> owned;
     std::vector<LmLayer> layers;
     bool finalized = false;
+    int weight_format = OMNITOK_LM_W_FP32;  // of the matrices a decode step streams (omnitok_lm_set_weight_format)
+    const void *head16 = nullptr;           // packed image of head.weight
     // cache + workspaces
     float *kv = nullptr;
     int max_batch = 0, max_len = 0;
@@ -1434,6 +1554,26 @@ extern "C" int omnitok_lm_set_weight(omnitok_lm *lm, const char *name, const voi
     return OMNITOK_OK;
 }
 
+extern "C" int omnitok_lm_set_weight_format(omnitok_lm *lm, int fmt) {
+    OT_CHECK_ARG(lm, "lm_set_weight_format: null engine");
+    OT_CHECK_ARG(fmt == OMNITOK_LM_W_FP32 || fmt == OMNITOK_LM_W_BF16 || fmt == OMNITOK_LM_W_FP16,
+                 "lm_set_weight_format: unknown format %d", fmt);
+    lm->weight_format = fmt;
+    lm->finalized = false;
+    return OMNITOK_OK;
+}
+
+extern "C" int omnitok_lm_weight_format(omnitok_lm *lm) {
+    OT_CHECK_ARG(lm, "lm_weight_format: null engine");
+    return lm->weight_format;
+}
+
+extern "C" int64_t omnitok_lm_step_weight_bytes(omnitok_lm *lm) {
+    if (!lm) return 0;
+    const int64_t C = lm->cfg.n_embd, V = lm->cfg.vocab_size;
+    return (12 * C * C * lm->cfg.n_layer + V * C) * (lm->weight_format == OMNITOK_LM_W_FP32 ? 4 : 2);
+}
+
 extern "C" int omnitok_lm_finalize(omnitok_lm *lm, omnitok_stream_t stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     OT_CHECK_ARG(lm, "lm_finalize: null");
@@ -1481,6 +1621,52 @@ extern "C" int omnitok_lm_finalize(omnitok_lm *lm, omnitok_stream_t stream_) {
         L.b2 = LW(lm, p + ".mlp.2.bias");
         lm->layers.push_back(L);
     }
+    lm->head16 = nullptr;
+    std::string overflow;  // the first tensor with an element outside the fp16 range
+    if (lm->weight_format != OMNITOK_LM_W_FP32) {
+        // 16-bit format: round the five matrix families on the device -- packed image for the decode GEMVs, rounded values back into
+        // the fp32 image for the prefill GEMMs.  One overflow flag per source tensor (6 per layer + the head).
+        const int fmt = lm->weight_format, nflags = 6 * lm->cfg.n_layer + 1;
+        const int64_t V = lm->cfg.vocab_size;
+        int *flags = nullptr;
+        OT_HIP(hipMalloc(reinterpret_cast<void **>(&flags), (size_t)nflags * sizeof(int)));
+        lm->owned.push_back(flags);
+        OT_HIP(hipMemsetAsync(flags, 0, (size_t)nflags * sizeof(int), stream));
+        auto round = [&](const float *w, int64_t n, int64_t seg, int *fl, const void **out) -> int {
+            void *p16 = nullptr;
+            OT_HIP(hipMalloc(&p16, (size_t)n * 2));
+            lm->owned.push_back(p16);
+            const int64_t n4 = n / 4;
+            const dim3 grid((unsigned)((n4 + 255) / 256));
+            if (fmt == OMNITOK_LM_W_BF16)
+                hipLaunchKernelGGL(lm_round_w16_kernel<OMNITOK_LM_W_BF16>, grid, dim3(256), 0, stream, const_cast<float *>(w),
+                                   static_cast<unsigned short *>(p16), n4, seg, fl);
+            else
+                hipLaunchKernelGGL(lm_round_w16_kernel<OMNITOK_LM_W_FP16>, grid, dim3(256), 0, stream, const_cast<float *>(w),
+                                   static_cast<unsigned short *>(p16), n4, seg, fl);
+            OT_LAUNCH_CHECK("lm_round_w16");
+            *out = p16;
+            return OMNITOK_OK;
+        };
+        for (int i = 0; i < lm->cfg.n_layer; ++i) {
+            LmLayer &L = lm->layers[i];
+            int *fl = flags + 6 * i;
+            if (int rc = round(L.wqkv, 3 * C * C, C * C, fl, &L.wqkv16)) return rc;
+            if (int rc = round(L.wproj, C * C, C * C, fl + 3, &L.wproj16)) return rc;
+            if (int rc = round(L.w1, 4 * C * C, 4 * C * C, fl + 4, &L.w116)) return rc;
+            if (int rc = round(L.w2, 4 * C * C, 4 * C * C, fl + 5, &L.w216)) return rc;
+        }
+        if (int rc = round(LW(lm, "head.weight"), V * C, V * C, flags + 6 * lm->cfg.n_layer, &lm->head16)) return rc;
+        std::vector<int> hf((size_t)nflags);
+        OT_HIP(hipMemcpyAsync(hf.data(), flags, (size_t)nflags * sizeof(int), hipMemcpyDeviceToHost, stream));
+        OT_HIP(hipStreamSynchronize(stream));
+        for (int f = 0; f < nflags && overflow.empty(); ++f)
+            if (hf[(size_t)f]) {
+                static const char *const names[6] = {".attn.query.weight", ".attn.key.weight", ".attn.value.weight",
+                                                     ".attn.proj.weight", ".mlp.0.weight", ".mlp.2.weight"};
+                overflow = f == nflags - 1 ? std::string("head.weight") : "blocks." + std::to_string(f / 6) + names[f % 6];
+            }
+    }
     // the separate q/k/v copies are no longer needed: free them (2.7 GB model -> no duplicate)
     OT_HIP(hipStreamSynchronize(stream));
     for (int i = 0; i < lm->cfg.n_layer; ++i)
@@ -1493,6 +1679,13 @@ extern "C" int omnitok_lm_finalize(omnitok_lm *lm, omnitok_stream_t stream_) {
                     lm->w[k] = nullptr;
                 }
             }
+    if (!overflow.empty()) {
+        // the fp32 images already hold the fp16-rounded values (some +-inf).  The q/k/v sources were released above like after any
+        // finalize, so a finalize in another format without setting the weights again is refused ("released by a previous finalize")
+        set_error("lm_finalize: %s has an element that rounds to +-inf in fp16 (|w| >= 65520); use OMNITOK_LM_W_BF16 or "
+                  "OMNITOK_LM_W_FP32 for this model, then set all weights again", overflow.c_str());
+        return OMNITOK_ERR_INVALID;
+    }
     lm->finalized = true;
     return OMNITOK_OK;
 }
@@ -1562,6 +1755,7 @@ extern "C" int omnitok_lm_step_ex(omnitok_lm *lm, const int64_t *idx, const floa
     const omnitok_lm_config &c = lm->cfg;
     const int C = c.n_embd, hd = C / c.n_head;
     const int64_t per_layer = (int64_t)lm->max_batch * c.n_head * lm->max_len * hd;
+    const int wf = lm->weight_format;
     hipLaunchKernelGGL(lm_embed_kernel, dim3(B), dim3(256), 0, stream, idx, pos, LW(lm, "tok_emb.weight"),
                        LW(lm, "pos_emb"), emb, pos_extra, lm->x, C, c.vocab_size, c.block_size);
     OT_LAUNCH_CHECK("lm_embed");
@@ -1569,23 +1763,23 @@ extern "C" int omnitok_lm_step_ex(omnitok_lm *lm, const int64_t *idx, const floa
         const LmLayer &L = lm->layers[i];
         float *kc = lm->kv + (int64_t)(2 * i) * per_layer, *vc = kc + per_layer;
         // x + proj(attn(ln1(x)))   (reference gpt.py:159-161)
-        if (int rc = omnitok_lm_gemv(lm->x, L.wqkv, L.bqkv, nullptr, L.ln1w, L.ln1b, lm->qkv, B, 3 * C, C, 0, stream))
+        if (int rc = lm_gemv_any(lm->x, L.wqkv, L.wqkv16, wf, L.bqkv, nullptr, L.ln1w, L.ln1b, lm->qkv, B, 3 * C, C, 0, nullptr, stream))
             return rc;
         if (int rc = lm_attn_partials(lm->qkv, kc, vc, cache_len, B, c.n_head, hd, lm->max_len, lm->part, stream, 0,
                                       lm->err_flag, lm->chunk))
             return rc;
         const LmMerge mg{lm->part, cache_len, c.n_head, hd, (lm->max_len + lm->chunk - 1) / lm->chunk, lm->chunk, lm->qkv};   // (qkv is free once the partials exist)
-        if (int rc = lm_gemv_any(nullptr, L.wproj, L.bproj, lm->x, nullptr, nullptr, lm->x, B, C, C, 0, &mg, stream))
+        if (int rc = lm_gemv_any(nullptr, L.wproj, L.wproj16, wf, L.bproj, lm->x, nullptr, nullptr, lm->x, B, C, C, 0, &mg, stream))
             return rc;
         // x + mlp(ln2(x))          (reference gpt.py:162, 150-155)
-        if (int rc = omnitok_lm_gemv(lm->x, L.w1, L.b1, nullptr, L.ln2w, L.ln2b, lm->hid, B, 4 * C, C, 1, stream))
+        if (int rc = lm_gemv_any(lm->x, L.w1, L.w116, wf, L.b1, nullptr, L.ln2w, L.ln2b, lm->hid, B, 4 * C, C, 1, nullptr, stream))
             return rc;
-        if (int rc = omnitok_lm_gemv(lm->hid, L.w2, L.b2, lm->x, nullptr, nullptr, lm->x, B, C, 4 * C, 0, stream))
+        if (int rc = lm_gemv_any(lm->hid, L.w2, L.w216, wf, L.b2, lm->x, nullptr, nullptr, lm->x, B, C, 4 * C, 0, nullptr, stream))
             return rc;
     }
     if (logits_out)  // ln_f + head (no bias), reference gpt.py:263-264
-        if (int rc = omnitok_lm_gemv(lm->x, LW(lm, "head.weight"), nullptr, nullptr, LW(lm, "ln_f.weight"),
-                                     LW(lm, "ln_f.bias"), logits_out, B, c.vocab_size, C, 0, stream))
+        if (int rc = lm_gemv_any(lm->x, LW(lm, "head.weight"), lm->head16, wf, nullptr, nullptr, LW(lm, "ln_f.weight"),
+                                 LW(lm, "ln_f.bias"), logits_out, B, c.vocab_size, C, 0, nullptr, stream))
             return rc;
     if (advance) {
         hipLaunchKernelGGL(lm_advance_kernel, dim3(1), dim3(64), 0, stream, pos, cache_len, B);

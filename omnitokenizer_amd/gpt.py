@@ -5,9 +5,10 @@ sampling path, plus its sampling loops `sample_with_past` (:327-359) and `sample
 
 The class owns the parameters under the reference's state_dict key names; all arithmetic of a decode
 step runs in libomnitok.so (include/omnitok_lm.h, csrc/lm.hip): a preallocated K/V cache instead of
-the reference's per-step torch.cat of all pasts, GEMV kernels that stream each fp32 weight matrix
-once per step, flash-decode attention, and -- because the step's launch sequence does not depend on
-the position -- one captured HIP graph replayed per token.  Token selection (temperature, the CFG blend,
+the reference's per-step torch.cat of all pasts, GEMV kernels that stream each weight matrix
+once per step (fp32, or bf16 / fp16 at half the bytes: GPT.set_weight_format), flash-decode
+attention, and -- because the step's launch sequence does not depend on the position -- one
+captured HIP graph replayed per token.  Token selection (temperature, the CFG blend,
 top-k / top-p filtering, argmax or one multinomial draw) is one more kernel (csrc/lm_select.hip); the only
 thing torch contributes is the uniform random number per stream (so torch.manual_seed governs the samples).
 Inference only; there is no CPU fallback.
@@ -23,6 +24,9 @@ import torch.nn.functional as F
 
 from . import _lib
 from ._lib import OmnitokLmConfig, check
+
+
+WEIGHT_FORMATS = {"fp32": 0, "bf16": 1, "fp16": 2}  # OMNITOK_LM_W_* of include/omnitok_lm.h
 
 
 class _Holder(nn.Module):
@@ -94,6 +98,7 @@ class GPT(nn.Module):
         self._cache_shape = (0, 0)
         self._pos = self._len = None
         self._graphs = {}
+        self._weight_format = "fp32"
 
     # ---- plumbing ---------------------------------------------------------------------------------
     @property
@@ -130,6 +135,30 @@ class GPT(nn.Module):
         except Exception:
             pass
 
+    @property
+    def weight_format(self) -> str:
+        return self._weight_format
+
+    def set_weight_format(self, fmt: str):
+        """Format of the matrices a decode step streams (include/omnitok_lm.h, omnitok_lm_set_weight_format): "fp32" (default),
+        "bf16" or "fp16".  A 16-bit format rounds the q/k/v, proj, mlp and head matrices inside the engine (round to nearest
+        even, torch's bits) and streams them at half the bytes per step; activations, accumulation, LayerNorm, attention and
+        the K/V cache stay fp32.  The module's parameters stay float32 tensors and state_dict() is unchanged: the engine
+        rounds its own copy at the next use.  "fp16" raises there if a matrix holds a value outside the fp16 range."""
+        if fmt not in WEIGHT_FORMATS:
+            raise ValueError(f"weight format {fmt!r}: expected one of {sorted(WEIGHT_FORMATS)}")
+        self._weight_format = fmt
+        self._engine_sig = None
+        self._graphs = {}
+        return self
+
+    def step_weight_bytes(self) -> int:
+        """Bytes of weight matrices one decode step with logits streams in the current format (needs no GPU)."""
+        if self._engine is not None and self._engine_sig is not None:  # a synced engine: its own count
+            return int(_lib.load().omnitok_lm_step_weight_bytes(self._engine))
+        per = 4 if self._weight_format == "fp32" else 2
+        return (12 * self.n_embd * self.n_embd * self.n_layer + self.vocab_size * self.n_embd) * per
+
     def _signature(self):
         return tuple((t.data_ptr(), t._version) for t in self.state_dict(keep_vars=True).values())
 
@@ -148,6 +177,7 @@ class GPT(nn.Module):
             h = ctypes.c_void_p()
             check(lib.omnitok_lm_create(ctypes.byref(cfg), ctypes.byref(h)), "lm_create")
             self._engine = h
+        check(lib.omnitok_lm_set_weight_format(self._engine, WEIGHT_FORMATS[self._weight_format]), "lm_set_weight_format")
         for name, t in self.state_dict(keep_vars=True).items():
             if name == "vtokens_pos_emb":  # gathered per call on the host side (cbox / tbox), not an engine weight
                 continue

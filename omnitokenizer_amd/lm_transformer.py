@@ -112,6 +112,9 @@ class Net2NetTransformer(nn.Module):
         self.transformer = GPT(args, gpt_vocab_size, args.block_size, n_layer=args.n_layer, n_head=args.n_head,
                                n_embd=args.n_embd, vtokens_pos=_get(args, "vtokens_pos", False),
                                n_unmasked=_get(args, "n_unmasked", 0))
+        # weight format of the decode step ("fp32" | "bf16" | "fp16", GPT.set_weight_format): an option of this port -- the reference
+        # trains the model under Lightning's precision="bf16" / 16 and samples in whatever dtype the checkpoint is cast to
+        self.transformer.set_weight_format(_get(args, "lm_weight_format", "fp32"))
         if ckpt_path is not None:
             self.init_from_ckpt(ckpt_path, ignore_keys=ignore_keys)
 

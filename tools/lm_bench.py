@@ -4,7 +4,7 @@ LM shape by default (scripts/lm_train/train_k600.sh: vocab 8192, block 5120, 24 
 1536 wide), synthetic weights.  One JSON line: throughput, per-step time at the start / end of the
 sequence, the HBM roofline of a step (weight bytes + K/V bytes read) and a CPU baseline (the oracle's
 KV-cached step on the host, bounded sample).
-    python tools/lm_bench.py [--batch 1] [--steps 512] [--ctx 0] [--no-cpu-baseline]"""
+    python tools/lm_bench.py [--batch 1] [--steps 512] [--ctx 0] [--weights fp32|bf16|fp16] [--also 8] [--no-cpu-baseline]"""
 import argparse
 import json
 import os
@@ -35,6 +35,9 @@ def main():
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-also", action="store_true", help="skip the 8-stream line (B = 1 runs only)")
+    ap.add_argument("--also", default="8", metavar="B[,B..]", help="stream counts of the extra lines of a B = 1 run (default 8)")
+    ap.add_argument("--weights", choices=("fp32", "bf16", "fp16"), default="fp32",
+                    help="format of the matrices a decode step streams (GPT.set_weight_format)")
     a = ap.parse_args()
     V, BS, L, H, C = a.vocab, a.block, a.layers, a.heads, a.embd
     for kv in a.option:
@@ -43,7 +46,7 @@ def main():
     sd = synth_gpt_state(V, BS, L, H, C, seed=0)
     m = og.GPT(argparse.Namespace(), V, BS, n_layer=L, n_head=H, n_embd=C)
     m.load_state_dict(sd, strict=True)
-    m = m.cuda().eval()
+    m = m.cuda().eval().set_weight_format(a.weights)
     B = a.batch
     g = torch.Generator().manual_seed(1)
     cond = torch.randint(0, V, (B, 1 + a.ctx), generator=g).cuda()
@@ -65,30 +68,38 @@ def main():
     idx_buf, logits_buf, replay = m.graph_step(B)
     torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    m._pos[:B] = a.ctx + a.steps
-    m._len[:B] = a.ctx + a.steps
-    e0.record()
     nrep = 50
-    for _ in range(nrep):
-        m._pos[:B] = a.ctx + a.steps
-        m._len[:B] = a.ctx + a.steps
-        replay()
-    e1.record()
-    torch.cuda.synchronize()
-    step_ms = e0.elapsed_time(e1) / nrep
+
+    def time_step(replay_fn, nb, length):
+        """ms per bare decode step at cache length `length`: median of 5 rounds of nrep replays, and the rounds' (min, max)"""
+        rounds = []
+        for _ in range(6):  # the first round warms up and is dropped
+            e0.record()
+            for _ in range(nrep):
+                m._pos[:nb] = length
+                m._len[:nb] = length
+                replay_fn()
+            e1.record()
+            torch.cuda.synchronize()
+            rounds.append(e0.elapsed_time(e1) / nrep)
+        rounds = sorted(rounds[1:])
+        return rounds[2], [round(rounds[0], 4), round(rounds[-1], 4)]
+
+    step_ms, step_spread = time_step(replay, B, a.ctx + a.steps)
     hd = C // H
-    weight_bytes = (L * 12 * C * C + V * C) * 4.0
+    weight_bytes = float(m.step_weight_bytes())
     kv_bytes = 2.0 * L * B * H * (a.ctx + a.steps) * hd * 4.0
     out_json = {
         "metric": "LM sampled tokens/sec (sample_with_past, top-k 2048 / top-p 0.9)",
         "value": round(B * a.steps / dt_sample, 1), "unit": "tokens/s", "n_gpus": 1, "batch_streams": B,
         "steps": a.steps, "ctx": a.ctx, "ms_per_token_step": round(dt_sample / a.steps * 1e3, 4),
-        "dtype": "f32", "data": "synthetic",
+        "dtype": "f32", "weights": a.weights, "data": "synthetic",
         "config": {"workload": f"GPT {L}x{C} ({H} heads, head_dim {hd}), vocab {V}, block {BS}; B={B} streams, "
                                f"{a.ctx} cached tokens + {a.steps} sampled"},
         "roofline": {"kernel": "decode step (graph replay) at the final context", "bound": "hbm",
                      "achieved": round((weight_bytes + kv_bytes) / (step_ms * 1e-3) / 1e9, 1), "peak": PEAK_HBM_GBS,
-                     "unit": "GB/s", "step_ms": round(step_ms, 4), "weight_bytes": weight_bytes, "kv_bytes": kv_bytes,
+                     "unit": "GB/s", "step_ms": round(step_ms, 4), "step_ms_min_max": step_spread,
+                     "weight_bytes": weight_bytes, "kv_bytes": kv_bytes,
                      "traffic": None},
         "kv_cache_gb": round(m.cache_bytes() / 2**30, 2),
         "prefill_ms": round(t_prefill * 1e3, 2),  # a.ctx prefix tokens (batched prefill) + 1 sampled token
@@ -101,9 +112,9 @@ def main():
             out_json["roofline"]["traffic_source"] = pmc["source"]
     except Exception:
         pass
-    if B == 1 and not a.no_also:
-        # the same model with 8 streams sampled together (one pass over the weights per step serves all of them)
-        B8, n8 = 8, min(a.steps, 128)
+    for B8 in ([int(b) for b in a.also.split(",")] if B == 1 and not a.no_also else []):
+        # the same model with 8 (--also) streams sampled together (one pass over the weights per step serves all of them)
+        n8 = min(a.steps, 128)
         cond8 = torch.randint(0, V, (B8, 1 + a.ctx), generator=g).cuda()
         og.sample_with_past(cond8, m, 8, top_k=2048, top_p=0.9, use_graph=not a.no_graph)
         torch.cuda.synchronize()
@@ -118,18 +129,12 @@ def main():
         # the bare decode step of the 8 streams at the final context
         _, _, replay8 = m.graph_step(B8)
         torch.cuda.synchronize()
-        e0.record()
-        for _ in range(nrep):
-            m._pos[:B8] = a.ctx + n8
-            m._len[:B8] = a.ctx + n8
-            replay8()
-        e1.record()
-        torch.cuda.synchronize()
-        step8 = e0.elapsed_time(e1) / nrep
+        step8, spread8 = time_step(replay8, B8, a.ctx + n8)
         kv8 = 2.0 * L * B8 * H * (a.ctx + n8) * hd * 4.0
-        out_json["also"] = {"b8": {"batch_streams": B8, "steps": n8, "tokens_s": round(B8 * n8 / dt8, 1),
+        out_json.setdefault("also", {})[f"b{B8}"] = {"batch_streams": B8, "steps": n8, "tokens_s": round(B8 * n8 / dt8, 1),
                                    "ms_per_token_step": round(dt8 / n8 * 1e3, 4), "step_ms": round(step8, 4),
-                                   "kv_bytes": kv8, "frac_hbm": round((weight_bytes + kv8) / (step8 * 1e-3) / 1e9 / PEAK_HBM_GBS, 4)}}
+                                                     "step_ms_min_max": spread8, "kv_bytes": kv8,
+                                                     "frac_hbm": round((weight_bytes + kv8) / (step8 * 1e-3) / 1e9 / PEAK_HBM_GBS, 4)}
     if not a.no_cpu_baseline:
         from oracle import gpt_oracle as go  # the CPU oracle is only the baseline / checker here
         torch.set_num_threads(min(32, os.cpu_count() or 1))
