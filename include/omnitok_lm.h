@@ -41,8 +41,8 @@ int omnitok_lm_set_weight(omnitok_lm *lm, const char *name, const void *dev_ptr,
 int omnitok_lm_finalize(omnitok_lm *lm, omnitok_stream_t stream);
 /* Format of the weight matrices a decode step streams -- per engine, default OMNITOK_LM_W_FP32 (nothing below applies then).  The
  * reference trains this model under Lightning's precision="bf16" / 16 (transformer_train.py:63-66): every nn.Linear sees 16-bit
- * weights there.  A 16-bit engine rounds ONLY the matrices; activations, accumulation, LayerNorm, attention and the K/V cache stay
- * fp32, and the decode step -- bound by the bytes of exactly these matrices -- streams half of them.
+ * weights there.  A 16-bit engine rounds ONLY the matrices; activations, accumulation, LayerNorm and attention stay fp32 (the K/V
+ * cache has a format switch of its own, omnitok_lm_set_cache_format below), and the decode step -- bound by the bytes of exactly these matrices -- streams half of them.
  *   Which tensors: wqkv (query | key | value, concatenated at finalize), attn.proj.weight, mlp.0.weight, mlp.2.weight of every
  *     block and head.weight.  Biases, LayerNorm parameters, tok_emb, pos_emb and the K/V cache stay fp32 (gathers, or a few KB
  *     per step).
@@ -66,9 +66,39 @@ int omnitok_lm_weight_format(omnitok_lm *lm); /* -1: null engine */
  * (12 * n_embd^2 * n_layer + vocab_size * n_embd) * sizeof(element).  Needs no GPU; 0 for a null engine. */
 int64_t omnitok_lm_step_weight_bytes(omnitok_lm *lm);
 
-/* K/V cache [n_layer][2][max_batch][n_head][max_len][head_dim] fp32 + step workspaces. */
+/* Format of the K/V cache -- per engine, default OMNITOK_LM_KV_FP32 (nothing below applies then), independent of the weight format
+ * (all 3 x 3 combinations work).  At long contexts the cache is the other half of a decode step's traffic (24 layers x 2 x 4608 rows
+ * x 1536 x 4 B = 1.36 GB per stream and step at the reference's context), and under the reference's precision="bf16" its own
+ * `present` K/V tensors are 16-bit.  A 16-bit cache stores half the bytes:
+ *   Rounding at the store: a token's K and V rows are rounded ONCE, where they are stored -- the decode step's append and the
+ *     prefill's scatter -- to nearest even: the bits of tensor.to(torch.bfloat16) / .to(torch.float16), fp16 subnormals kept,
+ *     NaN -> quiet NaN (the conversions of the weight images).
+ *   The own row stays fp32: in the step (or prefill row) that produces a token, the token's own K/V row enters the attention as the
+ *     fp32 values of qkv; every earlier row is read from the cache and widened to fp32 in registers, which is exact.
+ *   Everything else stays fp32: q, the scores, the softmax, the accumulators, the chunk partials, their merge and all activations.
+ *   Consequence: attention over a 16-bit cache is the fp32 kernel's arithmetic on a cache that holds the widened values, bit for bit.
+ *     Prefill and stepping stay the same arithmetic in the sense they are today: their fp32 K/V differ in the last bits (other
+ *     summation orders), so a few cached elements may round to neighbouring 16-bit values.
+ *   fp16 range: a stored element that rounds to +-inf raises bit 2 of the engine's flag word (omnitok_lm_overflowed); the cache then
+ *     holds the infinity.  bf16 has fp32's range.
+ * omnitok_lm_set_cache_format: -1 for a null engine or an unknown format (a refused format changes nothing).  It frees an allocated
+ * cache and its step workspaces -- the next step or prefill returns OMNITOK_ERR_STATE until omnitok_lm_alloc_cache runs again -- and
+ * touches neither `finalized` nor any weight. */
+#define OMNITOK_LM_KV_FP32 0
+#define OMNITOK_LM_KV_BF16 1
+#define OMNITOK_LM_KV_FP16 2
+int omnitok_lm_set_cache_format(omnitok_lm *lm, int fmt);
+int omnitok_lm_cache_format(omnitok_lm *lm); /* -1: null engine */
+
+/* K/V cache [n_layer][2][max_batch][n_head][max_len][head_dim] in the engine's cache format + step workspaces. */
 int omnitok_lm_alloc_cache(omnitok_lm *lm, int max_batch, int max_len);
-int64_t omnitok_lm_cache_bytes(omnitok_lm *lm);
+int64_t omnitok_lm_cache_bytes(omnitok_lm *lm); /* the bytes allocated: half for a 16-bit cache; 0 without a cache */
+/* Rows t0 .. t0 + n - 1 of stream b of one layer, widened to fp32: k_out / v_out [n_head, n, head_dim] on the device (the
+ * counterpart of the reference's `present`).  Every format; fp32 is a plain copy.  Rows beyond cache_len[b] hold whatever the cache
+ * holds.  -1: null pointers, layer outside [0, n_layer), b outside [0, max_batch), t0 < 0, n < 0 or t0 + n > max_len;
+ * OMNITOK_ERR_STATE: no cache. */
+int omnitok_lm_cache_read(omnitok_lm *lm, int layer, int b, int t0, int n, float *k_out, float *v_out,
+                          omnitok_stream_t stream);
 
 /* One decode step for B independent streams (GPT.forward_with_past with one new token per row,
  * gpt.py:236-275): token idx[b] enters at position embedding pos[b]; its K/V are appended to row
@@ -87,9 +117,12 @@ int omnitok_lm_step_ex(omnitok_lm *lm, const int64_t *idx, const float *emb, con
                        int32_t *pos, int32_t *cache_len, int B, float *logits_out, int advance,
                        omnitok_stream_t stream);
 
-/* 1 if a decode step since the last call found cache_len[b] >= max_len (a stream stepped past the cache that
- * omnitok_lm_alloc_cache sized; the step then stays inside the stream's own K/V slab and its logits are
- * invalid), 0 otherwise; clears the flag.  Synchronises the stream (call it once after a sampling loop). */
+/* A mask of what happened since the last call, 0 if nothing; clears the flags.  Synchronises the stream (call it once after a
+ * sampling loop).
+ *   1: a decode step found cache_len[b] >= max_len (a stream stepped past the cache that omnitok_lm_alloc_cache sized; the step
+ *      then stays inside the stream's own K/V slab and its logits are invalid);
+ *   2: a K/V value stored into an OMNITOK_LM_KV_FP16 cache (a step's append or a prefill) left the fp16 range and was stored as
+ *      +-inf: the logits from there on are invalid.  An fp32 or bf16 cache never returns 2. */
 int omnitok_lm_overflowed(omnitok_lm *lm, omnitok_stream_t stream);
 
 /* Batched prefill of a conditioning prefix into EMPTY streams (GPT.forward / the first
@@ -169,6 +202,13 @@ int omnitok_lm_gemv_w16(const float *x, const void *w16, int fmt, const float *b
 int omnitok_lm_attn_decode(const float *qkv, float *kc, float *vc, const int32_t *cache_len, int B,
                            int n_head, int head_dim, int max_len, float *scratch, float *out,
                            omnitok_stream_t stream);
+/* omnitok_lm_attn_decode over packed 16-bit caches kc16 / vc16 [max_batch][n_head][max_len][head_dim] (fmt = OMNITOK_LM_KV_BF16 |
+ * OMNITOK_LM_KV_FP16; anything else returns -1; 16-byte aligned, otherwise -1 "unaligned"): cached rows are widened to fp32 in
+ * registers, the new token's row is appended rounded to fmt.  Same contract otherwise; out equals omnitok_lm_attn_decode's on
+ * fp32 caches that hold the widened values, bit for bit. */
+int omnitok_lm_attn_decode_kv16(const float *qkv, void *kc16, void *vc16, int fmt, const int32_t *cache_len, int B,
+                                int n_head, int head_dim, int max_len, float *scratch, float *out,
+                                omnitok_stream_t stream);
 
 #ifdef __cplusplus
 }

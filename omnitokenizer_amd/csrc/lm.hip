@@ -10,7 +10,8 @@
 //                          of the (tiny, L2-resident) activations fused into the prologue, bias / exact
 //                          GELU / residual fused into the epilogue
 //   lm_attn_decode_kernel  flash-decode over the K/V cache: 256-key chunks per workgroup, 8 lanes per
-//                          key (coalesced 128-byte row segments), online softmax, partial (m, l, o)
+//                          key (coalesced 128-byte row segments), online softmax, partial (m, l, o); the cache rows are
+//                          fp32, or bf16 / fp16 at half the bytes (omnitok_lm_set_cache_format), widened in registers
 //   lm_attn_merge_kernel   merges the chunk partials
 //   lm_advance_kernel      cache_len++, pos++ on the device
 // Shapes and launch grids do not depend on the position (chunks beyond the cache length exit at
@@ -108,6 +109,48 @@ template <> struct LmW<lm_fp16> {
         return __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(rs, byte_off, 0, 2));
     }
 };
+
+// fp32 -> 16-bit, round to nearest even: the bits of tensor.to(torch.bfloat16) / .to(torch.float16), fp16 subnormals kept, NaN -> quiet
+// NaN.  One conversion for the weight images (lm_round_w16_kernel) and the K/V cache (the attention kernel's append, the prefill's
+// scatter).  f is a scalar copy: __builtin_bit_cast of a vector ELEMENT reads element 0 with this compiler.
+template <typename T> __device__ __forceinline__ unsigned short lm_round16(float f);
+template <> __device__ __forceinline__ unsigned short lm_round16<lm_bf16>(float f) {
+    const unsigned u = __builtin_bit_cast(unsigned, f);
+    return f != f ? (unsigned short)0x7FC0 : (unsigned short)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
+}
+template <> __device__ __forceinline__ unsigned short lm_round16<lm_fp16>(float f) {
+    return __builtin_bit_cast(unsigned short, (_Float16)f);  // v_cvt_f16_f32: round to nearest even, subnormal results kept
+}
+__device__ __forceinline__ bool lm_f16_is_inf(unsigned short h) { return (h & 0x7FFF) == 0x7C00; }
+
+// Element types of the K/V cache (omnitok_lm_set_cache_format): float, or one of the 16-bit types above.  A row is rounded ONCE, where
+// it is stored; it is read back through LmW<KT>::widen (exact).  Only an fp16 store can leave the range (CAN_OVERFLOW).
+template <typename KT> struct LmKV {
+    static constexpr bool CAN_OVERFLOW = __is_same(KT, lm_fp16);
+    static __device__ __forceinline__ KT store(float f, bool &inf) {
+        const unsigned short h = lm_round16<KT>(f);
+        if constexpr (CAN_OVERFLOW) inf = inf || lm_f16_is_inf(h);
+        return KT{h};
+    }
+    // 4 consecutive elements as one 8-byte value
+    static __device__ __forceinline__ u32x2 store4(const f32x4 &v, bool &inf) {
+        unsigned short h[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float f = v[e];
+            h[e] = lm_round16<KT>(f);
+            if constexpr (CAN_OVERFLOW) inf = inf || lm_f16_is_inf(h[e]);
+        }
+        return u32x2{(unsigned)h[0] | ((unsigned)h[1] << 16), (unsigned)h[2] | ((unsigned)h[3] << 16)};
+    }
+};
+template <> struct LmKV<float> {
+    static constexpr bool CAN_OVERFLOW = false;
+    static __device__ __forceinline__ float store(float f, bool &) { return f; }
+    static __device__ __forceinline__ f32x4 store4(const f32x4 &v, bool &) { return v; }
+};
+constexpr int LM_FLAG_PAST_CACHE = 1;  // bits of the engine's flag word (omnitok_lm_overflowed)
+constexpr int LM_FLAG_FP16_RANGE = 2;
 
 struct LmMerge {
     const float *part;         // [B][n_head][nchunk][2 + hd]
@@ -677,8 +720,14 @@ __global__ __launch_bounds__(NW * 64) void lm_gemv_ks_kernel(const float *__rest
 // clamped to the slab, the new token's row comes from qkv and is selected afterwards): q, cache_len and every K / V row of the chunk
 // are one memory round trip where the 4-wave form took three (q + length, then two batches of 32 keys) -- the kernel is a latency
 // chain at decode sizes, not a stream (profiles/r05_lm_balance.txt).
-template <int F4, int NWV, int CHUNK>
-__global__ __launch_bounds__(NWV * 64) void lm_attn_decode_kernel(const float *__restrict__ qkv, float *kc, float *vc,
+//
+// KT = element type of the cache (float | lm_bf16 | lm_fp16, omnitok_lm_set_cache_format).  A 16-bit cache keeps the lane mapping -- a
+// lane owns the same 4 consecutive dims per i, 8-byte loads where fp32 takes 16 -- the chunking, the keys per wave and the fmaf order:
+// rows are widened to fp32 in registers (exact), the token's own row stays the fp32 values of qkv (`fresh`), and its cache copy is
+// rounded once at the append.  So the kernel computes what the float instantiation computes on a cache that holds the widened values
+// (tests/test_gpu_lm_kv16.py).  An fp16 append that rounds to +-inf raises LM_FLAG_FP16_RANGE.  KT = float compiles to what it was.
+template <typename KT, int F4, int NWV, int CHUNK>
+__global__ __launch_bounds__(NWV * 64) void lm_attn_decode_kernel(const float *__restrict__ qkv, KT *kc, KT *vc,
                                                                   const int32_t *__restrict__ cache_len, int n_head,
                                                                   int max_len, int prefill_T,
                                                                   float *__restrict__ part, int nchunk,
@@ -696,8 +745,9 @@ __global__ __launch_bounds__(NWV * 64) void lm_attn_decode_kernel(const float *_
     const int slot = lane >> 3, ds = lane & 7;  // key slot 0..7, dim slot 0..7
     const float *qn = qkv + (int64_t)row * 3 * C + h * HD;
     const float *kn = qn + C, *vn = qn + 2 * C;
-    float *krow = kc + ((int64_t)b * n_head + h) * (int64_t)max_len * HD;
-    float *vrow = vc + ((int64_t)b * n_head + h) * (int64_t)max_len * HD;
+    KT *krow = kc + ((int64_t)b * n_head + h) * (int64_t)max_len * HD;
+    KT *vrow = vc + ((int64_t)b * n_head + h) * (int64_t)max_len * HD;
+    typedef typename LmW<KT>::quad kquad;  // 4 consecutive cache elements as loaded
     const int kbase = c * CHUNK + wave * KPW;
     // everything this lane will read, requested at once
     f32x4 q[F4], knv[F4], vnv[F4];
@@ -707,7 +757,7 @@ __global__ __launch_bounds__(NWV * 64) void lm_attn_decode_kernel(const float *_
         knv[i] = *reinterpret_cast<const f32x4 *>(kn + (ds + 8 * i) * 4);
         vnv[i] = *reinterpret_cast<const f32x4 *>(vn + (ds + 8 * i) * 4);
     }
-    f32x4 kk[4][F4], vv[4][F4];
+    kquad kk[4][F4], vv[4][F4];
     auto request = [&](int it0) {  // rows past the slab are read from row 0 (a safe address); rows past the sequence hold whatever
 #pragma unroll                     // the cache holds (never used: masked below)
         for (int j = 0; j < 4; ++j) {
@@ -715,8 +765,8 @@ __global__ __launch_bounds__(NWV * 64) void lm_attn_decode_kernel(const float *_
             const int64_t off = (int64_t)(key < max_len ? key : 0) * HD;
 #pragma unroll
             for (int i = 0; i < F4; ++i) {
-                kk[j][i] = *reinterpret_cast<const f32x4 *>(krow + off + (ds + 8 * i) * 4);
-                vv[j][i] = *reinterpret_cast<const f32x4 *>(vrow + off + (ds + 8 * i) * 4);
+                kk[j][i] = *reinterpret_cast<const kquad *>(krow + off + (ds + 8 * i) * 4);
+                vv[j][i] = *reinterpret_cast<const kquad *>(vrow + off + (ds + 8 * i) * 4);
             }
         }
     };
@@ -725,17 +775,23 @@ __global__ __launch_bounds__(NWV * 64) void lm_attn_decode_kernel(const float *_
     if (len >= max_len) {
         // a caller stepped past the cache it allocated: flag it (omnitok_lm_overflowed) and stay inside
         // this head's K/V slab instead of reading the neighbour's rows
-        if (err_flag && threadIdx.x == 0) *err_flag = 1;
+        if (err_flag && threadIdx.x == 0) {
+            if constexpr (LmKV<KT>::CAN_OVERFLOW) atomicOr(err_flag, LM_FLAG_PAST_CACHE);  // (the word has a second bit to keep)
+            else *err_flag = LM_FLAG_PAST_CACHE;
+        }
         len = max_len - 1;
     }
     const int total = len + 1;
     if (c * CHUNK >= total) return;   // chunk beyond the sequence (static launch grid)
     // append the new token's K/V (only the workgroup whose chunk holds index len)
     if (prefill_T == 0 && len >= c * CHUNK && len < (c + 1) * CHUNK && len < max_len) {
+        bool inf = false;
         for (int d = tid; d < HD; d += NWV * 64) {
-            krow[(int64_t)len * HD + d] = kn[d];
-            vrow[(int64_t)len * HD + d] = vn[d];
+            krow[(int64_t)len * HD + d] = LmKV<KT>::store(kn[d], inf);
+            vrow[(int64_t)len * HD + d] = LmKV<KT>::store(vn[d], inf);
         }
+        if constexpr (LmKV<KT>::CAN_OVERFLOW)
+            if (inf && err_flag) atomicOr(err_flag, LM_FLAG_FP16_RANGE);
     }
     const float scale = 1.0f / sqrtf((float)HD);
     float m = -INFINITY, l = 0.0f;
@@ -755,7 +811,7 @@ __global__ __launch_bounds__(NWV * 64) void lm_attn_decode_kernel(const float *_
             float s = 0.0f;
 #pragma unroll
             for (int i = 0; i < F4; ++i) {
-                const f32x4 kv = fresh ? knv[i] : kk[j][i];
+                const f32x4 kv = fresh ? knv[i] : LmW<KT>::widen(kk[j][i]);
                 s = fmaf(q[i][0], kv[0], s);
                 s = fmaf(q[i][1], kv[1], s);
                 s = fmaf(q[i][2], kv[2], s);
@@ -770,7 +826,7 @@ __global__ __launch_bounds__(NWV * 64) void lm_attn_decode_kernel(const float *_
                 const float corr = expf(m - mn), p = expf(s - mn);
                 l = l * corr + p;
 #pragma unroll
-                for (int i = 0; i < F4; ++i) o[i] = o[i] * corr + (fresh ? vnv[i] : vv[j][i]) * p;
+                for (int i = 0; i < F4; ++i) o[i] = o[i] * corr + (fresh ? vnv[i] : LmW<KT>::widen(vv[j][i])) * p;
                 m = mn;
             }
         }
@@ -906,18 +962,39 @@ __global__ __launch_bounds__(256) void lm_gelu_kernel(float *__restrict__ x, int
     reinterpret_cast<f32x4 *>(x)[i] = v;
 }
 
-// qkv[B*T, 3C] (query | key | value) -> K/V cache rows [b][h][t][hd]
-__global__ __launch_bounds__(256) void lm_kv_scatter_kernel(const float *__restrict__ qkv, float *__restrict__ kc,
-                                                            float *__restrict__ vc, int T, int n_head, int hd,
-                                                            int max_len) {
+// qkv[B*T, 3C] (query | key | value) -> K/V cache rows [b][h][t][hd], rounded to the cache's element type KT on the way (the prefill's
+// one rounding of a row; an fp16 element that becomes +-inf raises LM_FLAG_FP16_RANGE in the engine's flag word)
+template <typename KT>
+__global__ __launch_bounds__(256) void lm_kv_scatter_kernel(const float *__restrict__ qkv, KT *__restrict__ kc,
+                                                            KT *__restrict__ vc, int T, int n_head, int hd,
+                                                            int max_len, int *__restrict__ err_flag) {
     const int64_t row = blockIdx.x;  // b * T + t
     const int b = (int)(row / T), t = (int)(row % T), C = n_head * hd;
+    typedef typename LmW<KT>::quad kquad;
+    bool inf = false;
     for (int i = threadIdx.x * 4; i < C; i += 256 * 4) {
         const int h = i / hd, d = i - h * hd;
         const int64_t dst = (((int64_t)b * n_head + h) * max_len + t) * hd + d;
-        *reinterpret_cast<f32x4 *>(kc + dst) = *reinterpret_cast<const f32x4 *>(qkv + row * 3 * C + C + i);
-        *reinterpret_cast<f32x4 *>(vc + dst) = *reinterpret_cast<const f32x4 *>(qkv + row * 3 * C + 2 * C + i);
+        *reinterpret_cast<kquad *>(kc + dst) = LmKV<KT>::store4(*reinterpret_cast<const f32x4 *>(qkv + row * 3 * C + C + i), inf);
+        *reinterpret_cast<kquad *>(vc + dst) = LmKV<KT>::store4(*reinterpret_cast<const f32x4 *>(qkv + row * 3 * C + 2 * C + i), inf);
     }
+    if constexpr (LmKV<KT>::CAN_OVERFLOW)
+        if (inf && err_flag) atomicOr(err_flag, LM_FLAG_FP16_RANGE);
+}
+
+// omnitok_lm_cache_read: rows t0 .. t0 + n - 1 of one stream's K and V slabs [n_head][max_len][hd], gathered and widened to fp32
+// [n_head][n][hd].  One thread per 4 consecutive dims.
+template <typename KT>
+__global__ __launch_bounds__(256) void lm_kv_read_kernel(const KT *__restrict__ kc, const KT *__restrict__ vc, int t0, int n,
+                                                         int n_head, int hd, int max_len, float *__restrict__ k_out,
+                                                         float *__restrict__ v_out) {
+    const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;  // element of the output
+    if (i >= (int64_t)n_head * n * hd) return;
+    const int d = (int)(i % hd), t = (int)(i / hd % n), h = (int)(i / hd / n);
+    const int64_t src = ((int64_t)h * max_len + t0 + t) * hd + d;
+    typedef typename LmW<KT>::quad kquad;
+    *reinterpret_cast<f32x4 *>(k_out + i) = LmW<KT>::widen(*reinterpret_cast<const kquad *>(kc + src));
+    *reinterpret_cast<f32x4 *>(v_out + i) = LmW<KT>::widen(*reinterpret_cast<const kquad *>(vc + src));
 }
 
 __global__ void lm_set_len_kernel(int32_t *pos, int32_t *cache_len, int B, int T) {
@@ -959,14 +1036,12 @@ __global__ __launch_bounds__(256) void lm_round_w16_kernel(float *__restrict__ w
     for (int e = 0; e < 4; ++e) {
         const float f = v[e];  // (a scalar copy: __builtin_bit_cast of a vector ELEMENT reads element 0 with this compiler)
         if constexpr (FMT == OMNITOK_LM_W_BF16) {
-            const unsigned u = __builtin_bit_cast(unsigned, f);
-            h[e] = f != f ? (unsigned short)0x7FC0 : (unsigned short)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
+            h[e] = lm_round16<lm_bf16>(f);
             v[e] = __builtin_bit_cast(float, (unsigned)h[e] << 16);
         } else {
-            const _Float16 r = (_Float16)f;  // v_cvt_f16_f32: round to nearest even, subnormal results kept
-            h[e] = __builtin_bit_cast(unsigned short, r);
-            v[e] = (float)r;
-            inf = inf || (h[e] & 0x7FFF) == 0x7C00;
+            h[e] = lm_round16<lm_fp16>(f);
+            v[e] = (float)__builtin_bit_cast(_Float16, h[e]);
+            inf = inf || lm_f16_is_inf(h[e]);
         }
     }
     reinterpret_cast<f32x4 *>(w)[i] = v;
@@ -1387,7 +1462,7 @@ extern "C" int omnitok_lm_gemv_w16(const float *x, const void *w16, int fmt, con
 
 // chunk partials only (the engine merges them inside the proj GEMV)
 // prefill_T > 0: B * prefill_T query rows (row = b * T + t, keys 0..t), chunks sized for T keys
-static int lm_attn_partials(const float *qkv, float *kc, float *vc, const int32_t *cache_len, int B, int n_head,
+static int lm_attn_partials(const float *qkv, void *kc, void *vc, int kvfmt, const int32_t *cache_len, int B, int n_head,
                             int head_dim, int max_len, float *scratch, hipStream_t stream, int prefill_T = 0,
                             int *err_flag = nullptr, int chunk = LM_CHUNK) {
     OT_CHECK_ARG(qkv && kc && vc && (cache_len || prefill_T > 0) && scratch, "lm_attn_decode: null pointer");
@@ -1399,38 +1474,64 @@ static int lm_attn_partials(const float *qkv, float *kc, float *vc, const int32_
     OT_CHECK_ARG(rows <= 65535, "lm_attn_decode: %d query rows (max 65535)", rows);
     const dim3 grid(nchunk, n_head, rows);
     const bool wide = g_lm_attn_waves == 8;
-#define OT_LM_ATTN(F4_)                                                                                                                    \
-    if (chunk == LM_CHUNK_SHORT)                                                                                                          \
-        hipLaunchKernelGGL((lm_attn_decode_kernel<F4_, 4, LM_CHUNK_SHORT>), grid, dim3(256), 0, stream, qkv, kc, vc, cache_len, n_head,  \
-                           max_len, prefill_T, scratch, nchunk, err_flag);                                                               \
-    else if (wide)                                                                                                                        \
-        hipLaunchKernelGGL((lm_attn_decode_kernel<F4_, 8, LM_CHUNK>), grid, dim3(512), 0, stream, qkv, kc, vc, cache_len, n_head, max_len, \
-                           prefill_T, scratch, nchunk, err_flag);                                                                        \
-    else                                                                                                                                  \
-        hipLaunchKernelGGL((lm_attn_decode_kernel<F4_, 4, LM_CHUNK>), grid, dim3(256), 0, stream, qkv, kc, vc, cache_len, n_head, max_len, \
-                           prefill_T, scratch, nchunk, err_flag)
-    switch (head_dim) {
-        case 64: OT_LM_ATTN(2); break;
-        case 96: OT_LM_ATTN(3); break;
-        default: OT_LM_ATTN(4); break;
+#define OT_LM_ATTN(KT_, F4_)                                                                                                            \
+    if (chunk == LM_CHUNK_SHORT)                                                                                                        \
+        hipLaunchKernelGGL((lm_attn_decode_kernel<KT_, F4_, 4, LM_CHUNK_SHORT>), grid, dim3(256), 0, stream, qkv,                       \
+                           static_cast<KT_ *>(kc), static_cast<KT_ *>(vc), cache_len, n_head, max_len, prefill_T, scratch, nchunk,      \
+                           err_flag);                                                                                                   \
+    else if (wide)                                                                                                                      \
+        hipLaunchKernelGGL((lm_attn_decode_kernel<KT_, F4_, 8, LM_CHUNK>), grid, dim3(512), 0, stream, qkv, static_cast<KT_ *>(kc),     \
+                           static_cast<KT_ *>(vc), cache_len, n_head, max_len, prefill_T, scratch, nchunk, err_flag);                   \
+    else                                                                                                                                \
+        hipLaunchKernelGGL((lm_attn_decode_kernel<KT_, F4_, 4, LM_CHUNK>), grid, dim3(256), 0, stream, qkv, static_cast<KT_ *>(kc),     \
+                           static_cast<KT_ *>(vc), cache_len, n_head, max_len, prefill_T, scratch, nchunk, err_flag)
+#define OT_LM_ATTN_HD(KT_)                                                                                                              \
+    switch (head_dim) {                                                                                                                 \
+        case 64: OT_LM_ATTN(KT_, 2); break;                                                                                             \
+        case 96: OT_LM_ATTN(KT_, 3); break;                                                                                             \
+        default: OT_LM_ATTN(KT_, 4); break;                                                                                             \
     }
+    switch (kvfmt) {
+        case OMNITOK_LM_KV_FP32: OT_LM_ATTN_HD(float) break;
+        case OMNITOK_LM_KV_BF16: OT_LM_ATTN_HD(lm_bf16) break;
+        default: OT_LM_ATTN_HD(lm_fp16) break;
+    }
+#undef OT_LM_ATTN_HD
 #undef OT_LM_ATTN
     OT_LAUNCH_CHECK("lm_attn_decode");
+    return OMNITOK_OK;
+}
+
+// partials + merge launch over caches of element format kvfmt: the exported building blocks
+static int lm_attn_decode_any(const char *who, const float *qkv, void *kc, void *vc, int kvfmt, const int32_t *cache_len, int B,
+                              int n_head, int head_dim, int max_len, float *scratch, float *out, hipStream_t stream) {
+    OT_CHECK_ARG(out, "%s: null pointer", who);
+    if (int rc = lm_attn_partials(qkv, kc, vc, kvfmt, cache_len, B, n_head, head_dim, max_len, scratch, stream)) return rc;
+    const int nchunk = (max_len + LM_CHUNK - 1) / LM_CHUNK;
+    hipLaunchKernelGGL(lm_attn_merge_kernel, dim3(n_head, B), dim3(128), 0, stream, scratch, cache_len, n_head, head_dim,
+                       nchunk, 0, out, LM_CHUNK);
+    OT_LAUNCH_CHECK("lm_attn_merge");
     return OMNITOK_OK;
 }
 
 extern "C" int omnitok_lm_attn_decode(const float *qkv, float *kc, float *vc, const int32_t *cache_len, int B,
                                       int n_head, int head_dim, int max_len, float *scratch, float *out,
                                       omnitok_stream_t stream_) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (B == 0) return OMNITOK_OK;
-    OT_CHECK_ARG(out, "lm_attn_decode: null pointer");
-    if (int rc = lm_attn_partials(qkv, kc, vc, cache_len, B, n_head, head_dim, max_len, scratch, stream)) return rc;
-    const int nchunk = (max_len + LM_CHUNK - 1) / LM_CHUNK;
-    hipLaunchKernelGGL(lm_attn_merge_kernel, dim3(n_head, B), dim3(128), 0, stream, scratch, cache_len, n_head, head_dim,
-                       nchunk, 0, out, LM_CHUNK);
-    OT_LAUNCH_CHECK("lm_attn_merge");
-    return OMNITOK_OK;
+    return lm_attn_decode_any("lm_attn_decode", qkv, kc, vc, OMNITOK_LM_KV_FP32, cache_len, B, n_head, head_dim, max_len, scratch, out,
+                              static_cast<hipStream_t>(stream_));
+}
+
+extern "C" int omnitok_lm_attn_decode_kv16(const float *qkv, void *kc16, void *vc16, int fmt, const int32_t *cache_len, int B,
+                                           int n_head, int head_dim, int max_len, float *scratch, float *out,
+                                           omnitok_stream_t stream_) {
+    OT_CHECK_ARG(fmt == OMNITOK_LM_KV_BF16 || fmt == OMNITOK_LM_KV_FP16,
+                 "lm_attn_decode_kv16: fmt %d (OMNITOK_LM_KV_BF16 | OMNITOK_LM_KV_FP16)", fmt);
+    if (B == 0) return OMNITOK_OK;
+    OT_CHECK_ARG(qkv && kc16 && vc16, "lm_attn_decode_kv16: null pointer");
+    OT_CHECK_ARG(aligned16(kc16) && aligned16(vc16), "lm_attn_decode_kv16: unaligned cache pointer (16 bytes)");
+    return lm_attn_decode_any("lm_attn_decode_kv16", qkv, kc16, vc16, fmt, cache_len, B, n_head, head_dim, max_len, scratch, out,
+                              static_cast<hipStream_t>(stream_));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1453,10 +1554,12 @@ struct omnitok_lm {
     int weight_format = OMNITOK_LM_W_FP32;  // of the matrices a decode step streams (omnitok_lm_set_weight_format)
     const void *head16 = nullptr;           // packed image of head.weight
     // cache + workspaces
-    float *kv = nullptr;
+    void *kv = nullptr;                       // [n_layer][2][max_batch][n_head][max_len][head_dim] elements of cache_format
+    int cache_format = OMNITOK_LM_KV_FP32;    // element type of kv (omnitok_lm_set_cache_format; applies at omnitok_lm_alloc_cache)
     int max_batch = 0, max_len = 0;
     int chunk = LM_CHUNK;  // keys per attention chunk of the decode step (omnitok_lm_alloc_cache)
-    int *err_flag = nullptr;  // set by the attention kernel when a stream steps past max_len
+    int *err_flag = nullptr;  // LM_FLAG_PAST_CACHE: the attention kernel met a stream past max_len | LM_FLAG_FP16_RANGE: a K/V value
+                              // stored into an fp16 cache rounded to +-inf (the append, the prefill's scatter)
     float *x = nullptr, *qkv = nullptr, *att = nullptr, *hid = nullptr, *part = nullptr;
     int64_t cache_bytes = 0;
     // grow-only prefill workspace (rows = B * T)
@@ -1514,11 +1617,20 @@ extern "C" int omnitok_lm_create(const omnitok_lm_config *cfg, omnitok_lm **out)
 
 static void lm_free_cache(omnitok_lm *lm) {
     lm->pf_floats = lm->lg_floats = lm->ce_rows = lm->ce_bytes = 0;
-    for (float **p : {&lm->kv, &lm->x, &lm->qkv, &lm->att, &lm->hid, &lm->part, &lm->pf, &lm->lg, &lm->ce})
+    for (float **p : {&lm->x, &lm->qkv, &lm->att, &lm->hid, &lm->part, &lm->pf, &lm->lg, &lm->ce})
         if (*p) {
             (void)hipFree(*p);
             *p = nullptr;
         }
+    if (lm->kv) (void)hipFree(lm->kv);
+    lm->kv = nullptr;
+    lm->cache_bytes = 0;
+}
+
+static int lm_kv_elem_bytes(int fmt) { return fmt == OMNITOK_LM_KV_FP32 ? 4 : 2; }
+// K slab of layer i (the V slab follows it) in a cache of per_layer elements per slab
+static void *lm_kv_slab(const omnitok_lm *lm, int64_t slab, int64_t per_layer) {
+    return static_cast<char *>(lm->kv) + slab * per_layer * lm_kv_elem_bytes(lm->cache_format);
 }
 
 extern "C" void omnitok_lm_destroy(omnitok_lm *lm) {
@@ -1566,6 +1678,21 @@ extern "C" int omnitok_lm_set_weight_format(omnitok_lm *lm, int fmt) {
 extern "C" int omnitok_lm_weight_format(omnitok_lm *lm) {
     OT_CHECK_ARG(lm, "lm_weight_format: null engine");
     return lm->weight_format;
+}
+
+extern "C" int omnitok_lm_set_cache_format(omnitok_lm *lm, int fmt) {
+    OT_CHECK_ARG(lm, "lm_set_cache_format: null engine");
+    OT_CHECK_ARG(fmt == OMNITOK_LM_KV_FP32 || fmt == OMNITOK_LM_KV_BF16 || fmt == OMNITOK_LM_KV_FP16,
+                 "lm_set_cache_format: unknown format %d", fmt);
+    lm_free_cache(lm);  // the cache and the step workspaces: the next step / prefill asks for omnitok_lm_alloc_cache
+    lm->max_batch = lm->max_len = 0;
+    lm->cache_format = fmt;
+    return OMNITOK_OK;
+}
+
+extern "C" int omnitok_lm_cache_format(omnitok_lm *lm) {
+    OT_CHECK_ARG(lm, "lm_cache_format: null engine");
+    return lm->cache_format;
 }
 
 extern "C" int64_t omnitok_lm_step_weight_bytes(omnitok_lm *lm) {
@@ -1698,11 +1825,12 @@ extern "C" int omnitok_lm_alloc_cache(omnitok_lm *lm, int max_batch, int max_len
     const omnitok_lm_config &c = lm->cfg;
     const int64_t C = c.n_embd;
     const int hd = c.n_embd / c.n_head;
-    const int64_t per_layer = (int64_t)max_batch * c.n_head * max_len * hd;  // floats per K (or V)
+    const int64_t per_layer = (int64_t)max_batch * c.n_head * max_len * hd;  // elements per K (or V)
     lm->chunk = g_lm_attn_short && max_len <= LM_CHUNK_SHORT * LM_MAX_CHUNKS ? LM_CHUNK_SHORT : LM_CHUNK;
     const int nchunk = (max_len + lm->chunk - 1) / lm->chunk;
     auto alloc = [](float **p, int64_t n) { return hipMalloc(reinterpret_cast<void **>(p), (size_t)n * 4); };
-    OT_HIP(alloc(&lm->kv, per_layer * 2 * c.n_layer));
+    const int64_t kv_bytes = per_layer * 2 * c.n_layer * lm_kv_elem_bytes(lm->cache_format);
+    OT_HIP(hipMalloc(&lm->kv, (size_t)kv_bytes));
     OT_HIP(alloc(&lm->x, max_batch * C));
     OT_HIP(alloc(&lm->qkv, max_batch * 3 * C));
     OT_HIP(alloc(&lm->att, max_batch * C));
@@ -1710,7 +1838,7 @@ extern "C" int omnitok_lm_alloc_cache(omnitok_lm *lm, int max_batch, int max_len
     OT_HIP(alloc(&lm->part, (int64_t)max_batch * c.n_head * nchunk * (2 + hd)));
     lm->max_batch = max_batch;
     lm->max_len = max_len;
-    lm->cache_bytes = per_layer * 2 * c.n_layer * 4;
+    lm->cache_bytes = kv_bytes;
     if (!lm->err_flag) {
         OT_HIP(hipMalloc(reinterpret_cast<void **>(&lm->err_flag), sizeof(int)));
         OT_HIP(hipMemset(lm->err_flag, 0, sizeof(int)));
@@ -1727,7 +1855,41 @@ extern "C" int omnitok_lm_overflowed(omnitok_lm *lm, omnitok_stream_t stream_) {
     OT_HIP(hipStreamSynchronize(stream));
     if (h)
         if (int rc = device_fill_u32(lm->err_flag, 0u, 1, stream)) return rc;
-    return h ? 1 : 0;
+    return h & (LM_FLAG_PAST_CACHE | LM_FLAG_FP16_RANGE);
+}
+
+extern "C" int omnitok_lm_cache_read(omnitok_lm *lm, int layer, int b, int t0, int n, float *k_out, float *v_out,
+                                     omnitok_stream_t stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    OT_CHECK_ARG(lm && k_out && v_out, "lm_cache_read: null pointer");
+    OT_CHECK_ARG(layer >= 0 && layer < lm->cfg.n_layer && b >= 0 && t0 >= 0 && n >= 0,
+                 "lm_cache_read: layer %d (of %d), stream %d, rows %d + %d", layer, lm->cfg.n_layer, b, t0, n);
+    if (!lm->kv) {
+        set_error("lm_cache_read: no cache (omnitok_lm_alloc_cache)");
+        return OMNITOK_ERR_STATE;
+    }
+    OT_CHECK_ARG(b < lm->max_batch && (int64_t)t0 + n <= lm->max_len, "lm_cache_read: stream %d (of %d), rows %d + %d (of %d)", b,
+                 lm->max_batch, t0, n, lm->max_len);
+    if (n == 0) return OMNITOK_OK;
+    const omnitok_lm_config &c = lm->cfg;
+    const int hd = c.n_embd / c.n_head;
+    const int64_t per_layer = (int64_t)lm->max_batch * c.n_head * lm->max_len * hd, per_stream = (int64_t)c.n_head * lm->max_len * hd;
+    const int es = lm_kv_elem_bytes(lm->cache_format);
+    const char *kc = static_cast<const char *>(lm_kv_slab(lm, 2 * layer, per_layer)) + (int64_t)b * per_stream * es;
+    const char *vc = kc + per_layer * es;
+    const int64_t quads = (int64_t)c.n_head * n * hd / 4;
+    const dim3 grid((unsigned)((quads + 255) / 256));
+#define OT_LM_READ(KT_)                                                                                                          \
+    hipLaunchKernelGGL(lm_kv_read_kernel<KT_>, grid, dim3(256), 0, stream, reinterpret_cast<const KT_ *>(kc),                    \
+                       reinterpret_cast<const KT_ *>(vc), t0, n, c.n_head, hd, lm->max_len, k_out, v_out)
+    switch (lm->cache_format) {
+        case OMNITOK_LM_KV_FP32: OT_LM_READ(float); break;
+        case OMNITOK_LM_KV_BF16: OT_LM_READ(lm_bf16); break;
+        default: OT_LM_READ(lm_fp16); break;
+    }
+#undef OT_LM_READ
+    OT_LAUNCH_CHECK("lm_kv_read");
+    return OMNITOK_OK;
 }
 
 extern "C" int64_t omnitok_lm_cache_bytes(omnitok_lm *lm) { return lm ? lm->cache_bytes : 0; }
@@ -1761,11 +1923,11 @@ extern "C" int omnitok_lm_step_ex(omnitok_lm *lm, const int64_t *idx, const floa
     OT_LAUNCH_CHECK("lm_embed");
     for (int i = 0; i < c.n_layer; ++i) {
         const LmLayer &L = lm->layers[i];
-        float *kc = lm->kv + (int64_t)(2 * i) * per_layer, *vc = kc + per_layer;
+        void *kc = lm_kv_slab(lm, 2 * i, per_layer), *vc = lm_kv_slab(lm, 2 * i + 1, per_layer);
         // x + proj(attn(ln1(x)))   (reference gpt.py:159-161)
         if (int rc = lm_gemv_any(lm->x, L.wqkv, L.wqkv16, wf, L.bqkv, nullptr, L.ln1w, L.ln1b, lm->qkv, B, 3 * C, C, 0, nullptr, stream))
             return rc;
-        if (int rc = lm_attn_partials(lm->qkv, kc, vc, cache_len, B, c.n_head, hd, lm->max_len, lm->part, stream, 0,
+        if (int rc = lm_attn_partials(lm->qkv, kc, vc, lm->cache_format, cache_len, B, c.n_head, hd, lm->max_len, lm->part, stream, 0,
                                       lm->err_flag, lm->chunk))
             return rc;
         const LmMerge mg{lm->part, cache_len, c.n_head, hd, (lm->max_len + lm->chunk - 1) / lm->chunk, lm->chunk, lm->qkv};   // (qkv is free once the partials exist)
@@ -1844,14 +2006,21 @@ static int lm_prefill_layers(omnitok_lm *lm, const int64_t *idx, int T_tok, cons
     OT_LAUNCH_CHECK("lm_embed_seq");
     for (int i = 0; i < c.n_layer; ++i) {
         const LmLayer &L = lm->layers[i];
-        float *kc = lm->kv + (int64_t)(2 * i) * per_layer, *vc = kc + per_layer;
+        void *kc = lm_kv_slab(lm, 2 * i, per_layer), *vc = lm_kv_slab(lm, 2 * i + 1, per_layer);
         hipLaunchKernelGGL(lm_layernorm_rows_kernel, ln_grid, dim3(256), 0, stream, x, L.ln1w, L.ln1b, xn, M, C);
         OT_LAUNCH_CHECK("lm_layernorm_rows");
         if (int rc = lm_linear(xn, L.wqkv, L.bqkv, nullptr, qkv, M, 3 * C, C, stream)) return rc;
-        hipLaunchKernelGGL(lm_kv_scatter_kernel, dim3((unsigned)M), dim3(256), 0, stream, qkv, kc, vc, T, c.n_head, hd,
-                           lm->max_len);
+#define OT_LM_SCATTER(KT_)                                                                                                      \
+    hipLaunchKernelGGL(lm_kv_scatter_kernel<KT_>, dim3((unsigned)M), dim3(256), 0, stream, qkv, static_cast<KT_ *>(kc),          \
+                       static_cast<KT_ *>(vc), T, c.n_head, hd, lm->max_len, lm->err_flag)
+        switch (lm->cache_format) {
+            case OMNITOK_LM_KV_FP32: OT_LM_SCATTER(float); break;
+            case OMNITOK_LM_KV_BF16: OT_LM_SCATTER(lm_bf16); break;
+            default: OT_LM_SCATTER(lm_fp16); break;
+        }
+#undef OT_LM_SCATTER
         OT_LAUNCH_CHECK("lm_kv_scatter");
-        if (int rc = lm_attn_partials(qkv, kc, vc, nullptr, B, c.n_head, hd, lm->max_len, part, stream, T)) return rc;
+        if (int rc = lm_attn_partials(qkv, kc, vc, lm->cache_format, nullptr, B, c.n_head, hd, lm->max_len, part, stream, T)) return rc;
         hipLaunchKernelGGL(lm_attn_merge_kernel, dim3(c.n_head, (unsigned)M), dim3(128), 0, stream, part, nullptr,
                            c.n_head, hd, nchunk, T, att, LM_CHUNK);
         OT_LAUNCH_CHECK("lm_attn_merge");

@@ -7,7 +7,7 @@ The class owns the parameters under the reference's state_dict key names; all ar
 step runs in libomnitok.so (include/omnitok_lm.h, csrc/lm.hip): a preallocated K/V cache instead of
 the reference's per-step torch.cat of all pasts, GEMV kernels that stream each weight matrix
 once per step (fp32, or bf16 / fp16 at half the bytes: GPT.set_weight_format), flash-decode
-attention, and -- because the step's launch sequence does not depend on the position -- one
+attention over an fp32, bf16 or fp16 cache (GPT.set_cache_format), and -- because the step's launch sequence does not depend on the position -- one
 captured HIP graph replayed per token.  Token selection (temperature, the CFG blend,
 top-k / top-p filtering, argmax or one multinomial draw) is one more kernel (csrc/lm_select.hip); the only
 thing torch contributes is the uniform random number per stream (so torch.manual_seed governs the samples).
@@ -27,6 +27,7 @@ from ._lib import OmnitokLmConfig, check
 
 
 WEIGHT_FORMATS = {"fp32": 0, "bf16": 1, "fp16": 2}  # OMNITOK_LM_W_* of include/omnitok_lm.h
+KV_FORMATS = {"fp32": 0, "bf16": 1, "fp16": 2}      # OMNITOK_LM_KV_*
 
 
 class _Holder(nn.Module):
@@ -99,6 +100,8 @@ class GPT(nn.Module):
         self._pos = self._len = None
         self._graphs = {}
         self._weight_format = "fp32"
+        self._cache_format = "fp32"
+        self._generation = 0
 
     # ---- plumbing ---------------------------------------------------------------------------------
     @property
@@ -142,8 +145,8 @@ class GPT(nn.Module):
     def set_weight_format(self, fmt: str):
         """Format of the matrices a decode step streams (include/omnitok_lm.h, omnitok_lm_set_weight_format): "fp32" (default),
         "bf16" or "fp16".  A 16-bit format rounds the q/k/v, proj, mlp and head matrices inside the engine (round to nearest
-        even, torch's bits) and streams them at half the bytes per step; activations, accumulation, LayerNorm, attention and
-        the K/V cache stay fp32.  The module's parameters stay float32 tensors and state_dict() is unchanged: the engine
+        even, torch's bits) and streams them at half the bytes per step; activations, accumulation, LayerNorm and attention
+        stay fp32, and the K/V cache has its own, independent switch (set_cache_format).  The module's parameters stay float32 tensors and state_dict() is unchanged: the engine
         rounds its own copy at the next use.  "fp16" raises there if a matrix holds a value outside the fp16 range."""
         if fmt not in WEIGHT_FORMATS:
             raise ValueError(f"weight format {fmt!r}: expected one of {sorted(WEIGHT_FORMATS)}")
@@ -151,6 +154,42 @@ class GPT(nn.Module):
         self._engine_sig = None
         self._graphs = {}
         return self
+
+    @property
+    def cache_format(self) -> str:
+        return self._cache_format
+
+    def set_cache_format(self, fmt: str):
+        """Format of the K/V cache (include/omnitok_lm.h, omnitok_lm_set_cache_format): "fp32" (default), "bf16" or "fp16",
+        independent of the weight format.  A 16-bit cache rounds a token's K/V rows once, where they are stored (round to
+        nearest even, torch's bits), and a step reads half the bytes per cached token; the step that produces a token uses its
+        fp32 K/V, and all arithmetic stays fp32.  The cache and the captured graphs are dropped and handles of earlier streams
+        are rejected; the weights and state_dict() are left alone.  With "fp16", check_overflow() raises if a stored value left
+        the fp16 range."""
+        if fmt not in KV_FORMATS:
+            raise ValueError(f"cache format {fmt!r}: expected one of {sorted(KV_FORMATS)}")
+        self._cache_format = fmt
+        self._cache_shape = (0, 0)
+        self._graphs = {}
+        self._generation += 1
+        if self._engine is not None:  # frees the engine's cache; the next reset_streams allocates it in the new format
+            check(_lib.load().omnitok_lm_set_cache_format(self._engine, KV_FORMATS[fmt]), "lm_set_cache_format")
+        return self
+
+    def cache_rows(self, layer, stream, start=0, stop=None):
+        """(k, v) of rows start .. stop - 1 of one stream's cache in one layer, widened to fp32: [n_head, n, head_dim] each (the
+        counterpart of the reference's `present`).  stop=None: the stream's current length (one host synchronisation)."""
+        if self._engine is None or self._len is None:
+            raise RuntimeError("cache_rows: no streams yet (reset_streams / forward_with_past first)")
+        if stop is None:
+            stop = int(self._len[stream])
+        n = stop - start
+        hd = self.n_embd // self.n_head
+        k = torch.empty(self.n_head, max(n, 1), hd, device=self.device, dtype=torch.float32)  # (a valid address for n == 0 too)
+        v = torch.empty_like(k)
+        check(_lib.load().omnitok_lm_cache_read(self._engine, int(layer), int(stream), int(start), int(n), self._fp(k), self._fp(v),
+                                                torch.cuda.current_stream().cuda_stream), "lm_cache_read")
+        return k[:, :max(n, 0)], v[:, :max(n, 0)]
 
     def step_weight_bytes(self) -> int:
         """Bytes of weight matrices one decode step with logits streams in the current format (needs no GPU)."""
@@ -177,6 +216,8 @@ class GPT(nn.Module):
             h = ctypes.c_void_p()
             check(lib.omnitok_lm_create(ctypes.byref(cfg), ctypes.byref(h)), "lm_create")
             self._engine = h
+            # before the first alloc_cache (set_cache_format applies later changes to the engine itself)
+            check(lib.omnitok_lm_set_cache_format(self._engine, KV_FORMATS[self._cache_format]), "lm_set_cache_format")
         check(lib.omnitok_lm_set_weight_format(self._engine, WEIGHT_FORMATS[self._weight_format]), "lm_set_weight_format")
         for name, t in self.state_dict(keep_vars=True).items():
             if name == "vtokens_pos_emb":  # gathered per call on the host side (cbox / tbox), not an engine weight
@@ -217,18 +258,22 @@ class GPT(nn.Module):
         self._pos.zero_()
         self._len.zero_()
         # handles returned by forward_with_past before this point belong to streams that no longer exist
-        self._generation = getattr(self, "_generation", 0) + 1
+        self._generation += 1
 
     def check_overflow(self):
-        """Raises if a decode step since the last check ran past the allocated K/V cache (its logits are
-        invalid); one host synchronisation -- the sampling loops call it once at their end."""
+        """Raises if a decode step since the last check ran past the allocated K/V cache, or stored a K/V value outside the
+        fp16 range into an fp16 cache (the logits are invalid either way); one host synchronisation -- the sampling loops
+        call it once at their end."""
         if not self._engine:
             return
         rc = _lib.load().omnitok_lm_overflowed(self._engine, torch.cuda.current_stream().cuda_stream)
         if rc < 0:
             check(rc, "lm_overflowed")  # a failed read-back is an error, not "no overflow"
-        if rc > 0:
+        if rc & 1:
             raise RuntimeError("a stream stepped past the K/V cache length it was allocated with")
+        if rc & 2:
+            raise RuntimeError(f"a K/V value left the range of the {self._cache_format} cache format and was stored as inf: "
+                               "use set_cache_format('bf16') (fp32's range) for this model")
 
     @staticmethod
     def _fp(t):

@@ -4,7 +4,7 @@ LM shape by default (scripts/lm_train/train_k600.sh: vocab 8192, block 5120, 24 
 1536 wide), synthetic weights.  One JSON line: throughput, per-step time at the start / end of the
 sequence, the HBM roofline of a step (weight bytes + K/V bytes read) and a CPU baseline (the oracle's
 KV-cached step on the host, bounded sample).
-    python tools/lm_bench.py [--batch 1] [--steps 512] [--ctx 0] [--weights fp32|bf16|fp16] [--also 8] [--no-cpu-baseline]"""
+    python tools/lm_bench.py [--batch 1] [--steps 512] [--ctx 0] [--weights fp32|bf16|fp16] [--kv fp32|bf16|fp16] [--also 8] [--no-cpu-baseline]"""
 import argparse
 import json
 import os
@@ -38,6 +38,7 @@ def main():
     ap.add_argument("--also", default="8", metavar="B[,B..]", help="stream counts of the extra lines of a B = 1 run (default 8)")
     ap.add_argument("--weights", choices=("fp32", "bf16", "fp16"), default="fp32",
                     help="format of the matrices a decode step streams (GPT.set_weight_format)")
+    ap.add_argument("--kv", choices=("fp32", "bf16", "fp16"), default="fp32", help="format of the K/V cache (GPT.set_cache_format)")
     a = ap.parse_args()
     V, BS, L, H, C = a.vocab, a.block, a.layers, a.heads, a.embd
     for kv in a.option:
@@ -46,7 +47,7 @@ def main():
     sd = synth_gpt_state(V, BS, L, H, C, seed=0)
     m = og.GPT(argparse.Namespace(), V, BS, n_layer=L, n_head=H, n_embd=C)
     m.load_state_dict(sd, strict=True)
-    m = m.cuda().eval().set_weight_format(a.weights)
+    m = m.cuda().eval().set_weight_format(a.weights).set_cache_format(a.kv)
     B = a.batch
     g = torch.Generator().manual_seed(1)
     cond = torch.randint(0, V, (B, 1 + a.ctx), generator=g).cuda()
@@ -88,12 +89,13 @@ def main():
     step_ms, step_spread = time_step(replay, B, a.ctx + a.steps)
     hd = C // H
     weight_bytes = float(m.step_weight_bytes())
-    kv_bytes = 2.0 * L * B * H * (a.ctx + a.steps) * hd * 4.0
+    kv_elem = 4.0 if a.kv == "fp32" else 2.0  # bytes per cached K/V element
+    kv_bytes = 2.0 * L * B * H * (a.ctx + a.steps) * hd * kv_elem
     out_json = {
         "metric": "LM sampled tokens/sec (sample_with_past, top-k 2048 / top-p 0.9)",
         "value": round(B * a.steps / dt_sample, 1), "unit": "tokens/s", "n_gpus": 1, "batch_streams": B,
         "steps": a.steps, "ctx": a.ctx, "ms_per_token_step": round(dt_sample / a.steps * 1e3, 4),
-        "dtype": "f32", "weights": a.weights, "data": "synthetic",
+        "dtype": "f32", "weights": a.weights, "kv": a.kv, "data": "synthetic",
         "config": {"workload": f"GPT {L}x{C} ({H} heads, head_dim {hd}), vocab {V}, block {BS}; B={B} streams, "
                                f"{a.ctx} cached tokens + {a.steps} sampled"},
         "roofline": {"kernel": "decode step (graph replay) at the final context", "bound": "hbm",
@@ -130,7 +132,7 @@ def main():
         _, _, replay8 = m.graph_step(B8)
         torch.cuda.synchronize()
         step8, spread8 = time_step(replay8, B8, a.ctx + n8)
-        kv8 = 2.0 * L * B8 * H * (a.ctx + n8) * hd * 4.0
+        kv8 = 2.0 * L * B8 * H * (a.ctx + n8) * hd * kv_elem
         out_json.setdefault("also", {})[f"b{B8}"] = {"batch_streams": B8, "steps": n8, "tokens_s": round(B8 * n8 / dt8, 1),
                                    "ms_per_token_step": round(dt8 / n8 * 1e3, 4), "step_ms": round(step8, 4),
                                                      "step_ms_min_max": spread8, "kv_bytes": kv8,
