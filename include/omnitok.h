@@ -88,11 +88,12 @@ const char *omnitok_version(void);
  * 256-key attention chunk; "lm_attn_short" 1 (default, read by omnitok_lm_alloc_cache) 128-key chunks for caches of up to 4096
  * tokens | 0 always 256; "lm_ks_deep" 0 (default) 8 KiB | 1 16 KiB of weights in flight per wave of the K-sliced GEMV; "lm_mfma" 0 (default) | 1 groups of
  * 4 .. 8 streams on the fp32-MFMA GEMV (measured slower, profiles/r06_lm_mfma.txt); "lm_loss_chunk_rows" (default 2048, at least 1) rows per head-GEMM block of
- * omnitok_lm_prefill_loss.  Unknown names return OMNITOK_ERR_INVALID. */
+ * omnitok_lm_prefill_loss; "lm_streams_min" (default 17, at least 1) the smallest number of streams whose decode step and
+ * omnitok_lm_gemm_streams call take the many-stream MFMA GEMM (omnitok_lm_set_max_streams).  Unknown names return OMNITOK_ERR_INVALID. */
 int omnitok_set_option(const char *name, int value);
 /* Reads the process default of a data-flow option ("gemm_mode", "attn_mode", "gemm_pl", "pl_min_tokens", "temporal_chunk",
  * "prevq_fuse", "pl_cfg", "pl_tail", "sp_small_blocks") or of a kernel choice of the LM decode step ("lm_wide_u", "lm_balance",
- * "lm_ksliced", "lm_mfma", "lm_mfma_mult", "lm_ks_deep", "lm_attn_short", "lm_attn_waves") or "lm_loss_chunk_rows": what a clip-sharded job consults to
+ * "lm_ksliced", "lm_mfma", "lm_mfma_mult", "lm_ks_deep", "lm_attn_short", "lm_attn_waves", "lm_streams_min") or "lm_loss_chunk_rows": what a clip-sharded job consults to
  * pin ONE flow for all its ranks (omnitokenizer_amd/dist.py pin_data_flow), and what a test restores after an A/B arm. */
 int omnitok_get_option(const char *name, int *value);
 /* ------------------------------------------------------------------------------------------

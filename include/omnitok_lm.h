@@ -90,7 +90,30 @@ int64_t omnitok_lm_step_weight_bytes(omnitok_lm *lm);
 int omnitok_lm_set_cache_format(omnitok_lm *lm, int fmt);
 int omnitok_lm_cache_format(omnitok_lm *lm); /* -1: null engine */
 
-/* K/V cache [n_layer][2][max_batch][n_head][max_len][head_dim] in the engine's cache format + step workspaces. */
+/* Streams per engine -- default 16 (nothing below applies then).  omnitok_lm_alloc_cache accepts max_batch <= max_streams; with more
+ * than 16 streams one step serves all of them in ONE pass over every weight matrix (the <= 16-stream kernels read each matrix once
+ * per group of 8 streams), so tokens per second over all streams keep growing with the batch.  Classifier-free guidance doubles the
+ * batch: 2 B rows.
+ *   Routing: a step of B >= option "lm_streams_min" (default 17) streams runs the many-stream kernels (omnitok_lm_gemm_streams below,
+ *     the chunk partials of the attention merged into a tensor, LayerNorm as a pass of its own); a step of fewer streams runs exactly
+ *     the kernels it ran before, whatever max_streams is.  Both paths serve every B <= max_batch: with "lm_streams_min" above B a step of up
+ *     to 128 streams runs the <= 16-stream kernels in groups of 8 / 4 / 2 / 1 streams (one pass over the weights per group).  Prefill, omnitok_lm_prefill_loss, omnitok_lm_cache_read and
+ *     omnitok_lm_overflowed work for every B <= max_batch.
+ *   Arithmetic: unchanged -- fp32 activations, fp32 products with the weight's exact fp32 value, fp32 accumulation in a fixed order
+ *     (no atomics: two calls give equal bits).  A stream's logits do not depend on how many streams share the step, on its slot, or
+ *     on what the others hold.  The order of a dot product's partial sums differs from the <= 16-stream kernels': the two paths agree
+ *     to rounding, not to the bit.
+ *   Memory: the cache grows with max_batch.  At the reference's model (24 layers x 1536, 5121 positions) 128 streams are 193 GB in
+ *     fp32 and 97 GB in a 16-bit cache format (16 streams: 24 GB / 12 GB).  An allocation the device cannot satisfy makes
+ *     omnitok_lm_alloc_cache return OMNITOK_ERR_HIP with hipMalloc's message; the engine is then left without a cache.
+ * omnitok_lm_set_max_streams: -1 for a null engine or an n outside [1, 128] (a refused n changes nothing).  Like
+ * omnitok_lm_set_cache_format it frees an allocated cache and its step workspaces -- the next step or prefill returns
+ * OMNITOK_ERR_STATE until omnitok_lm_alloc_cache runs again -- and touches neither `finalized` nor any weight. */
+int omnitok_lm_set_max_streams(omnitok_lm *lm, int n);
+int omnitok_lm_max_streams(omnitok_lm *lm); /* -1: null engine */
+
+/* K/V cache [n_layer][2][max_batch][n_head][max_len][head_dim] in the engine's cache format + step workspaces;
+ * max_batch <= omnitok_lm_max_streams (16 unless raised), otherwise -1 with the limit in force in the message. */
 int omnitok_lm_alloc_cache(omnitok_lm *lm, int max_batch, int max_len);
 int64_t omnitok_lm_cache_bytes(omnitok_lm *lm); /* the bytes allocated: half for a 16-bit cache; 0 without a cache */
 /* Rows t0 .. t0 + n - 1 of stream b of one layer, widened to fp32: k_out / v_out [n_head, n, head_dim] on the device (the
@@ -196,6 +219,18 @@ int omnitok_lm_gemv(const float *x, const float *w, const float *bias, const flo
 int omnitok_lm_gemv_w16(const float *x, const void *w16, int fmt, const float *bias, const float *residual,
                         const float *ln_gamma, const float *ln_beta, float *y, int B, int N, int K, int act,
                         omnitok_stream_t stream);
+/* The many-stream form: y[B, N] = act(LN(x)[B, K] . w[N, K]^T + bias) (+ residual) for 1 <= B <= 128 in one pass over w, which is
+ * fp32, bf16 or fp16 (fmt = OMNITOK_LM_W_FP32 | _BF16 | _FP16; 16-byte aligned like x and y).  N >= 1, K % 256 == 0; -1 for null
+ * pointers, unaligned pointers, sizes outside these or an unknown fmt, before any HIP call.  Every product is an fp32 product of an
+ * fp32 activation and the weight's exact fp32 value (16-bit weights are widened in registers) accumulated in fp32 on the f32-input
+ * MFMA, the partial sums of a dot product joined in an order fixed by (N, K): row b of y depends on row b of x only, and its bits do
+ * not change with B, with the row's slot or with the other rows' contents (NaN / Inf included); two calls give equal bits.  LayerNorm
+ * (eps 1e-5) is a pass of its own in front; bias, exact-erf GELU and residual as omnitok_lm_gemv; residual may alias y.
+ * B < option "lm_streams_min" (default 17) is served by the kernels of omnitok_lm_gemv / _w16 in groups of up to 8 rows instead.
+ * Uses a process-wide grow-only scratch (may hipMalloc): calls on different streams must not overlap. */
+int omnitok_lm_gemm_streams(const float *x, const void *w, int fmt, const float *bias, const float *residual,
+                            const float *ln_gamma, const float *ln_beta, float *y, int B, int N, int K, int act,
+                            omnitok_stream_t stream);
 /* Decode attention for one layer: qkv[B, 3*C] = (query | key | value) of the new token; K/V cache of
  * this layer kc / vc [max_batch][n_head][max_len][head_dim]; out[B, C].  scratch: float
  * [B * n_head * ceil(max_len/256) * (2 + head_dim)]. */

@@ -89,6 +89,7 @@ int current_device_cus(int *n_cu) {
     X(lm_ks_deep, true, INT_MIN)        \
     X(lm_attn_short, true, INT_MIN)     \
     X(lm_attn_waves, true, INT_MIN)     \
+    X(lm_streams_min, true, 1)          \
     X(lm_loss_chunk_rows, true, 1)
 
 namespace omnitok {

@@ -13,6 +13,8 @@
 //                          key (coalesced 128-byte row segments), online softmax, partial (m, l, o); the cache rows are
 //                          fp32, or bf16 / fp16 at half the bytes (omnitok_lm_set_cache_format), widened in registers
 //   lm_attn_merge_kernel   merges the chunk partials
+//   lm_gemm_streams_kernel the GEMM of 17 .. 128 streams (omnitok_lm_set_max_streams): one pass over a weight matrix for the
+//                          whole batch on the fp32-input MFMA, K split over waves and workgroups and rejoined in a fixed order
 //   lm_advance_kernel      cache_len++, pos++ on the device
 // Shapes and launch grids do not depend on the position (chunks beyond the cache length exit at
 // once), so a step can be captured once in a HIP graph and replayed for every token.
@@ -22,6 +24,7 @@
 
 #include <algorithm>
 #include <map>
+#include <mutex>
 #include <string>
 #include <vector>
 #include <cmath>
@@ -1429,6 +1432,185 @@ static int lm_gemv_any(const float *x, const float *w, const void *w16, int fmt,
     return OMNITOK_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Many-stream decode GEMM (omnitok_lm_set_max_streams; B >= "lm_streams_min"): y[B, N] = act(x[B, K] . w[N, K]^T + bias) (+ residual)
+// for up to 128 streams in ONE pass over the weights, on v_mfma_f32_32x32x2_f32 -- fp32 in, fp32 accumulate, bit for bit an fmaf chain
+// in k order, so every product is still an fp32 product of an fp32 activation and the weight's exact (widened) fp32 value.
+//   * workgroup = 4 waves = one tile of 32 weight rows x one K split (blockIdx.y of KS); the 4 waves cut the split's k blocks (32 k
+//     each) into 4 contiguous slices, so a tile is reduced over KS * 4 slices.  KS depends on (N, K) only (lm_streams_ksplit): the
+//     summation order of an output never depends on the number of streams, the stream's slot or the CU count;
+//   * operands: lane (i = lane & 31, h = lane >> 5) holds w[n0 + i][kb + 8 c + 4 h + e] (A) and x[32 t + i][the same k] (B), c, e in
+//     0 .. 3: four 16-byte loads (8-byte for 16-bit weights, widened in registers) cover one 128-byte line of a row, and MFMA (c, e)
+//     multiplies k = kb + 8 c + e and kb + 8 c + 4 + e.  Stream tile t of NT = ceil(B / 32) has its own 16-register accumulator;
+//     rows past N and streams past B are clamped duplicates that are computed and never stored (a column of the product depends on
+//     its own stream only: NaN / Inf of one stream stay in its row);
+//   * the next block's weights and first-tile activations are requested before the current block's MFMAs, the next stream tile's
+//     activations (L2 hits: the activations are a few hundred KB) before the current tile's;
+//   * the 4 wave partials meet in LDS and are added in wave order; with KS == 1 bias / exact GELU / residual follow at once,
+//     otherwise the tile's partial goes to part[split][B][N] and lm_streams_reduce_kernel adds the splits in split order and applies
+//     the epilogue.  No atomics anywhere: two calls give equal bits.
+// LayerNorm is a pass of its own in front (lm_layernorm_rows_kernel: one wave per stream).
+// Sizes: the kernel itself needs K % 32 == 0 (whole 32-k blocks; any N >= 1, 1 <= B <= 128).  The exported omnitok_lm_gemm_streams asks
+// for K % 256 == 0 only because its small batches go to the VALU kernels, which need that; the engine's K is n_embd or 4 n_embd with
+// n_embd % 256 == 0 (omnitok_lm_create).
+constexpr int LMS_NW = 4;
+int g_lm_streams_min = 17;  // "lm_streams_min": the smallest number of streams that takes lm_gemm_streams_kernel (engine steps and
+                            // omnitok_lm_gemm_streams); below it the VALU kernels serve the streams in groups of 8 / 4 / 2 / 1
+
+template <typename WT, int NT>
+__global__ __launch_bounds__(LMS_NW * 64) void lm_gemm_streams_kernel(const float *__restrict__ x, const WT *__restrict__ w,
+                                                                       const float *__restrict__ bias, const float *residual,
+                                                                       float *y, float *__restrict__ part, int B, int N, int K,
+                                                                       int act, int KS) {
+    __shared__ float red[LMS_NW][32][33];  // [wave][stream of the tile][weight row] (+1: the writes stride over streams)
+    typedef typename LmW<WT>::quad wquad;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int i = lane & 31, h = lane >> 5;
+    const int n0 = blockIdx.x * 32, split = blockIdx.y;
+    const int nblk = K >> 5, slices = KS * LMS_NW, slice = split * LMS_NW + wave;
+    const int b_begin = (int)((int64_t)slice * nblk / slices), b_end = (int)((int64_t)(slice + 1) * nblk / slices);
+    const WT *wp = w + (int64_t)(n0 + i < N ? n0 + i : N - 1) * K + 4 * h;
+    const float *xp[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) xp[t] = x + (int64_t)(t * 32 + i < B ? t * 32 + i : B - 1) * K + 4 * h;
+    f32x16 acc[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[t][r] = 0.0f;
+    // plain loads, not nontemporal ones: a lane pair takes 32 bytes of a row's 128-byte line per instruction, so the line has to stay
+    // in the cache for the three loads that follow
+    wquad wq[4], wn[4];
+    f32x4 x0[4], x0n[4];  // the first stream tile's activations of this block / the next one
+    if (b_begin < b_end) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            wq[c] = *reinterpret_cast<const wquad *>(wp + b_begin * 32 + 8 * c);
+            x0[c] = *reinterpret_cast<const f32x4 *>(xp[0] + b_begin * 32 + 8 * c);
+        }
+    }
+    for (int blk = b_begin; blk < b_end; ++blk) {
+        const int kb = blk * 32, kn = (blk + 1 < b_end ? blk + 1 : blk) * 32;  // (the last block asks for itself again: no branch)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            wn[c] = *reinterpret_cast<const wquad *>(wp + kn + 8 * c);
+            x0n[c] = *reinterpret_cast<const f32x4 *>(xp[0] + kn + 8 * c);
+        }
+        f32x4 wf[4], xq[2][4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            wf[c] = LmW<WT>::widen(wq[c]);
+            xq[0][c] = x0[c];
+        }
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            if (t + 1 < NT) {
+#pragma unroll
+                for (int c = 0; c < 4; ++c) xq[(t + 1) & 1][c] = *reinterpret_cast<const f32x4 *>(xp[t + 1] + kb + 8 * c);
+            }
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(wf[c][e], xq[t & 1][c][e], acc[t], 0, 0, 0);
+        }
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            wq[c] = wn[c];
+            x0[c] = x0n[c];
+        }
+    }
+    // acc[t][r] of lane (i, h): weight row n0 + mfma32_row(r, h), stream 32 t + i
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        if (t) __syncthreads();  // the previous tile was read
+#pragma unroll
+        for (int r = 0; r < 16; ++r) red[wave][i][mfma32_row(r, h)] = acc[t][r];
+        __syncthreads();
+        for (int o = tid; o < 32 * 32; o += LMS_NW * 64) {
+            const int j = o >> 5, ii = o & 31, b = t * 32 + j, n = n0 + ii;
+            float v = ((red[0][j][ii] + red[1][j][ii]) + red[2][j][ii]) + red[3][j][ii];
+            if (b < B && n < N) {
+                if (KS > 1) {
+                    part[((int64_t)split * B + b) * N + n] = v;
+                } else {
+                    if (bias) v += bias[n];
+                    if (act == 1) v = gelu_erf(v);
+                    if (residual) v += residual[(int64_t)b * N + n];
+                    y[(int64_t)b * N + n] = v;
+                }
+            }
+        }
+    }
+}
+
+// y = act(part[0] + part[1] + ... + part[KS - 1] + bias) (+ residual), the splits in split order; residual may alias y
+__global__ __launch_bounds__(256) void lm_streams_reduce_kernel(const float *__restrict__ part, const float *__restrict__ bias,
+                                                                const float *residual, float *y, int64_t total, int N, int KS,
+                                                                int act) {
+    const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (o >= total) return;
+    float v = part[o];
+    for (int s = 1; s < KS; ++s) v += part[(int64_t)s * total + o];
+    if (bias) v += bias[(int)(o % N)];
+    if (act == 1) v = gelu_erf(v);
+    if (residual) v += residual[o];
+    y[o] = v;
+}
+
+// K splits across workgroups: enough workgroups for two per CU of a 256-CU device while a wave keeps at least 4 blocks of 32 k.
+// A function of (N, K) ONLY -- not of B, not of the device: the bits of an output do not depend on who shares its batch.
+static int lm_streams_ksplit(int N, int K) {
+    const int tiles = (N + 31) / 32, nblk = K / 32;
+    int ks = 512 / tiles, cap = nblk / (LMS_NW * 4);
+    if (cap > 16) cap = 16;
+    if (ks > cap) ks = cap;
+    return ks < 1 ? 1 : ks;
+}
+// floats of split partials a call needs (0: the epilogue runs inside the GEMM kernel)
+static int64_t lm_streams_part_floats(int B, int N, int K) {
+    const int ks = lm_streams_ksplit(N, K);
+    return ks > 1 ? (int64_t)ks * B * N : 0;
+}
+
+template <typename WT>
+static void lm_streams_launch(const float *x, const WT *w, const float *bias, const float *residual, float *y, float *part, int B,
+                              int N, int K, int act, hipStream_t stream) {
+    const int KS = lm_streams_ksplit(N, K);
+    const dim3 grid((N + 31) / 32, KS);
+#define OT_LMS(NT_)                                                                                                          \
+    hipLaunchKernelGGL((lm_gemm_streams_kernel<WT, NT_>), grid, dim3(LMS_NW * 64), 0, stream, x, w, bias, residual, y, part, B, N, K, \
+                       act, KS)
+    switch ((B + 31) / 32) {
+        case 1: OT_LMS(1); break;
+        case 2: OT_LMS(2); break;
+        case 3: OT_LMS(3); break;
+        default: OT_LMS(4); break;
+    }
+#undef OT_LMS
+    if (KS > 1) {
+        const int64_t total = (int64_t)B * N;
+        hipLaunchKernelGGL(lm_streams_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, part, bias, residual,
+                           y, total, N, KS, act);
+    }
+}
+
+// y = act(LN(x) W^T + b) (+ residual) for 1 <= B <= 128 streams on lm_gemm_streams_kernel.  xn: scratch [B, K] for the normalised
+// activations (needed when g != nullptr), part: scratch of lm_streams_part_floats(B, N, K) floats.  w | w16 as lm_gemv_any.
+static int lm_gemm_streams_any(const float *x, const float *w, const void *w16, int fmt, const float *bias, const float *residual,
+                               const float *g, const float *beta, float *y, int B, int N, int K, int act, float *xn, float *part,
+                               hipStream_t stream) {
+    if (g) {
+        hipLaunchKernelGGL(lm_layernorm_rows_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, stream, x, g, beta, xn, (int64_t)B, K);
+        OT_LAUNCH_CHECK("lm_layernorm_rows");
+        x = xn;
+    }
+    if (!w16) lm_streams_launch(x, w, bias, residual, y, part, B, N, K, act, stream);
+    else if (fmt == OMNITOK_LM_W_BF16) lm_streams_launch(x, static_cast<const lm_bf16 *>(w16), bias, residual, y, part, B, N, K, act, stream);
+    else lm_streams_launch(x, static_cast<const lm_fp16 *>(w16), bias, residual, y, part, B, N, K, act, stream);
+    OT_LAUNCH_CHECK("lm_gemm_streams");
+    return OMNITOK_OK;
+}
+
 }  // namespace omnitok
 
 using namespace omnitok;
@@ -1458,6 +1640,44 @@ extern "C" int omnitok_lm_gemv_w16(const float *x, const void *w16, int fmt, con
     OT_CHECK_ARG(act == 0 || act == 1, "lm_gemv_w16: act %d", act);
     OT_CHECK_ARG(aligned16(x) && aligned16(w16), "lm_gemv_w16: unaligned");
     return lm_gemv_any(x, nullptr, w16, fmt, bias, residual, ln_gamma, ln_beta, y, B, N, K, act, nullptr, stream);
+}
+
+// process-wide grow-only scratch of omnitok_lm_gemm_streams (an engine has its own): normalised activations | split partials
+static std::mutex g_streams_ws_mu;
+static float *g_streams_ws = nullptr;
+static int64_t g_streams_ws_floats = 0;
+static int g_streams_ws_dev = -1;
+
+extern "C" int omnitok_lm_gemm_streams(const float *x, const void *w, int fmt, const float *bias, const float *residual,
+                                       const float *ln_gamma, const float *ln_beta, float *y, int B, int N, int K, int act,
+                                       omnitok_stream_t stream_) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    OT_CHECK_ARG(fmt == OMNITOK_LM_W_FP32 || fmt == OMNITOK_LM_W_BF16 || fmt == OMNITOK_LM_W_FP16,
+                 "lm_gemm_streams: fmt %d (OMNITOK_LM_W_FP32 | OMNITOK_LM_W_BF16 | OMNITOK_LM_W_FP16)", fmt);
+    OT_CHECK_ARG(x && w && y, "lm_gemm_streams: null pointer");
+    OT_CHECK_ARG(B > 0 && B <= 128 && N > 0 && K > 0 && K % 256 == 0, "lm_gemm_streams: bad sizes B=%d N=%d K=%d (1 <= B <= 128, K %% 256 == 0)",
+                 B, N, K);
+    OT_CHECK_ARG((ln_gamma != nullptr) == (ln_beta != nullptr), "lm_gemm_streams: ln_gamma / ln_beta must come together");
+    OT_CHECK_ARG(act == 0 || act == 1, "lm_gemm_streams: act %d", act);
+    OT_CHECK_ARG(aligned16(x) && aligned16(w) && aligned16(y), "lm_gemm_streams: unaligned");
+    const float *w32 = fmt == OMNITOK_LM_W_FP32 ? static_cast<const float *>(w) : nullptr;
+    const void *w16 = fmt == OMNITOK_LM_W_FP32 ? nullptr : w;
+    if (B < g_lm_streams_min)  // the VALU kernels, in groups of 8 / 4 / 2 / 1 streams
+        return lm_gemv_any(x, w32, w16, fmt, bias, residual, ln_gamma, ln_beta, y, B, N, K, act, nullptr, stream);
+    const int64_t xn_floats = ln_gamma ? (int64_t)B * K : 0, need = xn_floats + lm_streams_part_floats(B, N, K);
+    std::lock_guard<std::mutex> lk(g_streams_ws_mu);
+    int dev = 0;
+    OT_HIP(hipGetDevice(&dev));
+    if (need > 0 && (g_streams_ws_floats < need || g_streams_ws_dev != dev)) {
+        if (g_streams_ws) (void)hipFree(g_streams_ws);  // (synchronises: no earlier call still uses it)
+        g_streams_ws = nullptr;
+        g_streams_ws_floats = 0;
+        OT_HIP(hipMalloc(reinterpret_cast<void **>(&g_streams_ws), (size_t)need * 4));
+        g_streams_ws_floats = need;
+        g_streams_ws_dev = dev;
+    }
+    return lm_gemm_streams_any(x, w32, w16, fmt, bias, residual, ln_gamma, ln_beta, y, B, N, K, act, g_streams_ws,
+                               g_streams_ws + xn_floats, stream);
 }
 
 // chunk partials only (the engine merges them inside the proj GEMV)
@@ -1557,10 +1777,12 @@ struct omnitok_lm {
     void *kv = nullptr;                       // [n_layer][2][max_batch][n_head][max_len][head_dim] elements of cache_format
     int cache_format = OMNITOK_LM_KV_FP32;    // element type of kv (omnitok_lm_set_cache_format; applies at omnitok_lm_alloc_cache)
     int max_batch = 0, max_len = 0;
+    int max_streams = 16;  // what omnitok_lm_alloc_cache accepts as max_batch (omnitok_lm_set_max_streams, up to 128)
     int chunk = LM_CHUNK;  // keys per attention chunk of the decode step (omnitok_lm_alloc_cache)
     int *err_flag = nullptr;  // LM_FLAG_PAST_CACHE: the attention kernel met a stream past max_len | LM_FLAG_FP16_RANGE: a K/V value
                               // stored into an fp16 cache rounded to +-inf (the append, the prefill's scatter)
     float *x = nullptr, *qkv = nullptr, *att = nullptr, *hid = nullptr, *part = nullptr;
+    float *gs = nullptr;  // K-split partials of lm_gemm_streams_kernel (the many-stream step)
     int64_t cache_bytes = 0;
     // grow-only prefill workspace (rows = B * T)
     float *pf = nullptr;
@@ -1617,7 +1839,7 @@ extern "C" int omnitok_lm_create(const omnitok_lm_config *cfg, omnitok_lm **out)
 
 static void lm_free_cache(omnitok_lm *lm) {
     lm->pf_floats = lm->lg_floats = lm->ce_rows = lm->ce_bytes = 0;
-    for (float **p : {&lm->x, &lm->qkv, &lm->att, &lm->hid, &lm->part, &lm->pf, &lm->lg, &lm->ce})
+    for (float **p : {&lm->x, &lm->qkv, &lm->att, &lm->hid, &lm->part, &lm->gs, &lm->pf, &lm->lg, &lm->ce})
         if (*p) {
             (void)hipFree(*p);
             *p = nullptr;
@@ -1693,6 +1915,20 @@ extern "C" int omnitok_lm_set_cache_format(omnitok_lm *lm, int fmt) {
 extern "C" int omnitok_lm_cache_format(omnitok_lm *lm) {
     OT_CHECK_ARG(lm, "lm_cache_format: null engine");
     return lm->cache_format;
+}
+
+extern "C" int omnitok_lm_set_max_streams(omnitok_lm *lm, int n) {
+    OT_CHECK_ARG(lm, "lm_set_max_streams: null engine");
+    OT_CHECK_ARG(n >= 1 && n <= 128, "lm_set_max_streams: %d streams (1 .. 128)", n);
+    lm_free_cache(lm);  // the cache and the step workspaces: the next step / prefill asks for omnitok_lm_alloc_cache
+    lm->max_batch = lm->max_len = 0;
+    lm->max_streams = n;
+    return OMNITOK_OK;
+}
+
+extern "C" int omnitok_lm_max_streams(omnitok_lm *lm) {
+    OT_CHECK_ARG(lm, "lm_max_streams: null engine");
+    return lm->max_streams;
 }
 
 extern "C" int64_t omnitok_lm_step_weight_bytes(omnitok_lm *lm) {
@@ -1818,24 +2054,42 @@ extern "C" int omnitok_lm_finalize(omnitok_lm *lm, omnitok_stream_t stream_) {
 }
 
 extern "C" int omnitok_lm_alloc_cache(omnitok_lm *lm, int max_batch, int max_len) {
-    OT_CHECK_ARG(lm && max_batch > 0 && max_batch <= 16 && max_len > 0, "lm_alloc_cache: bad sizes (max_batch <= 16)");
+    OT_CHECK_ARG(lm && max_batch > 0 && max_batch <= lm->max_streams && max_len > 0, "lm_alloc_cache: bad sizes (max_batch <= %d)",
+                 lm ? lm->max_streams : 16);
     OT_CHECK_ARG(max_len <= LM_CHUNK * LM_MAX_CHUNKS && lm->cfg.n_head <= LM_MAX_HEADS,
                  "lm_alloc_cache: max_len <= %d and n_head <= %d", LM_CHUNK * LM_MAX_CHUNKS, LM_MAX_HEADS);
     lm_free_cache(lm);
+    lm->max_batch = lm->max_len = 0;
     const omnitok_lm_config &c = lm->cfg;
     const int64_t C = c.n_embd;
     const int hd = c.n_embd / c.n_head;
     const int64_t per_layer = (int64_t)max_batch * c.n_head * max_len * hd;  // elements per K (or V)
     lm->chunk = g_lm_attn_short && max_len <= LM_CHUNK_SHORT * LM_MAX_CHUNKS ? LM_CHUNK_SHORT : LM_CHUNK;
     const int nchunk = (max_len + lm->chunk - 1) / lm->chunk;
-    auto alloc = [](float **p, int64_t n) { return hipMalloc(reinterpret_cast<void **>(p), (size_t)n * 4); };
     const int64_t kv_bytes = per_layer * 2 * c.n_layer * lm_kv_elem_bytes(lm->cache_format);
-    OT_HIP(hipMalloc(&lm->kv, (size_t)kv_bytes));
-    OT_HIP(alloc(&lm->x, max_batch * C));
-    OT_HIP(alloc(&lm->qkv, max_batch * 3 * C));
-    OT_HIP(alloc(&lm->att, max_batch * C));
-    OT_HIP(alloc(&lm->hid, max_batch * 4 * C));
-    OT_HIP(alloc(&lm->part, (int64_t)max_batch * c.n_head * nchunk * (2 + hd)));
+    // split partials of the many-stream GEMMs of a step: the largest of its five shapes
+    int64_t gs = 0;
+    const int shapes[5][2] = {{(int)(3 * C), (int)C}, {(int)C, (int)C}, {(int)(4 * C), (int)C}, {(int)C, (int)(4 * C)}, {c.vocab_size, (int)C}};
+    for (const auto &nk : shapes) gs = std::max(gs, lm_streams_part_floats(max_batch, nk[0], nk[1]));
+    // a failed allocation (193 GB of fp32 cache for 128 streams of the reference's model do not fit one device) returns its
+    // error and leaves the engine without a cache
+    auto alloc = [lm](void **p, int64_t bytes) {
+        const hipError_t e = hipMalloc(p, (size_t)bytes);
+        if (e != hipSuccess) {
+            *p = nullptr;
+            (void)hipGetLastError();
+            lm_free_cache(lm);
+            set_error("lm_alloc_cache: hipMalloc of %lld bytes failed: %s", (long long)bytes, hipGetErrorString(e));
+        }
+        return e == hipSuccess;
+    };
+    if (!alloc(&lm->kv, kv_bytes) || !alloc(reinterpret_cast<void **>(&lm->x), max_batch * C * 4) ||
+        !alloc(reinterpret_cast<void **>(&lm->qkv), max_batch * 3 * C * 4) ||
+        !alloc(reinterpret_cast<void **>(&lm->att), max_batch * C * 4) ||
+        !alloc(reinterpret_cast<void **>(&lm->hid), max_batch * 4 * C * 4) ||
+        !alloc(reinterpret_cast<void **>(&lm->part), (int64_t)max_batch * c.n_head * nchunk * (2 + hd) * 4) ||
+        (gs > 0 && !alloc(reinterpret_cast<void **>(&lm->gs), gs * 4)))
+        return OMNITOK_ERR_HIP;
     lm->max_batch = max_batch;
     lm->max_len = max_len;
     lm->cache_bytes = kv_bytes;
@@ -1921,6 +2175,42 @@ extern "C" int omnitok_lm_step_ex(omnitok_lm *lm, const int64_t *idx, const floa
     hipLaunchKernelGGL(lm_embed_kernel, dim3(B), dim3(256), 0, stream, idx, pos, LW(lm, "tok_emb.weight"),
                        LW(lm, "pos_emb"), emb, pos_extra, lm->x, C, c.vocab_size, c.block_size);
     OT_LAUNCH_CHECK("lm_embed");
+    if (B >= g_lm_streams_min) {
+        // the many-stream step (lm_gemm_streams_kernel): one pass over every matrix for the whole batch.  LayerNorm is a pass of its
+        // own into `att`, the chunk partials are merged into `att` as a tensor (free again by then)
+        const int nchunk = (lm->max_len + lm->chunk - 1) / lm->chunk;
+        for (int i = 0; i < c.n_layer; ++i) {
+            const LmLayer &L = lm->layers[i];
+            void *kc = lm_kv_slab(lm, 2 * i, per_layer), *vc = lm_kv_slab(lm, 2 * i + 1, per_layer);
+            if (int rc = lm_gemm_streams_any(lm->x, L.wqkv, L.wqkv16, wf, L.bqkv, nullptr, L.ln1w, L.ln1b, lm->qkv, B, 3 * C, C, 0, lm->att,
+                                             lm->gs, stream))
+                return rc;
+            if (int rc = lm_attn_partials(lm->qkv, kc, vc, lm->cache_format, cache_len, B, c.n_head, hd, lm->max_len, lm->part, stream, 0,
+                                          lm->err_flag, lm->chunk))
+                return rc;
+            hipLaunchKernelGGL(lm_attn_merge_kernel, dim3(c.n_head, B), dim3(128), 0, stream, lm->part, cache_len, c.n_head, hd, nchunk, 0,
+                               lm->att, lm->chunk);
+            OT_LAUNCH_CHECK("lm_attn_merge");
+            if (int rc = lm_gemm_streams_any(lm->att, L.wproj, L.wproj16, wf, L.bproj, lm->x, nullptr, nullptr, lm->x, B, C, C, 0, nullptr,
+                                             lm->gs, stream))
+                return rc;
+            if (int rc = lm_gemm_streams_any(lm->x, L.w1, L.w116, wf, L.b1, nullptr, L.ln2w, L.ln2b, lm->hid, B, 4 * C, C, 1, lm->att, lm->gs,
+                                             stream))
+                return rc;
+            if (int rc = lm_gemm_streams_any(lm->hid, L.w2, L.w216, wf, L.b2, lm->x, nullptr, nullptr, lm->x, B, C, 4 * C, 0, nullptr, lm->gs,
+                                             stream))
+                return rc;
+        }
+        if (logits_out)
+            if (int rc = lm_gemm_streams_any(lm->x, LW(lm, "head.weight"), lm->head16, wf, nullptr, nullptr, LW(lm, "ln_f.weight"),
+                                             LW(lm, "ln_f.bias"), logits_out, B, c.vocab_size, C, 0, lm->att, lm->gs, stream))
+                return rc;
+        if (advance) {
+            hipLaunchKernelGGL(lm_advance_kernel, dim3(1), dim3(128), 0, stream, pos, cache_len, B);
+            OT_LAUNCH_CHECK("lm_advance");
+        }
+        return OMNITOK_OK;
+    }
     for (int i = 0; i < c.n_layer; ++i) {
         const LmLayer &L = lm->layers[i];
         void *kc = lm_kv_slab(lm, 2 * i, per_layer), *vc = lm_kv_slab(lm, 2 * i + 1, per_layer);
@@ -1944,7 +2234,8 @@ extern "C" int omnitok_lm_step_ex(omnitok_lm *lm, const int64_t *idx, const floa
                                  LW(lm, "ln_f.bias"), logits_out, B, c.vocab_size, C, 0, nullptr, stream))
             return rc;
     if (advance) {
-        hipLaunchKernelGGL(lm_advance_kernel, dim3(1), dim3(64), 0, stream, pos, cache_len, B);
+        // one thread per stream: up to 128 of them also on this path ("lm_streams_min" above B sends any batch here)
+        hipLaunchKernelGGL(lm_advance_kernel, dim3(1), dim3(128), 0, stream, pos, cache_len, B);
         OT_LAUNCH_CHECK("lm_advance");
     }
     return OMNITOK_OK;
@@ -2058,7 +2349,7 @@ extern "C" int omnitok_lm_prefill_ex(omnitok_lm *lm, const int64_t *idx, int T_t
     if (int rc = lm_prefill_layers(lm, idx, T_tok, emb, T_emb, pos_extra, pos, cache_len, B, stream, &x, &xn)) return rc;
     if (logits_out)
         if (int rc = lm_head_rows(lm, x, xn, (int64_t)B * T, logits_out, stream)) return rc;
-    hipLaunchKernelGGL(lm_set_len_kernel, dim3(1), dim3(64), 0, stream, pos, cache_len, B, T);
+    hipLaunchKernelGGL(lm_set_len_kernel, dim3(1), dim3(128), 0, stream, pos, cache_len, B, T);
     OT_LAUNCH_CHECK("lm_set_len");
     return OMNITOK_OK;
 }
@@ -2115,7 +2406,7 @@ extern "C" int omnitok_lm_prefill_loss(omnitok_lm *lm, const int64_t *idx, int T
         if (int rc = lm_token_ce_rows(lm->lg, V, targets + r0, rows, (int)V, nll_w + r0, rank_w + r0, stream)) return rc;
     }
     if (int rc = lm_token_ce_reduce(nll_w, rank_w, M, (int)V, sums, red, red_bytes, stream)) return rc;
-    hipLaunchKernelGGL(lm_set_len_kernel, dim3(1), dim3(64), 0, stream, pos, cache_len, B, T);
+    hipLaunchKernelGGL(lm_set_len_kernel, dim3(1), dim3(128), 0, stream, pos, cache_len, B, T);
     OT_LAUNCH_CHECK("lm_set_len");
     return OMNITOK_OK;
 }

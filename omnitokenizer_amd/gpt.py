@@ -7,7 +7,8 @@ The class owns the parameters under the reference's state_dict key names; all ar
 step runs in libomnitok.so (include/omnitok_lm.h, csrc/lm.hip): a preallocated K/V cache instead of
 the reference's per-step torch.cat of all pasts, GEMV kernels that stream each weight matrix
 once per step (fp32, or bf16 / fp16 at half the bytes: GPT.set_weight_format), flash-decode
-attention over an fp32, bf16 or fp16 cache (GPT.set_cache_format), and -- because the step's launch sequence does not depend on the position -- one
+attention over an fp32, bf16 or fp16 cache (GPT.set_cache_format), up to 16 streams per engine or, on an fp32-MFMA GEMM that reads
+each matrix once for the whole batch, up to 128 (GPT.set_max_streams), and -- because the step's launch sequence does not depend on the position -- one
 captured HIP graph replayed per token.  Token selection (temperature, the CFG blend,
 top-k / top-p filtering, argmax or one multinomial draw) is one more kernel (csrc/lm_select.hip); the only
 thing torch contributes is the uniform random number per stream (so torch.manual_seed governs the samples).
@@ -101,6 +102,7 @@ class GPT(nn.Module):
         self._graphs = {}
         self._weight_format = "fp32"
         self._cache_format = "fp32"
+        self._max_streams = 16
         self._generation = 0
 
     # ---- plumbing ---------------------------------------------------------------------------------
@@ -176,6 +178,27 @@ class GPT(nn.Module):
             check(_lib.load().omnitok_lm_set_cache_format(self._engine, KV_FORMATS[fmt]), "lm_set_cache_format")
         return self
 
+    @property
+    def max_streams(self) -> int:
+        return self._max_streams
+
+    def set_max_streams(self, n: int):
+        """Streams one engine may hold (include/omnitok_lm.h, omnitok_lm_set_max_streams): 1 .. 128, default 16.  Above 16 streams a
+        decode step runs every weight matrix once for the whole batch on the fp32-input MFMA (same fp32 arithmetic, another
+        summation order than the <= 16-stream kernels); steps of up to 16 streams run what they ran before.  sample_with_past_cfg
+        uses 2 B rows.  The K/V cache grows with the batch: 128 streams x 5121 positions of the reference's 24 x 1536 model are
+        193 GB in fp32 and 97 GB in a 16-bit cache format.  The cache and the captured graphs are dropped and handles of earlier
+        streams are rejected; the weights and state_dict() are left alone."""
+        if not isinstance(n, int) or isinstance(n, bool) or not 1 <= n <= 128:
+            raise ValueError(f"max_streams {n!r}: expected an int in 1 .. 128")
+        self._max_streams = n
+        self._cache_shape = (0, 0)
+        self._graphs = {}
+        self._generation += 1
+        if self._engine is not None:  # frees the engine's cache; the next reset_streams allocates it again
+            check(_lib.load().omnitok_lm_set_max_streams(self._engine, n), "lm_set_max_streams")
+        return self
+
     def cache_rows(self, layer, stream, start=0, stop=None):
         """(k, v) of rows start .. stop - 1 of one stream's cache in one layer, widened to fp32: [n_head, n, head_dim] each (the
         counterpart of the reference's `present`).  stop=None: the stream's current length (one host synchronisation)."""
@@ -218,6 +241,7 @@ class GPT(nn.Module):
             self._engine = h
             # before the first alloc_cache (set_cache_format applies later changes to the engine itself)
             check(lib.omnitok_lm_set_cache_format(self._engine, KV_FORMATS[self._cache_format]), "lm_set_cache_format")
+            check(lib.omnitok_lm_set_max_streams(self._engine, self._max_streams), "lm_set_max_streams")
         check(lib.omnitok_lm_set_weight_format(self._engine, WEIGHT_FORMATS[self._weight_format]), "lm_set_weight_format")
         for name, t in self.state_dict(keep_vars=True).items():
             if name == "vtokens_pos_emb":  # gathered per call on the host side (cbox / tbox), not an engine weight
@@ -252,8 +276,9 @@ class GPT(nn.Module):
     def reset_streams(self, batch, max_len):
         """Starts `batch` empty streams (cache length 0, position 0) with room for max_len tokens."""
         self._sync_engine()
-        if batch > 16:
-            raise ValueError("at most 16 streams per engine")
+        if batch > self._max_streams:
+            raise ValueError(f"at most {self._max_streams} streams per engine"
+                             + (" (set_max_streams raises the limit, up to 128)" if self._max_streams < 128 else ""))
         self._ensure_cache(batch, max_len)
         self._pos.zero_()
         self._len.zero_()

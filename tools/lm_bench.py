@@ -4,7 +4,12 @@ LM shape by default (scripts/lm_train/train_k600.sh: vocab 8192, block 5120, 24 
 1536 wide), synthetic weights.  One JSON line: throughput, per-step time at the start / end of the
 sequence, the HBM roofline of a step (weight bytes + K/V bytes read) and a CPU baseline (the oracle's
 KV-cached step on the host, bounded sample).
-    python tools/lm_bench.py [--batch 1] [--steps 512] [--ctx 0] [--weights fp32|bf16|fp16] [--kv fp32|bf16|fp16] [--also 8] [--no-cpu-baseline]"""
+    python tools/lm_bench.py [--batch 1] [--steps 512] [--ctx 0] [--weights fp32|bf16|fp16] [--kv fp32|bf16|fp16] [--also 8] [--no-cpu-baseline]
+                             [--max-streams 16]
+--streams-session OUT.json: the many-stream record instead (GPT.set_max_streams; profiles/lm_streams_bench.json): the bare decode step
+(graph replay) of B in --session-batches streams at --session-ctx cached tokens, fp32 weights + fp32 cache first, then bf16 + bf16,
+and of 8 and 16 streams once more with "lm_streams_min" 1 (the many-stream kernel below its default threshold).  The cache lengths
+are set on the device, nothing is prefilled: a step's time depends on how many rows it reads, not on what they hold."""
 import argparse
 import json
 import os
@@ -19,6 +24,100 @@ from omnitokenizer_amd import gpt as og  # noqa: E402
 from omnitokenizer_amd.synth import synth_gpt_state  # noqa: E402
 
 PEAK_HBM_GBS = 8000.0
+PEAK_F32_MFMA_TFLOPS = 157.3
+
+
+def streams_session(a, m, dims):
+    """One session over (format, cached tokens, streams): see the module docstring.  Returns the record."""
+    from omnitokenizer_amd import _lib
+    V, BS, L, H, C = dims
+    hd = C // H
+    batches = [int(b) for b in a.session_batches.split(",")]
+    ctxs = [int(c) for c in a.session_ctx.split(",")]
+    NB = max(batches)
+    m.set_max_streams(NB)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    default_min = _lib.get_option("lm_streams_min")
+    flop_per_stream = 2.0 * (12.0 * C * C * L + V * C)
+    cells = []
+
+    def time_cell(B, length):
+        """median ms of 5 rounds of nrep graph replays of the B-stream step at cache length `length` (a first round is dropped)"""
+        _, _, replay = m.graph_step(B)
+
+        def one_round(n):
+            e0.record()
+            for _ in range(n):
+                m._pos[:B] = length
+                m._len[:B] = length
+                replay()
+            e1.record()
+            torch.cuda.synchronize()
+            return e0.elapsed_time(e1) / n
+        first = one_round(3)
+        nrep = max(5, min(50, int(250.0 / max(first, 1e-3))))
+        rounds = sorted(one_round(nrep) for _ in range(5))
+        return rounds[2], [round(rounds[0], 4), round(rounds[-1], 4)], nrep
+
+    for fmt in ("fp32", "bf16"):     # the fp32 arm first
+        m.set_weight_format(fmt).set_cache_format(fmt)
+        weight_bytes = float(m.step_weight_bytes())
+        kv_elem = 4.0 if fmt == "fp32" else 2.0
+        for ctx in ctxs:
+            # a cache sized for this context, as `--ctx` runs allocate it: the attention launch covers the whole cache, and a
+            # workgroup has requested its chunk's rows before it learns that the stream ends in front of them
+            m.set_cache_format(fmt)      # drops the cache: the next reset_streams allocates exactly ctx + 64 positions
+            try:
+                m.reset_streams(NB, ctx + 64)
+            except Exception as exc:     # a cache the device cannot hold: recorded, not fatal
+                cells.append({"weights": fmt, "kv": fmt, "ctx": ctx, "skipped": f"cache for {NB} streams x {ctx + 64} tokens: {exc}"})
+                continue
+            arms = [(B, default_min) for B in batches] + [(B, 1) for B in (8, 16) if B in batches and B < default_min]
+            for B, smin in arms:
+                _lib.set_option("lm_streams_min", smin)
+                m._graphs = {}       # the kernels are chosen when the step is captured
+                try:
+                    ms, spread, nrep = time_cell(B, ctx)
+                finally:
+                    _lib.set_option("lm_streams_min", default_min)
+                    m._graphs = {}
+                m.check_overflow()
+                kv_bytes = 2.0 * L * B * H * (ctx + 1) * hd * kv_elem
+                cells.append({"weights": fmt, "kv": fmt, "ctx": ctx, "streams": B, "lm_streams_min": smin,
+                              "path": "many-stream MFMA GEMM" if B >= smin else "VALU GEMV, groups of 8",
+                              "max_len": m._cache_shape[1], "step_ms": round(ms, 4), "step_ms_min_max": spread,
+                              "replays_per_round": nrep,
+                              "tokens_s": round(B / (ms * 1e-3), 1), "weight_bytes": weight_bytes, "kv_bytes": kv_bytes,
+                              "frac_hbm": round((weight_bytes + kv_bytes) / (ms * 1e-3) / 1e9 / PEAK_HBM_GBS, 4),
+                              # the step's GEMM FLOPs over the WHOLE step's time (attention, LayerNorm and every launch boundary
+                              # included) against the f32-MFMA peak: a rate of the step, not of the GEMM kernels
+                              "step_gemm_flops_over_f32_mfma_peak": round(B * flop_per_stream / (ms * 1e-3) / 1e12 / PEAK_F32_MFMA_TFLOPS, 4)})
+                print(json.dumps(cells[-1]), flush=True)
+    # the yardstick: a B-stream step against B / 16 steps of 16 streams (the <= 16-stream path, untouched)
+    verdict = []
+    for fmt in ("fp32", "bf16"):
+        for ctx in ctxs:
+            def cell(B, smin=default_min):
+                return next((c for c in cells if c.get("weights") == fmt and c.get("ctx") == ctx and c.get("streams") == B
+                             and c.get("lm_streams_min") == smin), None)
+            base = cell(16)
+            for B in batches:
+                c = cell(B)
+                if base and c and B > 16:
+                    verdict.append({"weights": fmt, "ctx": ctx, "streams": B, "step_ms": c["step_ms"],
+                                    "steps_of_16_ms": round(base["step_ms"] * B / 16, 4),
+                                    "speedup": round(base["step_ms"] * B / 16 / c["step_ms"], 3)})
+    return {"metric": "LM decode step (graph replay), many streams per engine", "unit": "ms per step",
+            "config": {"workload": f"GPT {L}x{C} ({H} heads, head_dim {hd}), vocab {V}, block {BS}", "max_streams": NB,
+                       "peak_hbm_gbs": PEAK_HBM_GBS, "peak_f32_mfma_tflops": PEAK_F32_MFMA_TFLOPS,
+                       "protocol": "graph replay, pos / cache_len reset before every replay, 1 dropped + 5 timed rounds, median; "
+                                   "fp32 arm first; cache contents not prefilled; the timed window includes the two small device fills that "
+                                   "reset pos / cache_len before each replay (the same in every cell, as in the tool's other records: "
+                                   "ratios stand, absolute times are high by those two launches)",
+                       "frac_hbm": "(weight bytes + K/V bytes of the cached tokens) / step time / peak_hbm_gbs",
+                       "step_gemm_flops_over_f32_mfma_peak": "2 B (12 C^2 L + V C) FLOP / WHOLE step time / peak: a rate of the step, "
+                                                             "attention and LayerNorm launches included, not of the GEMM kernels"},
+            "cells": cells, "vs_steps_of_16": verdict}
 
 
 def main():
@@ -35,10 +134,15 @@ def main():
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-also", action="store_true", help="skip the 8-stream line (B = 1 runs only)")
-    ap.add_argument("--also", default="8", metavar="B[,B..]", help="stream counts of the extra lines of a B = 1 run (default 8)")
+    ap.add_argument("--also", default="8", metavar="B[,B..]", help="stream counts of the extra lines of a B = 1 run (default 8; up to --max-streams)")
     ap.add_argument("--weights", choices=("fp32", "bf16", "fp16"), default="fp32",
                     help="format of the matrices a decode step streams (GPT.set_weight_format)")
     ap.add_argument("--kv", choices=("fp32", "bf16", "fp16"), default="fp32", help="format of the K/V cache (GPT.set_cache_format)")
+    ap.add_argument("--max-streams", type=int, default=16, help="streams per engine (GPT.set_max_streams, up to 128): the limit of "
+                                                                 "--batch and of every --also count")
+    ap.add_argument("--streams-session", metavar="OUT.json", help="write the many-stream record (see above) and exit")
+    ap.add_argument("--session-batches", default="8,16,32,64,128")
+    ap.add_argument("--session-ctx", default="0,4608")
     a = ap.parse_args()
     V, BS, L, H, C = a.vocab, a.block, a.layers, a.heads, a.embd
     for kv in a.option:
@@ -47,7 +151,14 @@ def main():
     sd = synth_gpt_state(V, BS, L, H, C, seed=0)
     m = og.GPT(argparse.Namespace(), V, BS, n_layer=L, n_head=H, n_embd=C)
     m.load_state_dict(sd, strict=True)
-    m = m.cuda().eval().set_weight_format(a.weights).set_cache_format(a.kv)
+    m = m.cuda().eval().set_weight_format(a.weights).set_cache_format(a.kv).set_max_streams(a.max_streams)
+    if a.streams_session:
+        rec = streams_session(a, m, (V, BS, L, H, C))
+        with open(a.streams_session, "w") as f:
+            json.dump(rec, f, indent=1)
+            f.write("\n")
+        print(json.dumps({"written": a.streams_session, "vs_steps_of_16": rec["vs_steps_of_16"]}), flush=True)
+        return
     B = a.batch
     g = torch.Generator().manual_seed(1)
     cond = torch.randint(0, V, (B, 1 + a.ctx), generator=g).cuda()
