@@ -4,7 +4,7 @@ sampling path, plus its sampling loops `sample_with_past` (:327-359) and `sample
 `decode()` (lm_transformer.py:262,434).
 
 The class owns the parameters under the reference's state_dict key names; all arithmetic of a decode
-step runs in libomnitok.so (include/omnitok_lm.h, csrc/lm.hip): a preallocated K/V cache instead of
+step runs in libomnitok.so (include/omnitok_lm.h, csrc/lm_engine.hip and the other csrc/lm_*.hip): a preallocated K/V cache instead of
 the reference's per-step torch.cat of all pasts, GEMV kernels that stream each weight matrix
 once per step (fp32, or bf16 / fp16 at half the bytes: GPT.set_weight_format), flash-decode
 attention over an fp32, bf16 or fp16 cache (GPT.set_cache_format), up to 16 streams per engine or, on an fp32-MFMA GEMM that reads

@@ -1,5 +1,5 @@
 """GPU (-m gpu): more than 16 streams per LM engine (omnitok_lm_set_max_streams, GPT.set_max_streams) on the many-stream MFMA GEMM
-(omnitok_lm_gemm_streams, csrc/lm.hip lm_gemm_streams_kernel).
+(omnitok_lm_gemm_streams, csrc/lm_gemm_mfma.hip lm_gemm_streams_kernel).
 
 What the kernel promises (include/omnitok_lm.h): fp32 products of fp32 activations with the weight's exact fp32 value, fp32
 accumulation in an order fixed by (N, K) -- so a row of the output is bit-equal whatever the batch around it holds -- and the

@@ -1,4 +1,4 @@
-"""GPU (-m gpu): the LM decode engine (csrc/lm.hip) at the reference's widths against the oracle run in float64.
+"""GPU (-m gpu): the LM decode engine (csrc/lm_*.hip) at the reference's widths against the oracle run in float64.
 
 Two-layer models at n_embd 1536 (24 / 16 / 12 heads: head_dim 64 / 96 / 128) and 2048 (32 / 16 heads) take the K-sliced GEMV for
 every decode projection (K = C and the FC2 input K = 4 C), with the flash-decode merge in the attention projection's prologue, and
@@ -36,7 +36,7 @@ LM_OPTIONS = tuple(BASE) + ("lm_attn_short",)
 
 
 def stream_groups(B):
-    """the VALU kernels' stream groups (csrc/lm.hip lm_gemv_any): 8 while 8 are left, then 4, 2, 1"""
+    """the VALU kernels' stream groups (csrc/lm_gemv.hip lm_gemv_any): 8 while 8 are left, then 4, 2, 1"""
     out, b0 = [], 0
     while b0 < B:
         left = B - b0
