@@ -112,6 +112,35 @@ int omnitok_lm_cache_format(omnitok_lm *lm); /* -1: null engine */
 int omnitok_lm_set_max_streams(omnitok_lm *lm, int n);
 int omnitok_lm_max_streams(omnitok_lm *lm); /* -1: null engine */
 
+/* How the batched prefill runs its GEMMs -- per engine, default OMNITOK_LM_PF_FP32 (nothing below applies then).  The prefill
+ * (omnitok_lm_prefill, _prefill_ex, _prefill_loss) is bound by its five nn.Linear GEMMs per block and the head GEMM, which run on the
+ * fp32-input MFMA (omnitok_gemm) at 1/16 of the matrix cores' 16-bit rate; under the reference's precision="bf16" its nn.Linears see
+ * 16-bit activations AND 16-bit weights.  OMNITOK_LM_PF_W16 runs these six GEMMs on the bf16 / fp16 MFMA (omnitok_lm_gemm16 below)
+ * over the packed weight images a 16-bit engine already holds:
+ *   Needs a 16-bit weight format: with OMNITOK_LM_W_FP32 in force the three prefill entry points return OMNITOK_ERR_STATE and name
+ *     both switches in omnitok_last_error() -- there is no fallback to the fp32 GEMM.
+ *   What is rounded: the A operand of each GEMM, ONCE, to the engine's weight format (round to nearest even, lm_round16: the bits
+ *     of tensor.to(torch.bfloat16) / .to(torch.float16)) -- the LayerNorm rows (ln1, ln2, ln_f), the merged attention output and
+ *     FC1's GELU output.  Each is the rounding of the fp32 value the fp32 prefill computes at that point (the same LayerNorm and
+ *     merge kernels with a 16-bit store; the GELU in the GEMM's fp32 epilogue).  Products are exact in fp32, accumulation is fp32 in
+ *     an order fixed by K alone (no split-K, no atomics): a row's results do not depend on B, T or the other rows, two calls give
+ *     equal bits, and omnitok_lm_prefill_loss gives equal bits for every "lm_loss_chunk_rows".
+ *   Everything else stays fp32: the embedding and the residual stream, qkv and the K/V scatter into the cache (in the cache's own
+ *     format), the attention partials and their merge, the LayerNorm statistics, bias / GELU / residual epilogues, the logits and
+ *     the token cross-entropy.  The decode step is unaffected.
+ *   "Same arithmetic as T decode steps" NO LONGER HOLDS: a step multiplies fp32 activations, a PF_W16 prefill rounded ones.  The
+ *     prefill's logits differ from the fp32 prefill's of the same 16-bit engine by the activation rounding: measured on the golden
+ *     models (3 streams x 40 tokens, logits of magnitude 3 .. 6) max |difference| 1.2e-2 .. 2.9e-2 in bf16 and 1.4e-3 .. 3.9e-3 in
+ *     fp16 (tests/test_gpu_lm_prefill16.py prints them); the K/V rows a PF_W16 prefill leaves in the cache differ in the same way.
+ *   fp16 range: an activation that rounds to +-inf raises bit 4 of the engine's flag word (omnitok_lm_overflowed).  bf16 has
+ *     fp32's range.
+ * omnitok_lm_set_prefill_format: -1 for a null engine or an unknown format (a refused format changes nothing); it touches neither
+ * `finalized`, the weights nor the cache, and applies from the next prefill on. */
+#define OMNITOK_LM_PF_FP32 0
+#define OMNITOK_LM_PF_W16 1
+int omnitok_lm_set_prefill_format(omnitok_lm *lm, int fmt);
+int omnitok_lm_prefill_format(omnitok_lm *lm); /* -1: null engine */
+
 /* K/V cache [n_layer][2][max_batch][n_head][max_len][head_dim] in the engine's cache format + step workspaces;
  * max_batch <= omnitok_lm_max_streams (16 unless raised), otherwise -1 with the limit in force in the message. */
 int omnitok_lm_alloc_cache(omnitok_lm *lm, int max_batch, int max_len);
@@ -145,13 +174,18 @@ int omnitok_lm_step_ex(omnitok_lm *lm, const int64_t *idx, const float *emb, con
  *   1: a decode step found cache_len[b] >= max_len (a stream stepped past the cache that omnitok_lm_alloc_cache sized; the step
  *      then stays inside the stream's own K/V slab and its logits are invalid);
  *   2: a K/V value stored into an OMNITOK_LM_KV_FP16 cache (a step's append or a prefill) left the fp16 range and was stored as
- *      +-inf: the logits from there on are invalid.  An fp32 or bf16 cache never returns 2. */
+ *      +-inf: the logits from there on are invalid.  An fp32 or bf16 cache never returns 2.
+ *   4: an activation of an OMNITOK_LM_PF_W16 prefill on an fp16 engine (a LayerNorm row, a merged attention row or FC1's GELU
+ *      output) left the fp16 range and entered its GEMM as +-inf: that prefill's logits and cache rows are invalid.  Never set by
+ *      the default prefill format or a bf16 engine. */
 int omnitok_lm_overflowed(omnitok_lm *lm, omnitok_stream_t stream);
 
 /* Batched prefill of a conditioning prefix into EMPTY streams (GPT.forward / the first
  * forward_with_past call of the reference, gpt.py:207-275, positions 0..T-1): idx[B, T] int64.
  * Same arithmetic as T decode steps, executed as [B*T]-row fp32-MFMA GEMMs (omnitok_gemm) + causal
- * flash attention over the cache.  Fills the K/V cache, sets pos[b] = cache_len[b] = T on the
+ * flash attention over the cache (with OMNITOK_LM_PF_W16 the GEMMs run on the 16-bit MFMA over
+ * rounded activations instead, and "same arithmetic" no longer holds: omnitok_lm_set_prefill_format
+ * above).  Fills the K/V cache, sets pos[b] = cache_len[b] = T on the
  * device.  logits_out (optional) [B, T, vocab]: teacher-forced logits of every position.
  * B * T <= 65535; may hipMalloc its (grow-only) workspace. */
 int omnitok_lm_prefill(omnitok_lm *lm, const int64_t *idx, int32_t *pos, int32_t *cache_len, int B,
@@ -231,6 +265,24 @@ int omnitok_lm_gemv_w16(const float *x, const void *w16, int fmt, const float *b
 int omnitok_lm_gemm_streams(const float *x, const void *w, int fmt, const float *bias, const float *residual,
                             const float *ln_gamma, const float *ln_beta, float *y, int B, int N, int K, int act,
                             omnitok_stream_t stream);
+/* The GEMM of an OMNITOK_LM_PF_W16 prefill: y[M, N] = act(a16[M, K] . w16[N, K]^T + bias) (+ residual) with a16 and w16 packed bf16 or
+ * fp16 (fmt = OMNITOK_LM_W_BF16 | OMNITOK_LM_W_FP16), row-major, 16-byte aligned, on v_mfma_f32_32x32x16_{bf16,f16}: exact products,
+ * fp32 accumulators.  1 <= M <= 65535, N >= 1, K % 32 == 0.  The partial sums of a dot product are joined in k order, an order fixed
+ * by K alone: row m of y depends on row m of a16 only -- not on M, the row's position or the other rows' contents (NaN / Inf included)
+ * -- and two calls give equal bits.  Epilogue in fp32: + bias [N] (optional), exact-erf GELU if act == 1, then
+ *   y32 != NULL: + residual [M, N] (optional, may alias y32), stored as fp32; or
+ *   y16 != NULL: rounded to fmt (round to nearest even, the bits of torch's .to()) into a packed [M, N] -- the next GEMM's operand; no
+ *     residual in this form.  An fp16 element that rounds to +-inf ORs 4 into *flag (flag may be NULL; bf16 never sets it).
+ * Exactly one of y32 / y16.  -1 before any HIP call for null or unaligned pointers, sizes outside the above, an unknown fmt or act,
+ * both or neither output, or a residual with y16. */
+int omnitok_lm_gemm16(const void *a16, const void *w16, int fmt, const float *bias, const float *residual,
+                      float *y32, void *y16, int64_t M, int N, int K, int act, int *flag, omnitok_stream_t stream);
+/* nn.LayerNorm (eps 1e-5, two-pass statistics in fp32: the arithmetic of the fp32 prefill's LayerNorm) of x [rows, K] fp32 with each
+ * result rounded once to fmt into y16 [rows, K] packed: the producer of omnitok_lm_gemm16's A operand.  All four pointers 16-byte
+ * aligned, rows >= 1, K % 32 == 0; an fp16 element that rounds to +-inf ORs 4 into *flag (may be NULL).  -1 before any HIP call for
+ * null or unaligned pointers, sizes outside these or an unknown fmt. */
+int omnitok_lm_layernorm16(const float *x, const float *gamma, const float *beta, void *y16, int fmt,
+                           int64_t rows, int K, int *flag, omnitok_stream_t stream);
 /* Decode attention for one layer: qkv[B, 3*C] = (query | key | value) of the new token; K/V cache of
  * this layer kc / vc [max_batch][n_head][max_len][head_dim]; out[B, C].  scratch: float
  * [B * n_head * ceil(max_len/256) * (2 + head_dim)]. */

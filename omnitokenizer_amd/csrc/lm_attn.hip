@@ -173,8 +173,11 @@ __global__ __launch_bounds__(NWV * 64) void lm_attn_decode_kernel(const float *_
     }
 }
 
+// OT = float: out [rows][n_head * HD] fp32 | lm_bf16 / lm_fp16: the same value rounded once (lm_round16) into a packed 16-bit row, the
+// proj GEMM's operand of a PF_W16 prefill; an fp16 result of +-inf raises LM_FLAG_PF16_RANGE in *flag
+template <typename OT>
 __global__ void lm_attn_merge_kernel(const float *__restrict__ part, const int32_t *__restrict__ cache_len, int n_head,
-                                     int HD, int nchunk, int prefill_T, float *__restrict__ out, int chunk) {
+                                     int HD, int nchunk, int prefill_T, OT *__restrict__ out, int chunk, int *__restrict__ flag) {
     const int h = blockIdx.x, b = blockIdx.y, d = threadIdx.x;  // b: query row
     if (d >= HD) return;
     const int total = (prefill_T > 0 ? b % prefill_T : cache_len[b]) + 1;
@@ -189,7 +192,13 @@ __global__ void lm_attn_merge_kernel(const float *__restrict__ part, const int32
         L += pp[c * (2 + HD) + 1] * f;
         O += pp[c * (2 + HD) + 2 + d] * f;
     }
-    out[((int64_t)b * n_head + h) * HD + d] = O / L;
+    if constexpr (__is_same(OT, float)) {
+        out[((int64_t)b * n_head + h) * HD + d] = O / L;
+    } else {
+        bool inf = false;
+        out[((int64_t)b * n_head + h) * HD + d] = LmKV<OT>::store(O / L, inf);
+        if (inf && flag) atomicOr(flag, LM_FLAG_PF16_RANGE);
+    }
 }
 
 // qkv[B*T, 3C] (query | key | value) -> K/V cache rows [b][h][t][hd], rounded to the cache's element type KT on the way (the prefill's
@@ -261,7 +270,20 @@ int lm_attn_partials(const float *qkv, void *kc, void *vc, int kvfmt, const int3
 
 void lm_attn_merge(const float *part, const int32_t *cache_len, int n_head, int hd, int nchunk, int prefill_T, int64_t rows, float *out,
                    int chunk, hipStream_t stream) {
-    hipLaunchKernelGGL(lm_attn_merge_kernel, dim3(n_head, (unsigned)rows), dim3(128), 0, stream, part, cache_len, n_head, hd, nchunk, prefill_T, out, chunk);
+    hipLaunchKernelGGL(lm_attn_merge_kernel<float>, dim3(n_head, (unsigned)rows), dim3(128), 0, stream, part, cache_len, n_head, hd, nchunk, prefill_T, out, chunk,
+                       static_cast<int *>(nullptr));
+}
+
+void lm_attn_merge16(const float *part, int n_head, int hd, int nchunk, int prefill_T, int64_t rows, void *out16, int fmt, int *flag,
+                     hipStream_t stream) {
+    const dim3 grid(n_head, (unsigned)rows);
+    const int32_t *no_len = nullptr;  // prefill rows: the key count comes from the row index
+    if (fmt == OMNITOK_LM_W_BF16)
+        hipLaunchKernelGGL(lm_attn_merge_kernel<lm_bf16>, grid, dim3(128), 0, stream, part, no_len, n_head, hd, nchunk, prefill_T,
+                           static_cast<lm_bf16 *>(out16), LM_CHUNK, flag);
+    else
+        hipLaunchKernelGGL(lm_attn_merge_kernel<lm_fp16>, grid, dim3(128), 0, stream, part, no_len, n_head, hd, nchunk, prefill_T,
+                           static_cast<lm_fp16 *>(out16), LM_CHUNK, flag);
 }
 
 int lm_kv_scatter(const float *qkv, void *kc, void *vc, int kvfmt, int64_t rows, int T, int n_head, int hd, int max_len,

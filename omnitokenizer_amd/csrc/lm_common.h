@@ -14,10 +14,12 @@
 //   lm_gemv_ks.hip    lm_gemv_ks_kernel (the K-sliced GEMV of K in {1536, 2048, 6144, 8192}) behind lm_gemv_ks_try; LM_TRACE
 //   lm_gemm_mfma.hip  lm_gemm4_kernel (4 .. 8 streams on the matrix cores, "lm_mfma" 1) behind lm_gemm4_try; lm_gemm_streams_kernel and
 //                     lm_streams_reduce_kernel (17 .. 128 streams, omnitok_lm_set_max_streams), omnitok_lm_gemm_streams
-//   lm_attn.hip       lm_attn_decode_kernel (flash-decode over the fp32 / bf16 / fp16 K/V cache, chunk partials), lm_attn_merge_kernel,
-//                     lm_kv_scatter_kernel, lm_kv_read_kernel, omnitok_lm_attn_decode[_kv16]
+//   lm_gemm16.hip     lm_gemm16_kernel (the 16-bit MFMA GEMM of a PF_W16 prefill, omnitok_lm_set_prefill_format), omnitok_lm_gemm16
+//   lm_attn.hip       lm_attn_decode_kernel (flash-decode over the fp32 / bf16 / fp16 K/V cache, chunk partials), lm_attn_merge_kernel
+//                     (fp32 or, for a PF_W16 prefill, 16-bit output), lm_kv_scatter_kernel, lm_kv_read_kernel, omnitok_lm_attn_decode[_kv16]
 //   lm_engine.hip     struct omnitok_lm and its exported functions (create .. finalize, alloc_cache, step, prefill, prefill_loss) and the
-//                     small kernels: embed, embed_seq, layernorm_rows, gelu, set_len, advance, concat3, round_w16
+//                     small kernels: embed, embed_seq, layernorm_rows (fp32 or 16-bit output, omnitok_lm_layernorm16), gelu, set_len,
+//                     advance, concat3, round_w16
 #pragma once
 #include "common.h"
 #include "../../include/omnitok_lm.h"
@@ -116,6 +118,7 @@ template <> struct LmKV<float> {
 };
 constexpr int LM_FLAG_PAST_CACHE = 1;  // bits of the engine's flag word (omnitok_lm_overflowed)
 constexpr int LM_FLAG_FP16_RANGE = 2;
+constexpr int LM_FLAG_PF16_RANGE = 4;  // an activation of an fp16 PF_W16 prefill rounded to +-inf
 
 struct LmMerge {
     const float *part;         // [B][n_head][nchunk][2 + hd]
@@ -201,6 +204,10 @@ int lm_attn_partials(const float *qkv, void *kc, void *vc, int kvfmt, const int3
 // the one launch of lm_attn_merge_kernel: out[rows][n_head * hd] from the partials of `rows` query rows (the caller checks the launch)
 void lm_attn_merge(const float *part, const int32_t *cache_len, int n_head, int hd, int nchunk, int prefill_T, int64_t rows, float *out,
                    int chunk, hipStream_t stream);
+// ... rounded to fmt (OMNITOK_LM_W_BF16 | _FP16) into out16: the proj GEMM's operand of a PF_W16 prefill; an fp16 +-inf raises
+// LM_FLAG_PF16_RANGE in *flag
+void lm_attn_merge16(const float *part, int n_head, int hd, int nchunk, int prefill_T, int64_t rows, void *out16, int fmt, int *flag,
+                     hipStream_t stream);
 // qkv [B * T, 3C] -> cache rows 0 .. T - 1 of every stream | rows t0 .. t0 + n - 1 of one stream's slabs -> fp32
 int lm_kv_scatter(const float *qkv, void *kc, void *vc, int kvfmt, int64_t rows, int T, int n_head, int hd, int max_len,
                   int *err_flag, hipStream_t stream);
@@ -208,5 +215,12 @@ int lm_kv_read(const void *kc, const void *vc, int kvfmt, int t0, int n, int n_h
                float *v_out, hipStream_t stream);
 // lm_engine.hip.  y = nn.LayerNorm(x) over `rows` rows of K floats
 int lm_layernorm_rows(const float *x, const float *g, const float *beta, float *y, int64_t rows, int K, hipStream_t stream);
+// ... the same arithmetic, each value rounded to fmt (OMNITOK_LM_W_BF16 | _FP16) into y16; an fp16 +-inf raises LM_FLAG_PF16_RANGE in *flag
+int lm_layernorm_rows16(const float *x, const float *g, const float *beta, void *y16, int fmt, int64_t rows, int K, int *flag,
+                        hipStream_t stream);
+// lm_gemm16.hip.  y = act(a16 [M, K] . w16 [N, K]^T + bias) (+ residual) on the 16-bit MFMA into y32 or (rounded to fmt) y16: the
+// contract of omnitok_lm_gemm16, its argument checks included
+int lm_gemm16(const void *a16, const void *w16, int fmt, const float *bias, const float *residual, float *y32, void *y16, int64_t M,
+              int N, int K, int act, int *flag, hipStream_t stream);
 
 }  // namespace omnitok

@@ -35,7 +35,8 @@ __global__ __launch_bounds__(256) void lm_embed_kernel(const int64_t *__restrict
     }
 }
 
-// ---- batched prefill of a conditioning prefix (the same arithmetic as T decode steps, as GEMMs) ------
+// ---- batched prefill of a conditioning prefix (the same arithmetic as T decode steps, as GEMMs; with OMNITOK_LM_PF_W16 the GEMMs run
+// on the 16-bit MFMA over activations rounded to the weight format instead: lm_gemm16.hip) ------
 // positions t < Te take the explicit embeddings emb[b, t] (prepended, gpt.py:214-216), the rest tok_emb[idx[b, t - Te]]
 __global__ __launch_bounds__(256) void lm_embed_seq_kernel(const int64_t *__restrict__ idx, const float *__restrict__ tok,
                                                            const float *__restrict__ pe, const float *__restrict__ emb,
@@ -59,10 +60,13 @@ __global__ __launch_bounds__(256) void lm_embed_seq_kernel(const int64_t *__rest
     }
 }
 
-// nn.LayerNorm over rows of any width (two-pass, eps 1e-5): one wave per row
+// nn.LayerNorm over rows of any width (two-pass, eps 1e-5): one wave per row.  OT = float: y fp32 | lm_bf16 / lm_fp16: the same
+// values rounded once (lm_round16) into packed 16-bit rows, the GEMM operand of a PF_W16 prefill; an fp16 result of +-inf raises
+// LM_FLAG_PF16_RANGE in *flag
+template <typename OT>
 __global__ __launch_bounds__(256) void lm_layernorm_rows_kernel(const float *__restrict__ x, const float *__restrict__ g,
-                                                                const float *__restrict__ beta, float *__restrict__ y,
-                                                                int64_t rows, int K) {
+                                                                const float *__restrict__ beta, OT *__restrict__ y,
+                                                                int64_t rows, int K, int *__restrict__ flag) {
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
@@ -85,7 +89,13 @@ __global__ __launch_bounds__(256) void lm_layernorm_rows_kernel(const float *__r
         const f32x4 g4 = *reinterpret_cast<const f32x4 *>(g + k), b4 = *reinterpret_cast<const f32x4 *>(beta + k);
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = (v[e] - mean) * rstd * g4[e] + b4[e];
-        *reinterpret_cast<f32x4 *>(y + row * K + k) = v;
+        if constexpr (__is_same(OT, float)) {
+            *reinterpret_cast<f32x4 *>(y + row * K + k) = v;
+        } else {
+            bool inf = false;
+            *reinterpret_cast<u32x2 *>(y + row * K + k) = LmKV<OT>::store4(v, inf);
+            if (inf && flag) atomicOr(flag, LM_FLAG_PF16_RANGE);
+        }
     }
 }
 
@@ -151,8 +161,20 @@ __global__ __launch_bounds__(256) void lm_round_w16_kernel(float *__restrict__ w
 }
 
 int lm_layernorm_rows(const float *x, const float *g, const float *beta, float *y, int64_t rows, int K, hipStream_t stream) {
-    hipLaunchKernelGGL(lm_layernorm_rows_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, x, g, beta, y, rows, K);
+    hipLaunchKernelGGL(lm_layernorm_rows_kernel<float>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, x, g, beta, y, rows, K,
+                       static_cast<int *>(nullptr));
     OT_LAUNCH_CHECK("lm_layernorm_rows");
+    return OMNITOK_OK;
+}
+
+int lm_layernorm_rows16(const float *x, const float *g, const float *beta, void *y16, int fmt, int64_t rows, int K, int *flag,
+                        hipStream_t stream) {
+    const dim3 grid((unsigned)((rows + 3) / 4));
+    if (fmt == OMNITOK_LM_W_BF16)
+        hipLaunchKernelGGL(lm_layernorm_rows_kernel<lm_bf16>, grid, dim3(256), 0, stream, x, g, beta, static_cast<lm_bf16 *>(y16), rows, K, flag);
+    else
+        hipLaunchKernelGGL(lm_layernorm_rows_kernel<lm_fp16>, grid, dim3(256), 0, stream, x, g, beta, static_cast<lm_fp16 *>(y16), rows, K, flag);
+    OT_LAUNCH_CHECK("lm_layernorm_rows16");
     return OMNITOK_OK;
 }
 
@@ -179,6 +201,7 @@ struct omnitok_lm {
     std::vector<LmLayer> layers;
     bool finalized = false;
     int weight_format = OMNITOK_LM_W_FP32;  // of the matrices a decode step streams (omnitok_lm_set_weight_format)
+    int prefill_format = OMNITOK_LM_PF_FP32;  // how the batched prefill runs its GEMMs (omnitok_lm_set_prefill_format)
     LmMat head = {nullptr, nullptr, OMNITOK_LM_W_FP32};  // head.weight
     // cache + workspaces
     void *kv = nullptr;                       // [n_layer][2][max_batch][n_head][max_len][head_dim] elements of cache_format
@@ -307,6 +330,18 @@ extern "C" int omnitok_lm_set_weight_format(omnitok_lm *lm, int fmt) {
 extern "C" int omnitok_lm_weight_format(omnitok_lm *lm) {
     OT_CHECK_ARG(lm, "lm_weight_format: null engine");
     return lm->weight_format;
+}
+
+extern "C" int omnitok_lm_set_prefill_format(omnitok_lm *lm, int fmt) {
+    OT_CHECK_ARG(lm, "lm_set_prefill_format: null engine");
+    OT_CHECK_ARG(fmt == OMNITOK_LM_PF_FP32 || fmt == OMNITOK_LM_PF_W16, "lm_set_prefill_format: unknown format %d", fmt);
+    lm->prefill_format = fmt;  // read at the next prefill: the weights, `finalized` and the cache are left alone
+    return OMNITOK_OK;
+}
+
+extern "C" int omnitok_lm_prefill_format(omnitok_lm *lm) {
+    OT_CHECK_ARG(lm, "lm_prefill_format: null engine");
+    return lm->prefill_format;
 }
 
 extern "C" int omnitok_lm_set_cache_format(omnitok_lm *lm, int fmt) {
@@ -513,7 +548,7 @@ extern "C" int omnitok_lm_overflowed(omnitok_lm *lm, omnitok_stream_t stream_) {
     OT_HIP(hipStreamSynchronize(stream));
     if (h)
         if (int rc = device_fill_u32(lm->err_flag, 0u, 1, stream)) return rc;
-    return h & (LM_FLAG_PAST_CACHE | LM_FLAG_FP16_RANGE);
+    return h & (LM_FLAG_PAST_CACHE | LM_FLAG_FP16_RANGE | LM_FLAG_PF16_RANGE);
 }
 
 extern "C" int omnitok_lm_cache_read(omnitok_lm *lm, int layer, int b, int t0, int n, float *k_out, float *v_out,
@@ -635,6 +670,12 @@ static int lm_prefill_layers(omnitok_lm *lm, const int64_t *idx, int T_tok, cons
         set_error("lm_prefill: engine not finalised (load the weights first)");
         return OMNITOK_ERR_STATE;
     }
+    if (lm->prefill_format == OMNITOK_LM_PF_W16 && (lm->weight_format == OMNITOK_LM_W_FP32 || !lm->head.w16)) {
+        set_error("lm_prefill: prefill format OMNITOK_LM_PF_W16 (omnitok_lm_set_prefill_format) needs the packed 16-bit weight images: "
+                  "set omnitok_lm_set_weight_format to OMNITOK_LM_W_BF16 or OMNITOK_LM_W_FP16 (it is OMNITOK_LM_W_FP32), or the prefill "
+                  "format back to OMNITOK_LM_PF_FP32");
+        return OMNITOK_ERR_STATE;
+    }
     if (!lm->kv || B > lm->max_batch || T > lm->max_len) {
         set_error("lm_prefill: cache not allocated for %d streams x %d tokens (omnitok_lm_alloc_cache)", B, T);
         return OMNITOK_ERR_STATE;
@@ -654,6 +695,31 @@ static int lm_prefill_layers(omnitok_lm *lm, const int64_t *idx, int T_tok, cons
     hipLaunchKernelGGL(lm_embed_seq_kernel, dim3((unsigned)M), dim3(256), 0, stream, idx, LW(lm, "tok_emb.weight"),
                        LW(lm, "pos_emb"), emb, T_emb, pos_extra, x, T, C, V);
     OT_LAUNCH_CHECK("lm_embed_seq");
+    if (lm->prefill_format == OMNITOK_LM_PF_W16) {
+        // The same passes with the five GEMMs on the 16-bit MFMA over the packed weight images.  Their A operands are the fp32 values
+        // of the loop below rounded once to the weight format: LayerNorm rows and the attention merge by their own kernels' 16-bit
+        // form, FC1's GELU output in its GEMM's epilogue (no [M, 4C] fp32 tensor, no GELU pass).  xn / att / hid hold packed 16-bit
+        // rows in the first half of their regions; x, qkv, the cache scatter and the attention partials stay fp32.
+        const int fmt = lm->weight_format;
+        int *fl = lm->err_flag;
+        for (int i = 0; i < c.n_layer; ++i) {
+            const LmLayer &L = lm->layers[i];
+            void *kc = lm_kv_slab(lm, 2 * i, per_layer), *vc = lm_kv_slab(lm, 2 * i + 1, per_layer);
+            if (int rc = lm_layernorm_rows16(x, L.ln1w, L.ln1b, xn, fmt, M, C, fl, stream)) return rc;
+            if (int rc = lm_gemm16(xn, L.wqkv.w16, fmt, L.bqkv, nullptr, qkv, nullptr, M, 3 * C, C, 0, fl, stream)) return rc;
+            if (int rc = lm_kv_scatter(qkv, kc, vc, lm->cache_format, M, T, c.n_head, hd, lm->max_len, lm->err_flag, stream)) return rc;
+            if (int rc = lm_attn_partials(qkv, kc, vc, lm->cache_format, nullptr, B, c.n_head, hd, lm->max_len, part, stream, T)) return rc;
+            lm_attn_merge16(part, c.n_head, hd, nchunk, T, M, att, fmt, fl, stream);
+            OT_LAUNCH_CHECK("lm_attn_merge16");
+            if (int rc = lm_gemm16(att, L.wproj.w16, fmt, L.bproj, x, x, nullptr, M, C, C, 0, fl, stream)) return rc;
+            if (int rc = lm_layernorm_rows16(x, L.ln2w, L.ln2b, xn, fmt, M, C, fl, stream)) return rc;
+            if (int rc = lm_gemm16(xn, L.w1.w16, fmt, L.b1, nullptr, nullptr, hid, M, 4 * C, C, 1, fl, stream)) return rc;
+            if (int rc = lm_gemm16(hid, L.w2.w16, fmt, L.b2, x, x, nullptr, M, C, 4 * C, 0, fl, stream)) return rc;
+        }
+        *x_out = x;
+        *xn_out = xn;
+        return OMNITOK_OK;
+    }
     for (int i = 0; i < c.n_layer; ++i) {
         const LmLayer &L = lm->layers[i];
         void *kc = lm_kv_slab(lm, 2 * i, per_layer), *vc = lm_kv_slab(lm, 2 * i + 1, per_layer);
@@ -678,6 +744,11 @@ static int lm_prefill_layers(omnitok_lm *lm, const int64_t *idx, int T_tok, cons
 // logits [rows, V] = head(ln_f(x [rows, C])); xn: scratch [rows, C]
 static int lm_head_rows(omnitok_lm *lm, const float *x, float *xn, int64_t rows, float *logits, hipStream_t stream) {
     const int C = lm->cfg.n_embd, V = lm->cfg.vocab_size;
+    if (lm->prefill_format == OMNITOK_LM_PF_W16) {  // (xn: packed 16-bit rows in the front half of the same scratch)
+        if (int rc = lm_layernorm_rows16(x, LW(lm, "ln_f.weight"), LW(lm, "ln_f.bias"), xn, lm->head.fmt, rows, C, lm->err_flag, stream))
+            return rc;
+        return lm_gemm16(xn, lm->head.w16, lm->head.fmt, nullptr, nullptr, logits, nullptr, rows, V, C, 0, lm->err_flag, stream);
+    }
     if (int rc = lm_layernorm_rows(x, LW(lm, "ln_f.weight"), LW(lm, "ln_f.bias"), xn, rows, C, stream)) return rc;
     return lm_linear(xn, LW(lm, "head.weight"), nullptr, nullptr, logits, rows, V, C, stream);
 }
@@ -745,6 +816,16 @@ extern "C" int omnitok_lm_prefill_loss(omnitok_lm *lm, const int64_t *idx, int T
     hipLaunchKernelGGL(lm_set_len_kernel, dim3(1), dim3(128), 0, stream, pos, cache_len, B, T);
     OT_LAUNCH_CHECK("lm_set_len");
     return OMNITOK_OK;
+}
+
+extern "C" int omnitok_lm_layernorm16(const float *x, const float *gamma, const float *beta, void *y16, int fmt, int64_t rows, int K,
+                                      int *flag, omnitok_stream_t stream) {
+    OT_CHECK_ARG(fmt == OMNITOK_LM_W_BF16 || fmt == OMNITOK_LM_W_FP16, "lm_layernorm16: fmt %d (OMNITOK_LM_W_BF16 | OMNITOK_LM_W_FP16)", fmt);
+    OT_CHECK_ARG(x && gamma && beta && y16, "lm_layernorm16: null pointer");
+    OT_CHECK_ARG(aligned16(x) && aligned16(gamma) && aligned16(beta) && aligned16(y16), "lm_layernorm16: unaligned pointer (16 bytes)");
+    OT_CHECK_ARG(rows >= 1 && rows <= 0x7fffffffLL && K >= 32 && K % 32 == 0, "lm_layernorm16: rows %lld (1 .. 2^31 - 1), K %d (K %% 32 == 0)",
+                 (long long)rows, K);
+    return lm_layernorm_rows16(x, gamma, beta, y16, fmt, rows, K, flag, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int64_t omnitok_lm_loss_workspace_bytes(omnitok_lm *lm) {

@@ -29,6 +29,7 @@ from ._lib import OmnitokLmConfig, check
 
 WEIGHT_FORMATS = {"fp32": 0, "bf16": 1, "fp16": 2}  # OMNITOK_LM_W_* of include/omnitok_lm.h
 KV_FORMATS = {"fp32": 0, "bf16": 1, "fp16": 2}      # OMNITOK_LM_KV_*
+PREFILL_FORMATS = {"fp32": 0, "w16": 1}             # OMNITOK_LM_PF_*
 
 
 class _Holder(nn.Module):
@@ -102,6 +103,7 @@ class GPT(nn.Module):
         self._graphs = {}
         self._weight_format = "fp32"
         self._cache_format = "fp32"
+        self._prefill_format = "fp32"
         self._max_streams = 16
         self._generation = 0
 
@@ -179,6 +181,25 @@ class GPT(nn.Module):
         return self
 
     @property
+    def prefill_format(self) -> str:
+        return self._prefill_format
+
+    def set_prefill_format(self, fmt: str):
+        """How the batched prefill -- forward, token_losses, prefill and the conditioning prefix of the sampling loops -- runs its
+        GEMMs (include/omnitok_lm.h, omnitok_lm_set_prefill_format): "fp32" (default: the fp32-input MFMA, unchanged) or "w16": the
+        bf16 / fp16 MFMA over the packed weight images of a 16-bit weight format, with the activations entering each GEMM rounded
+        once to that format (fp32 accumulation, fp32 residual stream, LayerNorm statistics, attention, logits and cross-entropy).
+        "w16" needs set_weight_format("bf16" | "fp16"): with fp32 weights the prefill raises, it never falls back.  The prefill is
+        then no longer the arithmetic of the decode steps (they keep fp32 activations).  The weights, the cache, the captured graphs
+        and state_dict() are left alone.  With fp16, check_overflow() raises if an activation left the fp16 range."""
+        if fmt not in PREFILL_FORMATS:
+            raise ValueError(f"prefill format {fmt!r}: expected one of {sorted(PREFILL_FORMATS)}")
+        self._prefill_format = fmt
+        if self._engine is not None:
+            check(_lib.load().omnitok_lm_set_prefill_format(self._engine, PREFILL_FORMATS[fmt]), "lm_set_prefill_format")
+        return self
+
+    @property
     def max_streams(self) -> int:
         return self._max_streams
 
@@ -243,6 +264,7 @@ class GPT(nn.Module):
             check(lib.omnitok_lm_set_cache_format(self._engine, KV_FORMATS[self._cache_format]), "lm_set_cache_format")
             check(lib.omnitok_lm_set_max_streams(self._engine, self._max_streams), "lm_set_max_streams")
         check(lib.omnitok_lm_set_weight_format(self._engine, WEIGHT_FORMATS[self._weight_format]), "lm_set_weight_format")
+        check(lib.omnitok_lm_set_prefill_format(self._engine, PREFILL_FORMATS[self._prefill_format]), "lm_set_prefill_format")
         for name, t in self.state_dict(keep_vars=True).items():
             if name == "vtokens_pos_emb":  # gathered per call on the host side (cbox / tbox), not an engine weight
                 continue
@@ -287,8 +309,8 @@ class GPT(nn.Module):
 
     def check_overflow(self):
         """Raises if a decode step since the last check ran past the allocated K/V cache, or stored a K/V value outside the
-        fp16 range into an fp16 cache (the logits are invalid either way); one host synchronisation -- the sampling loops
-        call it once at their end."""
+        fp16 range into an fp16 cache, or a "w16" prefill on fp16 weights rounded an activation to inf (the logits are invalid in
+        each case); one host synchronisation -- the sampling loops call it once at their end."""
         if not self._engine:
             return
         rc = _lib.load().omnitok_lm_overflowed(self._engine, torch.cuda.current_stream().cuda_stream)
@@ -299,6 +321,9 @@ class GPT(nn.Module):
         if rc & 2:
             raise RuntimeError(f"a K/V value left the range of the {self._cache_format} cache format and was stored as inf: "
                                "use set_cache_format('bf16') (fp32's range) for this model")
+        if rc & 4:
+            raise RuntimeError("an activation of a 'w16' prefill left the fp16 range and entered its GEMM as inf: use "
+                               "set_weight_format('bf16') (fp32's range) or set_prefill_format('fp32') for this model")
 
     @staticmethod
     def _fp(t):
@@ -326,7 +351,7 @@ class GPT(nn.Module):
     def prefill(self, idx, want_logits=False, emb=None, pos_extra=None):
         """Feeds emb [B, Te, C] (optional, prepended) then idx [B, T] into EMPTY streams in one batched pass
         (GEMMs + causal flash attention, include/omnitok_lm.h omnitok_lm_prefill_ex): same arithmetic as Te + T
-        steps.  pos_extra [B, Te + T, C] (optional): the vtokens_pos term.  Returns the teacher-forced logits
+        steps (with the default prefill format; set_prefill_format("w16") rounds the GEMM inputs).  pos_extra [B, Te + T, C] (optional): the vtokens_pos term.  Returns the teacher-forced logits
         [B, Te + T, vocab] if want_logits."""
         B, T = idx.shape
         Te = 0 if emb is None else emb.shape[1]

@@ -9,7 +9,10 @@ KV-cached step on the host, bounded sample).
 --streams-session OUT.json: the many-stream record instead (GPT.set_max_streams; profiles/lm_streams_bench.json): the bare decode step
 (graph replay) of B in --session-batches streams at --session-ctx cached tokens, fp32 weights + fp32 cache first, then bf16 + bf16,
 and of 8 and 16 streams once more with "lm_streams_min" 1 (the many-stream kernel below its default threshold).  The cache lengths
-are set on the device, nothing is prefilled: a step's time depends on how many rows it reads, not on what they hold."""
+are set on the device, nothing is prefilled: a step's time depends on how many rows it reads, not on what they hold.
+--prefill-session OUT.json: the batched-prefill record (GPT.set_prefill_format; profiles/lm_prefill16_bench.json): per weight format
+bf16 then fp16, GPT.forward and GPT.token_losses at (B, T) in --prefill-shapes with the fp32 prefill first and the "w16" prefill after
+it, and the bare omnitok_lm_gemm16 at the model's five GEMM shapes with M = the largest B * T."""
 import argparse
 import json
 import os
@@ -25,6 +28,7 @@ from omnitokenizer_amd.synth import synth_gpt_state  # noqa: E402
 
 PEAK_HBM_GBS = 8000.0
 PEAK_F32_MFMA_TFLOPS = 157.3
+PEAK_16BIT_MFMA_TFLOPS = 2500.0
 
 
 def streams_session(a, m, dims):
@@ -120,6 +124,104 @@ def streams_session(a, m, dims):
             "cells": cells, "vs_steps_of_16": verdict}
 
 
+def prefill_session(a, m, dims):
+    """One session over (weight format, prefill format, shape): see the module docstring.  Returns the record."""
+    import ctypes
+    from omnitokenizer_amd import _lib
+    V, BS, L, H, C = dims
+    lib = _lib.load()
+    shapes = [tuple(int(v) for v in s.split("x")) for s in a.prefill_shapes.split(",")]
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+    def timed(fn, reps):
+        """median ms of `reps` calls after one dropped call, and the (min, max)"""
+        fn()
+        torch.cuda.synchronize()
+        out = []
+        for _ in range(reps):
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            out.append(e0.elapsed_time(e1))
+        out.sort()
+        return out[len(out) // 2], [round(out[0], 3), round(out[-1], 3)]
+
+    cells, gemms = [], []
+    gen = torch.Generator().manual_seed(3)
+    for fmt in ("bf16", "fp16"):
+        m.set_weight_format(fmt)
+        for B, T in shapes:
+            M = B * T
+            flop = 2.0 * M * (12.0 * C * C * L + V * C)
+            idx = torch.randint(0, V, (B, T), generator=gen).cuda()
+            tg = torch.randint(0, V, (B, T), generator=gen).cuda()
+            for pf in ("fp32", "w16"):    # the fp32 arm first
+                m.set_prefill_format(pf)
+                peak = PEAK_F32_MFMA_TFLOPS if pf == "fp32" else PEAK_16BIT_MFMA_TFLOPS
+                cell = {"weights": fmt, "prefill": pf, "B": B, "T": T, "gemm_flop": flop}
+                for name, fn in (("forward", lambda: m(idx)), ("token_losses", lambda: m.token_losses(idx, tg))):
+                    ms, spread = timed(fn, a.prefill_reps)
+                    cell[name + "_ms"] = round(ms, 3)
+                    cell[name + "_ms_min_max"] = spread
+                    cell[name + "_tflops"] = round(flop / (ms * 1e-3) / 1e12, 1)
+                    cell[name + "_frac_of_peak"] = round(flop / (ms * 1e-3) / 1e12 / peak, 4)
+                cell["peak_tflops"] = peak
+                m.check_overflow()
+                cells.append(cell)
+                print(json.dumps(cell), flush=True)
+            del idx, tg
+        # the bare GEMM at the model's shapes, M = the largest B * T: operands uniform in [-1, 1) / 0.02 x that, not zeros
+        M = max(B * T for B, T in shapes)
+        dt = torch.bfloat16 if fmt == "bf16" else torch.float16
+        stream = torch.cuda.current_stream().cuda_stream
+        total = 0.0
+        for what, N, K, y16, per_model in (("qkv", 3 * C, C, False, L), ("proj", C, C, False, L), ("fc1 (GELU, 16-bit out)", 4 * C, C, True, L),
+                                            ("fc2", C, 4 * C, False, L), ("head", V, C, False, 1)):
+            x = (torch.rand(M, K, device="cuda") * 2 - 1).to(dt)
+            w = ((torch.rand(N, K, device="cuda") * 2 - 1) * 0.02).to(dt)
+            bias = torch.zeros(N, device="cuda")
+            y = torch.empty(M, N, device="cuda", dtype=dt if y16 else torch.float32)
+            P = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+
+            def call():
+                for _ in range(10):
+                    _lib.check(lib.omnitok_lm_gemm16(P(x), P(w), og.WEIGHT_FORMATS[fmt], P(bias), None, None if y16 else P(y),
+                                                     P(y) if y16 else None, M, N, K, int(y16), None, stream), "lm_gemm16")
+            ms, spread = timed(call, a.prefill_reps)
+            ms /= 10
+            tf = 2.0 * M * N * K / (ms * 1e-3) / 1e12
+            total += per_model * ms
+            gemms.append({"weights": fmt, "gemm": what, "M": M, "N": N, "K": K, "ms": round(ms, 4),
+                          "ms_min_max": [round(v / 10, 4) for v in spread], "tflops": round(tf, 1),
+                          "frac_of_16bit_peak": round(tf / PEAK_16BIT_MFMA_TFLOPS, 4), "calls_per_forward": per_model})
+            print(json.dumps(gemms[-1]), flush=True)
+            del x, w, y
+        big = next(c for c in cells if c["weights"] == fmt and c["prefill"] == "w16" and c["B"] * c["T"] == M)
+        gemms.append({"weights": fmt, "M": M, "gemm_ms_per_forward": round(total, 3), "forward_ms": big["forward_ms"],
+                      "non_gemm_ms_per_forward": round(big["forward_ms"] - total, 3)})
+        print(json.dumps(gemms[-1]), flush=True)
+    m.set_prefill_format("fp32")
+    verdict = []
+    for fmt in ("bf16", "fp16"):
+        for B, T in shapes:
+            f32, w16 = (next(c for c in cells if (c["weights"], c["prefill"], c["B"], c["T"]) == (fmt, pf, B, T)) for pf in ("fp32", "w16"))
+            verdict.append({"weights": fmt, "B": B, "T": T,
+                            "forward_speedup": round(f32["forward_ms"] / w16["forward_ms"], 3),
+                            "token_losses_speedup": round(f32["token_losses_ms"] / w16["token_losses_ms"], 3),
+                            "w16_faster": bool(w16["forward_ms"] < f32["forward_ms"] and w16["token_losses_ms"] < f32["token_losses_ms"])})
+    return {"metric": "LM batched prefill (GPT.forward / GPT.token_losses), fp32 prefill vs the 16-bit MFMA prefill", "unit": "ms per call",
+            "config": {"workload": f"GPT {L}x{C} ({H} heads, head_dim {C // H}), vocab {V}, block {BS}",
+                       "peak_f32_mfma_tflops": PEAK_F32_MFMA_TFLOPS, "peak_16bit_mfma_tflops": PEAK_16BIT_MFMA_TFLOPS,
+                       "protocol": f"one process; per weight format bf16 then fp16, per shape the fp32 prefill first, then w16; device events "
+                                   f"around each call, 1 dropped + {a.prefill_reps} timed calls, median (min, max beside it); bare GEMMs: 10 "
+                                   "back-to-back launches per timed call on uniform random operands",
+                       "tflops": "2 M (12 C^2 L + V C) FLOP of the six GEMM families / WHOLE call time (embedding, LayerNorm, attention, "
+                                 "cross-entropy and every launch boundary included): a rate of the call, not of the GEMM kernels",
+                       "non_gemm_ms_per_forward": "forward_ms of the w16 arm minus the bare GEMM times x their calls per forward"},
+            "cells": cells, "gemm16": gemms, "w16_vs_fp32": verdict}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=1)
@@ -143,6 +245,9 @@ def main():
     ap.add_argument("--streams-session", metavar="OUT.json", help="write the many-stream record (see above) and exit")
     ap.add_argument("--session-batches", default="8,16,32,64,128")
     ap.add_argument("--session-ctx", default="0,4608")
+    ap.add_argument("--prefill-session", metavar="OUT.json", help="write the batched-prefill record (see above) and exit")
+    ap.add_argument("--prefill-shapes", default="1x5120,8x5120", metavar="BxT[,BxT..]")
+    ap.add_argument("--prefill-reps", type=int, default=5)
     a = ap.parse_args()
     V, BS, L, H, C = a.vocab, a.block, a.layers, a.heads, a.embd
     for kv in a.option:
@@ -152,6 +257,13 @@ def main():
     m = og.GPT(argparse.Namespace(), V, BS, n_layer=L, n_head=H, n_embd=C)
     m.load_state_dict(sd, strict=True)
     m = m.cuda().eval().set_weight_format(a.weights).set_cache_format(a.kv).set_max_streams(a.max_streams)
+    if a.prefill_session:
+        rec = prefill_session(a, m, (V, BS, L, H, C))
+        with open(a.prefill_session, "w") as f:
+            json.dump(rec, f, indent=1)
+            f.write("\n")
+        print(json.dumps({"written": a.prefill_session, "w16_vs_fp32": rec["w16_vs_fp32"]}), flush=True)
+        return
     if a.streams_session:
         rec = streams_session(a, m, (V, BS, L, H, C))
         with open(a.streams_session, "w") as f:
