@@ -141,6 +141,30 @@ int omnitok_lm_max_streams(omnitok_lm *lm); /* -1: null engine */
 int omnitok_lm_set_prefill_format(omnitok_lm *lm, int fmt);
 int omnitok_lm_prefill_format(omnitok_lm *lm); /* -1: null engine */
 
+/* How the batched prefill runs its causal attention -- per engine, default OMNITOK_LM_PA_ROWS (nothing below applies then).  The
+ * rows mode is the decode step's attention kernel launched once per query row, head and 256-key chunk over the cache the prefill
+ * has just filled, plus a merge of [B * T, n_head, chunks, 2 + head_dim] partials: every row re-reads its whole K/V prefix and its
+ * dot products are fmaf chains on the VALU.  OMNITOK_LM_PA_TILED runs omnitok_lm_attn_prefill (below) instead: K/V tiles shared by
+ * 128 query rows, both products on the fp32-input MFMA, no partials (that term leaves the prefill workspace).
+ *   The arithmetic contract is kept: fp32 products, fp32 accumulation, expf in fp32, no value rounded that the rows mode does not
+ *     round.  The ORDER of the sums differs (one dot-product chain per score instead of eight partial chains; online softmax over
+ *     32-key tiles instead of 256-key chunks and a merge), so "same arithmetic as T decode steps" holds TO ROUNDING, NOT TO THE BIT,
+ *     under the tiled mode: its results differ from the rows mode's by fp32 rounding (tests/test_gpu_lm_prefill_attn.py holds both
+ *     to a derived bar against fp64).
+ *   Operands: K and V are read from qkv, not from the cache (a prefill fills empty streams: every key of a row is in qkv), so the
+ *     tiled attention does not depend on the cache format.  Under a 16-bit cache the rows mode reads the PAST rows rounded to the
+ *     cache format and the row's own K/V in fp32; the tiled mode reads every row in fp32.  The K/V scatter is unchanged: the cache
+ *     holds what the decode steps after the prefill read, rounded as before.
+ *   Independent of the weight, cache and prefill formats and of max_streams: every combination works.  With OMNITOK_LM_PF_W16 the
+ *     attention output is rounded once to the weight format (an fp16 +-inf raises bit 4 of the flag word), as the merge's was.
+ *   The decode step is unaffected.
+ * omnitok_lm_set_prefill_attention: -1 for a null engine or an unknown mode (a refused mode changes nothing); it touches neither
+ * `finalized`, the weights nor the cache, and applies from the next prefill on. */
+#define OMNITOK_LM_PA_ROWS 0
+#define OMNITOK_LM_PA_TILED 1
+int omnitok_lm_set_prefill_attention(omnitok_lm *lm, int mode);
+int omnitok_lm_prefill_attention(omnitok_lm *lm); /* -1: null engine */
+
 /* K/V cache [n_layer][2][max_batch][n_head][max_len][head_dim] in the engine's cache format + step workspaces;
  * max_batch <= omnitok_lm_max_streams (16 unless raised), otherwise -1 with the limit in force in the message. */
 int omnitok_lm_alloc_cache(omnitok_lm *lm, int max_batch, int max_len);
@@ -185,7 +209,8 @@ int omnitok_lm_overflowed(omnitok_lm *lm, omnitok_stream_t stream);
  * Same arithmetic as T decode steps, executed as [B*T]-row fp32-MFMA GEMMs (omnitok_gemm) + causal
  * flash attention over the cache (with OMNITOK_LM_PF_W16 the GEMMs run on the 16-bit MFMA over
  * rounded activations instead, and "same arithmetic" no longer holds: omnitok_lm_set_prefill_format
- * above).  Fills the K/V cache, sets pos[b] = cache_len[b] = T on the
+ * above; with OMNITOK_LM_PA_TILED the attention runs tiled on the fp32-input MFMA straight from qkv, and
+ * "same arithmetic" holds to rounding, not to the bit: omnitok_lm_set_prefill_attention above).  Fills the K/V cache, sets pos[b] = cache_len[b] = T on the
  * device.  logits_out (optional) [B, T, vocab]: teacher-forced logits of every position.
  * B * T <= 65535; may hipMalloc its (grow-only) workspace. */
 int omnitok_lm_prefill(omnitok_lm *lm, const int64_t *idx, int32_t *pos, int32_t *cache_len, int B,
@@ -296,6 +321,24 @@ int omnitok_lm_attn_decode(const float *qkv, float *kc, float *vc, const int32_t
 int omnitok_lm_attn_decode_kv16(const float *qkv, void *kc16, void *vc16, int fmt, const int32_t *cache_len, int B,
                                 int n_head, int head_dim, int max_len, float *scratch, float *out,
                                 omnitok_stream_t stream);
+/* Causal attention of a batched prefill (the OMNITOK_LM_PA_TILED mode).  qkv [B*T, 3C] fp32 (query | key | value), C = n_head * head_dim,
+ * head_dim 64, 96 or 128.  Row b*T + t attends to rows b*T .. b*T + t of its own stream.
+ * Exactly one of out32 [B*T, C] fp32 / out16 [B*T, C] packed (fmt = OMNITOK_LM_W_BF16 | _FP16, the value rounded
+ * once by lm_round16; an fp16 result of +-inf ORs 4 into *flag, which may be NULL).
+ * Arithmetic: score = (q . k) * (1.0f / sqrtf(head_dim)), the dot product ONE fmaf chain from 0 on v_mfma_f32_32x32x2_f32 (dims in the
+ * fixed order 0 4 1 5 2 6 3 7 | 8 12 ...), the scale applied to the finished dot; keys after the query's position are -inf before the
+ * softmax; online softmax over 32-key tiles anchored at key 0 of the stream, ascending, expf in fp32; P . V on the same MFMA with
+ * fp32 P (per tile the keys are added in the fixed order 0 4 1 5 2 6 3 7 | 8 12 ...); out = O / l, one division per element.  No
+ * atomics, no split over keys across workgroups, no partials: needs no scratch.
+ * Determinism: row (b, t) depends only on t and on the qkv rows of its own stream up to the end of its diagonal 32-key tile (rows
+ * 0 .. min(32 (t / 32) + 31, T - 1)) -- not on B, T, the stream's slot or other streams' contents (NaN / Inf included) -- and two
+ * calls give equal values (a masked key adds 0 * v, which may turn a -0 sum into +0: equal as numbers, torch.equal).
+ * One limit, stated and not fixed: a masked key's V row enters the MFMA with weight 0, so a NON-FINITE V in a later row of the same
+ * diagonal tile of the same stream turns the earlier rows of that tile into NaN, where the rows kernel skips it.
+ * -1 before any HIP call for null or non-16-byte-aligned pointers, B < 1, T < 1, B * T > 65535, n_head outside 1 .. 1024, an
+ * unsupported head_dim, both or neither output, or an unknown fmt with out16. */
+int omnitok_lm_attn_prefill(const float *qkv, int B, int T, int n_head, int head_dim, float *out32, void *out16, int fmt,
+                            int *flag, omnitok_stream_t stream);
 
 #ifdef __cplusplus
 }

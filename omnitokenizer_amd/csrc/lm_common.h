@@ -17,6 +17,8 @@
 //   lm_gemm16.hip     lm_gemm16_kernel (the 16-bit MFMA GEMM of a PF_W16 prefill, omnitok_lm_set_prefill_format), omnitok_lm_gemm16
 //   lm_attn.hip       lm_attn_decode_kernel (flash-decode over the fp32 / bf16 / fp16 K/V cache, chunk partials), lm_attn_merge_kernel
 //                     (fp32 or, for a PF_W16 prefill, 16-bit output), lm_kv_scatter_kernel, lm_kv_read_kernel, omnitok_lm_attn_decode[_kv16]
+//   lm_attn_prefill.hip  lm_attn_prefill_kernel (tiled causal attention of the prefill on the fp32-input MFMA, K/V tiles shared by 128
+//                     query rows; omnitok_lm_set_prefill_attention), omnitok_lm_attn_prefill
 //   lm_engine.hip     struct omnitok_lm and its exported functions (create .. finalize, alloc_cache, step, prefill, prefill_loss) and the
 //                     small kernels: embed, embed_seq, layernorm_rows (fp32 or 16-bit output, omnitok_lm_layernorm16), gelu, set_len,
 //                     advance, concat3, round_w16
@@ -213,6 +215,10 @@ int lm_kv_scatter(const float *qkv, void *kc, void *vc, int kvfmt, int64_t rows,
                   int *err_flag, hipStream_t stream);
 int lm_kv_read(const void *kc, const void *vc, int kvfmt, int t0, int n, int n_head, int hd, int max_len, float *k_out,
                float *v_out, hipStream_t stream);
+// lm_attn_prefill.hip.  Causal attention of B streams x T rows straight from qkv [B * T, 3C] into out32 [B * T, C] or (rounded to fmt) out16:
+// the contract of omnitok_lm_attn_prefill, its argument checks included
+int lm_attn_prefill(const float *qkv, int B, int T, int n_head, int head_dim, float *out32, void *out16, int fmt, int *flag,
+                    hipStream_t stream);
 // lm_engine.hip.  y = nn.LayerNorm(x) over `rows` rows of K floats
 int lm_layernorm_rows(const float *x, const float *g, const float *beta, float *y, int64_t rows, int K, hipStream_t stream);
 // ... the same arithmetic, each value rounded to fmt (OMNITOK_LM_W_BF16 | _FP16) into y16; an fp16 +-inf raises LM_FLAG_PF16_RANGE in *flag

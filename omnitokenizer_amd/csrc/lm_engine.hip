@@ -36,7 +36,9 @@ __global__ __launch_bounds__(256) void lm_embed_kernel(const int64_t *__restrict
 }
 
 // ---- batched prefill of a conditioning prefix (the same arithmetic as T decode steps, as GEMMs; with OMNITOK_LM_PF_W16 the GEMMs run
-// on the 16-bit MFMA over activations rounded to the weight format instead: lm_gemm16.hip) ------
+// on the 16-bit MFMA over activations rounded to the weight format instead: lm_gemm16.hip; with OMNITOK_LM_PA_TILED the attention runs
+// tiled on the fp32-input MFMA from qkv, lm_attn_prefill.hip, and "same arithmetic as T decode steps" holds to rounding, not to the
+// bit) ------
 // positions t < Te take the explicit embeddings emb[b, t] (prepended, gpt.py:214-216), the rest tok_emb[idx[b, t - Te]]
 __global__ __launch_bounds__(256) void lm_embed_seq_kernel(const int64_t *__restrict__ idx, const float *__restrict__ tok,
                                                            const float *__restrict__ pe, const float *__restrict__ emb,
@@ -202,6 +204,7 @@ struct omnitok_lm {
     bool finalized = false;
     int weight_format = OMNITOK_LM_W_FP32;  // of the matrices a decode step streams (omnitok_lm_set_weight_format)
     int prefill_format = OMNITOK_LM_PF_FP32;  // how the batched prefill runs its GEMMs (omnitok_lm_set_prefill_format)
+    int prefill_attention = OMNITOK_LM_PA_ROWS;  // how the batched prefill runs its attention (omnitok_lm_set_prefill_attention)
     LmMat head = {nullptr, nullptr, OMNITOK_LM_W_FP32};  // head.weight
     // cache + workspaces
     void *kv = nullptr;                       // [n_layer][2][max_batch][n_head][max_len][head_dim] elements of cache_format
@@ -342,6 +345,18 @@ extern "C" int omnitok_lm_set_prefill_format(omnitok_lm *lm, int fmt) {
 extern "C" int omnitok_lm_prefill_format(omnitok_lm *lm) {
     OT_CHECK_ARG(lm, "lm_prefill_format: null engine");
     return lm->prefill_format;
+}
+
+extern "C" int omnitok_lm_set_prefill_attention(omnitok_lm *lm, int mode) {
+    OT_CHECK_ARG(lm, "lm_set_prefill_attention: null engine");
+    OT_CHECK_ARG(mode == OMNITOK_LM_PA_ROWS || mode == OMNITOK_LM_PA_TILED, "lm_set_prefill_attention: unknown mode %d", mode);
+    lm->prefill_attention = mode;  // read at the next prefill: the weights, `finalized` and the cache are left alone
+    return OMNITOK_OK;
+}
+
+extern "C" int omnitok_lm_prefill_attention(omnitok_lm *lm) {
+    OT_CHECK_ARG(lm, "lm_prefill_attention: null engine");
+    return lm->prefill_attention;
 }
 
 extern "C" int omnitok_lm_set_cache_format(omnitok_lm *lm, int fmt) {
@@ -686,8 +701,13 @@ static int lm_prefill_layers(omnitok_lm *lm, const int64_t *idx, int T_tok, cons
     const int64_t M = (int64_t)B * T;
     OT_CHECK_ARG(M <= 65535, "lm_prefill: B * T = %lld rows (max 65535)", (long long)M);
     const int nchunk = (T + LM_CHUNK - 1) / LM_CHUNK;
-    // workspace: x | xn | att [M, C], qkv [M, 3C], hid [M, 4C], partials
-    const int64_t need = M * C * 3 + M * 3 * C + M * 4 * C + M * c.n_head * nchunk * (2 + hd);
+    // Attention.  OMNITOK_LM_PA_ROWS: the decode kernel per query row over the cache just scattered, chunk partials, a merge.
+    // OMNITOK_LM_PA_TILED: lm_attn_prefill straight from qkv (K/V tiles shared by 128 query rows on the fp32-input MFMA): no partials,
+    // no dependence on the cache format; "same arithmetic as T decode steps" then holds to rounding, not to the bit.  The scatter
+    // stays in both modes: the decode steps after the prefill read the cache.
+    const bool tiled = lm->prefill_attention == OMNITOK_LM_PA_TILED;
+    // workspace: x | xn | att [M, C], qkv [M, 3C], hid [M, 4C], partials (rows mode)
+    const int64_t need = M * C * 3 + M * 3 * C + M * 4 * C + (tiled ? 0 : M * c.n_head * nchunk * (2 + hd));
     if (int rc = lm_grow(reinterpret_cast<void **>(&lm->pf), &lm->pf_bytes, need * 4)) return rc;
     float *x = lm->pf, *xn = x + M * C, *att = xn + M * C, *qkv = att + M * C, *hid = qkv + M * 3 * C,
           *part = hid + M * 4 * C;
@@ -708,9 +728,13 @@ static int lm_prefill_layers(omnitok_lm *lm, const int64_t *idx, int T_tok, cons
             if (int rc = lm_layernorm_rows16(x, L.ln1w, L.ln1b, xn, fmt, M, C, fl, stream)) return rc;
             if (int rc = lm_gemm16(xn, L.wqkv.w16, fmt, L.bqkv, nullptr, qkv, nullptr, M, 3 * C, C, 0, fl, stream)) return rc;
             if (int rc = lm_kv_scatter(qkv, kc, vc, lm->cache_format, M, T, c.n_head, hd, lm->max_len, lm->err_flag, stream)) return rc;
-            if (int rc = lm_attn_partials(qkv, kc, vc, lm->cache_format, nullptr, B, c.n_head, hd, lm->max_len, part, stream, T)) return rc;
-            lm_attn_merge16(part, c.n_head, hd, nchunk, T, M, att, fmt, fl, stream);
-            OT_LAUNCH_CHECK("lm_attn_merge16");
+            if (tiled) {
+                if (int rc = lm_attn_prefill(qkv, B, T, c.n_head, hd, nullptr, att, fmt, fl, stream)) return rc;
+            } else {
+                if (int rc = lm_attn_partials(qkv, kc, vc, lm->cache_format, nullptr, B, c.n_head, hd, lm->max_len, part, stream, T)) return rc;
+                lm_attn_merge16(part, c.n_head, hd, nchunk, T, M, att, fmt, fl, stream);
+                OT_LAUNCH_CHECK("lm_attn_merge16");
+            }
             if (int rc = lm_gemm16(att, L.wproj.w16, fmt, L.bproj, x, x, nullptr, M, C, C, 0, fl, stream)) return rc;
             if (int rc = lm_layernorm_rows16(x, L.ln2w, L.ln2b, xn, fmt, M, C, fl, stream)) return rc;
             if (int rc = lm_gemm16(xn, L.w1.w16, fmt, L.b1, nullptr, nullptr, hid, M, 4 * C, C, 1, fl, stream)) return rc;
@@ -726,9 +750,13 @@ static int lm_prefill_layers(omnitok_lm *lm, const int64_t *idx, int T_tok, cons
         if (int rc = lm_layernorm_rows(x, L.ln1w, L.ln1b, xn, M, C, stream)) return rc;
         if (int rc = lm_linear(xn, L.wqkv.w32, L.bqkv, nullptr, qkv, M, 3 * C, C, stream)) return rc;
         if (int rc = lm_kv_scatter(qkv, kc, vc, lm->cache_format, M, T, c.n_head, hd, lm->max_len, lm->err_flag, stream)) return rc;
-        if (int rc = lm_attn_partials(qkv, kc, vc, lm->cache_format, nullptr, B, c.n_head, hd, lm->max_len, part, stream, T)) return rc;
-        lm_attn_merge(part, nullptr, c.n_head, hd, nchunk, T, M, att, LM_CHUNK, stream);
-        OT_LAUNCH_CHECK("lm_attn_merge");
+        if (tiled) {
+            if (int rc = lm_attn_prefill(qkv, B, T, c.n_head, hd, att, nullptr, 0, nullptr, stream)) return rc;
+        } else {
+            if (int rc = lm_attn_partials(qkv, kc, vc, lm->cache_format, nullptr, B, c.n_head, hd, lm->max_len, part, stream, T)) return rc;
+            lm_attn_merge(part, nullptr, c.n_head, hd, nchunk, T, M, att, LM_CHUNK, stream);
+            OT_LAUNCH_CHECK("lm_attn_merge");
+        }
         if (int rc = lm_linear(att, L.wproj.w32, L.bproj, x, x, M, C, C, stream)) return rc;
         if (int rc = lm_layernorm_rows(x, L.ln2w, L.ln2b, xn, M, C, stream)) return rc;
         if (int rc = lm_linear(xn, L.w1.w32, L.b1, nullptr, hid, M, 4 * C, C, stream)) return rc;

@@ -30,6 +30,7 @@ from ._lib import OmnitokLmConfig, check
 WEIGHT_FORMATS = {"fp32": 0, "bf16": 1, "fp16": 2}  # OMNITOK_LM_W_* of include/omnitok_lm.h
 KV_FORMATS = {"fp32": 0, "bf16": 1, "fp16": 2}      # OMNITOK_LM_KV_*
 PREFILL_FORMATS = {"fp32": 0, "w16": 1}             # OMNITOK_LM_PF_*
+PREFILL_ATTENTIONS = {"rows": 0, "tiled": 1}        # OMNITOK_LM_PA_*
 
 
 class _Holder(nn.Module):
@@ -104,6 +105,7 @@ class GPT(nn.Module):
         self._weight_format = "fp32"
         self._cache_format = "fp32"
         self._prefill_format = "fp32"
+        self._prefill_attention = "rows"
         self._max_streams = 16
         self._generation = 0
 
@@ -200,6 +202,24 @@ class GPT(nn.Module):
         return self
 
     @property
+    def prefill_attention(self) -> str:
+        return self._prefill_attention
+
+    def set_prefill_attention(self, mode: str):
+        """How the batched prefill -- forward, token_losses, prefill and the conditioning prefix of the sampling loops -- runs its
+        causal attention (include/omnitok_lm.h, omnitok_lm_set_prefill_attention): "rows" (default, unchanged: the decode step's
+        kernel per query row over the cache) or "tiled": K/V tiles shared by 128 query rows on the fp32-input MFMA, read from the
+        prefill's own qkv.  Same fp32 products, accumulation and expf in another order: the prefill then equals the decode steps to
+        fp32 rounding, not to the bit.  Works with every weight, cache and prefill format; the weights, the cache, the captured graphs
+        and state_dict() are left alone."""
+        if mode not in PREFILL_ATTENTIONS:
+            raise ValueError(f"prefill attention {mode!r}: expected one of {sorted(PREFILL_ATTENTIONS)}")
+        self._prefill_attention = mode
+        if self._engine is not None:
+            check(_lib.load().omnitok_lm_set_prefill_attention(self._engine, PREFILL_ATTENTIONS[mode]), "lm_set_prefill_attention")
+        return self
+
+    @property
     def max_streams(self) -> int:
         return self._max_streams
 
@@ -265,6 +285,7 @@ class GPT(nn.Module):
             check(lib.omnitok_lm_set_max_streams(self._engine, self._max_streams), "lm_set_max_streams")
         check(lib.omnitok_lm_set_weight_format(self._engine, WEIGHT_FORMATS[self._weight_format]), "lm_set_weight_format")
         check(lib.omnitok_lm_set_prefill_format(self._engine, PREFILL_FORMATS[self._prefill_format]), "lm_set_prefill_format")
+        check(lib.omnitok_lm_set_prefill_attention(self._engine, PREFILL_ATTENTIONS[self._prefill_attention]), "lm_set_prefill_attention")
         for name, t in self.state_dict(keep_vars=True).items():
             if name == "vtokens_pos_emb":  # gathered per call on the host side (cbox / tbox), not an engine weight
                 continue

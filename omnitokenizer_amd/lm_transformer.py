@@ -115,6 +115,8 @@ class Net2NetTransformer(nn.Module):
         # weight format of the decode step ("fp32" | "bf16" | "fp16", GPT.set_weight_format): an option of this port -- the reference
         # trains the model under Lightning's precision="bf16" / 16 and samples in whatever dtype the checkpoint is cast to
         self.transformer.set_weight_format(_get(args, "lm_weight_format", "fp32"))
+        # attention of the batched prefill ("rows" | "tiled", GPT.set_prefill_attention)
+        self.transformer.set_prefill_attention(_get(args, "lm_prefill_attention", "rows"))
         # streams per engine (GPT.set_max_streams: 16 by default, up to 128; classifier-free guidance takes two per sample)
         self.transformer.set_max_streams(int(_get(args, "lm_max_streams", 16)))
         if ckpt_path is not None:

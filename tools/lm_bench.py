@@ -12,7 +12,9 @@ and of 8 and 16 streams once more with "lm_streams_min" 1 (the many-stream kerne
 are set on the device, nothing is prefilled: a step's time depends on how many rows it reads, not on what they hold.
 --prefill-session OUT.json: the batched-prefill record (GPT.set_prefill_format; profiles/lm_prefill16_bench.json): per weight format
 bf16 then fp16, GPT.forward and GPT.token_losses at (B, T) in --prefill-shapes with the fp32 prefill first and the "w16" prefill after
-it, and the bare omnitok_lm_gemm16 at the model's five GEMM shapes with M = the largest B * T."""
+it, and the bare omnitok_lm_gemm16 at the model's five GEMM shapes with M = the largest B * T.  --prefill-attention rows,tiled adds the
+attention mode (GPT.set_prefill_attention; profiles/lm_prefill_attn_bench.json) as the outermost arm per shape, in the order given (the
+default "rows" alone is the record as it was); --prefill-weights picks the weight formats."""
 import argparse
 import json
 import os
@@ -149,17 +151,20 @@ def prefill_session(a, m, dims):
 
     cells, gemms = [], []
     gen = torch.Generator().manual_seed(3)
-    for fmt in ("bf16", "fp16"):
+    fmts = a.prefill_weights.split(",")
+    modes = a.prefill_attention.split(",")
+    for fmt in fmts:
         m.set_weight_format(fmt)
         for B, T in shapes:
             M = B * T
             flop = 2.0 * M * (12.0 * C * C * L + V * C)
             idx = torch.randint(0, V, (B, T), generator=gen).cuda()
             tg = torch.randint(0, V, (B, T), generator=gen).cuda()
-            for pf in ("fp32", "w16"):    # the fp32 arm first
+            for mode, pf in ((mode, pf) for mode in modes for pf in ("fp32", "w16")):    # the first mode first, in it the fp32 arm first
+                m.set_prefill_attention(mode)
                 m.set_prefill_format(pf)
                 peak = PEAK_F32_MFMA_TFLOPS if pf == "fp32" else PEAK_16BIT_MFMA_TFLOPS
-                cell = {"weights": fmt, "prefill": pf, "B": B, "T": T, "gemm_flop": flop}
+                cell = {"weights": fmt, "prefill": pf, "attention": mode, "B": B, "T": T, "gemm_flop": flop}
                 for name, fn in (("forward", lambda: m(idx)), ("token_losses", lambda: m.token_losses(idx, tg))):
                     ms, spread = timed(fn, a.prefill_reps)
                     cell[name + "_ms"] = round(ms, 3)
@@ -197,23 +202,36 @@ def prefill_session(a, m, dims):
                           "frac_of_16bit_peak": round(tf / PEAK_16BIT_MFMA_TFLOPS, 4), "calls_per_forward": per_model})
             print(json.dumps(gemms[-1]), flush=True)
             del x, w, y
-        big = next(c for c in cells if c["weights"] == fmt and c["prefill"] == "w16" and c["B"] * c["T"] == M)
-        gemms.append({"weights": fmt, "M": M, "gemm_ms_per_forward": round(total, 3), "forward_ms": big["forward_ms"],
-                      "non_gemm_ms_per_forward": round(big["forward_ms"] - total, 3)})
-        print(json.dumps(gemms[-1]), flush=True)
-    m.set_prefill_format("fp32")
-    verdict = []
-    for fmt in ("bf16", "fp16"):
+        for mode in modes:
+            big = next(c for c in cells if c["weights"] == fmt and c["prefill"] == "w16" and c["attention"] == mode and c["B"] * c["T"] == M)
+            gemms.append({"weights": fmt, "M": M, "gemm_ms_per_forward": round(total, 3), "forward_ms": big["forward_ms"],
+                          "non_gemm_ms_per_forward": round(big["forward_ms"] - total, 3), **({"attention": mode} if len(modes) > 1 else {})})
+            print(json.dumps(gemms[-1]), flush=True)
+    m.set_prefill_format("fp32").set_prefill_attention("rows")
+
+    def cell_of(fmt, pf, mode, B, T):
+        return next(c for c in cells if (c["weights"], c["prefill"], c["attention"], c["B"], c["T"]) == (fmt, pf, mode, B, T))
+    verdict, attn_verdict = [], []
+    for fmt in fmts:
         for B, T in shapes:
-            f32, w16 = (next(c for c in cells if (c["weights"], c["prefill"], c["B"], c["T"]) == (fmt, pf, B, T)) for pf in ("fp32", "w16"))
-            verdict.append({"weights": fmt, "B": B, "T": T,
-                            "forward_speedup": round(f32["forward_ms"] / w16["forward_ms"], 3),
-                            "token_losses_speedup": round(f32["token_losses_ms"] / w16["token_losses_ms"], 3),
-                            "w16_faster": bool(w16["forward_ms"] < f32["forward_ms"] and w16["token_losses_ms"] < f32["token_losses_ms"])})
-    return {"metric": "LM batched prefill (GPT.forward / GPT.token_losses), fp32 prefill vs the 16-bit MFMA prefill", "unit": "ms per call",
+            for mode in modes:
+                f32, w16 = (cell_of(fmt, pf, mode, B, T) for pf in ("fp32", "w16"))
+                verdict.append({"weights": fmt, "B": B, "T": T, **({"attention": mode} if len(modes) > 1 else {}),
+                                "forward_speedup": round(f32["forward_ms"] / w16["forward_ms"], 3),
+                                "token_losses_speedup": round(f32["token_losses_ms"] / w16["token_losses_ms"], 3),
+                                "w16_faster": bool(w16["forward_ms"] < f32["forward_ms"] and w16["token_losses_ms"] < f32["token_losses_ms"])})
+            if "rows" in modes and "tiled" in modes:
+                for pf in ("fp32", "w16"):
+                    r, t = cell_of(fmt, pf, "rows", B, T), cell_of(fmt, pf, "tiled", B, T)
+                    attn_verdict.append({"weights": fmt, "prefill": pf, "B": B, "T": T, "rows_forward_ms": r["forward_ms"],
+                                         "tiled_forward_ms": t["forward_ms"], "forward_speedup": round(r["forward_ms"] / t["forward_ms"], 3),
+                                         "token_losses_speedup": round(r["token_losses_ms"] / t["token_losses_ms"], 3)})
+    extra = {"tiled_vs_rows": attn_verdict} if attn_verdict else {}
+    return {**extra, "metric": "LM batched prefill (GPT.forward / GPT.token_losses), fp32 prefill vs the 16-bit MFMA prefill", "unit": "ms per call",
             "config": {"workload": f"GPT {L}x{C} ({H} heads, head_dim {C // H}), vocab {V}, block {BS}",
                        "peak_f32_mfma_tflops": PEAK_F32_MFMA_TFLOPS, "peak_16bit_mfma_tflops": PEAK_16BIT_MFMA_TFLOPS,
-                       "protocol": f"one process; per weight format bf16 then fp16, per shape the fp32 prefill first, then w16; device events "
+                       "protocol": f"one process; per weight format {' then '.join(fmts)}, per shape the attention mode(s) {' then '.join(modes)}, in each "
+                                   f"the fp32 prefill first, then w16; device events "
                                    f"around each call, 1 dropped + {a.prefill_reps} timed calls, median (min, max beside it); bare GEMMs: 10 "
                                    "back-to-back launches per timed call on uniform random operands",
                        "tflops": "2 M (12 C^2 L + V C) FLOP of the six GEMM families / WHOLE call time (embedding, LayerNorm, attention, "
@@ -248,6 +266,8 @@ def main():
     ap.add_argument("--prefill-session", metavar="OUT.json", help="write the batched-prefill record (see above) and exit")
     ap.add_argument("--prefill-shapes", default="1x5120,8x5120", metavar="BxT[,BxT..]")
     ap.add_argument("--prefill-reps", type=int, default=5)
+    ap.add_argument("--prefill-weights", default="bf16,fp16", metavar="FMT[,FMT]")
+    ap.add_argument("--prefill-attention", default="rows", metavar="MODE[,MODE]", help="rows | tiled | rows,tiled (GPT.set_prefill_attention)")
     a = ap.parse_args()
     V, BS, L, H, C = a.vocab, a.block, a.layers, a.heads, a.embd
     for kv in a.option:
