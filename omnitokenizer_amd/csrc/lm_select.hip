@@ -33,8 +33,12 @@ struct SelParams {
     int *err_flag;      // set to 1 if the survivors do not fit the sort buffer
 };
 
-__device__ __forceinline__ unsigned sel_key(float d) {  // larger float -> larger key
-    const unsigned u = __float_as_uint(d);
+// larger float -> larger key, EQUAL floats -> equal keys: -0 takes the key of +0 (the reference filters by float
+// comparison, `logits < kth`: a zero at the k-th value keeps the zeros of both signs, and among them the lower index
+// ranks first).  Only the key is canonical; sel_value and blend_out keep the sign.
+__device__ __forceinline__ unsigned sel_key(float d) {
+    unsigned u = __float_as_uint(d);
+    if (u == 0x80000000u) u = 0u;
     return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
 }
 
@@ -82,7 +86,7 @@ __global__ __launch_bounds__(SEL_THREADS) void lm_select_kernel(SelParams p) {
     __shared__ float s_red[SEL_THREADS / 64];
     __shared__ int s_redi[SEL_THREADS / 64];
     __shared__ unsigned s_hist[256];
-    __shared__ unsigned s_prefix, s_kleft, s_count;
+    __shared__ unsigned s_prefix, s_kleft, s_count, s_last;
     __shared__ float s_f[2];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t b = blockIdx.x;
@@ -173,7 +177,7 @@ __global__ __launch_bounds__(SEL_THREADS) void lm_select_kernel(SelParams p) {
         float total;
         const float before = block_exclusive_scan(loc, s_red, &total);
         const float target = u * total;
-        if (tid == 0) s_count = 0x7FFFFFFF;
+        if (tid == 0) { s_count = 0x7FFFFFFF; s_last = 0; }
         __syncthreads();
         // the chunk that holds the target: before <= target < before + loc; ties of zero-mass chunks resolve to
         // the first non-empty one
@@ -189,7 +193,21 @@ __global__ __launch_bounds__(SEL_THREADS) void lm_select_kernel(SelParams p) {
             if (pick >= 0) atomicMin(&s_count, (unsigned)pick);
         }
         __syncthreads();
-        if (tid == 0) p.out[b] = s_count == 0x7FFFFFFFu ? gidx : (int64_t)s_count;  // rounding fell off the end: mode
+        if (s_count == 0x7FFFFFFFu) {  // workgroup-uniform
+            // no chunk claimed the target: before + loc of a chunk and `before` of the next (or the total, at
+            // u = 1 - 2^-24) are rounded differently and can leave a gap of an ulp.  The draw is the column just below
+            // the gap: the last one with mass among the chunks that start at or below the target.
+            if (loc > 0.0f && before <= target) {
+                int pick = -1;
+                for (int i = i0; i < i1; ++i)
+                    if (mass(i) > 0.0f) pick = i;
+                if (pick >= 0) atomicMax(&s_last, (unsigned)pick + 1u);
+            }
+            __syncthreads();
+            if (tid == 0) p.out[b] = s_last ? (int64_t)s_last - 1 : gidx;  // a row without any mass: the mode
+        } else if (tid == 0) {
+            p.out[b] = (int64_t)s_count;
+        }
     };
     if (p.top_k < 0) {
         unsorted_draw(0u);
@@ -377,21 +395,27 @@ __global__ __launch_bounds__(SEL_THREADS) void lm_select_kernel(SelParams p) {
         __syncthreads();
     }
     const float target = u * s_f[1];
-    if (tid == 0) s_count = 0x7FFFFFFF;
+    if (tid == 0) { s_count = 0x7FFFFFFF; s_last = 0; }
     __syncthreads();
-    {
-        const int e1 = r1 < n_nuc ? r1 : n_nuc;
-        if (r0 < e1) {
-            float c = before;
-            for (int r = r0; r < e1; ++r) {
-                c += prob(r);
-                if (c > target) { atomicMin(&s_count, (unsigned)r); break; }
-            }
+    const int e1 = r1 < n_nuc ? r1 : n_nuc;
+    if (r0 < e1) {
+        float c = before;
+        for (int r = r0; r < e1; ++r) {
+            const float m = prob(r);
+            c += m;
+            // never a rank without mass (-inf survivors of top_k = 0 or top_k >= the finite count sort last): a
+            // chunk whose `before` is rounded above the target must not claim one
+            if (c > target && m > 0.0f) { atomicMin(&s_count, (unsigned)r); break; }
         }
     }
     __syncthreads();
+    if (s_count == 0x7FFFFFFFu) {  // workgroup-uniform; rounding fell off the end: the last kept rank WITH MASS
+        for (int r = e1 - 1; r >= r0; --r)
+            if (prob(r) > 0.0f) { atomicMax(&s_last, (unsigned)r); break; }
+        __syncthreads();
+    }
     if (tid == 0) {
-        int r = s_count == 0x7FFFFFFFu ? n_nuc - 1 : (int)s_count;  // rounding fell off the end: last kept rank
+        const int r = s_count == 0x7FFFFFFFu ? (int)s_last : (int)s_count;
         p.out[b] = (int64_t)(0xFFFFFFFFu - (unsigned)(sel_sort[r] & 0xFFFFFFFFull));
     }
 }

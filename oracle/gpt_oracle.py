@@ -159,25 +159,29 @@ def select_inverse_cdf(values, top_k, top_p, u):
 
 
 def sample_with_past(sd, x, n_head, steps, temperature=1.0, sample_logits=True, top_k=None, top_p=None,
-                     generator=None, return_logits=False, cbox=None):
-    """reference gpt.py:327-359: x [B, cond_len] conditioning -> [B, steps] new tokens."""
+                     generator=None, return_logits=False, cbox=None, forced=None):
+    """reference gpt.py:327-359: x [B, cond_len] conditioning -> [B, steps] new tokens.
+    forced [B, steps]: teacher forcing -- token n is forced[:, n] instead of a pick from the logits (the logits of a loop
+    that chose those tokens elsewhere)."""
     cond_len = x.shape[1]
     cache, out, all_logits = None, [], []
     for n in range(steps):
         logits, cache = forward_with_past(sd, x, n_head, cache, position=n + cond_len - 1, cbox=cbox)
         logits = logits[:, -1, :] / temperature
         all_logits.append(logits)
-        x = _pick(logits, sample_logits, top_k, top_p, generator)
+        x = _pick(logits, sample_logits, top_k, top_p, generator) if forced is None else forced[:, n:n + 1]
         out.append(x)
     out = torch.cat(out, dim=1)
     return (out, torch.stack(all_logits, 1)) if return_logits else out
 
 
 def sample_with_past_cfg(sd, x, n_head, steps, temperature=1.0, sample_logits=True, top_k=None, top_p=None,
-                         cfg_ratio=1.5, class_first=False, scale_cfg=False, generator=None, return_logits=False):
+                         cfg_ratio=1.5, class_first=False, scale_cfg=False, generator=None, return_logits=False,
+                         forced=None):
     """reference gpt.py:387-444 classifier-free guidance: conditional stream [class+1, sos] (or
     [sos, class+1]) and an unconditional stream [sos]; the unconditional stream's new tokens use
-    position past_length + 1 (forward_uncond, gpt.py:248) so both streams share positions."""
+    position past_length + 1 (forward_uncond, gpt.py:248) so both streams share positions.
+    forced [B, steps]: teacher forcing, as in sample_with_past."""
     x = x + 1
     sos = torch.zeros_like(x)
     xc = torch.cat((x, sos), 1) if class_first else torch.cat((sos, x), 1)
@@ -193,7 +197,7 @@ def sample_with_past_cfg(sd, x, n_head, steps, temperature=1.0, sample_logits=Tr
         t = cfg_ratio * ratio
         blend = (1 + t) * lc - t * lu
         all_logits.append(blend)
-        xc = xu = _pick(blend, sample_logits, top_k, top_p, generator)
+        xc = xu = _pick(blend, sample_logits, top_k, top_p, generator) if forced is None else forced[:, n:n + 1]
         out.append(xc)
     out = torch.cat(out, dim=1)
     return (out, torch.stack(all_logits, 1)) if return_logits else out
