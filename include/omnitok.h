@@ -69,7 +69,7 @@ const char *omnitok_version(void);
  *                all three agree to rounding
  *   "attn_window_mode" 1 (default, process-wide, with gemm_pl / qkv_pl) window attention on the fp16 matrix cores from packed
  *                operands (omnitok_stats_pack_windows -> packing epilogues -> omnitok_attn_window_h2) | 0 fp32 q|k|v and the
- *                fp32-MFMA kernel omnitok_attn_window_planes
+ *                fp32-MFMA kernel omnitok_attn_window (plane output)
  *   "qkv_pl"     1 (default, process-wide) with gemm_pl: the q|k|v projection reads centred planes from omnitok_stats_pack,
  *                has the LayerNorm folded into its weight and writes the attention kernel's packed Q / K / V itself | 0 the
  *                round-2 form (row_stats -> gemm_h2 with in-loop LayerNorm -> attn_pack)
@@ -388,87 +388,95 @@ int omnitok_transpose_tokens(const float *x, float *y, int64_t B, int64_t A, int
  * into host_cos/host_sin (fp32). */
 int omnitok_rope_table(int n_tokens, int dim_head, float theta, float *host_cos, float *host_sin);
 
-/* In-place q/k preparation of Attention (reference attention.py:417-437): optional 2-D RoPE
- * (cos/sin [N, 32], same table for all heads), l2norm over dim_head=64, * q_scale / k_scale[64];
- * q additionally * scale (the SDPA scale 8, a power of two, folded exactly).
- * q: rows x heads*64 (ld ldq), k: rows x heads*64 (ld ldk). cos may be NULL (no RoPE). */
-int omnitok_qk_prep(float *q, int64_t ldq, float *k, int64_t ldk, int64_t rows, int n_tokens,
-                    int heads, const float *cos, const float *sin, const float *q_scale,
-                    const float *k_scale, float scale, omnitok_stream_t stream);
+/* --- attention: seven kernels' entry points behind one descriptor ---------------------------------------------------
+ * A zero-initialised descriptor means "nothing optional".  A field that selects something the called kernel does not
+ * implement (listed per entry point below) is refused with OMNITOK_ERR_INVALID and the field's name; the range fields
+ * (q_bound ... seqs_per_clip) are ignored by the kernels that need no range. */
+typedef struct omnitok_attn_desc {
+    /* operands, fp32 rows: q [seqs * n_tokens, heads*64] (ld ldq), k and v rows with ld ldkv; 16-byte aligned, ld % 4 == 0.
+     * omnitok_qk_prep writes q and k in place, every other entry point only reads them.  omnitok_attn_window: q / ldq carry
+     * the fused qkv [rows, 3*heads*64] and its ld, k == v == NULL. */
+    float *q;
+    int64_t ldq;
+    float *k;
+    const float *v;
+    int64_t ldkv;
+    /* operands, packed: fp16 hi|lo planes in MFMA-fragment order, seqs * n_tokens * heads*64 * 4 bytes each (blocks of 32
+     * tokens of one head, 8 KiB).  omnitok_attn_pack writes them, the _h2 kernels read them. */
+    void *qp, *kp, *vp;
+    /* preparation (qk_prep, attn_pack, attn_temporal): optional 2-D RoPE (cos/sin [n_tokens, 32], same table for all
+     * heads; both or neither), l2norm over dim_head = 64, * q_scale / k_scale[64]; q additionally * scale (the SDPA scale
+     * 8, a power of two, folded exactly) */
+    const float *rope_cos, *rope_sin;
+    const float *q_scale, *k_scale;
+    float scale;
+    /* ranges (attn_pack and the _h2 kernels; v_* also the plane output of attn_temporal): q_bound >= max|q| (= scale *
+     * max|q_scale|), k_bound >= max|k| (= max|k_scale|), v_bound (times v_bound_dev[v_bound_stride * clip] when given,
+     * clip = sequence / seqs_per_clip) >= max|v| of a clip; they define the power-of-two operand scales, so the kernel
+     * that reads the planes must be given what the one that wrote them was given */
+    float q_bound, k_bound, v_bound;
+    const float *v_bound_dev;
+    int v_bound_stride;
+    int64_t seqs_per_clip;
+    /* bias and mask.  bias_table (spatial): NULL (sdpa mode) or the [(2*gh-1)*(2*gw-1), heads]
+     * ContinuousPositionBias table (entry (dy+gh-1, dx+gw-1) for query-key offset (dy,dx); legacy mode, reference
+     * attention.py:456-466), n_tokens == gh*gw.  bias_dense (window): [heads, 64(kv), 64(q)] =
+     * relative_position_bias_table gathered by relative_position_index (attention.py:277-281), transposed.
+     * alibi_slopes (temporal): NULL (sdpa) or [heads] (legacy, attention.py:473-474); causal: is_causal / causal mask. */
+    const float *bias_table;
+    const float *bias_dense;
+    const float *alibi_slopes;
+    int causal;
+    /* output: fp32 rows out [seqs * n_tokens, ldo] (token order), or, when out_planes is given (it wins over out), fp16
+     * hi|lo planes with K = heads * 64 -- the A operand of the out-projection omnitok_gemm_pl -- scaled by a power of two:
+     * of the clip's V bound (spatial_h2, temporal; out_scale[row] receives the factor that undoes it), of v_bound
+     * (window_h2) or of out_bound >= max|output| (window; the consumer takes a_scale_const = omnitok_pl_unscale(bound)) */
+    float *out;
+    int64_t ldo;
+    void *out_planes;
+    float *out_scale;
+    float out_bound;
+    /* geometry: seqs sequences (spatial, window: images; temporal: columns) of n_tokens tokens (window: gh * gw, n_tokens
+     * is not read); gh x gw the token grid of bias_table and of the 8 x 8 windows */
+    int64_t seqs;
+    int n_tokens, heads;
+    int gh, gw;
+} omnitok_attn_desc;
 
-/* Full (non-causal) spatial attention over N tokens per sequence, flash-style on fp32 MFMA:
- * out[b, n, h*64:(h+1)*64] = softmax(q k^T [+ bias]) v  with q,k already prepared by qk_prep.
- * q[Bn*N, heads*64] (ldq), k/v rows with ld ldkv. bias_table: NULL (sdpa mode) or
- * [(2*gh-1)*(2*gw-1), heads] ContinuousPositionBias table (entry (dy+gh-1, dx+gw-1) for query-key
- * offset (dy,dx)) for legacy mode (attention.py:456-466), N == gh*gw.  N % 64 == 0. */
-int omnitok_attn_spatial(const float *q, int64_t ldq, const float *k, const float *v, int64_t ldkv,
-                         float *out, int64_t ldo, int Bn, int N, int heads,
-                         const float *bias_table, int gh, int gw, omnitok_stream_t stream);
+/* In-place q/k preparation of Attention (reference attention.py:417-437): q, k, ldq, ldkv (the ld of k), the preparation
+ * fields.  Refused: bias_*, alibi_slopes, causal, out, out_planes. */
+int omnitok_qk_prep(const omnitok_attn_desc *d, omnitok_stream_t stream);
 
-/* fp16-split spatial attention (csrc/attn_h2.hip), the default of the engine ("attn_mode" 1): the same
- * operator as omnitok_qk_prep + omnitok_attn_spatial (reference attention.py:417-483) on the fp16 matrix
- * cores, every operand as an exact-scale fp16 hi|lo pair, three MFMA products per fp32 product, fp32
- * accumulation and softmax.
- *   omnitok_attn_pack: RoPE + l2norm + q/k scales exactly as omnitok_qk_prep, then q, k and v are written as
- *     hi|lo planes in MFMA-fragment order: qp / kp / vp are rows*heads*64*4 bytes each (blocks of 32 tokens of
- *     one head, 8 KiB).  q_bound >= max|q| (= scale * max|q_scale|), k_bound >= max|k| (= max|k_scale|);
- *     v_bound (times v_bound_dev[v_bound_stride * clip] if given, clip = row / rows_per_clip) >= max|v| of the
- *     rows of a clip.  n_tokens % 32 == 0.  v == vp == NULL: only q and k (V written by omnitok_gemm_h2 with v_planes).
- *   omnitok_attn_spatial_h2: out[Bn*N, heads*64] = softmax(q k^T [+ bias]) v from the packed operands; the same
- *     bounds must be passed (they define the power-of-two operand scales); seq_per_clip = sequences per clip
- *     for v_bound_dev.  N % 64 == 0. */
-int omnitok_attn_pack(const float *q, int64_t ldq, const float *k, const float *v, int64_t ldkv, int64_t rows,
-                      int n_tokens, int heads, const float *cos, const float *sin, const float *q_scale,
-                      const float *k_scale, float scale, float q_bound, float k_bound, float v_bound,
-                      const float *v_bound_dev, int v_bound_stride, int64_t rows_per_clip, void *qp, void *kp,
-                      void *vp, omnitok_stream_t stream);
-int omnitok_attn_spatial_h2(const void *qp, const void *kp, const void *vp, float *out, int64_t ldo, int Bn, int N,
-                            int heads, float q_bound, float k_bound, float v_bound, const float *v_bound_dev,
-                            int v_bound_stride, int seq_per_clip, const float *bias_table, int gh, int gw,
-                            omnitok_stream_t stream);
-/* The same kernel with the output written as fp16 hi|lo planes (out_planes != NULL; the A operand of the to_out GEMM,
- * omnitok_gemm_pl, K = heads * 64) instead of fp32 rows: scaled per clip by the power of two of the V bound (the
- * output is a convex combination of V rows), out_scale[row] receives the factor that undoes it. */
-int omnitok_attn_spatial_h2_planes(const void *qp, const void *kp, const void *vp, float *out, int64_t ldo,
-                                   void *out_planes, float *out_scale, int Bn, int N, int heads, float q_bound,
-                                   float k_bound, float v_bound, const float *v_bound_dev, int v_bound_stride,
-                                   int seq_per_clip, const float *bias_table, int gh, int gw, omnitok_stream_t stream);
+/* Full (non-causal) spatial attention over n_tokens per sequence, flash-style on fp32 MFMA:
+ * out[b, n, h*64:(h+1)*64] = softmax(q k^T [+ bias_table]) v  with q, k already prepared by qk_prep.  n_tokens % 64 == 0.
+ * Refused: qp/kp/vp, out_planes, bias_dense, alibi_slopes, causal. */
+int omnitok_attn_spatial(const omnitok_attn_desc *d, omnitok_stream_t stream);
 
-/* WindowAttention core (reference attention.py:266-286): qkv[Bn*N, 3*heads*64] from LN(x),
- * ws x ws (ws = 8) non-overlapping windows of the gh x gw grid, softmax(0.125 q k^T + bias) v.
- * bias_dense[heads, 64(kv), 64(q)] = relative_position_bias_table gathered by
- * relative_position_index (attention.py:277-281), transposed. out[Bn*N, heads*64]. */
-int omnitok_attn_window(const float *qkv, int64_t ldqkv, const float *bias_dense, float *out,
-                        int64_t ldo, int Bn, int gh, int gw, int heads, omnitok_stream_t stream);
-/* ... with the output as fp16 hi|lo planes (out_planes != NULL) scaled by the power of two of the static bound
- * out_bound >= max |output|; the consuming omnitok_gemm_pl takes a_scale_const = omnitok_pl_unscale(out_bound). */
-int omnitok_attn_window_planes(const float *qkv, int64_t ldqkv, const float *bias_dense, float *out, int64_t ldo,
-                               void *out_planes, float out_bound, int Bn, int gh, int gw, int heads,
-                               omnitok_stream_t stream);
-/* Window attention on the fp16 matrix cores from PACKED operands (csrc/attn_h2.hip; reference attention.py:254-293): qp / kp / vp
- * are the fragment-order hi|lo planes the q|k|v plane GEMM's packing epilogues (omnitok_pl_gemm epilogue 4 without scale
- * vectors, q_mul = the head scale; epilogue 3) write when the GEMM's rows are in window-major order
- * (omnitok_stats_pack_windows) with n_tokens = 64; q_bound / k_bound / v_bound the static bounds they were scaled with.
- * bias_dense: [heads][64 keys][64 queries].  Output rows in token order: fp32 `out` [Bn * gh * gw, ldo] or, when out_planes
- * is given, hi|lo planes (K = heads * 64) scaled by the power of two of v_bound. */
-int omnitok_attn_window_h2(const void *qp, const void *kp, const void *vp, const float *bias_dense, float *out, int64_t ldo,
-                           void *out_planes, float q_bound, float k_bound, float v_bound, int Bn, int gh, int gw, int heads,
-                           omnitok_stream_t stream);
+/* fp16-split spatial attention (csrc/attn_h2.hip), the default of the engine ("attn_mode" 1): the same operator as
+ * omnitok_qk_prep + omnitok_attn_spatial (reference attention.py:417-483) on the fp16 matrix cores, every operand as an
+ * exact-scale fp16 hi|lo pair, three MFMA products per fp32 product, fp32 accumulation and softmax.
+ *   omnitok_attn_pack: the preparation exactly as omnitok_qk_prep, then q, k and v are written as qp / kp / vp.
+ *     n_tokens % 32 == 0.  v == vp == NULL: only q and k (V written by omnitok_gemm_h2 with v_planes).  Refused as qk_prep.
+ *   omnitok_attn_spatial_h2: softmax(q k^T [+ bias_table]) v from qp / kp / vp, to out or out_planes + out_scale.
+ *     n_tokens % 64 == 0.  Refused: q/k/v, bias_dense, alibi_slopes, causal. */
+int omnitok_attn_pack(const omnitok_attn_desc *d, omnitok_stream_t stream);
+int omnitok_attn_spatial_h2(const omnitok_attn_desc *d, omnitok_stream_t stream);
 
-/* Temporal attention (reference attention.py:402-486 with is_spatial=False): per (column, head)
- * T tokens; l2norm, q/k scales and scale applied inside. causal: is_causal / causal mask;
- * alibi_slopes: NULL (sdpa) or [heads] (legacy, attention.py:473-474). q[cols*T, heads*64]. */
-int omnitok_attn_temporal(const float *q, int64_t ldq, const float *k, const float *v,
-                          int64_t ldkv, float *out, int64_t ldo, int64_t cols, int T, int heads,
-                          const float *q_scale, const float *k_scale, float scale, int causal,
-                          const float *alibi_slopes, omnitok_stream_t stream);
-/* ... with the output as fp16 hi|lo planes (out_planes != NULL; T <= 17, cols % 16 == 0), scaled per clip by the power
- * of two of v_bound (x v_bound_dev[v_bound_stride * (col / cols_per_clip)]) >= max |v|; out_scale[row] = the inverse. */
-int omnitok_attn_temporal_planes(const float *q, int64_t ldq, const float *k, const float *v, int64_t ldkv,
-                                 float *out, int64_t ldo, void *out_planes, float *out_scale, float v_bound,
-                                 const float *v_bound_dev, int v_bound_stride, int64_t cols_per_clip, int64_t cols,
-                                 int T, int heads, const float *q_scale, const float *k_scale, float scale,
-                                 int causal, const float *alibi_slopes, omnitok_stream_t stream);
+/* WindowAttention core (reference attention.py:266-286): qkv from LN(x), ws x ws (ws = 8) non-overlapping windows of the
+ * gh x gw grid, softmax(0.125 q k^T + bias_dense) v, to out or to out_planes scaled by out_bound.
+ * Refused: k/v, qp/kp/vp, bias_table, alibi_slopes, causal, v_bound_dev. */
+int omnitok_attn_window(const omnitok_attn_desc *d, omnitok_stream_t stream);
+/* Window attention on the fp16 matrix cores from PACKED operands (csrc/attn_h2.hip; reference attention.py:254-293): qp / kp
+ * / vp are what the q|k|v plane GEMM's packing epilogues (omnitok_pl_gemm epilogue 4 without scale vectors, q_mul = the head
+ * scale; epilogue 3) write when the GEMM's rows are in window-major order (omnitok_stats_pack_windows) with n_tokens = 64;
+ * q_bound / k_bound / v_bound the static bounds they were scaled with.  Refused: q/k/v, bias_table, alibi_slopes, causal,
+ * v_bound_dev. */
+int omnitok_attn_window_h2(const omnitok_attn_desc *d, omnitok_stream_t stream);
+
+/* Temporal attention (reference attention.py:402-486 with is_spatial=False): per (column, head) n_tokens = T steps; l2norm,
+ * q/k scales and scale applied inside.  Plane output: T <= 17, seqs % 16 == 0 (and seqs_per_clip % 16 == 0 with
+ * v_bound_dev).  Refused: qp/kp/vp, bias_table, bias_dense, rope_cos/rope_sin. */
+int omnitok_attn_temporal(const omnitok_attn_desc *d, omnitok_stream_t stream);
 
 /* z[n, 0:cdim] = l2norm(x[n, :] . w[cdim, D]^T + b)   (reference omnitokenizer.py:143-148 +
  * F.normalize :251-252; normalize skipped if l2 == 0).  cdim == 8, D % 64 == 0. */

@@ -70,6 +70,20 @@ class OmnitokRowGemm(Structure):
     ]
 
 
+class OmnitokAttnDesc(Structure):
+    """omnitok_attn_desc (include/omnitok.h): arguments of omnitok_qk_prep and the omnitok_attn_* entry points."""
+    _fields_ = [
+        ("q", c_void_p), ("ldq", c_int64), ("k", c_void_p), ("v", c_void_p), ("ldkv", c_int64),
+        ("qp", c_void_p), ("kp", c_void_p), ("vp", c_void_p),
+        ("rope_cos", c_void_p), ("rope_sin", c_void_p), ("q_scale", c_void_p), ("k_scale", c_void_p), ("scale", c_float),
+        ("q_bound", c_float), ("k_bound", c_float), ("v_bound", c_float), ("v_bound_dev", c_void_p),
+        ("v_bound_stride", c_int), ("seqs_per_clip", c_int64),
+        ("bias_table", c_void_p), ("bias_dense", c_void_p), ("alibi_slopes", c_void_p), ("causal", c_int),
+        ("out", c_void_p), ("ldo", c_int64), ("out_planes", c_void_p), ("out_scale", c_void_p), ("out_bound", c_float),
+        ("seqs", c_int64), ("n_tokens", c_int), ("heads", c_int), ("gh", c_int), ("gw", c_int),
+    ]
+
+
 class OmnitokFramesDesc(Structure):
     """omnitok_frames_desc (include/omnitok.h): one uint8 clip of omnitok_frames_to_pixels."""
     _fields_ = [("frames", c_void_p), ("frame_stride", c_int64), ("row_stride", c_int64),
@@ -123,14 +137,9 @@ _PROTOS = {
     "omnitok_pack_peg_weight": [P, c_int, P, P],
     "omnitok_transpose_tokens": [P, P, I64, I64, I64, c_int, P],
     "omnitok_rope_table": [c_int, c_int, c_float, P, P],
-    "omnitok_qk_prep": [P, I64, P, I64, I64, c_int, c_int, P, P, P, P, c_float, P],
-    "omnitok_attn_spatial": [P, I64, P, P, I64, P, I64, c_int, c_int, c_int, P, c_int, c_int, P],
-    "omnitok_attn_pack": [P, I64, P, P, I64, I64, c_int, c_int, P, P, P, P, c_float, c_float, c_float, c_float, P, c_int,
-                          I64, P, P, P, P],
-    "omnitok_attn_spatial_h2": [P, P, P, P, I64, c_int, c_int, c_int, c_float, c_float, c_float, P, c_int, c_int, P,
-                                c_int, c_int, P],
-    "omnitok_attn_window": [P, I64, P, P, I64, c_int, c_int, c_int, c_int, P],
-    "omnitok_attn_temporal": [P, I64, P, P, I64, P, I64, I64, c_int, c_int, P, P, c_float, c_int, P, P],
+    **{name: [POINTER(OmnitokAttnDesc), P] for name in (
+        "omnitok_qk_prep", "omnitok_attn_spatial", "omnitok_attn_pack", "omnitok_attn_spatial_h2", "omnitok_attn_window",
+        "omnitok_attn_window_h2", "omnitok_attn_temporal")},
     "omnitok_pre_vq": [P, P, P, P, I64, c_int, c_int, c_int, P],
     "omnitok_vq_prepare": [P, c_int, c_int, P, P, P],
     "omnitok_vq_argmin": [P, P, P, I64, c_int, P, P],
@@ -240,15 +249,9 @@ _PROTOS = {
     "omnitok_pl_pack_rows": [P, I64, I64, c_int, I64, P, P, c_float, P],
     "omnitok_gemm_pl": [POINTER(OmnitokPlGemm), P],
     "omnitok_stats_pack": [P, I64, c_int, c_float, c_int, P, I64, P, P, P, I64, P],
-    "omnitok_attn_spatial_h2_planes": [P, P, P, P, I64, P, P, c_int, c_int, c_int, c_float, c_float, c_float, P, c_int,
-                                       c_int, P, c_int, c_int, P],
-    "omnitok_attn_window_planes": [P, I64, P, P, I64, P, c_float, c_int, c_int, c_int, c_int, P],
     "omnitok_layernorm_planes": [P, I64, c_int, c_float, P, P, c_float, P, I64, P],
-    "omnitok_attn_window_h2": [P, P, P, P, P, I64, P, c_float, c_float, c_float, c_int, c_int, c_int, c_int, P],
     "omnitok_stats_pack_windows": [P, I64, c_int, c_float, c_int, P, I64, P, P, c_int, c_int, c_int, P],
     "omnitok_stats_pack_temporal": [P, I64, c_int, c_float, P, P, P, P, I64, P],
-    "omnitok_attn_temporal_planes": [P, I64, P, P, I64, P, I64, P, P, c_float, P, c_int, I64, I64, c_int, c_int, P, P,
-                                     c_float, c_int, P, P],
     # include/omnitok_comm.h
     "omnitok_comm_available": [c_char_p, c_int],
     "omnitok_comm_unique_id": [P],

@@ -29,6 +29,7 @@
 //   V:     [plane 2][j 2][d-half 2][h 2][d 32][8 halfs]  element = v[16 j + 8 (e >> 2) + 4 h + (e & 3)][32 mt + d]
 // so that every fragment is one conflict-free ds_read_b128 per lane (lanes 0-31 and 32-63 read two contiguous
 // 512-byte runs) and a K/V tile is staged by a linear copy.
+#include "attn_host.h"
 #include "h2_common.h"
 #include "planes.h"
 
@@ -1192,7 +1193,6 @@ __global__ __launch_bounds__(256, 2) void attn_window_h2_kernel(WinH2Params p, i
 // workgroups per CU (also what the legacy-bias path runs) | 2 the same with 64-key tiles | 1 the r02 / r03 pipelined + LDS-DMA kernel
 // | 0 the first kernel.  One box, C3 shape (profiles/r04_attn_variants.txt): 1.109 / 1.007 / 0.929 / 0.916 ms for 1 / 3 / 5 / 6.
 int g_attn_h2_variant = 6;
-//  // "attn_h2_variant": 1 pipelined + LDS-DMA kernel (default), 0 the first kernel
 
 }  // namespace omnitok
 
@@ -1200,32 +1200,26 @@ using namespace omnitok;
 
 // q_bound / k_bound: upper bounds of |q| (after RoPE, l2norm, q_scale and `scale`) and |k|: scale * max|q_scale|
 // and max|k_scale| (l2-normalised vectors have |x_d| <= 1).  v_bound (x v_bound_dev[stride * clip] when given):
-// upper bound of |v| for the rows of a clip (rows_per_clip consecutive rows).
-extern "C" int omnitok_attn_pack(const float *q, int64_t ldq, const float *k, const float *v, int64_t ldkv,
-                                 int64_t rows, int n_tokens, int heads, const float *cos, const float *sin,
-                                 const float *q_scale, const float *k_scale, float scale, float q_bound, float k_bound,
-                                 float v_bound, const float *v_bound_dev, int v_bound_stride, int64_t rows_per_clip,
-                                 void *qp, void *kp, void *vp, omnitok_stream_t stream_) {
+// upper bound of |v| for the rows of a clip (seqs_per_clip consecutive sequences).
+extern "C" int omnitok_attn_pack(const omnitok_attn_desc *d, omnitok_stream_t stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    OT_CHECK_ARG(q && k && q_scale && k_scale && qp && kp, "attn_pack: null pointer");
-    OT_CHECK_ARG((v == nullptr) == (vp == nullptr), "attn_pack: v and vp must both be given or both null (V packed elsewhere)");
-    OT_CHECK_ARG((cos == nullptr) == (sin == nullptr), "attn_pack: cos/sin must both be given or both null");
-    OT_CHECK_ARG(ldq % 4 == 0 && ldkv % 4 == 0 && aligned16(q) && aligned16(k) && (!v || aligned16(v)) && aligned16(qp) &&
-                     aligned16(kp) && (!vp || aligned16(vp)), "attn_pack: unaligned");
-    OT_CHECK_ARG(n_tokens > 0 && n_tokens % 32 == 0 && rows % n_tokens == 0, "attn_pack: %lld rows of %d-token sequences",
-                 (long long)rows, n_tokens);
-    OT_CHECK_ARG(q_bound > 0.0f && k_bound > 0.0f && (!v || v_bound > 0.0f), "attn_pack: operand bounds must be positive");
-    OT_CHECK_ARG(!v_bound_dev || (rows_per_clip > 0 && rows_per_clip % n_tokens == 0),
-                 "attn_pack: rows_per_clip must be a whole number of sequences");
+    if (int rc = attn_check_desc("attn_pack", d, AF_BIAS_TABLE | AF_BIAS_DENSE | AF_TEMPORAL | AF_OUT | AF_OUT_PLANES)) return rc;
+    const int n_tokens = d->n_tokens, heads = d->heads;
+    const int64_t rows = d->seqs * n_tokens;
+    if (int rc = attn_check_operands("attn_pack", *d, AF_Q | AF_K | AF_SCALES | AF_QKP, AF_V | AF_VP | AF_ROPE)) return rc;
+    OT_CHECK_ARG((d->v == nullptr) == (d->vp == nullptr), "attn_pack: v and vp must both be given or both null (V packed elsewhere)");
+    OT_CHECK_ARG(n_tokens > 0 && n_tokens % 32 == 0, "attn_pack: %lld rows of %d-token sequences", (long long)rows, n_tokens);
+    if (int rc = attn_check_ranges("attn_pack", *d, d->v != nullptr, "rows_per_clip must be a whole number of sequences")) return rc;
     if (rows == 0) return OMNITOK_OK;
     PackParams p;
-    p.q = q; p.ldq = ldq; p.k = k; p.v = v; p.ldkv = ldkv; p.n_tokens = n_tokens; p.heads = heads;
-    p.nblk = n_tokens / 32; p.cosT = cos; p.sinT = sin; p.q_scale = q_scale; p.k_scale = k_scale; p.scale = scale;
-    p.sq = h2_scale_of_bound(q_bound); p.sk = h2_scale_of_bound(k_bound);
-    p.v_bound = v_bound; p.v_bound_dev = v_bound_dev; p.v_bound_stride = v_bound_stride;
-    p.rows_per_clip = v_bound_dev ? rows_per_clip : rows;
-    p.qp = static_cast<unsigned char *>(qp); p.kp = static_cast<unsigned char *>(kp);
-    p.vp = static_cast<unsigned char *>(vp);
+    p.q = d->q; p.ldq = d->ldq; p.k = d->k; p.v = d->v; p.ldkv = d->ldkv; p.n_tokens = n_tokens; p.heads = heads;
+    p.nblk = n_tokens / 32; p.cosT = d->rope_cos; p.sinT = d->rope_sin; p.q_scale = d->q_scale; p.k_scale = d->k_scale;
+    p.scale = d->scale;
+    p.sq = h2_scale_of_bound(d->q_bound); p.sk = h2_scale_of_bound(d->k_bound);
+    p.v_bound = d->v_bound; p.v_bound_dev = d->v_bound_dev; p.v_bound_stride = d->v_bound_stride;
+    p.rows_per_clip = d->v_bound_dev ? d->seqs_per_clip * n_tokens : rows;
+    p.qp = static_cast<unsigned char *>(d->qp); p.kp = static_cast<unsigned char *>(d->kp);
+    p.vp = static_cast<unsigned char *>(d->vp);
     const int64_t units = rows / 32 * heads;
     OT_CHECK_ARG(units < (1ll << 31), "attn_pack: grid too large");
     hipLaunchKernelGGL(attn_pack_kernel, dim3((unsigned)units), dim3(256), 0, stream, p);
@@ -1233,39 +1227,29 @@ extern "C" int omnitok_attn_pack(const float *q, int64_t ldq, const float *k, co
     return OMNITOK_OK;
 }
 
-extern "C" int omnitok_attn_spatial_h2(const void *qp, const void *kp, const void *vp, float *out, int64_t ldo, int Bn,
-                                       int N, int heads, float q_bound, float k_bound, float v_bound,
-                                       const float *v_bound_dev, int v_bound_stride, int seq_per_clip,
-                                       const float *bias_table, int gh, int gw, omnitok_stream_t stream_) {
-    return omnitok_attn_spatial_h2_planes(qp, kp, vp, out, ldo, nullptr, nullptr, Bn, N, heads, q_bound, k_bound, v_bound,
-                                          v_bound_dev, v_bound_stride, seq_per_clip, bias_table, gh, gw, stream_);
-}
-
-extern "C" int omnitok_attn_spatial_h2_planes(const void *qp, const void *kp, const void *vp, float *out, int64_t ldo,
-                                              void *out_planes, float *out_scale, int Bn, int N, int heads, float q_bound,
-                                              float k_bound, float v_bound, const float *v_bound_dev, int v_bound_stride,
-                                              int seq_per_clip, const float *bias_table, int gh, int gw,
-                                              omnitok_stream_t stream_) {
+extern "C" int omnitok_attn_spatial_h2(const omnitok_attn_desc *d, omnitok_stream_t stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    OT_CHECK_ARG(qp && kp && vp && (out || out_planes), "attn_spatial_h2: null pointer");
-    OT_CHECK_ARG(!out_planes || (out_scale && aligned16(out_planes)), "attn_spatial_h2: plane output needs out_scale");
+    if (int rc = attn_check_desc("attn_spatial_h2", d, AF_ROWS | AF_BIAS_DENSE | AF_TEMPORAL)) return rc;
+    const int N = d->n_tokens, heads = d->heads, gh = d->gh, gw = d->gw;
+    const float *bias_table = d->bias_table;
+    if (int rc = attn_check_operands("attn_spatial_h2", *d, AF_PLANES | AF_OUT)) return rc;
+    OT_CHECK_ARG(!d->out_planes || (d->out_scale && aligned16(d->out_planes)), "attn_spatial_h2: plane output needs out_scale");
     OT_CHECK_ARG(N % 64 == 0 && N > 0, "attn_spatial_h2: N=%d must be a multiple of 64 tokens", N);
     OT_CHECK_ARG(!bias_table || gh * gw == N, "attn_spatial_h2: bias grid %dx%d != N=%d", gh, gw, N);
-    OT_CHECK_ARG((out_planes || ldo % 4 == 0) && aligned16(qp) && aligned16(kp) && aligned16(vp) && (!out || aligned16(out)),
-                 "attn_spatial_h2: unaligned");
-    OT_CHECK_ARG(q_bound > 0.0f && k_bound > 0.0f && v_bound > 0.0f, "attn_spatial_h2: operand bounds must be positive");
-    OT_CHECK_ARG(!v_bound_dev || seq_per_clip > 0, "attn_spatial_h2: seq_per_clip");
-    OT_CHECK_ARG((int64_t)heads * Bn * ((N + 127) / 128) < (1ll << 31) - 8, "attn_spatial_h2: grid too large");
-    if (Bn == 0) return OMNITOK_OK;
+    if (int rc = attn_check_ranges("attn_spatial_h2", *d, true, "seq_per_clip")) return rc;
+    OT_CHECK_ARG(d->seqs_per_clip < (1ll << 31), "attn_spatial_h2: seq_per_clip");  // the kernel's clip length is an int
+    OT_CHECK_ARG((int64_t)heads * d->seqs * ((N + 127) / 128) < (1ll << 31) - 8, "attn_spatial_h2: grid too large");
+    if (d->seqs == 0) return OMNITOK_OK;
+    const int Bn = (int)d->seqs;
     AttnH2Params p;
-    p.qp = static_cast<const unsigned char *>(qp); p.kp = static_cast<const unsigned char *>(kp);
-    p.vp = static_cast<const unsigned char *>(vp);
-    p.out = out; p.ldo = ldo; p.N = N; p.heads = heads;
-    p.s_unscale = 1.0f / (h2_scale_of_bound(q_bound) * h2_scale_of_bound(k_bound));
-    p.v_bound = v_bound; p.v_bound_dev = v_bound_dev; p.v_bound_stride = v_bound_stride;
-    p.seq_per_clip = v_bound_dev ? seq_per_clip : (Bn > 0 ? Bn : 1);
+    p.qp = static_cast<const unsigned char *>(d->qp); p.kp = static_cast<const unsigned char *>(d->kp);
+    p.vp = static_cast<const unsigned char *>(d->vp);
+    p.out = d->out; p.ldo = d->ldo; p.N = N; p.heads = heads;
+    p.s_unscale = 1.0f / (h2_scale_of_bound(d->q_bound) * h2_scale_of_bound(d->k_bound));
+    p.v_bound = d->v_bound; p.v_bound_dev = d->v_bound_dev; p.v_bound_stride = d->v_bound_stride;
+    p.seq_per_clip = (int)attn_clip_seqs(*d);
     p.bias_table = bias_table; p.gh = gh; p.gw = gw;
-    p.out_planes = static_cast<unsigned char *>(out_planes); p.out_scale = out_scale;
+    p.out_planes = static_cast<unsigned char *>(d->out_planes); p.out_scale = d->out_scale;
     if (int rc = set_max_dynamic_lds(reinterpret_cast<const void *>(attn_spatial_h2_kernel<false>), AH_LDS_BYTES)) return rc;
     if (int rc = set_max_dynamic_lds(reinterpret_cast<const void *>(attn_spatial_h2_kernel<true>), AH_LDS_BYTES)) return rc;
     p.nqb = (N + 127) / 128;
@@ -1341,28 +1325,26 @@ extern "C" int omnitok_attn_spatial_h2_planes(const void *qp, const void *kp, co
     return OMNITOK_OK;
 }
 
-// Window attention over packed operands (see attn_window_h2_kernel).  qp / kp / vp: the packed planes of Bn * (gh / 8) *
-// (gw / 8) windows x heads, 64 tokens each, rows in window-major order; q_bound / k_bound / v_bound: the static bounds the
-// packing epilogues scaled them with.  out (fp32 [Bn * gh * gw, ldo], token order) or out_planes (hi|lo planes, K = heads *
-// 64, scaled by the power of two of v_bound: the consumer's a_scale_const = omnitok_pl_unscale(v_bound)).
-extern "C" int omnitok_attn_window_h2(const void *qp, const void *kp, const void *vp, const float *bias_dense, float *out,
-                                      int64_t ldo, void *out_planes, float q_bound, float k_bound, float v_bound, int Bn, int gh,
-                                      int gw, int heads, omnitok_stream_t stream_) {
+// Window attention over packed operands (see attn_window_h2_kernel): seqs * (gh / 8) * (gw / 8) windows x heads, 64 tokens
+// each, rows in window-major order; the consumer of the plane output takes a_scale_const = omnitok_pl_unscale(v_bound)
+extern "C" int omnitok_attn_window_h2(const omnitok_attn_desc *d, omnitok_stream_t stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    OT_CHECK_ARG(qp && kp && vp && bias_dense && (out || out_planes), "attn_window_h2: null pointer");
+    if (int rc = attn_check_desc("attn_window_h2", d, AF_ROWS | AF_BIAS_TABLE | AF_TEMPORAL | AF_V_BOUND_DEV)) return rc;
+    const int gh = d->gh, gw = d->gw, heads = d->heads;
+    if (int rc = attn_check_operands("attn_window_h2", *d, AF_PLANES | AF_BIAS_DENSE | AF_OUT)) return rc;
     OT_CHECK_ARG(gh % 8 == 0 && gw % 8 == 0, "attn_window_h2: grid %dx%d not divisible by the 8x8 window", gh, gw);
-    OT_CHECK_ARG(aligned16(qp) && aligned16(kp) && aligned16(vp) && (!out || (aligned16(out) && ldo % 4 == 0)) &&
-                     (!out_planes || aligned16(out_planes)), "attn_window_h2: unaligned");
-    OT_CHECK_ARG(q_bound > 0.0f && k_bound > 0.0f && v_bound > 0.0f, "attn_window_h2: operand bounds must be positive");
+    // this kernel looks at ldo whenever out is given, plane output or not
+    OT_CHECK_ARG((!d->out || d->ldo % 4 == 0) && aligned16(d->out_planes), "attn_window_h2: unaligned");
+    if (int rc = attn_check_ranges("attn_window_h2", *d, true, nullptr)) return rc;
     WinH2Params p;
-    p.qp = static_cast<const unsigned char *>(qp); p.kp = static_cast<const unsigned char *>(kp);
-    p.vp = static_cast<const unsigned char *>(vp);
-    p.bias_dense = bias_dense; p.out = out; p.ldo = ldo; p.out_planes = static_cast<unsigned char *>(out_planes);
-    p.v_scale = h2_scale_of_bound(v_bound);
+    p.qp = static_cast<const unsigned char *>(d->qp); p.kp = static_cast<const unsigned char *>(d->kp);
+    p.vp = static_cast<const unsigned char *>(d->vp);
+    p.bias_dense = d->bias_dense; p.out = d->out; p.ldo = d->ldo; p.out_planes = static_cast<unsigned char *>(d->out_planes);
+    p.v_scale = h2_scale_of_bound(d->v_bound);
     p.out_mul = p.v_scale;
-    p.s_unscale = 1.0f / (h2_scale_of_bound(q_bound) * h2_scale_of_bound(k_bound));
+    p.s_unscale = 1.0f / (h2_scale_of_bound(d->q_bound) * h2_scale_of_bound(d->k_bound));
     p.gh = gh; p.gw = gw; p.heads = heads; p.nwin_x = gw / 8; p.nwin = (gh / 8) * (gw / 8);
-    const int64_t total = (int64_t)Bn * p.nwin * heads;
+    const int64_t total = d->seqs * p.nwin * heads;
     if (total == 0) return OMNITOK_OK;
     OT_CHECK_ARG((total + 3) / 4 < (1ll << 31), "attn_window_h2: grid too large");
     hipLaunchKernelGGL(attn_window_h2_kernel, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, stream, p, total);

@@ -16,7 +16,7 @@
 // lanes 32-63 d in [32,64), so every Q/K fragment is 32 contiguous floats (8 x 16-byte reads).
 // fp32 throughout: the reference computes this path in fp32 and the parity bar (ids bit-exact,
 // pixels 1e-4) does not survive bf16 (SURVEY.md section 7 "Hard parts").
-#include "common.h"
+#include "attn_host.h"
 
 #include "planes.h"
 
@@ -379,35 +379,32 @@ __global__ __launch_bounds__(256, 2) void attn_window_kernel(WinParams p, int64_
 
 using namespace omnitok;
 
-extern "C" int omnitok_qk_prep(float *q, int64_t ldq, float *k, int64_t ldk, int64_t rows, int n_tokens, int heads,
-                               const float *cos, const float *sin, const float *q_scale, const float *k_scale,
-                               float scale, omnitok_stream_t stream_) {
+extern "C" int omnitok_qk_prep(const omnitok_attn_desc *d, omnitok_stream_t stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    OT_CHECK_ARG(q && k && q_scale && k_scale, "qk_prep: null pointer");
-    OT_CHECK_ARG((cos == nullptr) == (sin == nullptr), "qk_prep: cos/sin must both be given or both null");
-    OT_CHECK_ARG(ldq % 4 == 0 && ldk % 4 == 0 && aligned16(q) && aligned16(k), "qk_prep: unaligned");
-    const int64_t threads = rows * heads * 16;
+    if (int rc = attn_check_desc("qk_prep", d, AF_BIAS_TABLE | AF_BIAS_DENSE | AF_TEMPORAL | AF_OUT | AF_OUT_PLANES)) return rc;
+    if (int rc = attn_check_operands("qk_prep", *d, AF_Q | AF_K | AF_SCALES, AF_ROPE)) return rc;
+    const int64_t rows = d->seqs * d->n_tokens;
+    const int64_t threads = rows * d->heads * 16;
     if (threads == 0) return OMNITOK_OK;
-    hipLaunchKernelGGL(qk_prep_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, q, ldq, k, ldk,
-                       rows, n_tokens, heads, cos, sin, q_scale, k_scale, scale);
+    hipLaunchKernelGGL(qk_prep_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, d->q, d->ldq, d->k, d->ldkv,
+                       rows, d->n_tokens, d->heads, d->rope_cos, d->rope_sin, d->q_scale, d->k_scale, d->scale);
     OT_LAUNCH_CHECK("qk_prep");
     return OMNITOK_OK;
 }
 
-extern "C" int omnitok_attn_spatial(const float *q, int64_t ldq, const float *k, const float *v, int64_t ldkv,
-                                    float *out, int64_t ldo, int Bn, int N, int heads, const float *bias_table,
-                                    int gh, int gw, omnitok_stream_t stream_) {
+extern "C" int omnitok_attn_spatial(const omnitok_attn_desc *d, omnitok_stream_t stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    OT_CHECK_ARG(q && k && v && out, "attn_spatial: null pointer");
+    if (int rc = attn_check_desc("attn_spatial", d, AF_PLANES | AF_OUT_PLANES | AF_BIAS_DENSE | AF_TEMPORAL)) return rc;
+    const int N = d->n_tokens, heads = d->heads, gh = d->gh, gw = d->gw;
+    if (int rc = attn_check_operands("attn_spatial", *d, AF_ROWS | AF_OUT)) return rc;
     OT_CHECK_ARG(N % 64 == 0 && N > 0, "attn_spatial: N=%d must be a multiple of 64 tokens", N);
-    OT_CHECK_ARG(!bias_table || gh * gw == N, "attn_spatial: bias grid %dx%d != N=%d", gh, gw, N);
-    OT_CHECK_ARG(ldq % 4 == 0 && ldkv % 4 == 0 && ldo % 4 == 0 && aligned16(q) && aligned16(k) && aligned16(v) &&
-                     aligned16(out), "attn_spatial: unaligned");
-    OT_CHECK_ARG((int64_t)heads * Bn * ((N + 127) / 128) < (1ll << 31) - 8, "attn_spatial: grid too large");
-    if (Bn == 0) return OMNITOK_OK;
+    OT_CHECK_ARG(!d->bias_table || gh * gw == N, "attn_spatial: bias grid %dx%d != N=%d", gh, gw, N);
+    OT_CHECK_ARG((int64_t)heads * d->seqs * ((N + 127) / 128) < (1ll << 31) - 8, "attn_spatial: grid too large");
+    if (d->seqs == 0) return OMNITOK_OK;
+    const int Bn = (int)d->seqs;
     AttnParams p;
-    p.q = q; p.k = k; p.v = v; p.out = out; p.ldq = ldq; p.ldkv = ldkv; p.ldo = ldo; p.N = N; p.heads = heads;
-    p.bias_table = bias_table; p.gh = gh; p.gw = gw;
+    p.q = d->q; p.k = d->k; p.v = d->v; p.out = d->out; p.ldq = d->ldq; p.ldkv = d->ldkv; p.ldo = d->ldo; p.N = N; p.heads = heads;
+    p.bias_table = d->bias_table; p.gh = gh; p.gw = gw;
     if (int rc = set_max_dynamic_lds(reinterpret_cast<const void *>(attn_spatial_kernel<false>), AT_LDS_BYTES)) return rc;
     if (int rc = set_max_dynamic_lds(reinterpret_cast<const void *>(attn_spatial_kernel<true>), AT_LDS_BYTES)) return rc;
     p.nqb = (N + 127) / 128;
@@ -416,7 +413,7 @@ extern "C" int omnitok_attn_spatial(const float *q, int64_t ldq, const float *k,
     const int ngrp = ((heads * Bn + 7) / 8) * 8;
     p.ngrp_real = heads * Bn;
     dim3 grid((unsigned)((int64_t)ngrp * p.nqb));
-    if (bias_table)
+    if (d->bias_table)
         hipLaunchKernelGGL(attn_spatial_kernel<true>, grid, dim3(256), AT_LDS_BYTES, stream, p);
     else
         hipLaunchKernelGGL(attn_spatial_kernel<false>, grid, dim3(256), AT_LDS_BYTES, stream, p);
@@ -424,27 +421,21 @@ extern "C" int omnitok_attn_spatial(const float *q, int64_t ldq, const float *k,
     return OMNITOK_OK;
 }
 
-extern "C" int omnitok_attn_window(const float *qkv, int64_t ldqkv, const float *bias_dense, float *out,
-                                   int64_t ldo, int Bn, int gh, int gw, int heads, omnitok_stream_t stream_) {
-    return omnitok_attn_window_planes(qkv, ldqkv, bias_dense, out, ldo, nullptr, 0.0f, Bn, gh, gw, heads, stream_);
-}
-
-// out_planes != NULL: the output goes to fp16 hi|lo planes (K = heads * 64; the A operand of the proj GEMM, gemm_pl.h)
-// scaled by the power of two of out_bound (>= max |output|; the consumer's a_scale_const = omnitok_pl_unscale(out_bound))
-extern "C" int omnitok_attn_window_planes(const float *qkv, int64_t ldqkv, const float *bias_dense, float *out,
-                                          int64_t ldo, void *out_planes, float out_bound, int Bn, int gh, int gw,
-                                          int heads, omnitok_stream_t stream_) {
+// q / ldq carry the fused qkv; the plane output (the A operand of the proj GEMM, gemm_pl.h) is scaled by the power of two of
+// out_bound >= max |output|
+extern "C" int omnitok_attn_window(const omnitok_attn_desc *d, omnitok_stream_t stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    OT_CHECK_ARG(qkv && bias_dense && (out || out_planes), "attn_window: null pointer");
+    if (int rc = attn_check_desc("attn_window", d, AF_K | AF_V | AF_PLANES | AF_BIAS_TABLE | AF_TEMPORAL | AF_V_BOUND_DEV)) return rc;
+    const int gh = d->gh, gw = d->gw, heads = d->heads;
+    if (int rc = attn_check_operands("attn_window", *d, AF_Q | AF_BIAS_DENSE | AF_OUT)) return rc;
     OT_CHECK_ARG(gh % 8 == 0 && gw % 8 == 0, "attn_window: grid %dx%d not divisible by the 8x8 window", gh, gw);
-    OT_CHECK_ARG(ldqkv % 4 == 0 && (out_planes || ldo % 4 == 0) && aligned16(qkv) && (!out || aligned16(out)), "attn_window: unaligned");
-    OT_CHECK_ARG(!out_planes || (out_bound > 0.0f && aligned16(out_planes)), "attn_window: plane output needs a bound");
+    OT_CHECK_ARG(!d->out_planes || (d->out_bound > 0.0f && aligned16(d->out_planes)), "attn_window: plane output needs a bound");
     WinParams p;
-    p.qkv = qkv; p.ldqkv = ldqkv; p.bias_dense = bias_dense; p.out = out; p.ldo = ldo;
+    p.qkv = d->q; p.ldqkv = d->ldq; p.bias_dense = d->bias_dense; p.out = d->out; p.ldo = d->ldo;
     p.gh = gh; p.gw = gw; p.heads = heads; p.nwin_x = gw / 8; p.nwin = (gh / 8) * (gw / 8);
-    p.out_planes = static_cast<unsigned char *>(out_planes);
-    p.out_mul = out_planes ? h2_scale_of_bound(out_bound) : 1.0f;
-    const int64_t total = (int64_t)Bn * p.nwin * heads;
+    p.out_planes = static_cast<unsigned char *>(d->out_planes);
+    p.out_mul = d->out_planes ? h2_scale_of_bound(d->out_bound) : 1.0f;
+    const int64_t total = d->seqs * p.nwin * heads;
     if (total == 0) return OMNITOK_OK;
     hipLaunchKernelGGL(attn_window_kernel, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, stream, p, total);
     OT_LAUNCH_CHECK("attn_window");

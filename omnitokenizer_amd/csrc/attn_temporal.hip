@@ -4,7 +4,7 @@
 // contiguous q/k/v per token), dot products are 4 FMAs + a 4-step DPP all-reduce.  l2norm, the
 // learned q/k scales and the SDPA scale are applied in registers, so q/k/v are read exactly once
 // and nothing but the output is written.
-#include "common.h"
+#include "attn_host.h"
 #include "planes.h"
 
 namespace omnitok {
@@ -249,36 +249,24 @@ __global__ __launch_bounds__(256) void attn_temporal_stream(TAttnParams p) {
 
 using namespace omnitok;
 
-extern "C" int omnitok_attn_temporal(const float *q, int64_t ldq, const float *k, const float *v, int64_t ldkv,
-                                     float *out, int64_t ldo, int64_t cols, int T, int heads, const float *q_scale,
-                                     const float *k_scale, float scale, int causal, const float *alibi_slopes,
-                                     omnitok_stream_t stream_) {
-    return omnitok_attn_temporal_planes(q, ldq, k, v, ldkv, out, ldo, nullptr, nullptr, 0.0f, nullptr, 1, 0, cols, T, heads,
-                                        q_scale, k_scale, scale, causal, alibi_slopes, stream_);
-}
-
-// out_planes != NULL (T <= 17, cols % 16 == 0): the output goes to fp16 hi|lo planes (K = heads * 64) scaled per clip by the
-// power of two of v_bound (x v_bound_dev[v_bound_stride * (col / cols_per_clip)]) >= max |v| >= max |output|;
-// out_scale[row] receives the factor that undoes it.
-extern "C" int omnitok_attn_temporal_planes(const float *q, int64_t ldq, const float *k, const float *v, int64_t ldkv,
-                                            float *out, int64_t ldo, void *out_planes, float *out_scale, float v_bound,
-                                            const float *v_bound_dev, int v_bound_stride, int64_t cols_per_clip,
-                                            int64_t cols, int T, int heads, const float *q_scale, const float *k_scale,
-                                            float scale, int causal, const float *alibi_slopes, omnitok_stream_t stream_) {
+// the plane output is scaled per clip by the power of two of v_bound (x v_bound_dev[...]) >= max |v| >= max |output|
+extern "C" int omnitok_attn_temporal(const omnitok_attn_desc *d, omnitok_stream_t stream_) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    OT_CHECK_ARG(q && k && v && (out || out_planes) && q_scale && k_scale, "attn_temporal: null pointer");
+    if (int rc = attn_check_desc("attn_temporal", d, AF_PLANES | AF_BIAS_TABLE | AF_BIAS_DENSE | AF_ROPE)) return rc;
+    const int64_t cols = d->seqs;
+    const int T = d->n_tokens, heads = d->heads, causal = d->causal;
+    void *const out_planes = d->out_planes;
+    if (int rc = attn_check_operands("attn_temporal", *d, AF_ROWS | AF_OUT | AF_SCALES)) return rc;
     OT_CHECK_ARG(T > 0, "attn_temporal: T=%d", T);
-    OT_CHECK_ARG(ldq % 4 == 0 && ldkv % 4 == 0 && (out_planes || ldo % 4 == 0) && aligned16(q) && aligned16(k) && aligned16(v) &&
-                     (!out || aligned16(out)), "attn_temporal: unaligned");
-    OT_CHECK_ARG(!out_planes || (out_scale && T <= 17 && cols % 16 == 0 && v_bound > 0.0f && aligned16(out_planes) &&
-                                 (!v_bound_dev || (cols_per_clip > 0 && cols_per_clip % 16 == 0))),
+    OT_CHECK_ARG(!out_planes || (d->out_scale && T <= 17 && cols % 16 == 0 && d->v_bound > 0.0f && aligned16(out_planes) &&
+                                 (!d->v_bound_dev || (d->seqs_per_clip > 0 && d->seqs_per_clip % 16 == 0))),
                  "attn_temporal: plane output needs out_scale, T <= 17, cols %% 16 == 0 and a bound of |v|");
     TAttnParams p;
-    p.q = q; p.k = k; p.v = v; p.out = out; p.ldq = ldq; p.ldkv = ldkv; p.ldo = ldo; p.cols = cols; p.T = T;
-    p.heads = heads; p.q_scale = q_scale; p.k_scale = k_scale; p.scale = scale; p.causal = causal;
-    p.alibi = alibi_slopes;
-    p.out_planes = static_cast<unsigned char *>(out_planes); p.out_scale = out_scale; p.v_bound = v_bound;
-    p.v_bound_dev = v_bound_dev; p.v_bound_stride = v_bound_stride; p.cols_per_clip = v_bound_dev ? cols_per_clip : (cols > 0 ? cols : 1);
+    p.q = d->q; p.k = d->k; p.v = d->v; p.out = d->out; p.ldq = d->ldq; p.ldkv = d->ldkv; p.ldo = d->ldo; p.cols = cols; p.T = T;
+    p.heads = heads; p.q_scale = d->q_scale; p.k_scale = d->k_scale; p.scale = d->scale; p.causal = causal;
+    p.alibi = d->alibi_slopes;
+    p.out_planes = static_cast<unsigned char *>(out_planes); p.out_scale = d->out_scale; p.v_bound = d->v_bound;
+    p.v_bound_dev = d->v_bound_dev; p.v_bound_stride = d->v_bound_stride; p.cols_per_clip = attn_clip_seqs(*d);
     const int64_t threads = cols * heads * 16;
     if (threads == 0) return OMNITOK_OK;
     const dim3 grid((unsigned)((threads + 255) / 256));

@@ -10,9 +10,9 @@
 //     temporal_fused5         T' = 5, causal, plane: stats_pack_temporal -> gemm_pl PL_TSCORE (q|k) -> gemm_pl PL_TPV (V)
 //     produce_qkv             plane: stats_pack -> gemm_pl (packing epilogues q|k + V | fp32 q|k|v, per chunk with
 //                             "temporal_chunk") | row_stats -> eg_gemm merged q|k|v [V planes] | layernorm -> eg_gemm q, kv
-//     run_attention           spatial: [attn_pack] -> attn_spatial_h2_planes | qk_prep -> attn_spatial; temporal: attn_temporal_planes
+//     run_attention           spatial: [attn_pack] -> attn_spatial_h2 | qk_prep -> attn_spatial; temporal: attn_temporal
 //     out-projection          plane: [pack_rows] -> gemm_out_pl (+ residual, LayerNorm planes of the FeedForward) | eg_gemm
-//   window_block 'w'          plane: stats_pack_windows -> gemm_pl q|k + V -> attn_window_h2 | stats_pack -> gemm_pl -> attn_window_planes
+//   window_block 'w'          plane: stats_pack_windows -> gemm_pl q|k + V -> attn_window_h2 | stats_pack -> gemm_pl -> attn_window (planes)
 //                             | row_stats / layernorm -> eg_gemm -> attn_window; out-projection as above
 //   feed_forward              plane: [layernorm -> pack_rows] -> gemm_pl GEGLU -> gemm_pl (+ residual) | row_stats / layernorm -> eg_gemm x 2
 //   norm_out                  layernorm_planes (to_pixels) | layernorm_prevq (encoder end) | layernorm_transposed | layernorm
@@ -203,6 +203,16 @@ struct Run {
         g.M = L;
         g.K = D;
         return g;
+    }
+    // the fields the attention calls of a 't' block share: fp32 q | k|v rows, the q/k scales, the ranges of q, k and (per clip)
+    // of V = of the output, the output as fp32 rows (AO) and, with `planes`, as planes (AO) with row scales (ST)
+    omnitok_attn_desc attn_base(const Layer &ly, const TBlock &t, float *Q, float *KV, bool planes) const {
+        omnitok_attn_desc a{};
+        a.q = Q; a.ldq = D; a.k = KV; a.v = KV + D; a.ldkv = 2 * D;
+        a.q_scale = ly.t.q_scale; a.k_scale = ly.t.k_scale; a.scale = 8.0f; a.heads = heads;
+        a.q_bound = t.qb; a.k_bound = t.kb; a.v_bound = t.ab_ao.stat; a.v_bound_dev = t.ab_ao.dev; a.v_bound_stride = 2;
+        a.out = e->AO.p; a.ldo = D; a.out_planes = planes ? e->AO.p : nullptr; a.out_scale = planes ? e->ST.p : nullptr;
+        return a;
     }
 
     void decide_flow();
@@ -582,10 +592,11 @@ int Run::produce_qkv_chunked(const Layer &ly, const TBlock &t, const omnitok_pl_
         gc.M = Lc;
         OT_RUN("gemm_qkv", 2.0 * (double)Lc * D * 3 * D, omnitok_gemm_pl(&gc, stream));
         // out_scale rows [r0, r0 + Lc) of ST: behind every (mean, rstd) pair a later chunk still reads
-        OT_RUN("attn_temporal", 4.0 * Lc * D * 4.0,
-               omnitok_attn_temporal_planes(Qc, D, KVc, KVc + D, 2 * D, nullptr, D, reinterpret_cast<char *>(e->AO.p) + pl_off,
-                                            e->ST.p + r0, t.ab_ao.stat, t.ab_ao.dev + 2 * c0, 2, S, (int64_t)nb * S, T, heads,
-                                            ly.t.q_scale, ly.t.k_scale, 8.0f, c.causal_temporal, alibi, stream));
+        omnitok_attn_desc a = attn_base(ly, t, Qc, KVc, true);
+        a.out = nullptr; a.out_planes = reinterpret_cast<char *>(e->AO.p) + pl_off; a.out_scale = e->ST.p + r0;
+        a.v_bound_dev = t.ab_ao.dev + 2 * c0; a.seqs = (int64_t)nb * S; a.seqs_per_clip = S; a.n_tokens = T;
+        a.causal = c.causal_temporal; a.alibi_slopes = alibi;
+        OT_RUN("attn_temporal", 4.0 * Lc * D * 4.0, omnitok_attn_temporal(&a, stream));
     }
     st.temporal_done = true;
     st.ao_planes = true;
@@ -593,8 +604,6 @@ int Run::produce_qkv_chunked(const Layer &ly, const TBlock &t, const omnitok_pl_
 }
 
 int Run::run_attention(const Layer &ly, const TBlock &t, QkvState &st) {
-    float *Q = t.Q, *KV = t.KV;
-    const int64_t ldq = D, ldkv = 2 * D;
     if (spatial) {
         const float *cosp = nullptr, *sinp = nullptr;
         if (c.spatial_rope)
@@ -602,30 +611,31 @@ int Run::run_attention(const Layer &ly, const TBlock &t, QkvState &st) {
         const float *bias = nullptr;
         if (!ly.t.bias_prefix.empty())
             if (int rc = get_bias_table(e, ly.t.bias_prefix, gh, gw, &bias, stream)) return rc;
+        // Two launches, one descriptor each.  prep (RoPE + l2norm + scales of q and k; with attn_h2 also the packing) has the
+        // rows, scales and ranges of attn_base and no output; a (the attention kernel) adds the bias and keeps the output
+        omnitok_attn_desc prep = attn_base(ly, t, t.Q, t.KV, false), a = attn_base(ly, t, t.Q, t.KV, pl && t.attn_h2);
+        prep.seqs = a.seqs = (int64_t)B * T; prep.seqs_per_clip = a.seqs_per_clip = T; prep.n_tokens = a.n_tokens = S;
+        prep.rope_cos = cosp; prep.rope_sin = sinp; prep.out = nullptr;
+        a.bias_table = bias; a.gh = gh; a.gw = gw;
         if (t.attn_h2) {
-            if (!st.qk_packed)
-                OT_RUN("qk_prep", (st.vpacked ? 4.0 : 6.0) * L * D * 4.0,
-                       omnitok_attn_pack(Q, ldq, KV, st.vpacked ? nullptr : KV + D, ldkv, L, S, heads, cosp, sinp, ly.t.q_scale,
-                                         ly.t.k_scale, 8.0f, t.qb, t.kb, t.ab_ao.stat, t.ab_ao.dev, 2, t.rpc, t.p.qp, t.p.kp,
-                                         st.vpacked ? nullptr : t.p.vp, stream));
-            OT_RUN("attn_spatial", 4.0 * (double)B * T * heads * (double)S * S * 64.0,
-                   omnitok_attn_spatial_h2_planes(t.p.qp, t.p.kp, t.p.vp, e->AO.p, D, pl ? e->AO.p : nullptr,
-                                                  pl ? e->ST.p : nullptr, B * T, S, heads, t.qb, t.kb, t.ab_ao.stat, t.ab_ao.dev,
-                                                  2, T, bias, gh, gw, stream));
+            a.qp = prep.qp = t.p.qp; a.kp = prep.kp = t.p.kp; a.vp = t.p.vp;
+            if (st.vpacked) prep.v = nullptr;  // the q|k|v launch wrote the V planes: pack q and k only
+            else prep.vp = t.p.vp;
+            if (!st.qk_packed) OT_RUN("qk_prep", (st.vpacked ? 4.0 : 6.0) * L * D * 4.0, omnitok_attn_pack(&prep, stream));
+            a.q = a.k = nullptr; a.v = nullptr;  // attn_spatial_h2 reads the planes only (and refuses the fp32 rows)
+            OT_RUN("attn_spatial", 4.0 * (double)B * T * heads * (double)S * S * 64.0, omnitok_attn_spatial_h2(&a, stream));
             st.ao_planes = pl;
         } else {
-            OT_RUN("qk_prep", 4.0 * L * D * 4.0,
-                   omnitok_qk_prep(Q, ldq, KV, ldkv, L, S, heads, cosp, sinp, ly.t.q_scale, ly.t.k_scale, 8.0f, stream));
-            OT_RUN("attn_spatial", 4.0 * (double)B * T * heads * (double)S * S * 64.0,
-                   omnitok_attn_spatial(Q, ldq, KV, KV + D, ldkv, e->AO.p, D, B * T, S, heads, bias, gh, gw, stream));
+            OT_RUN("qk_prep", 4.0 * L * D * 4.0, omnitok_qk_prep(&prep, stream));
+            OT_RUN("attn_spatial", 4.0 * (double)B * T * heads * (double)S * S * 64.0, omnitok_attn_spatial(&a, stream));
         }
     } else if (!st.temporal_done) {
         const float *alibi = (c.legacy_attention && c.causal_temporal) ? e->alibi : nullptr;
         const bool tp = pl && t.bs && T <= 17 && S % 16 == 0;
-        OT_RUN("attn_temporal", 4.0 * L * D * 4.0,
-               omnitok_attn_temporal_planes(Q, ldq, KV, KV + D, ldkv, e->AO.p, D, tp ? e->AO.p : nullptr, tp ? e->ST.p : nullptr,
-                                            t.ab_ao.stat, t.ab_ao.dev, 2, S, (int64_t)B * S, T, heads, ly.t.q_scale, ly.t.k_scale,
-                                            8.0f, c.causal_temporal, alibi, stream));
+        omnitok_attn_desc a = attn_base(ly, t, t.Q, t.KV, tp);
+        a.seqs = (int64_t)B * S; a.seqs_per_clip = S; a.n_tokens = T;
+        a.causal = c.causal_temporal; a.alibi_slopes = alibi;
+        OT_RUN("attn_temporal", 4.0 * L * D * 4.0, omnitok_attn_temporal(&a, stream));
         st.ao_planes = tp;
     }
     return OMNITOK_OK;
@@ -634,6 +644,8 @@ int Run::run_attention(const Layer &ly, const TBlock &t, QkvState &st) {
 // 'w' block: 8 x 8 window attention (reference attention.py:254-293), q, k, v all from LN(x)
 int Run::window_block(const Layer &ly) {
     const auto okb = [](float v) { return v > 0.0f && v < 1e30f; };
+    omnitok_attn_desc a{};  // what the three forms of the attention call share
+    a.bias_dense = ly.w.bias_dense; a.seqs = (int64_t)B * T; a.gh = gh; a.gw = gw; a.heads = heads;
     if (pl && g_qkv_pl && g_attn_window_mode == 1 && ly.w.wqkv_fold && e->plw.count(ly.w.wqkv_fold) && c.window_size == 8 &&
         gh % 8 == 0 && gw % 8 == 0 && c.dim_head == 64 && okb(ly.w.q_bound) && okb(ly.w.k_bound) && okb(ly.w.ao_bound)) {
         // Window attention on packed operands (reference attention.py:254-293): the centred rows go out in
@@ -672,9 +684,9 @@ int Run::window_block(const Layer &ly) {
         v.heads = heads;
         v.v_bound = ly.w.ao_bound;
         OT_RUN("gemm_qkv", gemm_f * D, omnitok_gemm_pl(&v, stream));
-        OT_RUN("attn_window", 4.0 * (double)L * 64.0 * D,
-               omnitok_attn_window_h2(p.qp, p.kp, p.vp, ly.w.bias_dense, nullptr, 0, e->AO.p, ly.w.q_bound, ly.w.k_bound,
-                                      ly.w.ao_bound, B * T, gh, gw, heads, stream));
+        a.qp = p.qp; a.kp = p.kp; a.vp = p.vp; a.out_planes = e->AO.p;
+        a.q_bound = ly.w.q_bound; a.k_bound = ly.w.k_bound; a.v_bound = ly.w.ao_bound;
+        OT_RUN("attn_window", 4.0 * (double)L * 64.0 * D, omnitok_attn_window_h2(&a, stream));
         return gemm_out_pl(ly, e->AO.p, nullptr, omnitok_pl_unscale(ly.w.ao_bound), ly.w.wproj, ly.w.bproj);
     }
     if (pl && g_qkv_pl && ly.w.wqkv_fold && e->plw.count(ly.w.wqkv_fold)) {
@@ -707,14 +719,14 @@ int Run::window_block(const Layer &ly) {
         }
         OT_RUN("gemm_qkv", gemm_f * 3 * D, eg_gemm(e, g, stream));
     }
+    a.q = e->QKV.p; a.ldq = 3 * D;  // fp32 q|k|v: the fused rows go in q
     if (pl && ly.w.ao_bound > 0.0f) {
-        OT_RUN("attn_window", 4.0 * (double)L * 64.0 * D,
-               omnitok_attn_window_planes(e->QKV.p, 3 * D, ly.w.bias_dense, nullptr, 0, e->AO.p, ly.w.ao_bound, B * T, gh, gw, heads,
-                                          stream));
+        a.out_planes = e->AO.p; a.out_bound = ly.w.ao_bound;
+        OT_RUN("attn_window", 4.0 * (double)L * 64.0 * D, omnitok_attn_window(&a, stream));
         return gemm_out_pl(ly, e->AO.p, nullptr, omnitok_pl_unscale(ly.w.ao_bound), ly.w.wproj, ly.w.bproj);
     }
-    OT_RUN("attn_window", 4.0 * (double)L * 64.0 * D,
-           omnitok_attn_window(e->QKV.p, 3 * D, ly.w.bias_dense, e->AO.p, D, B * T, gh, gw, heads, stream));
+    a.out = e->AO.p; a.ldo = D;
+    OT_RUN("attn_window", 4.0 * (double)L * 64.0 * D, omnitok_attn_window(&a, stream));
     EgGemm g;
     g.a = e->AO.p; g.lda = D;
     g.w = ly.w.wproj; g.ldw = D;

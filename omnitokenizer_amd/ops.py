@@ -66,6 +66,14 @@ def _row_gemm(x, out, M, N, K, ldc, flags, **fields):
     return g
 
 
+def _attn(entry, what, **fields):
+    """Calls the attention entry point `entry` with an omnitok_attn_desc; a tensor among `fields` is passed as its device pointer."""
+    d = _lib.OmnitokAttnDesc()
+    for name, v in fields.items():
+        setattr(d, name, v.data_ptr() if isinstance(v, torch.Tensor) else v)
+    check(getattr(_lib.load(), entry)(ctypes.byref(d), _stream()), what)
+
+
 def _ln_fields(ln, K, ln_cols):
     """ln = (stats, gamma, beta|None) or None -> the fused-LayerNorm fields of omnitok_row_gemm."""
     st, g, b = ln if ln is not None else (None, None, None)
@@ -351,16 +359,11 @@ def attn_window_h2(qp, kp, vp, bias_dense, q_bound, k_bound, v_bound, Bn, gh, gw
     """Window attention from packed operands (omnitok_attn_window_h2): fp32 [Bn * gh * gw, heads * 64] in token order, or with
     planes=True the hi|lo planes of it (scaled by the power of two of v_bound)."""
     rows = Bn * gh * gw
-    if planes:
-        out = torch.empty(_pad256(rows) * heads * 64, device=qp.device, dtype=torch.int32)
-        check(_lib.load().omnitok_attn_window_h2(_p(qp), _p(kp), _p(vp), _p(_req(bias_dense, "bias_dense")), None, 0, _p(out),
-                                                 float(q_bound), float(k_bound), float(v_bound), Bn, gh, gw, heads, _stream()),
-              "attn_window_h2")
-        return out
-    out = torch.empty(rows, heads * 64, device=qp.device, dtype=torch.float32)
-    check(_lib.load().omnitok_attn_window_h2(_p(qp), _p(kp), _p(vp), _p(_req(bias_dense, "bias_dense")), _p(out), heads * 64, None,
-                                             float(q_bound), float(k_bound), float(v_bound), Bn, gh, gw, heads, _stream()),
-          "attn_window_h2")
+    out = torch.empty(_pad256(rows) * heads * 64, device=qp.device, dtype=torch.int32) if planes else \
+        torch.empty(rows, heads * 64, device=qp.device, dtype=torch.float32)
+    dst = dict(out_planes=out) if planes else dict(out=out, ldo=heads * 64)
+    _attn("omnitok_attn_window_h2", "attn_window_h2", qp=qp, kp=kp, vp=vp, bias_dense=_req(bias_dense, "bias_dense"),
+          q_bound=float(q_bound), k_bound=float(k_bound), v_bound=float(v_bound), seqs=Bn, gh=gh, gw=gw, heads=heads, **dst)
     return out
 
 
@@ -467,19 +470,17 @@ def attn_spatial_h2_planes(packed, bounds, Bn, N, heads, bias_table=None, gh=0, 
     """attn_spatial_h2 with the output as (planes, row scales) of K = heads * 64 (the to_out GEMM's operand)."""
     planes = torch.empty(_pad256(Bn * N) * heads * 64, device=packed.device, dtype=torch.int32)
     scales = torch.empty(Bn * N, device=packed.device, dtype=torch.float32)
-    check(_lib.load().omnitok_attn_spatial_h2_planes(_p(packed[0]), _p(packed[1]), _p(packed[2]), None, 0, _p(planes),
-                                                     _p(scales), Bn, N, heads, bounds[0], bounds[1], bounds[2],
-                                                     _p(v_bound_dev), v_bound_stride, seq_per_clip, _p(bias_table), gh, gw,
-                                                     _stream()), "attn_spatial_h2_planes")
+    _attn("omnitok_attn_spatial_h2", "attn_spatial_h2_planes", qp=packed[0], kp=packed[1], vp=packed[2], out_planes=planes,
+          out_scale=scales, seqs=Bn, n_tokens=N, heads=heads, q_bound=bounds[0], k_bound=bounds[1], v_bound=bounds[2],
+          v_bound_dev=v_bound_dev, v_bound_stride=v_bound_stride, seqs_per_clip=seq_per_clip, bias_table=bias_table, gh=gh, gw=gw)
     return planes, scales
 
 
 def attn_window_planes(qkv, bias_dense, Bn, gh, gw, heads, out_bound):
     qkv = _req(qkv, "qkv")
     planes = torch.empty(_pad256(qkv.shape[0]) * heads * 64, device=qkv.device, dtype=torch.int32)
-    check(_lib.load().omnitok_attn_window_planes(_p(qkv), qkv.shape[1], _p(_req(bias_dense, "bias_dense")), None, 0,
-                                                 _p(planes), float(out_bound), Bn, gh, gw, heads, _stream()),
-          "attn_window_planes")
+    _attn("omnitok_attn_window", "attn_window_planes", q=qkv, ldq=qkv.shape[1], bias_dense=_req(bias_dense, "bias_dense"),
+          out_planes=planes, out_bound=float(out_bound), seqs=Bn, gh=gh, gw=gw, heads=heads)
     return planes
 
 
@@ -488,10 +489,10 @@ def attn_temporal_planes(q, k, v, cols, T, heads, q_scale, k_scale, causal, v_bo
     assert k.stride(0) == v.stride(0)
     planes = torch.empty(_pad256(q.shape[0]) * heads * 64, device=q.device, dtype=torch.int32)
     scales = torch.empty(q.shape[0], device=q.device, dtype=torch.float32)
-    check(_lib.load().omnitok_attn_temporal_planes(_p(q), q.stride(0), _p(k), _p(v), k.stride(0), None, 0, _p(planes),
-                                                   _p(scales), float(v_bound), _p(v_bound_dev), v_bound_stride,
-                                                   cols_per_clip, cols, T, heads, _p(q_scale), _p(k_scale), scale,
-                                                   int(bool(causal)), _p(alibi), _stream()), "attn_temporal_planes")
+    _attn("omnitok_attn_temporal", "attn_temporal_planes", q=q, ldq=q.stride(0), k=k, v=v, ldkv=k.stride(0), out_planes=planes,
+          out_scale=scales, v_bound=float(v_bound), v_bound_dev=v_bound_dev, v_bound_stride=v_bound_stride,
+          seqs_per_clip=cols_per_clip, seqs=cols, n_tokens=T, heads=heads, q_scale=q_scale, k_scale=k_scale, scale=scale,
+          causal=int(bool(causal)), alibi_slopes=alibi)
     return planes, scales
 
 
@@ -578,17 +579,19 @@ def qk_prep_(q, k, n_tokens, heads, q_scale, k_scale, cos=None, sin=None, scale=
     assert q.dim() == 2 and k.dim() == 2 and q.stride(1) == 1 and k.stride(1) == 1
     _opt(cos, "cos", n_tokens * 32)
     _opt(sin, "sin", n_tokens * 32)
-    check(_lib.load().omnitok_qk_prep(_p(q), q.stride(0), _p(k), k.stride(0), q.shape[0], n_tokens, heads, _p(cos),
-                                      _p(sin), _p(_req(q_scale, "q_scale")), _p(_req(k_scale, "k_scale")), scale,
-                                      _stream()), "qk_prep")
+    if n_tokens <= 0 or q.shape[0] % n_tokens:   # the descriptor counts whole sequences
+        raise ValueError(f"qk_prep: {q.shape[0]} rows are no whole number of {n_tokens}-token sequences")
+    _attn("omnitok_qk_prep", "qk_prep", q=q, ldq=q.stride(0), k=k, ldkv=k.stride(0), seqs=q.shape[0] // n_tokens,
+          n_tokens=n_tokens, heads=heads, rope_cos=cos, rope_sin=sin, q_scale=_req(q_scale, "q_scale"),
+          k_scale=_req(k_scale, "k_scale"), scale=scale)
 
 
 def attn_spatial(q, k, v, Bn, N, heads, bias_table=None, gh=0, gw=0):
     """q [Bn*N, heads*64]; k, v: [Bn*N, heads*64] views sharing one row stride."""
     assert k.stride(0) == v.stride(0) and q.stride(1) == 1
     out = torch.empty(q.shape[0], heads * 64, device=q.device, dtype=torch.float32)
-    check(_lib.load().omnitok_attn_spatial(_p(q), q.stride(0), _p(k), _p(v), k.stride(0), _p(out), heads * 64, Bn, N,
-                                           heads, _p(bias_table), gh, gw, _stream()), "attn_spatial")
+    _attn("omnitok_attn_spatial", "attn_spatial", q=q, ldq=q.stride(0), k=k, v=v, ldkv=k.stride(0), out=out, ldo=heads * 64,
+          seqs=Bn, n_tokens=N, heads=heads, bias_table=bias_table, gh=gh, gw=gw)
     return out
 
 
@@ -611,10 +614,14 @@ def attn_pack(q, k, v, n_tokens, heads, q_scale, k_scale, cos=None, sin=None, sc
     _opt(v_bound_dev, "v_bound_dev")
     _opt(cos, "cos", n_tokens * 32)
     _opt(sin, "sin", n_tokens * 32)
-    check(_lib.load().omnitok_attn_pack(_p(q), q.stride(0), _p(k), _p(v), k.stride(0), rows, n_tokens, heads, _p(cos),
-                                        _p(sin), _p(q_scale), _p(k_scale), scale, q_bound, k_bound, v_bound,
-                                        _p(v_bound_dev), v_bound_stride, rows_per_clip, _p(packed[0]), _p(packed[1]),
-                                        _p(packed[2]), _stream()), "attn_pack")
+    if n_tokens <= 0 or rows % n_tokens:
+        raise ValueError(f"attn_pack: {rows} rows of {n_tokens}-token sequences")
+    if v_bound_dev is not None and rows_per_clip % n_tokens:
+        raise ValueError("attn_pack: rows_per_clip must be a whole number of sequences")
+    _attn("omnitok_attn_pack", "attn_pack", q=q, ldq=q.stride(0), k=k, v=v, ldkv=k.stride(0), seqs=rows // n_tokens,
+          n_tokens=n_tokens, heads=heads, rope_cos=cos, rope_sin=sin, q_scale=q_scale, k_scale=k_scale, scale=scale,
+          q_bound=q_bound, k_bound=k_bound, v_bound=v_bound, v_bound_dev=v_bound_dev, v_bound_stride=v_bound_stride,
+          seqs_per_clip=rows_per_clip // n_tokens, qp=packed[0], kp=packed[1], vp=packed[2])
     return packed, (q_bound, k_bound, v_bound)
 
 
@@ -622,26 +629,26 @@ def attn_spatial_h2(packed, bounds, Bn, N, heads, bias_table=None, gh=0, gw=0, v
                     seq_per_clip=0):
     """softmax(q k^T [+ bias]) v on the fp16 matrix cores from the operands of attn_pack -> [Bn*N, heads*64]."""
     out = torch.empty(Bn * N, heads * 64, device=packed.device, dtype=torch.float32)
-    check(_lib.load().omnitok_attn_spatial_h2(_p(packed[0]), _p(packed[1]), _p(packed[2]), _p(out), heads * 64, Bn, N,
-                                              heads, bounds[0], bounds[1], bounds[2], _p(v_bound_dev), v_bound_stride,
-                                              seq_per_clip, _p(bias_table), gh, gw, _stream()), "attn_spatial_h2")
+    _attn("omnitok_attn_spatial_h2", "attn_spatial_h2", qp=packed[0], kp=packed[1], vp=packed[2], out=out, ldo=heads * 64,
+          seqs=Bn, n_tokens=N, heads=heads, q_bound=bounds[0], k_bound=bounds[1], v_bound=bounds[2], v_bound_dev=v_bound_dev,
+          v_bound_stride=v_bound_stride, seqs_per_clip=seq_per_clip, bias_table=bias_table, gh=gh, gw=gw)
     return out
 
 
 def attn_window(qkv, bias_dense, Bn, gh, gw, heads):
     qkv = _req(qkv, "qkv")
     out = torch.empty(qkv.shape[0], heads * 64, device=qkv.device, dtype=torch.float32)
-    check(_lib.load().omnitok_attn_window(_p(qkv), qkv.shape[1], _p(_req(bias_dense, "bias_dense")), _p(out),
-                                          heads * 64, Bn, gh, gw, heads, _stream()), "attn_window")
+    _attn("omnitok_attn_window", "attn_window", q=qkv, ldq=qkv.shape[1], bias_dense=_req(bias_dense, "bias_dense"), out=out,
+          ldo=heads * 64, seqs=Bn, gh=gh, gw=gw, heads=heads)
     return out
 
 
 def attn_temporal(q, k, v, cols, T, heads, q_scale, k_scale, causal, alibi=None, scale=8.0):
     assert k.stride(0) == v.stride(0)
     out = torch.empty(q.shape[0], heads * 64, device=q.device, dtype=torch.float32)
-    check(_lib.load().omnitok_attn_temporal(_p(q), q.stride(0), _p(k), _p(v), k.stride(0), _p(out), heads * 64, cols,
-                                            T, heads, _p(q_scale), _p(k_scale), scale, int(bool(causal)), _p(alibi),
-                                            _stream()), "attn_temporal")
+    _attn("omnitok_attn_temporal", "attn_temporal", q=q, ldq=q.stride(0), k=k, v=v, ldkv=k.stride(0), out=out, ldo=heads * 64,
+          seqs=cols, n_tokens=T, heads=heads, q_scale=q_scale, k_scale=k_scale, scale=scale, causal=int(bool(causal)),
+          alibi_slopes=alibi)
     return out
 
 

@@ -248,15 +248,16 @@ def test_new_entry_points_validate_arguments_without_gpu(lib):
     one = C.c_void_p(256)  # any non-null, 16-byte aligned value: the checks fire before it is dereferenced
     f = C.c_float
     # attn_pack: n_tokens not a multiple of 32; non-positive bounds
-    assert lib.omnitok_attn_pack(one, 512, one, one, 1024, 48, 48, 8, None, None, one, one, f(8.0), f(8.0), f(1.0), f(1.0),
-                                 None, 0, 0, one, one, one, None) == -1
+    pack = dict(q=256, ldq=512, k=256, v=256, ldkv=1024, seqs=1, heads=8, q_scale=256, k_scale=256, scale=8.0, q_bound=8.0,
+                k_bound=1.0, v_bound=1.0, qp=256, kp=256, vp=256)
+    assert lib.omnitok_attn_pack(C.byref(_attn_desc(**pack, n_tokens=48)), None) == -1
     assert b"attn_pack" in lib.omnitok_last_error()
-    assert lib.omnitok_attn_pack(one, 512, one, one, 1024, 64, 64, 8, None, None, one, one, f(8.0), f(0.0), f(1.0), f(1.0),
-                                 None, 0, 0, one, one, one, None) == -1
-    assert b"bounds" in lib.omnitok_last_error()
+    for bound in ("q_bound", "k_bound"):
+        assert lib.omnitok_attn_pack(C.byref(_attn_desc(**{**pack, "n_tokens": 64, bound: 0.0})), None) == -1
+        assert b"bounds" in lib.omnitok_last_error()
     # attn_spatial_h2: N not a multiple of 64
-    assert lib.omnitok_attn_spatial_h2(one, one, one, one, 512, 1, 96, 8, f(8.0), f(1.0), f(1.0), None, 0, 0, None, 0, 0,
-                                       None) == -1
+    h2 = _attn_desc(qp=256, kp=256, vp=256, out=256, ldo=512, seqs=1, n_tokens=96, heads=8, q_bound=8.0, k_bound=1.0, v_bound=1.0)
+    assert lib.omnitok_attn_spatial_h2(C.byref(h2), None) == -1
     # lm_select: non-positive temperature, sampling without uniforms, top_p <= 0
     assert lib.omnitok_lm_select(one, None, 1, 100, f(0.0), f(1.0), f(0.0), -1, f(1.0), 0, None, one, None, None, None) == -1
     assert b"temperature" in lib.omnitok_last_error()
@@ -333,6 +334,105 @@ def test_row_gemm_vpack_entry_point_is_gone(lib):
     # v_planes under a precondition the packed-V epilogue does not meet (a flag set) is refused, as before
     g = _row_gemm("omnitok_gemm_h2", v_planes=256, flags=1, bias=256)
     assert lib.omnitok_gemm_h2(ctypes.byref(g), None) == -1 and b"packed-V" in lib.omnitok_last_error()
+
+
+def _attn_desc(**fields):
+    from omnitokenizer_amd._lib import OmnitokAttnDesc
+    return OmnitokAttnDesc(**fields)
+
+
+# per entry point: a descriptor that passes every argument check (pointers are a non-null, 16-byte aligned dummy: every check
+# fires before a dereference)
+_ROWS = dict(q=256, ldq=128, k=256, v=256, ldkv=256)
+_PLANES = dict(qp=256, kp=256, vp=256)
+_PREP = dict(q_scale=256, k_scale=256, scale=8.0)
+_BOUNDS = dict(q_bound=8.0, k_bound=1.0, v_bound=1.0)
+_OUT = dict(out=256, ldo=128)
+ATTN_OK = {
+    "omnitok_qk_prep": dict(**_ROWS, **_PREP, seqs=1, n_tokens=64, heads=2),
+    "omnitok_attn_pack": dict(**_ROWS, **_PLANES, **_PREP, **_BOUNDS, seqs=1, n_tokens=64, heads=2),
+    "omnitok_attn_spatial": dict(**_ROWS, **_OUT, seqs=1, n_tokens=64, heads=2),
+    "omnitok_attn_spatial_h2": dict(**_PLANES, **_BOUNDS, **_OUT, seqs=1, n_tokens=64, heads=2),
+    "omnitok_attn_window": dict(q=256, ldq=384, bias_dense=256, **_OUT, seqs=1, gh=8, gw=8, heads=2),
+    "omnitok_attn_window_h2": dict(**_PLANES, **_BOUNDS, bias_dense=256, **_OUT, seqs=1, gh=8, gw=8, heads=2),
+    "omnitok_attn_temporal": dict(**_ROWS, **_PREP, **_OUT, seqs=16, n_tokens=5, heads=2, causal=1),
+}
+
+
+def _attn_call(lib, name, **fields):
+    """(status, message) of entry point `name` on ATTN_OK[name] with `fields` replaced."""
+    rc = getattr(lib, name)(ctypes.byref(_attn_desc(**{**ATTN_OK[name], **fields})), None)
+    return rc, lib.omnitok_last_error()
+
+
+@pytest.mark.parametrize("name,fields,echo", [
+    ("omnitok_attn_spatial", dict(bias_table=256, gh=3, gw=5), b"bias grid 3x5 != N=64"),
+    ("omnitok_attn_spatial_h2", dict(bias_table=256, gh=3, gw=5), b"bias grid 3x5 != N=64"),
+    ("omnitok_attn_window", dict(gh=12, gw=8), b"grid 12x8"),
+    ("omnitok_attn_window_h2", dict(gh=12, gw=8), b"grid 12x8"),
+    ("omnitok_attn_temporal", dict(n_tokens=0), b"T=0"),
+    ("omnitok_attn_pack", dict(n_tokens=48), b"48 rows of 48-token"),
+    ("omnitok_qk_prep", dict(ldq=6), b"unaligned")])
+def test_attn_descriptor_layout(lib, name, fields, echo):
+    """omnitok_attn_desc through ctypes: fields late in the struct (the geometry sits behind every pointer, float and int64) land
+    where the C struct has them -- the message of the check they fail echoes them."""
+    rc, err = _attn_call(lib, name, **fields)
+    assert rc == -1 and echo in err and name[len("omnitok_"):].encode() + b":" in err, err
+
+
+@pytest.mark.parametrize("name", sorted(ATTN_OK))
+def test_attn_null_descriptor_and_operand_refused(lib, name):
+    """A NULL descriptor and a NULL required operand are refused before the first HIP call."""
+    short = name[len("omnitok_"):].encode()
+    assert getattr(lib, name)(None, None) == -1
+    assert short + b": null descriptor" in lib.omnitok_last_error()
+    for operand in ("q", "qp"):
+        if operand in ATTN_OK[name]:
+            rc, err = _attn_call(lib, name, **{operand: None})
+            assert rc == -1 and short + b": null pointer" in err, err
+    if "out" in ATTN_OK[name]:
+        rc, err = _attn_call(lib, name, out=None)
+        assert rc == -1 and short + b": null pointer" in err, err
+
+
+ATTN_REFUSED = {
+    "omnitok_attn_spatial": "qp kp vp out_planes bias_dense alibi_slopes causal",
+    "omnitok_attn_spatial_h2": "q k v bias_dense alibi_slopes causal",
+    "omnitok_attn_window": "k v qp kp vp bias_table alibi_slopes causal v_bound_dev",
+    "omnitok_attn_window_h2": "q k v bias_table alibi_slopes causal v_bound_dev",
+    "omnitok_attn_temporal": "qp kp vp bias_table bias_dense rope_cos rope_sin",
+    "omnitok_qk_prep": "bias_table bias_dense alibi_slopes causal out out_planes",
+    "omnitok_attn_pack": "bias_table bias_dense alibi_slopes causal out out_planes",
+}
+
+
+@pytest.mark.parametrize("name,field", [(n, f) for n, fs in sorted(ATTN_REFUSED.items()) for f in fs.split()])
+def test_attn_refuses_fields_the_kernel_does_not_implement(lib, name, field):
+    rc, err = _attn_call(lib, name, **{field: 256})
+    assert rc == -1 and f"{name[len('omnitok_'):]}: {field} is set".encode() in err, err
+
+
+def test_attn_planes_entry_points_are_gone(lib):
+    """The plane outputs are out_planes of the seven entry points; header, library and binding agree on the symbol set."""
+    from omnitokenizer_amd import _lib
+    hdr = open(os.path.join(ROOT, "include", "omnitok.h")).read()
+    raw = ctypes.CDLL(_lib.LIB_PATH)
+    for gone in ("omnitok_attn_spatial_h2_planes", "omnitok_attn_window_planes", "omnitok_attn_temporal_planes"):
+        assert gone not in _lib.EXPORTED_SYMBOLS and not hasattr(raw, gone) and gone not in hdr, gone
+    declared = set(re.findall(r"\b(omnitok_(?:attn[a-z0-9_]*|qk_prep))\s*\(", hdr))
+    assert declared == set(ATTN_OK)
+    assert declared == {n for n in _lib.EXPORTED_SYMBOLS if n.startswith("omnitok_attn") or n == "omnitok_qk_prep"}
+
+
+@pytest.mark.parametrize("name,fields,message", [
+    ("omnitok_attn_temporal", dict(out_planes=256, out_scale=256, v_bound=1.0, n_tokens=18),
+     b"attn_temporal: plane output needs out_scale, T <= 17, cols % 16 == 0 and a bound of |v|"),
+    ("omnitok_attn_window", dict(out_planes=256, out_bound=0.0), b"attn_window: plane output needs a bound"),
+    ("omnitok_attn_spatial_h2", dict(out_planes=256, out_scale=None), b"attn_spatial_h2: plane output needs out_scale")])
+def test_attn_plane_output_preconditions(lib, name, fields, message):
+    """out_planes selects what the _planes entry points did, under their preconditions and with their messages."""
+    rc, err = _attn_call(lib, name, **fields)
+    assert rc == -1 and message in err, err
 
 
 # every option a test or tool sets and then has to restore: the LM decode step's kernel choices and the stats_pack form
