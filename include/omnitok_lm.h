@@ -165,6 +165,36 @@ int omnitok_lm_prefill_format(omnitok_lm *lm); /* -1: null engine */
 int omnitok_lm_set_prefill_attention(omnitok_lm *lm, int mode);
 int omnitok_lm_prefill_attention(omnitok_lm *lm); /* -1: null engine */
 
+/* Operand format of the tiled prefill attention -- per engine, default OMNITOK_LM_AOP_FP32 (nothing below applies then: the bits of
+ * omnitok_lm_set_prefill_attention above).  With OMNITOK_LM_AOP_BF16 / _FP16 and OMNITOK_LM_PA_TILED the prefill runs
+ * omnitok_lm_attn_prefill16 (below) instead of omnitok_lm_attn_prefill: the same tiling with both products on the bf16 / fp16 MFMA
+ * (16 x the rate of the fp32-input one).  This is the arithmetic of attention under autocast: 16-bit operands, fp32 accumulation.
+ *   Rounded, each ONCE to lm_round16's bits (those of tensor.to(torch.bfloat16 / float16); a NaN stays a NaN, its payload is not
+ *     specified): every element of Q, K and V, where the kernel stages it (no packed copy of qkv, no workspace), and every softmax
+ *     weight P on its way into the P . V product.
+ *   fp32: the accumulation of both products, the scale, the running max, the running sum l (of the weights BEFORE their rounding),
+ *     the rescale, O and the division out = O / l.
+ *   "Same arithmetic as T decode steps" does NOT hold in this mode, neither to the bit nor to fp32 rounding: the results differ from
+ *     the fp32 modes' by the operand rounding (2^-9 relative per bf16 operand, 2^-12 per fp16 operand).  tests/lm_prefill_attn16_ref.py
+ *     derives the bar against fp64 attention over the rounded operands.
+ *   Deterministic: a row depends only on its position and its own stream's rows up to the end of its diagonal 32-key tile, and two
+ *     calls give equal values (the statement of omnitok_lm_attn_prefill, its one limit included).  Key tiles of KT = 32; the
+ *     exponential is v_exp_f32 on base-2 scores (log2(e) folded into the scale), documented error 1 ulp.
+ *   fp16 range: a Q, K or V element that rounds to +-inf raises bit 8 of the engine's flag word (omnitok_lm_overflowed).  bf16 has
+ *     fp32's range and never does.
+ *   Independent of the weight, cache and prefill formats and of max_streams: an fp32-weight engine may use it.  With OMNITOK_LM_PF_W16
+ *     the attention output is rounded once to the WEIGHT format, as before.  The K/V scatter (the cache holds the unrounded rows in
+ *     the cache format) and the decode step are unchanged.
+ *   With OMNITOK_LM_PA_ROWS and operands other than OMNITOK_LM_AOP_FP32, omnitok_lm_prefill, _prefill_ex and _prefill_loss return
+ *     OMNITOK_ERR_STATE with both switches named in the message: there is no fallback.
+ * omnitok_lm_set_prefill_attention_operands: -1 for a null engine or an unknown value (a refused value changes nothing); it touches
+ * neither `finalized`, the weights nor the cache, and applies from the next prefill on. */
+#define OMNITOK_LM_AOP_FP32 0
+#define OMNITOK_LM_AOP_BF16 1
+#define OMNITOK_LM_AOP_FP16 2
+int omnitok_lm_set_prefill_attention_operands(omnitok_lm *lm, int fmt);
+int omnitok_lm_prefill_attention_operands(omnitok_lm *lm); /* -1: null engine */
+
 /* K/V cache [n_layer][2][max_batch][n_head][max_len][head_dim] in the engine's cache format + step workspaces;
  * max_batch <= omnitok_lm_max_streams (16 unless raised), otherwise -1 with the limit in force in the message. */
 int omnitok_lm_alloc_cache(omnitok_lm *lm, int max_batch, int max_len);
@@ -201,7 +231,10 @@ int omnitok_lm_step_ex(omnitok_lm *lm, const int64_t *idx, const float *emb, con
  *      +-inf: the logits from there on are invalid.  An fp32 or bf16 cache never returns 2.
  *   4: an activation of an OMNITOK_LM_PF_W16 prefill on an fp16 engine (a LayerNorm row, a merged attention row or FC1's GELU
  *      output) left the fp16 range and entered its GEMM as +-inf: that prefill's logits and cache rows are invalid.  Never set by
- *      the default prefill format or a bf16 engine. */
+ *      the default prefill format or a bf16 engine.
+ *   8: a Q, K or V element of a prefill attention with OMNITOK_LM_AOP_FP16 operands left the fp16 range and entered its MFMA as
+ *      +-inf: that prefill's logits are invalid (the cache rows are stored unrounded and are not).  Never set by fp32 or bf16
+ *      operands. */
 int omnitok_lm_overflowed(omnitok_lm *lm, omnitok_stream_t stream);
 
 /* Batched prefill of a conditioning prefix into EMPTY streams (GPT.forward / the first
@@ -339,6 +372,20 @@ int omnitok_lm_attn_decode_kv16(const float *qkv, void *kc16, void *vc16, int fm
  * unsupported head_dim, both or neither output, or an unknown fmt with out16. */
 int omnitok_lm_attn_prefill(const float *qkv, int B, int T, int n_head, int head_dim, float *out32, void *out16, int fmt,
                             int *flag, omnitok_stream_t stream);
+/* The same attention with 16-bit operands (omnitok_lm_set_prefill_attention_operands): qkv, B, T, n_head, head_dim, out32 / out16 /
+ * out_fmt and the argument checks as omnitok_lm_attn_prefill; op_fmt = OMNITOK_LM_W_BF16 | _FP16 is the operand format (any other value:
+ * -1, "op_fmt" in the message).
+ * Arithmetic: every element of Q, K and V rounded ONCE to op_fmt (lm_round16's bits) where it is staged; score = (q . k) * (1 / sqrt(head_dim))
+ * with exact 16-bit products accumulated in fp32 on v_mfma_f32_32x32x16_bf16 / _f16, the scale applied to the finished dot (as ONE
+ * fp32 constant log2(e) / sqrt(head_dim): the scores are kept in base 2); keys after the query's position are -inf before the
+ * softmax; online softmax over key tiles of KT = 32 anchored at key 0 of the stream, ascending, with fp32 running max, sum and
+ * rescale; the weight is v_exp_f32 of an fp32 difference (documented error 1 ulp); l sums the weights BEFORE their rounding; P is
+ * rounded ONCE to op_fmt on its way into the P . V MFMA (fp32 accumulation); out = O / l, one division per element, fp32 or rounded
+ * once to out_fmt.  No atomics on the result, no split over keys across workgroups, no partials: needs no scratch.
+ * Determinism and the one limit (a non-finite V in a masked key of the diagonal tile): as omnitok_lm_attn_prefill.
+ * *flag (may be NULL): an fp16 OPERAND that rounds to +-inf ORs 8, an fp16 OUTPUT of +-inf ORs 4; bf16 sets neither. */
+int omnitok_lm_attn_prefill16(const float *qkv, int B, int T, int n_head, int head_dim, int op_fmt, float *out32, void *out16,
+                              int out_fmt, int *flag, omnitok_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -220,6 +220,8 @@ _PROTOS = {
     "omnitok_lm_prefill_format": [P],
     "omnitok_lm_set_prefill_attention": [P, c_int],
     "omnitok_lm_prefill_attention": [P],
+    "omnitok_lm_set_prefill_attention_operands": [P, c_int],
+    "omnitok_lm_prefill_attention_operands": [P],
     "omnitok_lm_set_max_streams": [P, c_int],
     "omnitok_lm_max_streams": [P],
     "omnitok_lm_cache_read": [P, c_int, c_int, c_int, c_int, P, P, P],
@@ -243,6 +245,7 @@ _PROTOS = {
     "omnitok_lm_attn_decode": [P, P, P, P, c_int, c_int, c_int, c_int, P, P, P],
     "omnitok_lm_attn_decode_kv16": [P, P, P, c_int, P, c_int, c_int, c_int, c_int, P, P, P],
     "omnitok_lm_attn_prefill": [P, c_int, c_int, c_int, c_int, P, P, c_int, P, P],
+    "omnitok_lm_attn_prefill16": [P, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P, P],
     "omnitok_pl_planes_bytes": [I64, c_int, c_int],
     "omnitok_pl_unscale": [c_float],
     "omnitok_pl_pack_weight": [P, I64, c_int, c_int, c_int, P, P, P],

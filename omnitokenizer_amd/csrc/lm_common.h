@@ -19,6 +19,8 @@
 //                     (fp32 or, for a PF_W16 prefill, 16-bit output), lm_kv_scatter_kernel, lm_kv_read_kernel, omnitok_lm_attn_decode[_kv16]
 //   lm_attn_prefill.hip  lm_attn_prefill_kernel (tiled causal attention of the prefill on the fp32-input MFMA, K/V tiles shared by 128
 //                     query rows; omnitok_lm_set_prefill_attention), omnitok_lm_attn_prefill
+//   lm_attn_prefill16.hip  lm_attn_prefill16_kernel (the same tiling on the bf16 / fp16 MFMA, Q / K / V / P rounded once to the operand
+//                     format; omnitok_lm_set_prefill_attention_operands), omnitok_lm_attn_prefill16
 //   lm_engine.hip     struct omnitok_lm and its exported functions (create .. finalize, alloc_cache, step, prefill, prefill_loss) and the
 //                     small kernels: embed, embed_seq, layernorm_rows (fp32 or 16-bit output, omnitok_lm_layernorm16), gelu, set_len,
 //                     advance, concat3, round_w16
@@ -121,6 +123,7 @@ template <> struct LmKV<float> {
 constexpr int LM_FLAG_PAST_CACHE = 1;  // bits of the engine's flag word (omnitok_lm_overflowed)
 constexpr int LM_FLAG_FP16_RANGE = 2;
 constexpr int LM_FLAG_PF16_RANGE = 4;  // an activation of an fp16 PF_W16 prefill rounded to +-inf
+constexpr int LM_FLAG_AOP16_RANGE = 8;  // a Q / K / V element of a prefill attention with fp16 operands rounded to +-inf
 
 struct LmMerge {
     const float *part;         // [B][n_head][nchunk][2 + hd]
@@ -219,6 +222,10 @@ int lm_kv_read(const void *kc, const void *vc, int kvfmt, int t0, int n, int n_h
 // the contract of omnitok_lm_attn_prefill, its argument checks included
 int lm_attn_prefill(const float *qkv, int B, int T, int n_head, int head_dim, float *out32, void *out16, int fmt, int *flag,
                     hipStream_t stream);
+// lm_attn_prefill16.hip.  The same attention with Q, K, V and P rounded once to op_fmt (OMNITOK_LM_W_BF16 | _FP16) on the 16-bit MFMA: the
+// contract of omnitok_lm_attn_prefill16, its argument checks included; an fp16 operand of +-inf raises LM_FLAG_AOP16_RANGE in *flag
+int lm_attn_prefill16(const float *qkv, int B, int T, int n_head, int head_dim, int op_fmt, float *out32, void *out16, int out_fmt, int *flag,
+                      hipStream_t stream);
 // lm_engine.hip.  y = nn.LayerNorm(x) over `rows` rows of K floats
 int lm_layernorm_rows(const float *x, const float *g, const float *beta, float *y, int64_t rows, int K, hipStream_t stream);
 // ... the same arithmetic, each value rounded to fmt (OMNITOK_LM_W_BF16 | _FP16) into y16; an fp16 +-inf raises LM_FLAG_PF16_RANGE in *flag

@@ -38,7 +38,7 @@ __global__ __launch_bounds__(256) void lm_embed_kernel(const int64_t *__restrict
 // ---- batched prefill of a conditioning prefix (the same arithmetic as T decode steps, as GEMMs; with OMNITOK_LM_PF_W16 the GEMMs run
 // on the 16-bit MFMA over activations rounded to the weight format instead: lm_gemm16.hip; with OMNITOK_LM_PA_TILED the attention runs
 // tiled on the fp32-input MFMA from qkv, lm_attn_prefill.hip, and "same arithmetic as T decode steps" holds to rounding, not to the
-// bit) ------
+// bit; with 16-bit attention operands on the bf16 / fp16 MFMA, lm_attn_prefill16.hip, and it no longer holds) ------
 // positions t < Te take the explicit embeddings emb[b, t] (prepended, gpt.py:214-216), the rest tok_emb[idx[b, t - Te]]
 __global__ __launch_bounds__(256) void lm_embed_seq_kernel(const int64_t *__restrict__ idx, const float *__restrict__ tok,
                                                            const float *__restrict__ pe, const float *__restrict__ emb,
@@ -205,6 +205,7 @@ struct omnitok_lm {
     int weight_format = OMNITOK_LM_W_FP32;  // of the matrices a decode step streams (omnitok_lm_set_weight_format)
     int prefill_format = OMNITOK_LM_PF_FP32;  // how the batched prefill runs its GEMMs (omnitok_lm_set_prefill_format)
     int prefill_attention = OMNITOK_LM_PA_ROWS;  // how the batched prefill runs its attention (omnitok_lm_set_prefill_attention)
+    int prefill_attention_operands = OMNITOK_LM_AOP_FP32;  // operand format of the tiled attention (omnitok_lm_set_prefill_attention_operands)
     LmMat head = {nullptr, nullptr, OMNITOK_LM_W_FP32};  // head.weight
     // cache + workspaces
     void *kv = nullptr;                       // [n_layer][2][max_batch][n_head][max_len][head_dim] elements of cache_format
@@ -357,6 +358,19 @@ extern "C" int omnitok_lm_set_prefill_attention(omnitok_lm *lm, int mode) {
 extern "C" int omnitok_lm_prefill_attention(omnitok_lm *lm) {
     OT_CHECK_ARG(lm, "lm_prefill_attention: null engine");
     return lm->prefill_attention;
+}
+
+extern "C" int omnitok_lm_set_prefill_attention_operands(omnitok_lm *lm, int fmt) {
+    OT_CHECK_ARG(lm, "lm_set_prefill_attention_operands: null engine");
+    OT_CHECK_ARG(fmt == OMNITOK_LM_AOP_FP32 || fmt == OMNITOK_LM_AOP_BF16 || fmt == OMNITOK_LM_AOP_FP16,
+                 "lm_set_prefill_attention_operands: unknown operands format %d", fmt);
+    lm->prefill_attention_operands = fmt;  // read at the next prefill: the weights, `finalized` and the cache are left alone
+    return OMNITOK_OK;
+}
+
+extern "C" int omnitok_lm_prefill_attention_operands(omnitok_lm *lm) {
+    OT_CHECK_ARG(lm, "lm_prefill_attention_operands: null engine");
+    return lm->prefill_attention_operands;
 }
 
 extern "C" int omnitok_lm_set_cache_format(omnitok_lm *lm, int fmt) {
@@ -563,7 +577,7 @@ extern "C" int omnitok_lm_overflowed(omnitok_lm *lm, omnitok_stream_t stream_) {
     OT_HIP(hipStreamSynchronize(stream));
     if (h)
         if (int rc = device_fill_u32(lm->err_flag, 0u, 1, stream)) return rc;
-    return h & (LM_FLAG_PAST_CACHE | LM_FLAG_FP16_RANGE | LM_FLAG_PF16_RANGE);
+    return h & (LM_FLAG_PAST_CACHE | LM_FLAG_FP16_RANGE | LM_FLAG_PF16_RANGE | LM_FLAG_AOP16_RANGE);
 }
 
 extern "C" int omnitok_lm_cache_read(omnitok_lm *lm, int layer, int b, int t0, int n, float *k_out, float *v_out,
@@ -691,6 +705,12 @@ static int lm_prefill_layers(omnitok_lm *lm, const int64_t *idx, int T_tok, cons
                   "format back to OMNITOK_LM_PF_FP32");
         return OMNITOK_ERR_STATE;
     }
+    if (lm->prefill_attention_operands != OMNITOK_LM_AOP_FP32 && lm->prefill_attention != OMNITOK_LM_PA_TILED) {
+        set_error("lm_prefill: 16-bit attention operands (omnitok_lm_set_prefill_attention_operands) need the tiled attention: set "
+                  "omnitok_lm_set_prefill_attention to OMNITOK_LM_PA_TILED (it is OMNITOK_LM_PA_ROWS), or the operands back to "
+                  "OMNITOK_LM_AOP_FP32");
+        return OMNITOK_ERR_STATE;
+    }
     if (!lm->kv || B > lm->max_batch || T > lm->max_len) {
         set_error("lm_prefill: cache not allocated for %d streams x %d tokens (omnitok_lm_alloc_cache)", B, T);
         return OMNITOK_ERR_STATE;
@@ -706,6 +726,11 @@ static int lm_prefill_layers(omnitok_lm *lm, const int64_t *idx, int T_tok, cons
     // no dependence on the cache format; "same arithmetic as T decode steps" then holds to rounding, not to the bit.  The scatter
     // stays in both modes: the decode steps after the prefill read the cache.
     const bool tiled = lm->prefill_attention == OMNITOK_LM_PA_TILED;
+    // ... with 16-bit operands (omnitok_lm_set_prefill_attention_operands; refused above without the tiled mode): lm_attn_prefill16, Q / K /
+    // V / P rounded once to that format on the bf16 / fp16 MFMA.  aop: 0, or the operand format as OMNITOK_LM_W_BF16 | _FP16
+    const int aop = lm->prefill_attention_operands == OMNITOK_LM_AOP_BF16   ? OMNITOK_LM_W_BF16
+                    : lm->prefill_attention_operands == OMNITOK_LM_AOP_FP16 ? OMNITOK_LM_W_FP16
+                                                                            : 0;
     // workspace: x | xn | att [M, C], qkv [M, 3C], hid [M, 4C], partials (rows mode)
     const int64_t need = M * C * 3 + M * 3 * C + M * 4 * C + (tiled ? 0 : M * c.n_head * nchunk * (2 + hd));
     if (int rc = lm_grow(reinterpret_cast<void **>(&lm->pf), &lm->pf_bytes, need * 4)) return rc;
@@ -729,7 +754,9 @@ static int lm_prefill_layers(omnitok_lm *lm, const int64_t *idx, int T_tok, cons
             if (int rc = lm_gemm16(xn, L.wqkv.w16, fmt, L.bqkv, nullptr, qkv, nullptr, M, 3 * C, C, 0, fl, stream)) return rc;
             if (int rc = lm_kv_scatter(qkv, kc, vc, lm->cache_format, M, T, c.n_head, hd, lm->max_len, lm->err_flag, stream)) return rc;
             if (tiled) {
-                if (int rc = lm_attn_prefill(qkv, B, T, c.n_head, hd, nullptr, att, fmt, fl, stream)) return rc;
+                if (aop) {
+                    if (int rc = lm_attn_prefill16(qkv, B, T, c.n_head, hd, aop, nullptr, att, fmt, fl, stream)) return rc;
+                } else if (int rc = lm_attn_prefill(qkv, B, T, c.n_head, hd, nullptr, att, fmt, fl, stream)) return rc;
             } else {
                 if (int rc = lm_attn_partials(qkv, kc, vc, lm->cache_format, nullptr, B, c.n_head, hd, lm->max_len, part, stream, T)) return rc;
                 lm_attn_merge16(part, c.n_head, hd, nchunk, T, M, att, fmt, fl, stream);
@@ -751,7 +778,9 @@ static int lm_prefill_layers(omnitok_lm *lm, const int64_t *idx, int T_tok, cons
         if (int rc = lm_linear(xn, L.wqkv.w32, L.bqkv, nullptr, qkv, M, 3 * C, C, stream)) return rc;
         if (int rc = lm_kv_scatter(qkv, kc, vc, lm->cache_format, M, T, c.n_head, hd, lm->max_len, lm->err_flag, stream)) return rc;
         if (tiled) {
-            if (int rc = lm_attn_prefill(qkv, B, T, c.n_head, hd, att, nullptr, 0, nullptr, stream)) return rc;
+            if (aop) {
+                if (int rc = lm_attn_prefill16(qkv, B, T, c.n_head, hd, aop, att, nullptr, 0, lm->err_flag, stream)) return rc;
+            } else if (int rc = lm_attn_prefill(qkv, B, T, c.n_head, hd, att, nullptr, 0, nullptr, stream)) return rc;
         } else {
             if (int rc = lm_attn_partials(qkv, kc, vc, lm->cache_format, nullptr, B, c.n_head, hd, lm->max_len, part, stream, T)) return rc;
             lm_attn_merge(part, nullptr, c.n_head, hd, nchunk, T, M, att, LM_CHUNK, stream);

@@ -31,6 +31,7 @@ WEIGHT_FORMATS = {"fp32": 0, "bf16": 1, "fp16": 2}  # OMNITOK_LM_W_* of include/
 KV_FORMATS = {"fp32": 0, "bf16": 1, "fp16": 2}      # OMNITOK_LM_KV_*
 PREFILL_FORMATS = {"fp32": 0, "w16": 1}             # OMNITOK_LM_PF_*
 PREFILL_ATTENTIONS = {"rows": 0, "tiled": 1}        # OMNITOK_LM_PA_*
+PREFILL_ATTENTION_OPERANDS = {"fp32": 0, "bf16": 1, "fp16": 2}  # OMNITOK_LM_AOP_*
 
 
 class _Holder(nn.Module):
@@ -106,6 +107,7 @@ class GPT(nn.Module):
         self._cache_format = "fp32"
         self._prefill_format = "fp32"
         self._prefill_attention = "rows"
+        self._prefill_attention_operands = "fp32"
         self._max_streams = 16
         self._generation = 0
 
@@ -220,6 +222,26 @@ class GPT(nn.Module):
         return self
 
     @property
+    def prefill_attention_operands(self) -> str:
+        return self._prefill_attention_operands
+
+    def set_prefill_attention_operands(self, fmt: str):
+        """Operand format of the "tiled" prefill attention (include/omnitok_lm.h, omnitok_lm_set_prefill_attention_operands): "fp32"
+        (default, unchanged) or "bf16" / "fp16": Q, K, V and the softmax weights are each rounded once to that format and both
+        products run on the 16-bit MFMA with fp32 accumulation, the arithmetic of attention under autocast; max, sum, rescale and
+        the division stay fp32.  The prefill is then no longer the arithmetic of the decode steps.  Needs set_prefill_attention(
+        "tiled"): with "rows" the prefill raises, it never falls back.  Independent of the weight, cache and prefill formats; the
+        weights, the cache, the captured graphs and state_dict() are left alone.  With "fp16", check_overflow() raises if an element
+        of Q, K or V left the fp16 range."""
+        if fmt not in PREFILL_ATTENTION_OPERANDS:
+            raise ValueError(f"prefill attention operands {fmt!r}: expected one of {sorted(PREFILL_ATTENTION_OPERANDS)}")
+        self._prefill_attention_operands = fmt
+        if self._engine is not None:
+            check(_lib.load().omnitok_lm_set_prefill_attention_operands(self._engine, PREFILL_ATTENTION_OPERANDS[fmt]),
+                  "lm_set_prefill_attention_operands")
+        return self
+
+    @property
     def max_streams(self) -> int:
         return self._max_streams
 
@@ -286,6 +308,8 @@ class GPT(nn.Module):
         check(lib.omnitok_lm_set_weight_format(self._engine, WEIGHT_FORMATS[self._weight_format]), "lm_set_weight_format")
         check(lib.omnitok_lm_set_prefill_format(self._engine, PREFILL_FORMATS[self._prefill_format]), "lm_set_prefill_format")
         check(lib.omnitok_lm_set_prefill_attention(self._engine, PREFILL_ATTENTIONS[self._prefill_attention]), "lm_set_prefill_attention")
+        check(lib.omnitok_lm_set_prefill_attention_operands(self._engine, PREFILL_ATTENTION_OPERANDS[self._prefill_attention_operands]),
+              "lm_set_prefill_attention_operands")
         for name, t in self.state_dict(keep_vars=True).items():
             if name == "vtokens_pos_emb":  # gathered per call on the host side (cbox / tbox), not an engine weight
                 continue
@@ -330,8 +354,8 @@ class GPT(nn.Module):
 
     def check_overflow(self):
         """Raises if a decode step since the last check ran past the allocated K/V cache, or stored a K/V value outside the
-        fp16 range into an fp16 cache, or a "w16" prefill on fp16 weights rounded an activation to inf (the logits are invalid in
-        each case); one host synchronisation -- the sampling loops call it once at their end."""
+        fp16 range into an fp16 cache, or a "w16" prefill on fp16 weights rounded an activation to inf, or a prefill attention with
+        fp16 operands rounded an element of Q, K or V to inf (the logits are invalid in each case); one host synchronisation -- the sampling loops call it once at their end."""
         if not self._engine:
             return
         rc = _lib.load().omnitok_lm_overflowed(self._engine, torch.cuda.current_stream().cuda_stream)
@@ -345,6 +369,9 @@ class GPT(nn.Module):
         if rc & 4:
             raise RuntimeError("an activation of a 'w16' prefill left the fp16 range and entered its GEMM as inf: use "
                                "set_weight_format('bf16') (fp32's range) or set_prefill_format('fp32') for this model")
+        if rc & 8:
+            raise RuntimeError("a Q, K or V element of a prefill attention with fp16 operands left the fp16 range and entered its "
+                               "product as inf: use set_prefill_attention_operands('bf16') (fp32's range) for this model")
 
     @staticmethod
     def _fp(t):

@@ -117,6 +117,8 @@ class Net2NetTransformer(nn.Module):
         self.transformer.set_weight_format(_get(args, "lm_weight_format", "fp32"))
         # attention of the batched prefill ("rows" | "tiled", GPT.set_prefill_attention)
         self.transformer.set_prefill_attention(_get(args, "lm_prefill_attention", "rows"))
+        # ... and the operand format of the tiled mode ("fp32" | "bf16" | "fp16", GPT.set_prefill_attention_operands)
+        self.transformer.set_prefill_attention_operands(_get(args, "lm_prefill_attention_operands", "fp32"))
         # streams per engine (GPT.set_max_streams: 16 by default, up to 128; classifier-free guidance takes two per sample)
         self.transformer.set_max_streams(int(_get(args, "lm_max_streams", 16)))
         if ckpt_path is not None:

@@ -14,7 +14,13 @@ are set on the device, nothing is prefilled: a step's time depends on how many r
 bf16 then fp16, GPT.forward and GPT.token_losses at (B, T) in --prefill-shapes with the fp32 prefill first and the "w16" prefill after
 it, and the bare omnitok_lm_gemm16 at the model's five GEMM shapes with M = the largest B * T.  --prefill-attention rows,tiled adds the
 attention mode (GPT.set_prefill_attention; profiles/lm_prefill_attn_bench.json) as the outermost arm per shape, in the order given (the
-default "rows" alone is the record as it was); --prefill-weights picks the weight formats."""
+default "rows" alone is the record as it was); --prefill-weights picks the weight formats; --prefill-attention-operands fp32,bf16,fp16
+adds the operand format of the tiled attention (GPT.set_prefill_attention_operands; profiles/lm_prefill_attn16_bench.json) as the
+INNERMOST arm, in the order given, under the attention mode "tiled" only (the default "fp32" alone is the record as it was).
+--attn-kernel-session OUT.json: the bare attention kernels instead, no model: omnitok_lm_attn_prefill, then omnitok_lm_attn_prefill16
+with bf16, then fp16 operands, on the same standard-normal qkv at every BxTxHEADSxHEAD_DIM of --attn-shapes, 6 calls each, the median
+of the last 5 by device events (run it under `rocprofv3 --kernel-trace --stats -- python tools/lm_bench.py ...` for the kernels' own
+times)."""
 import argparse
 import json
 import os
@@ -126,6 +132,47 @@ def streams_session(a, m, dims):
             "cells": cells, "vs_steps_of_16": verdict}
 
 
+def attn_kernel_session(a):
+    """The bare prefill-attention kernels, fp32 operands first: see the module docstring.  Returns the record."""
+    import ctypes
+    from omnitokenizer_amd import _lib
+    lib = _lib.load()
+    stream = torch.cuda.current_stream().cuda_stream
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    P = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    cells = []
+    for B, T, H, hd in (tuple(int(v) for v in s.split("x")) for s in a.attn_shapes.split(",")):
+        C = H * hd
+        qkv = torch.randn(B * T, 3 * C, generator=torch.Generator().manual_seed(5)).cuda()
+        out = torch.empty(B * T, C, device="cuda")
+        flop = 4.0 * (T * (T + 1) / 2) * C * B
+        calls = {"fp32": lambda: lib.omnitok_lm_attn_prefill(P(qkv), B, T, H, hd, P(out), None, 0, None, stream)}
+        for op in ("bf16", "fp16"):
+            calls[op] = lambda op=op: lib.omnitok_lm_attn_prefill16(P(qkv), B, T, H, hd, og.WEIGHT_FORMATS[op], P(out), None, 0, None, stream)
+        base = None
+        for op, fn in calls.items():
+            ms = []
+            for _ in range(6):
+                e0.record()
+                _lib.check(fn(), "lm_attn_prefill")
+                e1.record()
+                torch.cuda.synchronize()
+                ms.append(e0.elapsed_time(e1))
+            last = sorted(ms[1:])
+            med = last[len(last) // 2]
+            base = med if op == "fp32" else base
+            cells.append({"B": B, "T": T, "heads": H, "head_dim": hd, "operands": op, "ms": round(med, 4),
+                          "ms_min_max": [round(last[0], 4), round(last[-1], 4)], "first_call_ms": round(ms[0], 4),
+                          "tflops": round(flop / (med * 1e-3) / 1e12, 1), "fp32_over_this": round(base / med, 3)})
+            print(json.dumps(cells[-1]), flush=True)
+        del qkv, out
+    return {"metric": "bare prefill attention kernels (omnitok_lm_attn_prefill, omnitok_lm_attn_prefill16)", "unit": "ms per call",
+            "config": {"protocol": "one process; per shape fp32 operands first, then bf16, then fp16, on the same standard-normal qkv, fp32 output; "
+                                   "device events around each call, 6 calls, the median (min, max) of the last 5",
+                       "tflops": "4 (T (T + 1) / 2) C B FLOP / call time"},
+            "cells": cells}
+
+
 def prefill_session(a, m, dims):
     """One session over (weight format, prefill format, shape): see the module docstring.  Returns the record."""
     import ctypes
@@ -153,6 +200,9 @@ def prefill_session(a, m, dims):
     gen = torch.Generator().manual_seed(3)
     fmts = a.prefill_weights.split(",")
     modes = a.prefill_attention.split(",")
+    aops = a.prefill_attention_operands.split(",")
+    arms = [(mode, pf, aop) for mode in modes for pf in ("fp32", "w16") for aop in (aops if mode == "tiled" else ["fp32"])]
+    aop0 = "fp32" if "fp32" in aops else aops[0]   # the operand format of the tiled cells the older verdicts compare
     for fmt in fmts:
         m.set_weight_format(fmt)
         for B, T in shapes:
@@ -160,11 +210,13 @@ def prefill_session(a, m, dims):
             flop = 2.0 * M * (12.0 * C * C * L + V * C)
             idx = torch.randint(0, V, (B, T), generator=gen).cuda()
             tg = torch.randint(0, V, (B, T), generator=gen).cuda()
-            for mode, pf in ((mode, pf) for mode in modes for pf in ("fp32", "w16")):    # the first mode first, in it the fp32 arm first
+            for mode, pf, aop in arms:    # the first mode first, in it the fp32 arm first, in it the operand formats in the order given
                 m.set_prefill_attention(mode)
                 m.set_prefill_format(pf)
+                m.set_prefill_attention_operands(aop)
                 peak = PEAK_F32_MFMA_TFLOPS if pf == "fp32" else PEAK_16BIT_MFMA_TFLOPS
-                cell = {"weights": fmt, "prefill": pf, "attention": mode, "B": B, "T": T, "gemm_flop": flop}
+                cell = {"weights": fmt, "prefill": pf, "attention": mode, **({"operands": aop} if aops != ["fp32"] else {}),
+                        "B": B, "T": T, "gemm_flop": flop}
                 for name, fn in (("forward", lambda: m(idx)), ("token_losses", lambda: m.token_losses(idx, tg))):
                     ms, spread = timed(fn, a.prefill_reps)
                     cell[name + "_ms"] = round(ms, 3)
@@ -203,15 +255,18 @@ def prefill_session(a, m, dims):
             print(json.dumps(gemms[-1]), flush=True)
             del x, w, y
         for mode in modes:
-            big = next(c for c in cells if c["weights"] == fmt and c["prefill"] == "w16" and c["attention"] == mode and c["B"] * c["T"] == M)
+            big = next(c for c in cells if c["weights"] == fmt and c["prefill"] == "w16" and c["attention"] == mode and c["B"] * c["T"] == M
+                       and c.get("operands", "fp32") == (aop0 if mode == "tiled" else "fp32"))
             gemms.append({"weights": fmt, "M": M, "gemm_ms_per_forward": round(total, 3), "forward_ms": big["forward_ms"],
                           "non_gemm_ms_per_forward": round(big["forward_ms"] - total, 3), **({"attention": mode} if len(modes) > 1 else {})})
             print(json.dumps(gemms[-1]), flush=True)
-    m.set_prefill_format("fp32").set_prefill_attention("rows")
+    m.set_prefill_format("fp32").set_prefill_attention("rows").set_prefill_attention_operands("fp32")
 
-    def cell_of(fmt, pf, mode, B, T):
-        return next(c for c in cells if (c["weights"], c["prefill"], c["attention"], c["B"], c["T"]) == (fmt, pf, mode, B, T))
-    verdict, attn_verdict = [], []
+    def cell_of(fmt, pf, mode, B, T, aop=None):
+        aop = aop or (aop0 if mode == "tiled" else "fp32")
+        return next(c for c in cells if (c["weights"], c["prefill"], c["attention"], c["B"], c["T"], c.get("operands", "fp32"))
+                    == (fmt, pf, mode, B, T, aop))
+    verdict, attn_verdict, aop_verdict = [], [], []
     for fmt in fmts:
         for B, T in shapes:
             for mode in modes:
@@ -226,12 +281,22 @@ def prefill_session(a, m, dims):
                     attn_verdict.append({"weights": fmt, "prefill": pf, "B": B, "T": T, "rows_forward_ms": r["forward_ms"],
                                          "tiled_forward_ms": t["forward_ms"], "forward_speedup": round(r["forward_ms"] / t["forward_ms"], 3),
                                          "token_losses_speedup": round(r["token_losses_ms"] / t["token_losses_ms"], 3)})
+            if "tiled" in modes and "fp32" in aops:
+                for pf in ("fp32", "w16"):
+                    base = cell_of(fmt, pf, "tiled", B, T)
+                    for aop in (o for o in aops if o != "fp32"):
+                        c = cell_of(fmt, pf, "tiled", B, T, aop)
+                        aop_verdict.append({"weights": fmt, "prefill": pf, "B": B, "T": T, "operands": aop, "fp32_operands_forward_ms": base["forward_ms"],
+                                            "forward_ms": c["forward_ms"], "forward_speedup": round(base["forward_ms"] / c["forward_ms"], 3),
+                                            "token_losses_speedup": round(base["token_losses_ms"] / c["token_losses_ms"], 3)})
     extra = {"tiled_vs_rows": attn_verdict} if attn_verdict else {}
+    if aop_verdict:
+        extra["operands_16bit_vs_fp32"] = aop_verdict
     return {**extra, "metric": "LM batched prefill (GPT.forward / GPT.token_losses), fp32 prefill vs the 16-bit MFMA prefill", "unit": "ms per call",
             "config": {"workload": f"GPT {L}x{C} ({H} heads, head_dim {C // H}), vocab {V}, block {BS}",
                        "peak_f32_mfma_tflops": PEAK_F32_MFMA_TFLOPS, "peak_16bit_mfma_tflops": PEAK_16BIT_MFMA_TFLOPS,
                        "protocol": f"one process; per weight format {' then '.join(fmts)}, per shape the attention mode(s) {' then '.join(modes)}, in each "
-                                   f"the fp32 prefill first, then w16; device events "
+                                   f"the fp32 prefill first, then w16{'' if aops == ['fp32'] else ', in each (tiled mode) the attention operands ' + ' then '.join(aops)}; device events "
                                    f"around each call, 1 dropped + {a.prefill_reps} timed calls, median (min, max beside it); bare GEMMs: 10 "
                                    "back-to-back launches per timed call on uniform random operands",
                        "tflops": "2 M (12 C^2 L + V C) FLOP of the six GEMM families / WHOLE call time (embedding, LayerNorm, attention, "
@@ -268,7 +333,18 @@ def main():
     ap.add_argument("--prefill-reps", type=int, default=5)
     ap.add_argument("--prefill-weights", default="bf16,fp16", metavar="FMT[,FMT]")
     ap.add_argument("--prefill-attention", default="rows", metavar="MODE[,MODE]", help="rows | tiled | rows,tiled (GPT.set_prefill_attention)")
+    ap.add_argument("--prefill-attention-operands", default="fp32", metavar="FMT[,FMT]",
+                    help="fp32 | bf16 | fp16, comma-separated: the innermost arm of the tiled mode (GPT.set_prefill_attention_operands)")
+    ap.add_argument("--attn-kernel-session", metavar="OUT.json", help="write the bare attention kernels' record (see above) and exit")
+    ap.add_argument("--attn-shapes", default="1x5120x16x96,8x5120x16x96,8x5120x12x128,8x5120x24x64", metavar="BxTxHEADSxHEAD_DIM[,..]")
     a = ap.parse_args()
+    if a.attn_kernel_session:
+        rec = attn_kernel_session(a)
+        with open(a.attn_kernel_session, "w") as f:
+            json.dump(rec, f, indent=1)
+            f.write("\n")
+        print(json.dumps({"written": a.attn_kernel_session}), flush=True)
+        return
     V, BS, L, H, C = a.vocab, a.block, a.layers, a.heads, a.embd
     for kv in a.option:
         from omnitokenizer_amd import _lib
