@@ -236,29 +236,28 @@ __global__ __launch_bounds__(256) void lm_kv_read_kernel(const KT *__restrict__ 
     *reinterpret_cast<f32x4 *>(v_out + i) = LmW<KT>::widen(*reinterpret_cast<const kquad *>(vc + src));
 }
 
-int lm_attn_partials(const float *qkv, void *kc, void *vc, int kvfmt, const int32_t *cache_len, int B, int n_head, int head_dim,
-                     int max_len, float *scratch, hipStream_t stream, int prefill_T, int *err_flag, int chunk) {
-    OT_CHECK_ARG(qkv && kc && vc && (cache_len || prefill_T > 0) && scratch, "lm_attn_decode: null pointer");
-    OT_CHECK_ARG(head_dim == 64 || head_dim == 96 || head_dim == 128, "lm_attn_decode: head_dim %d (64 | 96 | 128)",
-                 head_dim);
-    OT_CHECK_ARG(max_len > 0 && n_head > 0, "lm_attn_decode: bad sizes");
-    const int nchunk = ((prefill_T > 0 ? prefill_T : max_len) + chunk - 1) / chunk;
-    const int rows = prefill_T > 0 ? B * prefill_T : B;
+int lm_attn_partials(const LmAttnArgs &a, hipStream_t stream) {
+    OT_CHECK_ARG(a.qkv && a.kc && a.vc && (a.cache_len || a.prefill_T > 0) && a.part, "lm_attn_decode: null pointer");
+    OT_CHECK_ARG(a.head_dim == 64 || a.head_dim == 96 || a.head_dim == 128, "lm_attn_decode: head_dim %d (64 | 96 | 128)",
+                 a.head_dim);
+    OT_CHECK_ARG(a.max_len > 0 && a.n_head > 0, "lm_attn_decode: bad sizes");
+    const int chunk = a.chunk, nchunk = ((a.prefill_T > 0 ? a.prefill_T : a.max_len) + chunk - 1) / chunk;
+    const int rows = a.prefill_T > 0 ? a.B * a.prefill_T : a.B;
     OT_CHECK_ARG(rows <= 65535, "lm_attn_decode: %d query rows (max 65535)", rows);
-    const dim3 grid(nchunk, n_head, rows);
+    const dim3 grid(nchunk, a.n_head, rows);
     const bool wide = g_lm_attn_waves == 8;
-    lm_with_kt(kvfmt, [&](auto kt) {
+    lm_with_kt(a.kvfmt, [&](auto kt) {
         typedef decltype(kt) KT;
-        KT *k = static_cast<KT *>(kc), *v = static_cast<KT *>(vc);
+        KT *k = static_cast<KT *>(a.kc), *v = static_cast<KT *>(a.vc);
         auto launch = [&](auto f4) {
             constexpr int F4 = decltype(f4)::value;
             const bool w8 = wide && chunk != LM_CHUNK_SHORT;
             const auto kernel = chunk == LM_CHUNK_SHORT ? lm_attn_decode_kernel<KT, F4, 4, LM_CHUNK_SHORT>
                                 : wide ? lm_attn_decode_kernel<KT, F4, 8, LM_CHUNK> : lm_attn_decode_kernel<KT, F4, 4, LM_CHUNK>;
-            hipLaunchKernelGGL(kernel, grid, dim3(w8 ? 512 : 256), 0, stream, qkv, k, v, cache_len, n_head, max_len, prefill_T, scratch,
-                               nchunk, err_flag);
+            hipLaunchKernelGGL(kernel, grid, dim3(w8 ? 512 : 256), 0, stream, a.qkv, k, v, a.cache_len, a.n_head, a.max_len, a.prefill_T,
+                               a.part, nchunk, a.err_flag);
         };
-        switch (head_dim) {
+        switch (a.head_dim) {
             case 64: launch(std::integral_constant<int, 2>{}); break;
             case 96: launch(std::integral_constant<int, 3>{}); break;
             default: launch(std::integral_constant<int, 4>{}); break;
@@ -268,22 +267,16 @@ int lm_attn_partials(const float *qkv, void *kc, void *vc, int kvfmt, const int3
     return OMNITOK_OK;
 }
 
-void lm_attn_merge(const float *part, const int32_t *cache_len, int n_head, int hd, int nchunk, int prefill_T, int64_t rows, float *out,
-                   int chunk, hipStream_t stream) {
-    hipLaunchKernelGGL(lm_attn_merge_kernel<float>, dim3(n_head, (unsigned)rows), dim3(128), 0, stream, part, cache_len, n_head, hd, nchunk, prefill_T, out, chunk,
-                       static_cast<int *>(nullptr));
-}
-
-void lm_attn_merge16(const float *part, int n_head, int hd, int nchunk, int prefill_T, int64_t rows, void *out16, int fmt, int *flag,
-                     hipStream_t stream) {
+void lm_attn_merge(const float *part, const int32_t *cache_len, int n_head, int hd, int nchunk, int prefill_T, float *out32, void *out16,
+                   int fmt, int64_t rows, int *flag, int chunk, hipStream_t stream) {
     const dim3 grid(n_head, (unsigned)rows);
-    const int32_t *no_len = nullptr;  // prefill rows: the key count comes from the row index
-    if (fmt == OMNITOK_LM_W_BF16)
-        hipLaunchKernelGGL(lm_attn_merge_kernel<lm_bf16>, grid, dim3(128), 0, stream, part, no_len, n_head, hd, nchunk, prefill_T,
-                           static_cast<lm_bf16 *>(out16), LM_CHUNK, flag);
-    else
-        hipLaunchKernelGGL(lm_attn_merge_kernel<lm_fp16>, grid, dim3(128), 0, stream, part, no_len, n_head, hd, nchunk, prefill_T,
-                           static_cast<lm_fp16 *>(out16), LM_CHUNK, flag);
+    auto launch = [&](auto *out, int *fl) {
+        typedef std::remove_pointer_t<decltype(out)> OT;
+        hipLaunchKernelGGL(lm_attn_merge_kernel<OT>, grid, dim3(128), 0, stream, part, cache_len, n_head, hd, nchunk, prefill_T, out, chunk, fl);
+    };
+    if (out32) launch(out32, static_cast<int *>(nullptr));
+    else if (fmt == OMNITOK_LM_W_BF16) launch(static_cast<lm_bf16 *>(out16), flag);
+    else launch(static_cast<lm_fp16 *>(out16), flag);
 }
 
 int lm_kv_scatter(const float *qkv, void *kc, void *vc, int kvfmt, int64_t rows, int T, int n_head, int hd, int max_len,
@@ -314,8 +307,12 @@ int lm_kv_read(const void *kc, const void *vc, int kvfmt, int t0, int n, int n_h
 static int lm_attn_decode_any(const char *who, const float *qkv, void *kc, void *vc, int kvfmt, const int32_t *cache_len, int B,
                               int n_head, int head_dim, int max_len, float *scratch, float *out, hipStream_t stream) {
     OT_CHECK_ARG(out, "%s: null pointer", who);
-    if (int rc = lm_attn_partials(qkv, kc, vc, kvfmt, cache_len, B, n_head, head_dim, max_len, scratch, stream)) return rc;
-    lm_attn_merge(scratch, cache_len, n_head, head_dim, (max_len + LM_CHUNK - 1) / LM_CHUNK, 0, B, out, LM_CHUNK, stream);
+    LmAttnArgs a = {};
+    a.qkv = qkv; a.kc = kc; a.vc = vc; a.kvfmt = kvfmt;
+    a.cache_len = cache_len; a.B = B; a.n_head = n_head; a.head_dim = head_dim; a.max_len = max_len;
+    a.part = scratch; a.chunk = LM_CHUNK;
+    if (int rc = lm_attn_partials(a, stream)) return rc;
+    lm_attn_merge(scratch, cache_len, n_head, head_dim, (max_len + LM_CHUNK - 1) / LM_CHUNK, 0, out, nullptr, 0, B, nullptr, LM_CHUNK, stream);
     OT_LAUNCH_CHECK("lm_attn_merge");
     return OMNITOK_OK;
 }

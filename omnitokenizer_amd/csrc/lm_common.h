@@ -17,10 +17,10 @@
 //   lm_gemm16.hip     lm_gemm16_kernel (the 16-bit MFMA GEMM of a PF_W16 prefill, omnitok_lm_set_prefill_format), omnitok_lm_gemm16
 //   lm_attn.hip       lm_attn_decode_kernel (flash-decode over the fp32 / bf16 / fp16 K/V cache, chunk partials), lm_attn_merge_kernel
 //                     (fp32 or, for a PF_W16 prefill, 16-bit output), lm_kv_scatter_kernel, lm_kv_read_kernel, omnitok_lm_attn_decode[_kv16]
-//   lm_attn_prefill.hip  lm_attn_prefill_kernel (tiled causal attention of the prefill on the fp32-input MFMA, K/V tiles shared by 128
-//                     query rows; omnitok_lm_set_prefill_attention), omnitok_lm_attn_prefill
-//   lm_attn_prefill16.hip  lm_attn_prefill16_kernel (the same tiling on the bf16 / fp16 MFMA, Q / K / V / P rounded once to the operand
-//                     format; omnitok_lm_set_prefill_attention_operands), omnitok_lm_attn_prefill16
+//   lm_attn_prefill.hip  the tiled causal attention of the prefill, K/V tiles shared by 128 query rows (omnitok_lm_set_prefill_attention):
+//                     lm_attn_prefill_kernel on the fp32-input MFMA and lm_attn_prefill16_kernel on the bf16 / fp16 MFMA (Q / K / V / P
+//                     rounded once to the operand format; omnitok_lm_set_prefill_attention_operands) behind one host side,
+//                     lm_attn_prefill_any; omnitok_lm_attn_prefill, omnitok_lm_attn_prefill16
 //   lm_engine.hip     struct omnitok_lm and its exported functions (create .. finalize, alloc_cache, step, prefill, prefill_loss) and the
 //                     small kernels: embed, embed_seq, layernorm_rows (fp32 or 16-bit output, omnitok_lm_layernorm16), gelu, set_len,
 //                     advance, concat3, round_w16
@@ -204,33 +204,38 @@ int lm_gemm_streams_any(const LmLinear &c, float *xn, float *part, hipStream_t s
 int64_t lm_streams_part_floats(int B, int N, int K);
 // lm_attn.hip.  chunk partials only (the engine merges them inside the proj GEMV)
 // prefill_T > 0: B * prefill_T query rows (row = b * T + t, keys 0..t), chunks sized for T keys
-int lm_attn_partials(const float *qkv, void *kc, void *vc, int kvfmt, const int32_t *cache_len, int B, int n_head, int head_dim,
-                     int max_len, float *scratch, hipStream_t stream, int prefill_T = 0, int *err_flag = nullptr, int chunk = LM_CHUNK);
-// the one launch of lm_attn_merge_kernel: out[rows][n_head * hd] from the partials of `rows` query rows (the caller checks the launch)
-void lm_attn_merge(const float *part, const int32_t *cache_len, int n_head, int hd, int nchunk, int prefill_T, int64_t rows, float *out,
-                   int chunk, hipStream_t stream);
-// ... rounded to fmt (OMNITOK_LM_W_BF16 | _FP16) into out16: the proj GEMM's operand of a PF_W16 prefill; an fp16 +-inf raises
-// LM_FLAG_PF16_RANGE in *flag
-void lm_attn_merge16(const float *part, int n_head, int hd, int nchunk, int prefill_T, int64_t rows, void *out16, int fmt, int *flag,
-                     hipStream_t stream);
+struct LmAttnArgs {
+    const float *qkv;
+    void *kc, *vc;             // K / V slabs of one layer, elements of kvfmt
+    int kvfmt;
+    const int32_t *cache_len;  // [B] (unused when prefill_T > 0)
+    int B, n_head, head_dim, max_len;
+    float *part;               // [rows][n_head][nchunk][2 + head_dim]
+    int prefill_T;
+    int *err_flag;             // may be nullptr
+    int chunk;                 // keys per chunk: LM_CHUNK | LM_CHUNK_SHORT
+};
+int lm_attn_partials(const LmAttnArgs &a, hipStream_t stream);
+// the one launch of lm_attn_merge_kernel from the partials of `rows` query rows (the caller checks the launch) into out32 [rows][n_head * hd]
+// or, rounded to fmt (OMNITOK_LM_W_BF16 | _FP16), out16: the proj GEMM's operand of a PF_W16 prefill; an fp16 +-inf raises
+// LM_FLAG_PF16_RANGE in *flag.  Exactly one of out32 / out16.  The decode step passes cache_len and its chunk, the prefill prefill_T and LM_CHUNK
+void lm_attn_merge(const float *part, const int32_t *cache_len, int n_head, int hd, int nchunk, int prefill_T, float *out32, void *out16,
+                   int fmt, int64_t rows, int *flag, int chunk, hipStream_t stream);
 // qkv [B * T, 3C] -> cache rows 0 .. T - 1 of every stream | rows t0 .. t0 + n - 1 of one stream's slabs -> fp32
 int lm_kv_scatter(const float *qkv, void *kc, void *vc, int kvfmt, int64_t rows, int T, int n_head, int hd, int max_len,
                   int *err_flag, hipStream_t stream);
 int lm_kv_read(const void *kc, const void *vc, int kvfmt, int t0, int n, int n_head, int hd, int max_len, float *k_out,
                float *v_out, hipStream_t stream);
-// lm_attn_prefill.hip.  Causal attention of B streams x T rows straight from qkv [B * T, 3C] into out32 [B * T, C] or (rounded to fmt) out16:
-// the contract of omnitok_lm_attn_prefill, its argument checks included
-int lm_attn_prefill(const float *qkv, int B, int T, int n_head, int head_dim, float *out32, void *out16, int fmt, int *flag,
-                    hipStream_t stream);
-// lm_attn_prefill16.hip.  The same attention with Q, K, V and P rounded once to op_fmt (OMNITOK_LM_W_BF16 | _FP16) on the 16-bit MFMA: the
-// contract of omnitok_lm_attn_prefill16, its argument checks included; an fp16 operand of +-inf raises LM_FLAG_AOP16_RANGE in *flag
-int lm_attn_prefill16(const float *qkv, int B, int T, int n_head, int head_dim, int op_fmt, float *out32, void *out16, int out_fmt, int *flag,
+// lm_attn_prefill.hip.  Causal attention of B streams x T rows straight from qkv [B * T, 3C] into out32 [B * T, C] or (rounded to out_fmt)
+// out16, with fp32 operands (op_fmt 0) or Q, K, V and P rounded once to op_fmt (OMNITOK_LM_W_BF16 | _FP16) on the 16-bit MFMA: the contract
+// of omnitok_lm_attn_prefill / omnitok_lm_attn_prefill16, their argument checks included (`who` names the entry in the messages); an fp16
+// operand of +-inf raises LM_FLAG_AOP16_RANGE in *flag
+int lm_attn_prefill_any(const char *who, const float *qkv, int B, int T, int n_head, int head_dim, int op_fmt, float *out32, void *out16,
+                        int out_fmt, int *flag, hipStream_t stream);
+// lm_engine.hip.  nn.LayerNorm(x) over `rows` rows of K floats into y32 or, each value rounded to fmt (OMNITOK_LM_W_BF16 | _FP16), y16; an
+// fp16 +-inf raises LM_FLAG_PF16_RANGE in *flag.  Exactly one of y32 / y16
+int lm_layernorm_rows(const float *x, const float *g, const float *beta, float *y32, void *y16, int fmt, int64_t rows, int K, int *flag,
                       hipStream_t stream);
-// lm_engine.hip.  y = nn.LayerNorm(x) over `rows` rows of K floats
-int lm_layernorm_rows(const float *x, const float *g, const float *beta, float *y, int64_t rows, int K, hipStream_t stream);
-// ... the same arithmetic, each value rounded to fmt (OMNITOK_LM_W_BF16 | _FP16) into y16; an fp16 +-inf raises LM_FLAG_PF16_RANGE in *flag
-int lm_layernorm_rows16(const float *x, const float *g, const float *beta, void *y16, int fmt, int64_t rows, int K, int *flag,
-                        hipStream_t stream);
 // lm_gemm16.hip.  y = act(a16 [M, K] . w16 [N, K]^T + bias) (+ residual) on the 16-bit MFMA into y32 or (rounded to fmt) y16: the
 // contract of omnitok_lm_gemm16, its argument checks included
 int lm_gemm16(const void *a16, const void *w16, int fmt, const float *bias, const float *residual, float *y32, void *y16, int64_t M,

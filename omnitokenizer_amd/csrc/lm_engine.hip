@@ -37,8 +37,8 @@ __global__ __launch_bounds__(256) void lm_embed_kernel(const int64_t *__restrict
 
 // ---- batched prefill of a conditioning prefix (the same arithmetic as T decode steps, as GEMMs; with OMNITOK_LM_PF_W16 the GEMMs run
 // on the 16-bit MFMA over activations rounded to the weight format instead: lm_gemm16.hip; with OMNITOK_LM_PA_TILED the attention runs
-// tiled on the fp32-input MFMA from qkv, lm_attn_prefill.hip, and "same arithmetic as T decode steps" holds to rounding, not to the
-// bit; with 16-bit attention operands on the bf16 / fp16 MFMA, lm_attn_prefill16.hip, and it no longer holds) ------
+// tiled from qkv, lm_attn_prefill.hip: on the fp32-input MFMA, and "same arithmetic as T decode steps" holds to rounding, not to the
+// bit, or with 16-bit operands on the bf16 / fp16 MFMA, and it no longer holds.  One layer loop for all of them: LmPrefill) ------
 // positions t < Te take the explicit embeddings emb[b, t] (prepended, gpt.py:214-216), the rest tok_emb[idx[b, t - Te]]
 __global__ __launch_bounds__(256) void lm_embed_seq_kernel(const int64_t *__restrict__ idx, const float *__restrict__ tok,
                                                            const float *__restrict__ pe, const float *__restrict__ emb,
@@ -162,21 +162,16 @@ __global__ __launch_bounds__(256) void lm_round_w16_kernel(float *__restrict__ w
     if (inf) flags[(i * 4) / seg] = 1;
 }
 
-int lm_layernorm_rows(const float *x, const float *g, const float *beta, float *y, int64_t rows, int K, hipStream_t stream) {
-    hipLaunchKernelGGL(lm_layernorm_rows_kernel<float>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, x, g, beta, y, rows, K,
-                       static_cast<int *>(nullptr));
-    OT_LAUNCH_CHECK("lm_layernorm_rows");
-    return OMNITOK_OK;
-}
-
-int lm_layernorm_rows16(const float *x, const float *g, const float *beta, void *y16, int fmt, int64_t rows, int K, int *flag,
-                        hipStream_t stream) {
-    const dim3 grid((unsigned)((rows + 3) / 4));
-    if (fmt == OMNITOK_LM_W_BF16)
-        hipLaunchKernelGGL(lm_layernorm_rows_kernel<lm_bf16>, grid, dim3(256), 0, stream, x, g, beta, static_cast<lm_bf16 *>(y16), rows, K, flag);
-    else
-        hipLaunchKernelGGL(lm_layernorm_rows_kernel<lm_fp16>, grid, dim3(256), 0, stream, x, g, beta, static_cast<lm_fp16 *>(y16), rows, K, flag);
-    OT_LAUNCH_CHECK("lm_layernorm_rows16");
+int lm_layernorm_rows(const float *x, const float *g, const float *beta, float *y32, void *y16, int fmt, int64_t rows, int K, int *flag,
+                      hipStream_t stream) {
+    auto launch = [&](auto *y, int *fl) {
+        typedef std::remove_pointer_t<decltype(y)> OT;
+        hipLaunchKernelGGL(lm_layernorm_rows_kernel<OT>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, x, g, beta, y, rows, K, fl);
+    };
+    if (y32) launch(y32, static_cast<int *>(nullptr));
+    else if (fmt == OMNITOK_LM_W_BF16) launch(static_cast<lm_bf16 *>(y16), flag);
+    else launch(static_cast<lm_fp16 *>(y16), flag);
+    OT_LAUNCH_CHECK(y32 ? "lm_layernorm_rows" : "lm_layernorm_rows16");
     return OMNITOK_OK;
 }
 
@@ -194,6 +189,8 @@ struct LmLayer {
     LmMat wproj, w1, w2;  // (w16: the packed 16-bit image, weight_format != FP32)
     const float *bproj, *b1, *b2;
 };
+
+static int lm_kv_elem_bytes(int fmt) { return fmt == OMNITOK_LM_KV_FP32 ? 4 : 2; }
 
 struct omnitok_lm {
     omnitok_lm_config cfg;
@@ -226,6 +223,11 @@ struct omnitok_lm {
     int64_t lg_bytes = 0;
     float *ce = nullptr;
     int64_t ce_rows = 0, ce_bytes = 0;
+    int head_dim() const { return cfg.n_embd / cfg.n_head; }
+    // the K slab of a layer and the V slab that follows it: [max_batch][n_head][max_len][head_dim] elements of cache_format each
+    int64_t slab_bytes() const { return (int64_t)max_batch * cfg.n_head * max_len * head_dim() * lm_kv_elem_bytes(cache_format); }
+    void *k_slab(int layer) const { return static_cast<char *>(kv) + 2 * layer * slab_bytes(); }
+    void *v_slab(int layer) const { return static_cast<char *>(kv) + (2 * layer + 1) * slab_bytes(); }
 };
 
 static const float *LW(omnitok_lm *lm, const std::string &k) {
@@ -281,12 +283,6 @@ static void lm_free_cache(omnitok_lm *lm) {
     if (lm->kv) (void)hipFree(lm->kv);
     lm->kv = nullptr;
     lm->cache_bytes = 0;
-}
-
-static int lm_kv_elem_bytes(int fmt) { return fmt == OMNITOK_LM_KV_FP32 ? 4 : 2; }
-// K slab of layer i (the V slab follows it) in a cache of per_layer elements per slab
-static void *lm_kv_slab(const omnitok_lm *lm, int64_t slab, int64_t per_layer) {
-    return static_cast<char *>(lm->kv) + slab * per_layer * lm_kv_elem_bytes(lm->cache_format);
 }
 
 extern "C" void omnitok_lm_destroy(omnitok_lm *lm) {
@@ -594,12 +590,10 @@ extern "C" int omnitok_lm_cache_read(omnitok_lm *lm, int layer, int b, int t0, i
                  lm->max_batch, t0, n, lm->max_len);
     if (n == 0) return OMNITOK_OK;
     const omnitok_lm_config &c = lm->cfg;
-    const int hd = c.n_embd / c.n_head;
-    const int64_t per_layer = (int64_t)lm->max_batch * c.n_head * lm->max_len * hd, per_stream = (int64_t)c.n_head * lm->max_len * hd;
-    const int es = lm_kv_elem_bytes(lm->cache_format);
-    const char *kc = static_cast<const char *>(lm_kv_slab(lm, 2 * layer, per_layer)) + (int64_t)b * per_stream * es;
-    const char *vc = kc + per_layer * es;
-    return lm_kv_read(kc, vc, lm->cache_format, t0, n, c.n_head, hd, lm->max_len, k_out, v_out, stream);
+    const int hd = lm->head_dim();
+    const int64_t off = (int64_t)b * c.n_head * lm->max_len * hd * lm_kv_elem_bytes(lm->cache_format);  // the stream's rows in a slab
+    return lm_kv_read(static_cast<const char *>(lm->k_slab(layer)) + off, static_cast<const char *>(lm->v_slab(layer)) + off,
+                      lm->cache_format, t0, n, c.n_head, hd, lm->max_len, k_out, v_out, stream);
 }
 
 extern "C" int64_t omnitok_lm_cache_bytes(omnitok_lm *lm) { return lm ? lm->cache_bytes : 0; }
@@ -617,7 +611,7 @@ extern "C" int omnitok_lm_step(omnitok_lm *lm, const int64_t *idx, int32_t *pos,
 static int lm_step_linear(omnitok_lm *lm, LmLinear c, const LmMerge *mg, hipStream_t stream) {
     if (c.B < g_lm_streams_min) return lm_gemv_any(c, mg, stream);
     if (mg) {
-        lm_attn_merge(mg->part, mg->cache_len, mg->n_head, mg->hd, mg->nchunk, 0, c.B, lm->att, mg->chunk, stream);
+        lm_attn_merge(mg->part, mg->cache_len, mg->n_head, mg->hd, mg->nchunk, 0, lm->att, nullptr, 0, c.B, nullptr, mg->chunk, stream);
         OT_LAUNCH_CHECK("lm_attn_merge");
         c.x = lm->att;
     }
@@ -640,20 +634,21 @@ extern "C" int omnitok_lm_step_ex(omnitok_lm *lm, const int64_t *idx, const floa
         return OMNITOK_ERR_STATE;
     }
     const omnitok_lm_config &c = lm->cfg;
-    const int C = c.n_embd, hd = C / c.n_head;
-    const int64_t per_layer = (int64_t)lm->max_batch * c.n_head * lm->max_len * hd;
+    const int C = c.n_embd, hd = lm->head_dim();
     hipLaunchKernelGGL(lm_embed_kernel, dim3(B), dim3(256), 0, stream, idx, pos, LW(lm, "tok_emb.weight"),
                        LW(lm, "pos_emb"), emb, pos_extra, lm->x, C, c.vocab_size, c.block_size);
     OT_LAUNCH_CHECK("lm_embed");
     const LmMerge mg{lm->part, cache_len, c.n_head, hd, (lm->max_len + lm->chunk - 1) / lm->chunk, lm->chunk, lm->qkv};   // (qkv is free once the partials exist)
+    LmAttnArgs at = {};
+    at.qkv = lm->qkv; at.kvfmt = lm->cache_format; at.cache_len = cache_len;
+    at.B = B; at.n_head = c.n_head; at.head_dim = hd; at.max_len = lm->max_len;
+    at.part = lm->part; at.err_flag = lm->err_flag; at.chunk = lm->chunk;
     for (int i = 0; i < c.n_layer; ++i) {
         const LmLayer &L = lm->layers[i];
-        void *kc = lm_kv_slab(lm, 2 * i, per_layer), *vc = lm_kv_slab(lm, 2 * i + 1, per_layer);
+        at.kc = lm->k_slab(i); at.vc = lm->v_slab(i);
         // x + proj(attn(ln1(x)))   (reference gpt.py:159-161)
         if (int rc = lm_step_linear(lm, {lm->x, L.wqkv, L.bqkv, nullptr, L.ln1w, L.ln1b, lm->qkv, B, 3 * C, C, 0}, nullptr, stream)) return rc;
-        if (int rc = lm_attn_partials(lm->qkv, kc, vc, lm->cache_format, cache_len, B, c.n_head, hd, lm->max_len, lm->part, stream, 0,
-                                      lm->err_flag, lm->chunk))
-            return rc;
+        if (int rc = lm_attn_partials(at, stream)) return rc;
         if (int rc = lm_step_linear(lm, {nullptr, L.wproj, L.bproj, lm->x, nullptr, nullptr, lm->x, B, C, C, 0}, &mg, stream)) return rc;
         // x + mlp(ln2(x))          (reference gpt.py:162, 150-155)
         if (int rc = lm_step_linear(lm, {lm->x, L.w1, L.b1, nullptr, L.ln2w, L.ln2b, lm->hid, B, 4 * C, C, 1}, nullptr, stream)) return rc;
@@ -673,26 +668,80 @@ extern "C" int omnitok_lm_step_ex(omnitok_lm *lm, const int64_t *idx, const floa
 
 extern "C" int omnitok_lm_prefill(omnitok_lm *lm, const int64_t *idx, int32_t *pos, int32_t *cache_len, int B, int T,
                                   float *logits_out, omnitok_stream_t stream_) {
-    return omnitok_lm_prefill_ex(lm, idx, T, nullptr, 0, nullptr, pos, cache_len, B, logits_out, stream_);
+    return omnitok_lm_prefill_ex(lm, idx, T, /*emb*/ nullptr, /*T_emb*/ 0, /*pos_extra*/ nullptr, pos, cache_len, B, logits_out, stream_);
 }
 
-// nn.Linear of the prefill on the fp32-MFMA GEMM: y [M, N] = x [M, K] . w [N, K]^T (+ bias) (+ residual [M, N], may be y), dense rows
-static int lm_linear(const float *x, const float *w, const float *bias, const float *residual, float *y, int64_t M, int N,
-                     int K, hipStream_t stream) {
-    omnitok_row_gemm g = {};
-    g.a = x; g.lda = K; g.w = w; g.ldw = K;
-    g.bias = bias; g.residual = residual; g.ldr = N; g.c = y; g.ldc = N;
-    g.M = M; g.N = N; g.K = K;
-    g.flags = (bias ? OMNITOK_GEMM_BIAS : 0) | (residual ? OMNITOK_GEMM_RESIDUAL : 0);
-    return omnitok_gemm(&g, stream);
-}
+// One batched prefill: the engine's four switches (prefill_format, prefill_attention, prefill_attention_operands, weight_format)
+// resolved once per call by lm_prefill_plan, and the stages of a block, each of which picks its fp32 or 16-bit form.
+// w16 (OMNITOK_LM_PF_W16): the five GEMMs run on the 16-bit MFMA over the packed weight images.  Their A operands are the fp32 prefill's
+// values rounded once to the weight format: LayerNorm rows and the attention output by their own kernels' 16-bit form, FC1's GELU output
+// in its GEMM's epilogue (no [M, 4C] fp32 tensor, no GELU pass).  xn / att / hid then hold packed 16-bit rows in the first half of their
+// regions; x, qkv, the cache scatter and the attention partials stay fp32.  The attention modes: LmPrefill::attention.
+struct LmPrefill {
+    omnitok_lm *lm;
+    hipStream_t stream;
+    int B, T, nchunk;
+    int64_t M;                                // rows: B * T, or those of a row block (rows())
+    float *x, *xn, *att, *qkv, *hid, *part;   // workspace: x | xn | att [M, C], qkv [M, 3C], hid [M, 4C], partials (rows mode)
+    bool w16, tiled;
+    int wfmt, aop;  // w16: the weight format | 0; operands of the tiled attention: 0 (fp32), or OMNITOK_LM_W_BF16 | _FP16
 
-// Embedding and the n_layer blocks of a batched prefill, shared by omnitok_lm_prefill_ex and omnitok_lm_prefill_loss: checks the
-// arguments, grows the workspace, fills the K/V cache; *x_out [M, C] is the residual stream after the last block, *xn_out [M, C]
-// scratch for its ln_f.  B * T > 0.
-static int lm_prefill_layers(omnitok_lm *lm, const int64_t *idx, int T_tok, const float *emb, int T_emb,
-                             const float *pos_extra, int32_t *pos, int32_t *cache_len, int B, hipStream_t stream,
-                             float **x_out, float **xn_out) {
+    float *o32(float *p) const { return w16 ? nullptr : p; }  // a stage's output: exactly one of the two
+    void *o16(float *p) const { return w16 ? p : nullptr; }
+    // rows r0 .. r0 + n - 1 of x and xn (for ln and linear)
+    LmPrefill rows(int64_t r0, int64_t n) const {
+        LmPrefill v = *this;
+        v.x += r0 * lm->cfg.n_embd; v.xn += r0 * lm->cfg.n_embd; v.M = n;
+        return v;
+    }
+    // xn = nn.LayerNorm(x)
+    int ln(const float *gamma, const float *beta) const {
+        return lm_layernorm_rows(x, gamma, beta, o32(xn), o16(xn), wfmt, M, lm->cfg.n_embd, lm->err_flag, stream);
+    }
+    // nn.Linear: y [M, N] = act(a [M, K] . m [N, K]^T + bias) (+ residual [M, N], may be y); act 1 = exact GELU.  fp32: the fp32-MFMA GEMM
+    // over dense rows and a GELU pass | w16: lm_gemm16, whose GELU output is packed 16-bit rows (FC1 into hid)
+    int linear(const float *a, const LmMat &m, const float *bias, const float *residual, float *y, int N, int K, int act) const {
+        if (w16) return lm_gemm16(a, m.w16, m.fmt, bias, residual, act ? nullptr : y, act ? y : nullptr, M, N, K, act, lm->err_flag, stream);
+        omnitok_row_gemm g = {};
+        g.a = a; g.lda = K; g.w = m.w32; g.ldw = K;
+        g.bias = bias; g.residual = residual; g.ldr = N; g.c = y; g.ldc = N;
+        g.M = M; g.N = N; g.K = K;
+        g.flags = (bias ? OMNITOK_GEMM_BIAS : 0) | (residual ? OMNITOK_GEMM_RESIDUAL : 0);
+        if (int rc = omnitok_gemm(&g, stream)) return rc;
+        if (act) {
+            hipLaunchKernelGGL(lm_gelu_kernel, dim3((unsigned)((M * N / 4 + 255) / 256)), dim3(256), 0, stream, y, M * N / 4);
+            OT_LAUNCH_CHECK("lm_gelu");
+        }
+        return OMNITOK_OK;
+    }
+    int scatter(int layer) const {
+        return lm_kv_scatter(qkv, lm->k_slab(layer), lm->v_slab(layer), lm->cache_format, M, T, lm->cfg.n_head, lm->head_dim(), lm->max_len,
+                             lm->err_flag, stream);
+    }
+    // att = causal attention of qkv.  rows (OMNITOK_LM_PA_ROWS): the decode kernel per query row over the cache just scattered, chunk
+    // partials, a merge | tiled: straight from qkv, K/V tiles shared by 128 query rows on the fp32-input MFMA: no partials, no dependence on
+    // the cache format; "same arithmetic as T decode steps" then holds to rounding, not to the bit | tiled with aop (refused without the
+    // tiled mode): Q / K / V / P rounded once to that format on the bf16 / fp16 MFMA.  The scatter stays in every mode: the decode steps
+    // after the prefill read the cache.
+    int attention(int layer) const {
+        const int n_head = lm->cfg.n_head, hd = lm->head_dim();
+        if (tiled)
+            return lm_attn_prefill_any(aop ? "lm_attn_prefill16" : "lm_attn_prefill", qkv, B, T, n_head, hd, aop, o32(att), o16(att), wfmt,
+                                       lm->err_flag, stream);
+        LmAttnArgs a = {};
+        a.qkv = qkv; a.kc = lm->k_slab(layer); a.vc = lm->v_slab(layer); a.kvfmt = lm->cache_format;
+        a.B = B; a.n_head = n_head; a.head_dim = hd; a.max_len = lm->max_len;
+        a.part = part; a.prefill_T = T; a.chunk = LM_CHUNK;
+        if (int rc = lm_attn_partials(a, stream)) return rc;
+        lm_attn_merge(part, nullptr, n_head, hd, nchunk, T, o32(att), o16(att), wfmt, M, lm->err_flag, LM_CHUNK, stream);
+        OT_LAUNCH_CHECK(w16 ? "lm_attn_merge16" : "lm_attn_merge");
+        return OMNITOK_OK;
+    }
+};
+
+// Checks the arguments and the engine's state for a prefill of B streams x T rows, grows the workspace and fills p.  B * T > 0.
+static int lm_prefill_plan(omnitok_lm *lm, const int64_t *idx, int T_tok, const float *emb, int T_emb, int32_t *pos, int32_t *cache_len,
+                           int B, hipStream_t stream, LmPrefill &p) {
     const int T = T_tok + T_emb;
     OT_CHECK_ARG((idx || T_tok == 0) && (emb || T_emb == 0) && pos && cache_len, "lm_prefill: null pointer");
     if (!lm->finalized) {
@@ -717,97 +766,52 @@ static int lm_prefill_layers(omnitok_lm *lm, const int64_t *idx, int T_tok, cons
     }
     const omnitok_lm_config &c = lm->cfg;
     OT_CHECK_ARG(T <= c.block_size, "lm_prefill: %d tokens exceed block_size %d", T, c.block_size);
-    const int C = c.n_embd, hd = C / c.n_head, V = c.vocab_size;
-    const int64_t M = (int64_t)B * T;
+    const int64_t C = c.n_embd, M = (int64_t)B * T;
     OT_CHECK_ARG(M <= 65535, "lm_prefill: B * T = %lld rows (max 65535)", (long long)M);
-    const int nchunk = (T + LM_CHUNK - 1) / LM_CHUNK;
-    // Attention.  OMNITOK_LM_PA_ROWS: the decode kernel per query row over the cache just scattered, chunk partials, a merge.
-    // OMNITOK_LM_PA_TILED: lm_attn_prefill straight from qkv (K/V tiles shared by 128 query rows on the fp32-input MFMA): no partials,
-    // no dependence on the cache format; "same arithmetic as T decode steps" then holds to rounding, not to the bit.  The scatter
-    // stays in both modes: the decode steps after the prefill read the cache.
-    const bool tiled = lm->prefill_attention == OMNITOK_LM_PA_TILED;
-    // ... with 16-bit operands (omnitok_lm_set_prefill_attention_operands; refused above without the tiled mode): lm_attn_prefill16, Q / K /
-    // V / P rounded once to that format on the bf16 / fp16 MFMA.  aop: 0, or the operand format as OMNITOK_LM_W_BF16 | _FP16
-    const int aop = lm->prefill_attention_operands == OMNITOK_LM_AOP_BF16   ? OMNITOK_LM_W_BF16
-                    : lm->prefill_attention_operands == OMNITOK_LM_AOP_FP16 ? OMNITOK_LM_W_FP16
-                                                                            : 0;
-    // workspace: x | xn | att [M, C], qkv [M, 3C], hid [M, 4C], partials (rows mode)
-    const int64_t need = M * C * 3 + M * 3 * C + M * 4 * C + (tiled ? 0 : M * c.n_head * nchunk * (2 + hd));
+    p.lm = lm; p.stream = stream; p.B = B; p.T = T; p.M = M;
+    p.nchunk = (T + LM_CHUNK - 1) / LM_CHUNK;
+    p.w16 = lm->prefill_format == OMNITOK_LM_PF_W16;
+    p.wfmt = p.w16 ? lm->weight_format : 0;
+    p.tiled = lm->prefill_attention == OMNITOK_LM_PA_TILED;
+    p.aop = lm->prefill_attention_operands == OMNITOK_LM_AOP_BF16   ? OMNITOK_LM_W_BF16
+            : lm->prefill_attention_operands == OMNITOK_LM_AOP_FP16 ? OMNITOK_LM_W_FP16
+                                                                    : 0;
+    const int64_t need = M * C * 3 + M * 3 * C + M * 4 * C + (p.tiled ? 0 : M * c.n_head * p.nchunk * (2 + lm->head_dim()));
     if (int rc = lm_grow(reinterpret_cast<void **>(&lm->pf), &lm->pf_bytes, need * 4)) return rc;
-    float *x = lm->pf, *xn = x + M * C, *att = xn + M * C, *qkv = att + M * C, *hid = qkv + M * 3 * C,
-          *part = hid + M * 4 * C;
-    const int64_t per_layer = (int64_t)lm->max_batch * c.n_head * lm->max_len * hd;
-    hipLaunchKernelGGL(lm_embed_seq_kernel, dim3((unsigned)M), dim3(256), 0, stream, idx, LW(lm, "tok_emb.weight"),
-                       LW(lm, "pos_emb"), emb, T_emb, pos_extra, x, T, C, V);
-    OT_LAUNCH_CHECK("lm_embed_seq");
-    if (lm->prefill_format == OMNITOK_LM_PF_W16) {
-        // The same passes with the five GEMMs on the 16-bit MFMA over the packed weight images.  Their A operands are the fp32 values
-        // of the loop below rounded once to the weight format: LayerNorm rows and the attention merge by their own kernels' 16-bit
-        // form, FC1's GELU output in its GEMM's epilogue (no [M, 4C] fp32 tensor, no GELU pass).  xn / att / hid hold packed 16-bit
-        // rows in the first half of their regions; x, qkv, the cache scatter and the attention partials stay fp32.
-        const int fmt = lm->weight_format;
-        int *fl = lm->err_flag;
-        for (int i = 0; i < c.n_layer; ++i) {
-            const LmLayer &L = lm->layers[i];
-            void *kc = lm_kv_slab(lm, 2 * i, per_layer), *vc = lm_kv_slab(lm, 2 * i + 1, per_layer);
-            if (int rc = lm_layernorm_rows16(x, L.ln1w, L.ln1b, xn, fmt, M, C, fl, stream)) return rc;
-            if (int rc = lm_gemm16(xn, L.wqkv.w16, fmt, L.bqkv, nullptr, qkv, nullptr, M, 3 * C, C, 0, fl, stream)) return rc;
-            if (int rc = lm_kv_scatter(qkv, kc, vc, lm->cache_format, M, T, c.n_head, hd, lm->max_len, lm->err_flag, stream)) return rc;
-            if (tiled) {
-                if (aop) {
-                    if (int rc = lm_attn_prefill16(qkv, B, T, c.n_head, hd, aop, nullptr, att, fmt, fl, stream)) return rc;
-                } else if (int rc = lm_attn_prefill(qkv, B, T, c.n_head, hd, nullptr, att, fmt, fl, stream)) return rc;
-            } else {
-                if (int rc = lm_attn_partials(qkv, kc, vc, lm->cache_format, nullptr, B, c.n_head, hd, lm->max_len, part, stream, T)) return rc;
-                lm_attn_merge16(part, c.n_head, hd, nchunk, T, M, att, fmt, fl, stream);
-                OT_LAUNCH_CHECK("lm_attn_merge16");
-            }
-            if (int rc = lm_gemm16(att, L.wproj.w16, fmt, L.bproj, x, x, nullptr, M, C, C, 0, fl, stream)) return rc;
-            if (int rc = lm_layernorm_rows16(x, L.ln2w, L.ln2b, xn, fmt, M, C, fl, stream)) return rc;
-            if (int rc = lm_gemm16(xn, L.w1.w16, fmt, L.b1, nullptr, nullptr, hid, M, 4 * C, C, 1, fl, stream)) return rc;
-            if (int rc = lm_gemm16(hid, L.w2.w16, fmt, L.b2, x, x, nullptr, M, C, 4 * C, 0, fl, stream)) return rc;
-        }
-        *x_out = x;
-        *xn_out = xn;
-        return OMNITOK_OK;
-    }
-    for (int i = 0; i < c.n_layer; ++i) {
-        const LmLayer &L = lm->layers[i];
-        void *kc = lm_kv_slab(lm, 2 * i, per_layer), *vc = lm_kv_slab(lm, 2 * i + 1, per_layer);
-        if (int rc = lm_layernorm_rows(x, L.ln1w, L.ln1b, xn, M, C, stream)) return rc;
-        if (int rc = lm_linear(xn, L.wqkv.w32, L.bqkv, nullptr, qkv, M, 3 * C, C, stream)) return rc;
-        if (int rc = lm_kv_scatter(qkv, kc, vc, lm->cache_format, M, T, c.n_head, hd, lm->max_len, lm->err_flag, stream)) return rc;
-        if (tiled) {
-            if (aop) {
-                if (int rc = lm_attn_prefill16(qkv, B, T, c.n_head, hd, aop, att, nullptr, 0, lm->err_flag, stream)) return rc;
-            } else if (int rc = lm_attn_prefill(qkv, B, T, c.n_head, hd, att, nullptr, 0, nullptr, stream)) return rc;
-        } else {
-            if (int rc = lm_attn_partials(qkv, kc, vc, lm->cache_format, nullptr, B, c.n_head, hd, lm->max_len, part, stream, T)) return rc;
-            lm_attn_merge(part, nullptr, c.n_head, hd, nchunk, T, M, att, LM_CHUNK, stream);
-            OT_LAUNCH_CHECK("lm_attn_merge");
-        }
-        if (int rc = lm_linear(att, L.wproj.w32, L.bproj, x, x, M, C, C, stream)) return rc;
-        if (int rc = lm_layernorm_rows(x, L.ln2w, L.ln2b, xn, M, C, stream)) return rc;
-        if (int rc = lm_linear(xn, L.w1.w32, L.b1, nullptr, hid, M, 4 * C, C, stream)) return rc;
-        hipLaunchKernelGGL(lm_gelu_kernel, dim3((unsigned)((M * C + 255) / 256)), dim3(256), 0, stream, hid, M * C);
-        OT_LAUNCH_CHECK("lm_gelu");
-        if (int rc = lm_linear(hid, L.w2.w32, L.b2, x, x, M, C, 4 * C, stream)) return rc;
-    }
-    *x_out = x;
-    *xn_out = xn;
+    p.x = lm->pf; p.xn = p.x + M * C; p.att = p.xn + M * C;
+    p.qkv = p.att + M * C; p.hid = p.qkv + M * 3 * C; p.part = p.hid + M * 4 * C;
     return OMNITOK_OK;
 }
 
-// logits [rows, V] = head(ln_f(x [rows, C])); xn: scratch [rows, C]
-static int lm_head_rows(omnitok_lm *lm, const float *x, float *xn, int64_t rows, float *logits, hipStream_t stream) {
-    const int C = lm->cfg.n_embd, V = lm->cfg.vocab_size;
-    if (lm->prefill_format == OMNITOK_LM_PF_W16) {  // (xn: packed 16-bit rows in the front half of the same scratch)
-        if (int rc = lm_layernorm_rows16(x, LW(lm, "ln_f.weight"), LW(lm, "ln_f.bias"), xn, lm->head.fmt, rows, C, lm->err_flag, stream))
-            return rc;
-        return lm_gemm16(xn, lm->head.w16, lm->head.fmt, nullptr, nullptr, logits, nullptr, rows, V, C, 0, lm->err_flag, stream);
+// Embedding and the n_layer blocks of a batched prefill, shared by omnitok_lm_prefill_ex and omnitok_lm_prefill_loss: fills the K/V
+// cache; p.x [M, C] is the residual stream after the last block, p.xn scratch for its ln_f.  B * T > 0.
+static int lm_prefill_layers(omnitok_lm *lm, const int64_t *idx, int T_tok, const float *emb, int T_emb,
+                             const float *pos_extra, int32_t *pos, int32_t *cache_len, int B, hipStream_t stream, LmPrefill &p) {
+    if (int rc = lm_prefill_plan(lm, idx, T_tok, emb, T_emb, pos, cache_len, B, stream, p)) return rc;
+    const int C = lm->cfg.n_embd;
+    hipLaunchKernelGGL(lm_embed_seq_kernel, dim3((unsigned)p.M), dim3(256), 0, stream, idx, LW(lm, "tok_emb.weight"),
+                       LW(lm, "pos_emb"), emb, T_emb, pos_extra, p.x, p.T, C, lm->cfg.vocab_size);
+    OT_LAUNCH_CHECK("lm_embed_seq");
+    for (int i = 0; i < lm->cfg.n_layer; ++i) {
+        const LmLayer &L = lm->layers[i];
+        // x + proj(attn(ln1(x)))   (reference gpt.py:159-161)
+        if (int rc = p.ln(L.ln1w, L.ln1b)) return rc;
+        if (int rc = p.linear(p.xn, L.wqkv, L.bqkv, nullptr, p.qkv, 3 * C, C, 0)) return rc;
+        if (int rc = p.scatter(i)) return rc;
+        if (int rc = p.attention(i)) return rc;
+        if (int rc = p.linear(p.att, L.wproj, L.bproj, p.x, p.x, C, C, 0)) return rc;
+        // x + mlp(ln2(x))          (reference gpt.py:162, 150-155)
+        if (int rc = p.ln(L.ln2w, L.ln2b)) return rc;
+        if (int rc = p.linear(p.xn, L.w1, L.b1, nullptr, p.hid, 4 * C, C, 1)) return rc;
+        if (int rc = p.linear(p.hid, L.w2, L.b2, p.x, p.x, C, 4 * C, 0)) return rc;
     }
-    if (int rc = lm_layernorm_rows(x, LW(lm, "ln_f.weight"), LW(lm, "ln_f.bias"), xn, rows, C, stream)) return rc;
-    return lm_linear(xn, LW(lm, "head.weight"), nullptr, nullptr, logits, rows, V, C, stream);
+    return OMNITOK_OK;
+}
+
+// logits [p.M, V] = head(ln_f(p.x)), through p.xn
+static int lm_head_rows(const LmPrefill &p, float *logits) {
+    if (int rc = p.ln(LW(p.lm, "ln_f.weight"), LW(p.lm, "ln_f.bias"))) return rc;
+    return p.linear(p.xn, p.lm->head, nullptr, nullptr, logits, p.lm->cfg.vocab_size, p.lm->cfg.n_embd, 0);
 }
 
 extern "C" int omnitok_lm_prefill_ex(omnitok_lm *lm, const int64_t *idx, int T_tok, const float *emb, int T_emb,
@@ -818,10 +822,10 @@ extern "C" int omnitok_lm_prefill_ex(omnitok_lm *lm, const int64_t *idx, int T_t
     OT_CHECK_ARG(T_tok >= 0 && T_emb >= 0, "lm_prefill: negative length");
     const int T = T_tok + T_emb;
     if (B == 0 || T == 0) return OMNITOK_OK;
-    float *x = nullptr, *xn = nullptr;
-    if (int rc = lm_prefill_layers(lm, idx, T_tok, emb, T_emb, pos_extra, pos, cache_len, B, stream, &x, &xn)) return rc;
+    LmPrefill pf;
+    if (int rc = lm_prefill_layers(lm, idx, T_tok, emb, T_emb, pos_extra, pos, cache_len, B, stream, pf)) return rc;
     if (logits_out)
-        if (int rc = lm_head_rows(lm, x, xn, (int64_t)B * T, logits_out, stream)) return rc;
+        if (int rc = lm_head_rows(pf, logits_out)) return rc;
     hipLaunchKernelGGL(lm_set_len_kernel, dim3(1), dim3(128), 0, stream, pos, cache_len, B, T);
     OT_LAUNCH_CHECK("lm_set_len");
     return OMNITOK_OK;
@@ -838,12 +842,12 @@ extern "C" int omnitok_lm_prefill_loss(omnitok_lm *lm, const int64_t *idx, int T
                  "lm_prefill_loss: targets / sums are not 8-byte aligned");
     const int T = T_tok + T_emb;
     OT_CHECK_ARG(B > 0 && T > 0, "lm_prefill_loss: no rows (B %d, T %d)", B, T);
-    const int64_t M = (int64_t)B * T, V = lm->cfg.vocab_size, C = lm->cfg.n_embd;
+    const int64_t M = (int64_t)B * T, V = lm->cfg.vocab_size;
     OT_CHECK_ARG(M <= 65535, "lm_prefill_loss: B * T = %lld rows (max 65535)", (long long)M);
     OT_CHECK_ARG(g_lm_loss_chunk_rows >= 1, "lm_prefill_loss: option lm_loss_chunk_rows = %d", g_lm_loss_chunk_rows);
     const int64_t R = std::min<int64_t>(g_lm_loss_chunk_rows, M);
-    float *x = nullptr, *xn = nullptr;
-    if (int rc = lm_prefill_layers(lm, idx, T_tok, emb, T_emb, pos_extra, pos, cache_len, B, stream, &x, &xn)) return rc;
+    LmPrefill pf;
+    if (int rc = lm_prefill_layers(lm, idx, T_tok, emb, T_emb, pos_extra, pos, cache_len, B, stream, pf)) return rc;
     // workspaces (grow-only)
     if (int rc = lm_grow(reinterpret_cast<void **>(&lm->lg), &lm->lg_bytes, R * V * 4)) return rc;
     const int64_t red_bytes = omnitok_lm_token_ce_workspace(M);
@@ -865,7 +869,7 @@ extern "C" int omnitok_lm_prefill_loss(omnitok_lm *lm, const int64_t *idx, int T
         bool any = false;
         for (int64_t i = r0; i < r0 + rows && !any; ++i) any = tg[(size_t)i] >= 0;
         if (any)
-            if (int rc = lm_head_rows(lm, x + r0 * C, xn + r0 * C, rows, lm->lg, stream)) return rc;
+            if (int rc = lm_head_rows(pf.rows(r0, rows), lm->lg)) return rc;
         // an all-ignored block: the kernel writes nll 0 / rank -1 from the targets alone and reads no logits
         if (int rc = lm_token_ce_rows(lm->lg, V, targets + r0, rows, (int)V, nll_w + r0, rank_w + r0, stream)) return rc;
     }
@@ -882,7 +886,7 @@ extern "C" int omnitok_lm_layernorm16(const float *x, const float *gamma, const 
     OT_CHECK_ARG(aligned16(x) && aligned16(gamma) && aligned16(beta) && aligned16(y16), "lm_layernorm16: unaligned pointer (16 bytes)");
     OT_CHECK_ARG(rows >= 1 && rows <= 0x7fffffffLL && K >= 32 && K % 32 == 0, "lm_layernorm16: rows %lld (1 .. 2^31 - 1), K %d (K %% 32 == 0)",
                  (long long)rows, K);
-    return lm_layernorm_rows16(x, gamma, beta, y16, fmt, rows, K, flag, static_cast<hipStream_t>(stream));
+    return lm_layernorm_rows(x, gamma, beta, nullptr, y16, fmt, rows, K, flag, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int64_t omnitok_lm_loss_workspace_bytes(omnitok_lm *lm) {

@@ -370,7 +370,7 @@ static void lm_streams_launch(const float *x, const WT *w, const LmLinear &c, fl
 int lm_gemm_streams_any(const LmLinear &c, float *xn, float *part, hipStream_t stream) {
     const float *x = c.x;
     if (c.ln_g) {
-        if (int rc = lm_layernorm_rows(x, c.ln_g, c.ln_b, xn, c.B, c.K, stream)) return rc;
+        if (int rc = lm_layernorm_rows(x, c.ln_g, c.ln_b, xn, nullptr, 0, c.B, c.K, nullptr, stream)) return rc;
         x = xn;
     }
     lm_with_wt(c.w, [&](auto *w) { lm_streams_launch(x, w, c, part, stream); });

@@ -324,7 +324,7 @@ int lm_gemv_any(const LmLinear &c, const LmMerge *mg, hipStream_t stream) {
             g.B = left > 8 ? 8 : left;
             if (mg) {   // the merged attention output as a tensor first (the VALU path merges inside its prologue)
                 float *merged = mg->merged + (int64_t)b0 * K;
-                lm_attn_merge(m2.part, m2.cache_len, mg->n_head, mg->hd, mg->nchunk, 0, g.B, merged, mg->chunk, stream);
+                lm_attn_merge(m2.part, m2.cache_len, mg->n_head, mg->hd, mg->nchunk, 0, merged, nullptr, 0, g.B, nullptr, mg->chunk, stream);
                 g.x = merged;
             }
             if (lm_gemm4_try(g, stream)) {

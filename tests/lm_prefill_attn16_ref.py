@@ -30,7 +30,7 @@ from tests import lm_prefill_attn_ref as ar
 
 FMT = pr.FMT
 U16 = {"bf16": 2.0 ** -8, "fp16": 2.0 ** -11}
-EXP_ULPS = 1     # v_exp_f32: 1 ulp (the header of csrc/lm_attn_prefill16.hip)
+EXP_ULPS = 1     # v_exp_f32: 1 ulp (the 16-bit kernel's header in csrc/lm_attn_prefill.hip)
 KT = 32          # its key tile
 
 
