@@ -12,7 +12,7 @@
 // is split  x = hi + lo + r,  hi = fp16(x),  lo = fp16(x - hi),  |r| <= 2^-22 |x|;  each product is accumulated
 // in fp32 as lo.hi' + hi.lo' + hi.hi' (three v_mfma_f32_32x32x16_f16; the dropped lo.lo' and r terms are below
 // 2^-21 |x y|).  The softmax itself (max, exp2, sum, rescale) is the fp32 code of attn_spatial.hip; P is scaled
-// by 2^14 before it is split (the factor cancels in O / l).  Error class: tests/test_gpu_attn_h2.py puts the
+// by 2^14 before it is split (2^9 in the 64-query kernel; the factor cancels in O / l).  Error class: tests/test_gpu_attn_h2.py puts the
 // result within the fp32-MFMA kernel's distance of an fp64 reference.
 //
 // MFMA formulation: transposed like attn_spatial.hip so that each lane owns one query column --
@@ -139,12 +139,31 @@ __global__ __launch_bounds__(256) void attn_pack_kernel(PackParams p) {
 }
 
 // -------------------------------------------------------------------------------------------
-// Attention.  Workgroup = 4 waves = 128 queries of one (sequence, head); each wave owns 32 queries.
-// K/V tiles of 64 keys (16 KiB + 16 KiB, already in fragment order) are staged global -> registers ->
-// LDS, double-buffered: the next tile's loads are in flight during the current tile's 48 MFMAs.
+// Spatial attention: two kernels, attn_spatial_h2w_kernel (64 queries per wave, "attn_h2_variant" 6, the default, and
+// its measurement arms 4, 5, 7) and attn_spatial_h2x_kernel (32 queries per wave, "attn_h2_variant" 3, and every legacy
+// bias table that does not fit the LDS form of the first).  What they share:
+//   * Operands: the packed Q / K / V blocks above.  A lane owns query column r32 = lane & 31 of a 32-query block, its
+//     half hi = lane >> 5 picks the 8-channel (Q, K) or 4-key (V, P) group; a fragment is one 16-byte read at
+//     block + plane * 4096 + step * 1024 + hi * 512 + r32 * 16.
+//   * Products: S^T = K . Q^T and O^T = V^T . P^T, each as lo.hi' + hi.lo' + hi.hi' in that order on
+//     v_mfma_f32_32x32x16_f16 with fp32 accumulators (12 MFMAs per 32 keys x 32 queries x 64 channels and product).
+//   * Softmax: online, per lane (the lane's query), in base 2: cs = log2(e) x s_unscale turns a raw accumulator into
+//     log2 units (with a bias: the accumulator is first unscaled and the bias added in fp32, cs = log2(e)); P is formed
+//     as exp2(s cs - m + shift), where the shift (a power of two that cancels in O / l) lifts P into the range in which
+//     the fp16 hi|lo pair carries 22 bits; the two lane halves of a query meet through v_permlane32_swap.
+//   * K / V tiles of 32 keys (8 KiB + 8 KiB, already in fragment order) go global -> LDS directly
+//     (global_load_lds_dwordx4: the packed layout is lane-linear), double-buffered; those loads are tracked by vmcnt
+//     only, so they are drained explicitly before the barrier that publishes a tile.  All fragment reads of a phase are
+//     issued as one batch before the phase that precedes their use, pinned with sched_barrier fences, so that every
+//     MFMA chain finds its operands in registers (profiles/r04_attn_h2_isa.txt).
+//   * XCD mapping: workgroups go round-robin over the 8 XCDs by blockIdx.x & 7, so group = (sequence, head) is
+//     (jb / nqb) * 8 + (b & 7) with jb = b >> 3, and its query block is jb % nqb: all query blocks of one group run on
+//     one XCD and share its K / V in that L2.  The host rounds the groups up to a multiple of 8; the pad groups return.
+//   * Epilogue: O[q][d] = O^T[d][q] / (l sv) with sv the power-of-two scale of the clip's V bound (exact), as fp32 rows
+//     or as fp16 hi|lo planes for the to_out GEMM.
+// History: arms 0, 1, 2 (register-staged, pipelined LDS-DMA, 32 queries on 64-key tiles) were closed by
+// profiles/r04_attn_variants.txt and r04_attn_ablation.txt; last tree with the arms: 977962e.
 // -------------------------------------------------------------------------------------------
-constexpr int AH_TILE_BYTES = 32768;            // K (2 blocks) | V (2 blocks)
-constexpr int AH_LDS_BYTES = 2 * AH_TILE_BYTES;
 
 struct AttnH2Params {
     const unsigned char *qp, *kp, *vp;
@@ -161,198 +180,25 @@ struct AttnH2Params {
     float *out_scale;
 };
 
-template <bool HAS_BIAS>
-__global__ __launch_bounds__(256, 2) void attn_spatial_h2_kernel(AttnH2Params p) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_h2[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r32 = lane & 31, hi = lane >> 5;
-    // XCD-aware mapping as attn_spatial_kernel: all query blocks of one (sequence, head) on one XCD
-    const int nqb = p.nqb;
-    const int b = blockIdx.x, jb = b >> 3;
-    const int grp = (jb / nqb) * 8 + (b & 7);
-    if (grp >= p.ngrp_real) return;
-    const int qb = jb % nqb, head = grp % p.heads, seq = grp / p.heads;
-    const int nblk = p.N / 32;
-    const int64_t unit0 = ((int64_t)seq * p.heads + head) * nblk;  // first 32-token block of this (sequence, head)
-    const bool wave_active = qb * 128 + wave * 32 < p.N;
-    const int qblk = wave_active ? qb * 4 + wave : 0;
-    const int q_local = qblk * 32 + r32;  // this lane's query
-
-    // Q fragments (B operand): plane, k-step -> 8 halfs of query r32, channels 16 ks + 8 hi + (0..7)
-    u32x4 qf[2][4];
-    {
-        const unsigned char *qb_ = p.qp + (unit0 + qblk) * 8192 + hi * 512 + r32 * 16;
-#pragma unroll
-        for (int pl = 0; pl < 2; ++pl)
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks)
-                qf[pl][ks] = *reinterpret_cast<const u32x4 *>(qb_ + (pl * 4 + ks) * 1024);
-    }
-    int qy = 0, qx = 0;
-    const float *btab = nullptr;
-    if constexpr (HAS_BIAS) {
-        qy = q_local / p.gw; qx = q_local % p.gw;
-        btab = p.bias_table + head;
-    }
-
-    // loader: a tile is 2 x 16 KiB of contiguous global memory; thread -> 16-byte slots tid + 256 i
-    const unsigned char *kg = p.kp + unit0 * 8192 + tid * 16;
-    const unsigned char *vg = p.vp + unit0 * 8192 + tid * 16;
-    u32x4 rk[4], rv[4];
-    auto gload = [&](int t) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            rk[i] = *reinterpret_cast<const u32x4 *>(kg + (int64_t)t * 16384 + i * 4096);
-            rv[i] = *reinterpret_cast<const u32x4 *>(vg + (int64_t)t * 16384 + i * 4096);
-        }
-    };
-    auto lstore = [&](int buf) {
-        unsigned char *s = smem_h2 + buf * AH_TILE_BYTES + tid * 16;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            *reinterpret_cast<u32x4 *>(s + i * 4096) = rk[i];
-            *reinterpret_cast<u32x4 *>(s + 16384 + i * 4096) = rv[i];
-        }
-    };
-
-    f32x16 ot[2];
-#pragma unroll
-    for (int d = 0; d < 2; ++d)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) ot[d][r] = 0.0f;
-    float m_run = -INFINITY, l_run = 0.0f;
-    // logits = s_unscale * acc (+ bias); softmax in exp2 form
-    const float cs = HAS_BIAS ? 1.44269504088896340736f : p.s_unscale * 1.44269504088896340736f;
-
-    const int ntiles = p.N / 64;
-    gload(0);
-    lstore(0);
-    __syncthreads();
-
-    for (int t = 0; t < ntiles; ++t) {
-        const int buf = t & 1;
-        if (t + 1 < ntiles) gload(t + 1);
-        const unsigned char *Ks = smem_h2 + buf * AH_TILE_BYTES + hi * 512 + r32 * 16;
-        const unsigned char *Vs = Ks + 16384;
-#pragma unroll
-        for (int sub = 0; sub < 2; ++sub) {
-            // ---- S^T = K . Q^T for 32 keys x 32 queries ---------------------------------------
-            f32x16 st;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) st[r] = 0.0f;
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                const f16x8 kh = __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4 *>(Ks + sub * 8192 + ks * 1024));
-                const f16x8 kl = __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4 *>(Ks + sub * 8192 + (4 + ks) * 1024));
-                st = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl, __builtin_bit_cast(f16x8, qf[0][ks]), st, 0, 0, 0);
-                st = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, __builtin_bit_cast(f16x8, qf[1][ks]), st, 0, 0, 0);
-                st = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, __builtin_bit_cast(f16x8, qf[0][ks]), st, 0, 0, 0);
-            }
-            if constexpr (HAS_BIAS) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int kv = t * 64 + sub * 32 + mfma32_row(r, hi);
-                    const int ky = kv / p.gw, kx = kv % p.gw;
-                    st[r] = fmaf(st[r], p.s_unscale,
-                                 btab[((qy - ky + p.gh - 1) * (2 * p.gw - 1) + (qx - kx + p.gw - 1)) * p.heads]);
-                }
-            }
-            // ---- online softmax (per-lane query), in units of the raw accumulators -----------------
-            float mx = st[0];
-#pragma unroll
-            for (int r = 1; r < 16; ++r) mx = fmaxf(mx, st[r]);
-            mx = fmaxf(mx, swap32(mx));
-            const float m_new = fmaxf(m_run, mx);
-            const float mc = fmaf(m_new, cs, -P_SHIFT);  // exp2(s cs - mc) = 2^14 exp(logit - max)
-            float ps = 0.0f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                st[r] = __builtin_amdgcn_exp2f(fmaf(st[r], cs, -mc));
-                ps += st[r];
-            }
-            ps += swap32(ps);
-            if (__any(m_new != m_run)) {  // wave-uniform; alpha == 1 for every lane otherwise
-                const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * cs);  // 0 on the first tile
-                l_run *= alpha;
-#pragma unroll
-                for (int d = 0; d < 2; ++d)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) ot[d][r] *= alpha;
-            }
-            l_run += ps;
-            m_run = m_new;
-            // ---- split P (2 k-steps of 16 keys: accumulators 8 j .. 8 j + 7) and O^T += V^T . P^T ------
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                f32x4 pa, pb;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    pa[e] = st[8 * j + e];
-                    pb[e] = st[8 * j + 4 + e];
-                }
-                const f16x4 ha = __builtin_convertvector(pa, f16x4), hb = __builtin_convertvector(pb, f16x4);
-                const f16x4 la = __builtin_convertvector(pa - __builtin_convertvector(ha, f32x4), f16x4);
-                const f16x4 lb = __builtin_convertvector(pb - __builtin_convertvector(hb, f32x4), f16x4);
-                const f16x8 ph = __builtin_shufflevector(ha, hb, 0, 1, 2, 3, 4, 5, 6, 7);
-                const f16x8 pl = __builtin_shufflevector(la, lb, 0, 1, 2, 3, 4, 5, 6, 7);
-#pragma unroll
-                for (int mt = 0; mt < 2; ++mt) {
-                    const f16x8 vh = __builtin_bit_cast(
-                        f16x8, *reinterpret_cast<const u32x4 *>(Vs + sub * 8192 + (j * 2 + mt) * 1024));
-                    const f16x8 vl = __builtin_bit_cast(
-                        f16x8, *reinterpret_cast<const u32x4 *>(Vs + sub * 8192 + 4096 + (j * 2 + mt) * 1024));
-                    ot[mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl, ph, ot[mt], 0, 0, 0);
-                    ot[mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, pl, ot[mt], 0, 0, 0);
-                    ot[mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, ph, ot[mt], 0, 0, 0);
-                }
-            }
-        }
-        if (t + 1 < ntiles) lstore(buf ^ 1);
-        __syncthreads();
-    }
-
-    // ---- epilogue: O[q][d] = O^T[d][q] / (l sv); lane owns q, d = mt*32 + 8g + 4hi + (0..3) -------------
-    if (!wave_active) return;
-    float bound = p.v_bound;
-    if (p.v_bound_dev) bound *= p.v_bound_dev[(int64_t)p.v_bound_stride * (seq / p.seq_per_clip)];
-    const float inv_l = 1.0f / (l_run * h2_scale_of_bound(bound));  // the scale is a power of two: exact
-    if (p.out_planes) {
-        const float so = h2_scale_of_bound(bound);
-        const int64_t row = (int64_t)seq * p.N + q_local;
-        if (head == 0 && hi == 0) p.out_scale[row] = 1.0f / so;
-#pragma unroll
-        for (int d = 0; d < 2; ++d) pl_store_ot_block(ot[d], inv_l * so, p.out_planes, row, head * 2 + d, p.heads * 2, hi);
-        return;
-    }
-    float *orow = p.out + ((int64_t)seq * p.N + q_local) * p.ldo + head * 64;
-#pragma unroll
-    for (int d = 0; d < 2; ++d)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            f32x4 o;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = ot[d][g * 4 + e] * inv_l;
-            *reinterpret_cast<f32x4 *>(orow + d * 32 + g * 8 + hi * 4) = o;
-        }
-}
-
-
-// -------------------------------------------------------------------------------------------
-// Variant 2 ("attn_h2_variant" 1, the default): the same arithmetic, restructured around what the first kernel
-// measured (matrix pipe ~35 % busy: every wave alternates MFMA bursts with ~140-instruction softmax bursts):
-//   * K/V tiles go global -> LDS directly (global_load_lds_dwordx4: the packed layout is lane-linear), no
-//     staging registers and no ds_write pass;
-//   * inside a 64-key tile the two 32-key sub-blocks are software-pipelined: S^T of sub-block b is issued
-//     before the softmax of sub-block a, and the P.V MFMAs of a before the softmax of b, so the VALU work of one
-//     sub-block sits in the shadow of the other's MFMAs within ONE wave (regions without branches);
-//   * the two half-wave reductions use v_permlane32_swap instead of ds_bpermute.
-// -------------------------------------------------------------------------------------------
 typedef __attribute__((address_space(3))) void lds_void_t;
 typedef __attribute__((address_space(1))) const void glob_void_t;
 
+// -------------------------------------------------------------------------------------------
+// 32 queries per wave ("attn_h2_variant" 3).  Workgroup = 4 waves = 128 queries of one (sequence, head); 2 x 16 KiB of
+// LDS and <= 168 registers: three workgroups per CU, so that a SIMD has three waves in different phases (one in its MFMA
+// chain, the others in softmax / waiting on the barrier).  Per 32-key tile a wave reads the K fragments, runs the S^T
+// chain, requests the V fragments (they land under the softmax), then softmax, rescale and the P.V chain.
+//   * Softmax: m_run is the running maximum in units of the logits, alpha = exp2((m_old - m_new) cs) (1 when the maximum
+//     did not grow, 0 on the first tile) scales l on every tile and O behind a wave-uniform branch (exact: alpha == 1 for
+//     every lane otherwise).  P = 2^P_SHIFT exp(logit - max) is in (0, 2^14] and is split by conversion and subtraction.
+//   * Legacy relative-position bias (reference attention.py:453-483, 535-583): gathered per score from the global table
+//     [(2 gh - 1)(2 gw - 1), heads] at (qy - ky + gh - 1, qx - kx + gw - 1) -- any grid, a division per score.  This is
+//     why the entry point sends every table that the LDS form of the wide kernel cannot take here.
+// -------------------------------------------------------------------------------------------
 template <bool HAS_BIAS>
-__global__ __launch_bounds__(256, 2) void attn_spatial_h2p_kernel(AttnH2Params p) {
+__global__ __launch_bounds__(256, 3) void attn_spatial_h2x_kernel(AttnH2Params p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_h2[];
+    constexpr int TILE = 16384;  // K block (8 KiB) | V block (8 KiB) of 32 keys
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r32 = lane & 31, hi = lane >> 5;
     const int nqb = p.nqb;
@@ -382,18 +228,17 @@ __global__ __launch_bounds__(256, 2) void attn_spatial_h2p_kernel(AttnH2Params p
         btab = p.bias_table + head;
     }
 
-    // tile t = 16 KiB of K + 16 KiB of V, contiguous in global memory and lane-linear in LDS: wave w moves the
-    // 1 KiB chunks 4 i + w (i = 0..3) of each half
+    // tile t = 8 KiB of K + 8 KiB of V; wave w moves the 1 KiB chunks 4 i + w of each half
     const unsigned char *kg = p.kp + unit0 * 8192 + wave * 1024 + lane * 16;
     const unsigned char *vg = p.vp + unit0 * 8192 + wave * 1024 + lane * 16;
     auto dma = [&](int t, int buf) {
-        unsigned char *s = smem_h2 + buf * AH_TILE_BYTES + wave * 1024;
+        unsigned char *s = smem_h2 + buf * TILE + wave * 1024;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            __builtin_amdgcn_global_load_lds((glob_void_t *)(kg + (int64_t)t * 16384 + i * 4096),
+        for (int i = 0; i < 2; ++i) {
+            __builtin_amdgcn_global_load_lds((glob_void_t *)(kg + (int64_t)t * 8192 + i * 4096),
                                              (lds_void_t *)(s + i * 4096), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((glob_void_t *)(vg + (int64_t)t * 16384 + i * 4096),
-                                             (lds_void_t *)(s + 16384 + i * 4096), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((glob_void_t *)(vg + (int64_t)t * 8192 + i * 4096),
+                                             (lds_void_t *)(s + 8192 + i * 4096), 16, 0, 0);
         }
     };
 
@@ -405,7 +250,7 @@ __global__ __launch_bounds__(256, 2) void attn_spatial_h2p_kernel(AttnH2Params p
     float m_run = -INFINITY, l_run = 0.0f;
     const float cs = HAS_BIAS ? 1.44269504088896340736f : p.s_unscale * 1.44269504088896340736f;
 
-    const int ntiles = p.N / 64;
+    const int ntiles = p.N / 32;
     dma(0, 0);
     // the LDS-DMA loads are tracked by vmcnt only: drain them explicitly before the barrier that publishes the tile
     // (hipcc adds this wait itself when it knows a global_load_lds is outstanding; stated here so that the
@@ -416,17 +261,25 @@ __global__ __launch_bounds__(256, 2) void attn_spatial_h2p_kernel(AttnH2Params p
     for (int t = 0; t < ntiles; ++t) {
         const int buf = t & 1;
         if (t + 1 < ntiles) dma(t + 1, buf ^ 1);
-        const unsigned char *Ks = smem_h2 + buf * AH_TILE_BYTES + hi * 512 + r32 * 16;
-        const unsigned char *Vs = Ks + 16384;
+        const unsigned char *Ks = smem_h2 + buf * TILE + hi * 512 + r32 * 16;
+        const unsigned char *Vs = Ks + 8192;
 
-        auto qk = [&](int sub) {
+        // fragment batches: 8 x ds_read_b128 each
+        auto load_k = [&](u32x4 (&f)[8]) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) f[i] = *reinterpret_cast<const u32x4 *>(Ks + i * 1024);  // [plane][ks]
+        };
+        auto load_v = [&](u32x4 (&f)[8]) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) f[i] = *reinterpret_cast<const u32x4 *>(Vs + i * 1024);  // [plane][j * 2 + mt]
+        };
+        auto qk = [&](const u32x4 (&kf)[8]) {
             f32x16 st;
 #pragma unroll
             for (int r = 0; r < 16; ++r) st[r] = 0.0f;
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) {
-                const f16x8 kh = __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4 *>(Ks + sub * 8192 + ks * 1024));
-                const f16x8 kl = __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4 *>(Ks + sub * 8192 + (4 + ks) * 1024));
+                const f16x8 kh = __builtin_bit_cast(f16x8, kf[ks]), kl = __builtin_bit_cast(f16x8, kf[4 + ks]);
                 st = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl, __builtin_bit_cast(f16x8, qf[0][ks]), st, 0, 0, 0);
                 st = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, __builtin_bit_cast(f16x8, qf[1][ks]), st, 0, 0, 0);
                 st = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, __builtin_bit_cast(f16x8, qf[0][ks]), st, 0, 0, 0);
@@ -434,7 +287,7 @@ __global__ __launch_bounds__(256, 2) void attn_spatial_h2p_kernel(AttnH2Params p
             if constexpr (HAS_BIAS) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int kv = t * 64 + sub * 32 + mfma32_row(r, hi);
+                    const int kv = t * 32 + mfma32_row(r, hi);
                     const int ky = kv / p.gw, kx = kv % p.gw;
                     st[r] = fmaf(st[r], p.s_unscale,
                                  btab[((qy - ky + p.gh - 1) * (2 * p.gw - 1) + (qx - kx + p.gw - 1)) * p.heads]);
@@ -442,15 +295,15 @@ __global__ __launch_bounds__(256, 2) void attn_spatial_h2p_kernel(AttnH2Params p
             }
             return st;
         };
-        // online softmax of one sub-block: updates m_run / l_run, returns alpha (1 when the maximum did not grow)
-        // and P as hi|lo fp16 fragments of the two 16-key steps
+        // online softmax of the tile: updates m_run / l_run, returns alpha (1 when the maximum did not grow) and P as
+        // hi|lo fp16 fragments of the two 16-key steps
         auto softmax = [&](f32x16 &st, f16x8 (&ph)[2], f16x8 (&pl)[2]) {
             float mx = fmaxf(fmaxf(st[0], st[1]), st[2]);
 #pragma unroll
             for (int r = 3; r < 15; r += 2) mx = fmaxf(fmaxf(mx, st[r]), st[r + 1]);
             mx = halves_max(fmaxf(mx, st[15]));
             const float m_new = fmaxf(m_run, mx);
-            const float mc = fmaf(m_new, cs, -P_SHIFT);
+            const float mc = fmaf(m_new, cs, -P_SHIFT);  // exp2(s cs - mc) = 2^14 exp(logit - max)
             float ps = 0.0f;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
@@ -458,7 +311,7 @@ __global__ __launch_bounds__(256, 2) void attn_spatial_h2p_kernel(AttnH2Params p
                 ps += st[r];
             }
             ps = halves_sum(ps);
-            const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * cs);  // 1 if unchanged, 0 on the first block
+            const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * cs);  // 0 on the first tile
             l_run = fmaf(l_run, alpha, ps);
             m_run = m_new;
 #pragma unroll
@@ -470,9 +323,9 @@ __global__ __launch_bounds__(256, 2) void attn_spatial_h2p_kernel(AttnH2Params p
                     pb[e] = st[8 * j + 4 + e];
                 }
                 const f16x4 ha = __builtin_convertvector(pa, f16x4), hb = __builtin_convertvector(pb, f16x4);
+                ph[j] = __builtin_shufflevector(ha, hb, 0, 1, 2, 3, 4, 5, 6, 7);
                 const f16x4 la = __builtin_convertvector(pa - __builtin_convertvector(ha, f32x4), f16x4);
                 const f16x4 lb = __builtin_convertvector(pb - __builtin_convertvector(hb, f32x4), f16x4);
-                ph[j] = __builtin_shufflevector(ha, hb, 0, 1, 2, 3, 4, 5, 6, 7);
                 pl[j] = __builtin_shufflevector(la, lb, 0, 1, 2, 3, 4, 5, 6, 7);
             }
             return alpha;
@@ -485,30 +338,29 @@ __global__ __launch_bounds__(256, 2) void attn_spatial_h2p_kernel(AttnH2Params p
                     for (int r = 0; r < 16; ++r) ot[d][r] *= alpha;
             }
         };
-        auto pv = [&](int sub, const f16x8 (&ph)[2], const f16x8 (&pl)[2]) {
+        auto pv = [&](const u32x4 (&vf)[8], const f16x8 (&ph)[2], const f16x8 (&pl)[2]) {
 #pragma unroll
             for (int j = 0; j < 2; ++j)
 #pragma unroll
                 for (int mt = 0; mt < 2; ++mt) {
-                    const f16x8 vh = __builtin_bit_cast(
-                        f16x8, *reinterpret_cast<const u32x4 *>(Vs + sub * 8192 + (j * 2 + mt) * 1024));
-                    const f16x8 vl = __builtin_bit_cast(
-                        f16x8, *reinterpret_cast<const u32x4 *>(Vs + sub * 8192 + 4096 + (j * 2 + mt) * 1024));
+                    const f16x8 vh = __builtin_bit_cast(f16x8, vf[j * 2 + mt]), vl = __builtin_bit_cast(f16x8, vf[4 + j * 2 + mt]);
                     ot[mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl, ph[j], ot[mt], 0, 0, 0);
                     ot[mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, pl[j], ot[mt], 0, 0, 0);
                     ot[mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, ph[j], ot[mt], 0, 0, 0);
                 }
         };
 
-        f16x8 pha[2], pla[2], phb[2], plb[2];
-        f32x16 sa = qk(0);
-        f32x16 sb = qk(1);                       // S^T(b) MFMAs ...
-        const float alpha_a = softmax(sa, pha, pla);   // ... beside the softmax of a
-        rescale(alpha_a);
-        pv(0, pha, pla);                         // P.V(a) MFMAs ...
-        const float alpha_b = softmax(sb, phb, plb);   // ... beside the softmax of b
-        rescale(alpha_b);
-        pv(1, phb, plb);
+        u32x4 kf[8], vf[8];
+        f16x8 ph[2], pl[2];
+        load_k(kf);
+        __builtin_amdgcn_sched_barrier(0);
+        f32x16 st = qk(kf);
+        __builtin_amdgcn_sched_barrier(0);
+        load_v(vf);                               // lands under the softmax
+        __builtin_amdgcn_sched_barrier(0);
+        const float alpha = softmax(st, ph, pl);
+        rescale(alpha);
+        pv(vf, ph, pl);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // tile t + 1 has landed (see the prologue)
         __syncthreads();
     }
@@ -539,255 +391,31 @@ __global__ __launch_bounds__(256, 2) void attn_spatial_h2p_kernel(AttnH2Params p
 
 
 // -------------------------------------------------------------------------------------------
-// Variants 2 and 3 ("attn_h2_variant" 2 / 3): the arithmetic and the operand formats of the kernel above, with the
-// instruction stream of a tile arranged around what its ISA showed (profiles/r04_attn_h2_isa.txt).  hipcc emitted the K
-// and V fragment reads right in front of their uses -- `2 x ds_read_b128, s_waitcnt lgkmcnt(0), 3 x MFMA` twelve times per
-// sub-block -- so every MFMA triple started with an exposed LDS round trip, and it kept the softmax of sub-block a
-// AFTER the S^T MFMAs of sub-block b in program order (an in-order wave then runs them one after the other whatever the
-// source intended).  Here
-//   * all fragment reads of a phase are issued as one batch BEFORE the phase that precedes their use (the K fragments
-//     of both sub-blocks at the top of the tile, the V fragments of a sub-block before its softmax), pinned with
-//     sched_barrier fences: every MFMA chain finds its operands in registers and issues back to back;
-//   * SUBS = 2 (variant 2): 64-key tiles, two workgroups per CU as before.  SUBS = 1 (variant 3): 32-key tiles, 32 KiB of
-//     LDS per workgroup and <= 168 registers: three workgroups per CU, so that a SIMD has three waves in different phases
-//     (one in its MFMA chain, the others in softmax / waiting on the barrier).
-// -------------------------------------------------------------------------------------------
-template <bool HAS_BIAS, int SUBS, int MINB = (SUBS == 1 ? 3 : 2)>
-__global__ __launch_bounds__(256, MINB) void attn_spatial_h2x_kernel(AttnH2Params p) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_h2[];
-    constexpr int TILE = SUBS * 16384;  // K (SUBS blocks of 8 KiB) | V (SUBS blocks)
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r32 = lane & 31, hi = lane >> 5;
-    const int nqb = p.nqb;
-    const int b = blockIdx.x, jb = b >> 3;
-    const int grp = (jb / nqb) * 8 + (b & 7);
-    if (grp >= p.ngrp_real) return;
-    const int qb = jb % nqb, head = grp % p.heads, seq = grp / p.heads;
-    const int nblk = p.N / 32;
-    const int64_t unit0 = ((int64_t)seq * p.heads + head) * nblk;
-    const bool wave_active = qb * 128 + wave * 32 < p.N;
-    const int qblk = wave_active ? qb * 4 + wave : 0;
-    const int q_local = qblk * 32 + r32;
-
-    u32x4 qf[2][4];
-    {
-        const unsigned char *qb_ = p.qp + (unit0 + qblk) * 8192 + hi * 512 + r32 * 16;
-#pragma unroll
-        for (int pl = 0; pl < 2; ++pl)
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks)
-                qf[pl][ks] = *reinterpret_cast<const u32x4 *>(qb_ + (pl * 4 + ks) * 1024);
-    }
-    int qy = 0, qx = 0;
-    const float *btab = nullptr;
-    if constexpr (HAS_BIAS) {
-        qy = q_local / p.gw; qx = q_local % p.gw;
-        btab = p.bias_table + head;
-    }
-
-    // tile t = SUBS x 8 KiB of K + SUBS x 8 KiB of V; wave w moves the 1 KiB chunks 4 i + w of each half
-    const unsigned char *kg = p.kp + unit0 * 8192 + wave * 1024 + lane * 16;
-    const unsigned char *vg = p.vp + unit0 * 8192 + wave * 1024 + lane * 16;
-    auto dma = [&](int t, int buf) {
-        unsigned char *s = smem_h2 + buf * TILE + wave * 1024;
-#pragma unroll
-        for (int i = 0; i < 2 * SUBS; ++i) {
-            __builtin_amdgcn_global_load_lds((glob_void_t *)(kg + (int64_t)t * (SUBS * 8192) + i * 4096),
-                                             (lds_void_t *)(s + i * 4096), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((glob_void_t *)(vg + (int64_t)t * (SUBS * 8192) + i * 4096),
-                                             (lds_void_t *)(s + SUBS * 8192 + i * 4096), 16, 0, 0);
-        }
-    };
-
-    f32x16 ot[2];
-#pragma unroll
-    for (int d = 0; d < 2; ++d)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) ot[d][r] = 0.0f;
-    float m_run = -INFINITY, l_run = 0.0f;
-    const float cs = HAS_BIAS ? 1.44269504088896340736f : p.s_unscale * 1.44269504088896340736f;
-
-    const int ntiles = p.N / (32 * SUBS);
-    dma(0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-
-    for (int t = 0; t < ntiles; ++t) {
-        const int buf = t & 1;
-        if (t + 1 < ntiles) dma(t + 1, buf ^ 1);
-        const unsigned char *Ks = smem_h2 + buf * TILE + hi * 512 + r32 * 16;
-        const unsigned char *Vs = Ks + SUBS * 8192;
-
-        // fragment batches: 8 x ds_read_b128 each
-        auto load_k = [&](int sub, u32x4 (&f)[8]) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) f[i] = *reinterpret_cast<const u32x4 *>(Ks + sub * 8192 + i * 1024);  // [plane][ks]
-        };
-        auto load_v = [&](int sub, u32x4 (&f)[8]) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) f[i] = *reinterpret_cast<const u32x4 *>(Vs + sub * 8192 + i * 1024);  // [plane][j * 2 + mt]
-        };
-        auto qk = [&](int sub, const u32x4 (&kf)[8]) {
-            f32x16 st;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) st[r] = 0.0f;
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                const f16x8 kh = __builtin_bit_cast(f16x8, kf[ks]), kl = __builtin_bit_cast(f16x8, kf[4 + ks]);
-                st = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl, __builtin_bit_cast(f16x8, qf[0][ks]), st, 0, 0, 0);
-                st = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, __builtin_bit_cast(f16x8, qf[1][ks]), st, 0, 0, 0);
-                st = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, __builtin_bit_cast(f16x8, qf[0][ks]), st, 0, 0, 0);
-            }
-            if constexpr (HAS_BIAS) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int kv = t * (32 * SUBS) + sub * 32 + mfma32_row(r, hi);
-                    const int ky = kv / p.gw, kx = kv % p.gw;
-                    st[r] = fmaf(st[r], p.s_unscale,
-                                 btab[((qy - ky + p.gh - 1) * (2 * p.gw - 1) + (qx - kx + p.gw - 1)) * p.heads]);
-                }
-            }
-            return st;
-        };
-        auto softmax = [&](f32x16 &st, f16x8 (&ph)[2], f16x8 (&pl)[2]) {
-            float alpha = 1.0f;
-            float mx = fmaxf(fmaxf(st[0], st[1]), st[2]);
-#pragma unroll
-            for (int r = 3; r < 15; r += 2) mx = fmaxf(fmaxf(mx, st[r]), st[r + 1]);
-            mx = halves_max(fmaxf(mx, st[15]));
-            const float m_new = fmaxf(m_run, mx);
-            const float mc = fmaf(m_new, cs, -P_SHIFT);
-            float ps = 0.0f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                st[r] = __builtin_amdgcn_exp2f(fmaf(st[r], cs, -mc));
-                ps += st[r];
-            }
-            ps = halves_sum(ps);
-            alpha = __builtin_amdgcn_exp2f((m_run - m_new) * cs);
-            l_run = fmaf(l_run, alpha, ps);
-            m_run = m_new;
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                f32x4 pa, pb;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    pa[e] = st[8 * j + e];
-                    pb[e] = st[8 * j + 4 + e];
-                }
-                const f16x4 ha = __builtin_convertvector(pa, f16x4), hb = __builtin_convertvector(pb, f16x4);
-                ph[j] = __builtin_shufflevector(ha, hb, 0, 1, 2, 3, 4, 5, 6, 7);
-                const f16x4 la = __builtin_convertvector(pa - __builtin_convertvector(ha, f32x4), f16x4);
-                const f16x4 lb = __builtin_convertvector(pb - __builtin_convertvector(hb, f32x4), f16x4);
-                pl[j] = __builtin_shufflevector(la, lb, 0, 1, 2, 3, 4, 5, 6, 7);
-            }
-            return alpha;
-        };
-        auto rescale = [&](float alpha) {
-            if (__any(alpha != 1.0f)) {
-#pragma unroll
-                for (int d = 0; d < 2; ++d)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) ot[d][r] *= alpha;
-            }
-        };
-        auto pv = [&](const u32x4 (&vf)[8], const f16x8 (&ph)[2], const f16x8 (&pl)[2]) {
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int mt = 0; mt < 2; ++mt) {
-                    const f16x8 vh = __builtin_bit_cast(f16x8, vf[j * 2 + mt]), vl = __builtin_bit_cast(f16x8, vf[4 + j * 2 + mt]);
-                    ot[mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl, ph[j], ot[mt], 0, 0, 0);
-                    ot[mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, pl[j], ot[mt], 0, 0, 0);
-                    ot[mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, ph[j], ot[mt], 0, 0, 0);
-                }
-        };
-
-        if constexpr (SUBS == 2) {
-            u32x4 ka[8], kb[8], va[8], vb[8];
-            f16x8 pha[2], pla[2], phb[2], plb[2];
-            load_k(0, ka);
-            load_k(1, kb);
-            __builtin_amdgcn_sched_barrier(0);
-            f32x16 sa = qk(0, ka);
-            __builtin_amdgcn_sched_barrier(0);
-            load_v(0, va);                            // lands under the S^T MFMAs of b and the softmax of a
-            __builtin_amdgcn_sched_barrier(0);
-            f32x16 sb = qk(1, kb);
-            __builtin_amdgcn_sched_barrier(0);
-            const float alpha_a = softmax(sa, pha, pla);
-            rescale(alpha_a);
-            load_v(1, vb);                            // lands under the P.V MFMAs of a and the softmax of b
-            __builtin_amdgcn_sched_barrier(0);
-            pv(va, pha, pla);
-            __builtin_amdgcn_sched_barrier(0);
-            const float alpha_b = softmax(sb, phb, plb);
-            rescale(alpha_b);
-            pv(vb, phb, plb);
-        } else {
-            u32x4 ka[8], va[8];
-            f16x8 pha[2], pla[2];
-            load_k(0, ka);
-            __builtin_amdgcn_sched_barrier(0);
-            f32x16 sa = qk(0, ka);
-            __builtin_amdgcn_sched_barrier(0);
-            load_v(0, va);
-            __builtin_amdgcn_sched_barrier(0);
-            const float alpha_a = softmax(sa, pha, pla);
-            rescale(alpha_a);
-            pv(va, pha, pla);
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-    }
-
-    if (!wave_active) return;
-    float bound = p.v_bound;
-    if (p.v_bound_dev) bound *= p.v_bound_dev[(int64_t)p.v_bound_stride * (seq / p.seq_per_clip)];
-    const float inv_l = 1.0f / (l_run * h2_scale_of_bound(bound));
-    if (p.out_planes) {
-        const float so = h2_scale_of_bound(bound);
-        const int64_t row = (int64_t)seq * p.N + q_local;
-        if (head == 0 && hi == 0) p.out_scale[row] = 1.0f / so;
-#pragma unroll
-        for (int d = 0; d < 2; ++d) pl_store_ot_block(ot[d], inv_l * so, p.out_planes, row, head * 2 + d, p.heads * 2, hi);
-        return;
-    }
-    float *orow = p.out + ((int64_t)seq * p.N + q_local) * p.ldo + head * 64;
-#pragma unroll
-    for (int d = 0; d < 2; ++d)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            f32x4 o;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = ot[d][g * 4 + e] * inv_l;
-            *reinterpret_cast<f32x4 *>(orow + d * 32 + g * 8 + hi * 4) = o;
-        }
-}
-
-
-// -------------------------------------------------------------------------------------------
-// Variant 4 ("attn_h2_variant" 4): 64 queries per wave.  The ablation arms of variant 3 (profiles/r04_attn_ablation.txt)
-// price the launch at  MFMA 0.53 ms + softmax VALU 0.22 ms + LDS fragment reads / DMA / barriers 0.41 ms, almost additive
-// (1.00 ms measured): a wave reads the whole 16 KiB K|V sub-block from LDS for 24 MFMAs, and an in-order wave runs its
-// phases one after the other.  Here a wave owns TWO 32-query blocks (A, B) of the same (sequence, head):
-//   * every K / V fragment read from LDS feeds 6 MFMAs instead of 3 (half the LDS bytes per flop, half the barriers and
-//     DMA issues per flop: a workgroup covers 256 queries);
-//   * the two blocks are independent, so the softmax of A is interleaved INTO the S^T MFMAs of B and the softmax of B into
-//     the P.V MFMAs of A by sched_group_barrier pipelines (1 MFMA : ~10 VALU) -- matrix and vector work of ONE wave overlap.
-// Arithmetic per query block is that of variants 1 - 3, bit for bit.  ILV = false: the same kernel without the pipelines.
-// -------------------------------------------------------------------------------------------
-//
-// OPT (variant 6): two cuts of the softmax's VALU work, which the ablation shows is paid in full beside the MFMAs --
-//   * the rescale of O is DEFERRED (cdna guide T13): a block's row maximum replaces the reference maximum only when it
-//     exceeds it by more than 2^6.5 (wave-uniform decision, taken before the block's P is formed, so nothing is scaled
-//     twice or not at all); otherwise P = exp(s - m_ref) may reach 2^6.5, which is why P is scaled by 2^9 instead of 2^14
-//     before the fp16 split (2^15.5 < 65504; the split stays a 22-bit hi|lo pair, and O / l is unchanged in exact
-//     arithmetic).  On l2-normalised q, k the running maximum settles within the first blocks: the 32 multiplies per
-//     block and query block, taken ~85 % of the time before, become rare;
+// 64 queries per wave ("attn_h2_variant" 6, the default: <HAS_BIAS, ILV = false, OPT = true, NWAVE = 4>).  Workgroup = 4
+// waves = 256 queries of one (sequence, head), 2 x 16 KiB of LDS (+ the bias table), two workgroups per CU.  The 32-query
+// kernel's launch is priced at MFMA 0.53 ms + softmax VALU 0.22 ms + LDS fragment reads / DMA / barriers 0.41 ms, almost
+// additive (profiles/r04_attn_ablation.txt).  Here a wave owns TWO 32-query blocks (A, B) of the same (sequence, head):
+//   * every K / V fragment read from LDS feeds 6 MFMAs instead of 3 (half the LDS bytes, barriers and DMA issues per flop);
+//   * the two blocks are independent: in program order the softmax of A follows the S^T chain of B, and the softmax of B
+//     the P.V chain of A.
+// Three measurement arms of it are still built (closed by profiles/r04_attn_variants.txt, kept with their tests for now):
+//   * OPT = false ("attn_h2_variant" 5): the softmax of the 32-query kernel per query block, bit for bit (running maximum,
+//     alpha on every tile, P scaled by 2^P_SHIFT, split by conversion and subtraction);
+//   * ILV = true (4): 5 with sched_group_barrier pipelines (1 MFMA : ~10 VALU) that interleave the softmax of A INTO the
+//     S^T MFMAs of B and the softmax of B into the P.V MFMAs of A;
+//   * NWAVE = 8 (7): 6 with 512 queries per workgroup, one workgroup per CU; built without a bias only.
+// OPT cuts the softmax's VALU work, which the ablation shows is paid in full beside the MFMAs, twice:
+//   * the rescale of O is DEFERRED (cdna guide T13).  m_run is a REFERENCE maximum in log2 units, not the running one: a
+//     block's row maximum replaces it only when it exceeds it by more than 6.5 (a factor 2^6.5; wave-uniform decision,
+//     taken before the block's P is formed, so nothing is scaled twice or not at all), and only then are l and O
+//     multiplied by exp2(m_old - m_new) (0 on the first block).  Otherwise P = exp2(s - m_ref) may reach 2^6.5, which is
+//     why P is scaled by 2^9 here instead of 2^P_SHIFT before the fp16 split (2^15.5 < 65504; the split stays a 22-bit
+//     hi|lo pair, and O / l is unchanged in exact arithmetic).  On l2-normalised q, k the maximum settles within the
+//     first blocks: the 32 multiplies per block and query block, taken ~85 % of the time without this, become rare;
 //   * the lo plane of P comes from v_fma_mix_f32 (hi as fp16 operand: lo = p - hi in one instruction instead of a
 //     conversion and a subtraction): 4 instead of 6 instructions per pair of probabilities.
-// NWAVE = 8 (variant 7): 512 queries per workgroup, one workgroup per CU -- half the L2 -> LDS traffic and barriers per flop again.
+// Legacy bias: the head's table in LDS, see below; needs lg_gw >= 0, which the entry point guarantees.
+// -------------------------------------------------------------------------------------------
 template <bool HAS_BIAS, bool ILV, bool OPT = false, int NWAVE = 4>
 __global__ __launch_bounds__(64 * NWAVE, NWAVE == 4 ? 2 : 1) void attn_spatial_h2w_kernel(AttnH2Params p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_h2[];
@@ -1188,10 +816,11 @@ __global__ __launch_bounds__(256, 2) void attn_window_h2_kernel(WinH2Params p, i
     }
 }
 
-// "attn_h2_variant": 6 (default) 64 queries per wave, deferred rescale, v_fma_mix split | 5 64 queries per wave, softmax of
-// variants 1 - 3 | 4 = 5 with sched_group_barrier pipelines | 3 32 queries per wave, hoisted fragment reads, 32-key tiles, three
-// workgroups per CU (also what the legacy-bias path runs) | 2 the same with 64-key tiles | 1 the r02 / r03 pipelined + LDS-DMA kernel
-// | 0 the first kernel.  One box, C3 shape (profiles/r04_attn_variants.txt): 1.109 / 1.007 / 0.929 / 0.916 ms for 1 / 3 / 5 / 6.
+// "attn_h2_variant": 6 (default) attn_spatial_h2w_kernel, 64 queries per wave, deferred rescale, v_fma_mix split | 3
+// attn_spatial_h2x_kernel, 32 queries per wave, three workgroups per CU (also what a legacy bias table outside the LDS form
+// runs) | measurement arms of the first: 5 the softmax of 3, 4 = 5 with sched_group_barrier pipelines, 7 = 6 with 8 waves.
+// Any other value is refused by omnitok_attn_spatial_h2.  One box, C3 shape (profiles/r04_attn_variants.txt):
+// 1.007 / 0.929 / 0.916 ms for 3 / 5 / 6.
 int g_attn_h2_variant = 6;
 
 }  // namespace omnitok
@@ -1239,6 +868,8 @@ extern "C" int omnitok_attn_spatial_h2(const omnitok_attn_desc *d, omnitok_strea
     if (int rc = attn_check_ranges("attn_spatial_h2", *d, true, "seq_per_clip")) return rc;
     OT_CHECK_ARG(d->seqs_per_clip < (1ll << 31), "attn_spatial_h2: seq_per_clip");  // the kernel's clip length is an int
     OT_CHECK_ARG((int64_t)heads * d->seqs * ((N + 127) / 128) < (1ll << 31) - 8, "attn_spatial_h2: grid too large");
+    OT_CHECK_ARG(g_attn_h2_variant >= 3 && g_attn_h2_variant <= 7,
+                 "attn_spatial_h2: option attn_h2_variant=%d, accepted values are 6, 3 and the measurement arms 4, 5, 7", g_attn_h2_variant);
     if (d->seqs == 0) return OMNITOK_OK;
     const int Bn = (int)d->seqs;
     AttnH2Params p;
@@ -1250,17 +881,13 @@ extern "C" int omnitok_attn_spatial_h2(const omnitok_attn_desc *d, omnitok_strea
     p.seq_per_clip = (int)attn_clip_seqs(*d);
     p.bias_table = bias_table; p.gh = gh; p.gw = gw;
     p.out_planes = static_cast<unsigned char *>(d->out_planes); p.out_scale = d->out_scale;
-    if (int rc = set_max_dynamic_lds(reinterpret_cast<const void *>(attn_spatial_h2_kernel<false>), AH_LDS_BYTES)) return rc;
-    if (int rc = set_max_dynamic_lds(reinterpret_cast<const void *>(attn_spatial_h2_kernel<true>), AH_LDS_BYTES)) return rc;
     p.nqb = (N + 127) / 128;
     const int ngrp = ((heads * Bn + 7) / 8) * 8;
     p.ngrp_real = heads * Bn;
     dim3 grid((unsigned)((int64_t)ngrp * p.nqb));
-    if (int rc = set_max_dynamic_lds(reinterpret_cast<const void *>(attn_spatial_h2p_kernel<false>), AH_LDS_BYTES)) return rc;
-    if (int rc = set_max_dynamic_lds(reinterpret_cast<const void *>(attn_spatial_h2p_kernel<true>), AH_LDS_BYTES)) return rc;
     // legacy bias on the 64-query kernels (variants 4 - 7): the head's table lives in LDS (see attn_spatial_h2w_kernel), which needs
     // a power-of-two grid width >= 8 (position by shift / mask) and a table of at most 32 KiB (grids up to 32 x 64: two workgroups
-    // per CU keep fitting); anything else -- and variant 7's 512-query form, not built with a bias -- takes variant 3's global gather
+    // per CU keep fitting); anything else takes variant 3's global gather, and variant 7's 512-query form, not built with a bias, runs as 6
     int lg = -1;
     if (bias_table && gw >= 8 && (gw & (gw - 1)) == 0 && (int64_t)(2 * gh - 1) * (2 * gw - 1) * 4 <= 32768) {
         lg = 0;
@@ -1296,31 +923,10 @@ extern "C" int omnitok_attn_spatial_h2(const omnitok_attn_desc *d, omnitok_strea
             if (ilv) hipLaunchKernelGGL((attn_spatial_h2w_kernel<false, true>), gridw, dim3(256), lds, stream, p);
             else hipLaunchKernelGGL((attn_spatial_h2w_kernel<false, false>), gridw, dim3(256), lds, stream, p);
         }
-    } else if (variant == 2 || variant == 3) {
-        const bool v3 = variant == 3;
-        const int lds = v3 ? 2 * 16384 : 2 * 32768;
-        if (v3) {
-            if (bias_table)
-                hipLaunchKernelGGL((attn_spatial_h2x_kernel<true, 1>), grid, dim3(256), lds, stream, p);
-            else
-                hipLaunchKernelGGL((attn_spatial_h2x_kernel<false, 1>), grid, dim3(256), lds, stream, p);
-        } else {
-            if (int rc = set_max_dynamic_lds(reinterpret_cast<const void *>(attn_spatial_h2x_kernel<false, 2>), lds)) return rc;
-            if (int rc = set_max_dynamic_lds(reinterpret_cast<const void *>(attn_spatial_h2x_kernel<true, 2>), lds)) return rc;
-            if (bias_table)
-                hipLaunchKernelGGL((attn_spatial_h2x_kernel<true, 2>), grid, dim3(256), lds, stream, p);
-            else
-                hipLaunchKernelGGL((attn_spatial_h2x_kernel<false, 2>), grid, dim3(256), lds, stream, p);
-        }
-    } else if (variant == 1) {
-        if (bias_table)
-            hipLaunchKernelGGL(attn_spatial_h2p_kernel<true>, grid, dim3(256), AH_LDS_BYTES, stream, p);
-        else
-            hipLaunchKernelGGL(attn_spatial_h2p_kernel<false>, grid, dim3(256), AH_LDS_BYTES, stream, p);
-    } else if (bias_table)
-        hipLaunchKernelGGL(attn_spatial_h2_kernel<true>, grid, dim3(256), AH_LDS_BYTES, stream, p);
+    } else if (bias_table)  // variant 3: 128 queries per workgroup
+        hipLaunchKernelGGL(attn_spatial_h2x_kernel<true>, grid, dim3(256), 2 * 16384, stream, p);
     else
-        hipLaunchKernelGGL(attn_spatial_h2_kernel<false>, grid, dim3(256), AH_LDS_BYTES, stream, p);
+        hipLaunchKernelGGL(attn_spatial_h2x_kernel<false>, grid, dim3(256), 2 * 16384, stream, p);
     OT_LAUNCH_CHECK("attn_spatial_h2");
     return OMNITOK_OK;
 }

@@ -435,6 +435,27 @@ def test_attn_plane_output_preconditions(lib, name, fields, message):
     assert rc == -1 and message in err, err
 
 
+def test_attn_spatial_h2_refuses_retired_variants(lib):
+    """"attn_h2_variant" takes 6 (64 queries per wave), 3 (32 queries per wave) or the measurement arms 4, 5, 7 of the first; every
+    other value -- the retired arms 0, 1, 2 among them -- is refused by the entry point as its last argument check, so before the
+    first HIP call."""
+    from omnitokenizer_amd import _lib
+    try:
+        for v in (0, 1, 2, -1, 8):
+            _lib.set_option("attn_h2_variant", v)
+            rc, err = _attn_call(lib, "omnitok_attn_spatial_h2")
+            assert rc == -1 and f"attn_h2_variant={v},".encode() in err and b"6, 3 and" in err, (v, err)
+            # last among the checks: a descriptor that fails an earlier one reports that one
+            rc, err = _attn_call(lib, "omnitok_attn_spatial_h2", n_tokens=48)
+            assert rc == -1 and b"N=48" in err, (v, err)
+        for v in (6, 3, 4, 5, 7):
+            _lib.set_option("attn_h2_variant", v)
+            rc, err = _attn_call(lib, "omnitok_attn_spatial_h2", seqs=0)
+            assert rc == 0, (v, err)
+    finally:
+        _lib.set_option("attn_h2_variant", 6)
+
+
 # every option a test or tool sets and then has to restore: the LM decode step's kernel choices and the stats_pack form
 READABLE_OPTIONS = ("gemm_mode", "attn_mode", "gemm_pl", "pl_min_tokens", "temporal_chunk", "prevq_fuse", "pl_cfg", "pl_tail",
                     "sp_small_blocks", "lm_wide_u", "lm_balance", "lm_ksliced", "lm_mfma", "lm_mfma_mult", "lm_ks_deep",

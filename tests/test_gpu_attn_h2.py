@@ -18,10 +18,11 @@ def ops():
     return _ops
 
 
-@pytest.fixture(params=[6, 3, 1, 0, 2, 4, 5, 7], ids=["wide_deferred_rescale", "hoisted_32key", "pipelined_dma", "reg_staged", "hoisted_64key", "wide_interleaved", "wide", "wide_8waves"])
+@pytest.fixture(params=[6, 3, 4, 5, 7], ids=["wide_deferred_rescale", "hoisted_32key", "wide_interleaved", "wide", "wide_8waves"])
 def variant(request):
-    """every build of the attention kernel ("attn_h2_variant": 1 = software-pipelined + LDS-DMA, 0 = register-staged, 2 / 3 = fragment
-    reads hoisted in front of the MFMA chains with 64- / 32-key tiles)."""
+    """every build of the attention kernels ("attn_h2_variant": 6 = attn_spatial_h2w_kernel, 64 queries per wave with the deferred
+    rescale, 3 = attn_spatial_h2x_kernel, 32 queries per wave; 5, 4, 7 = the first with the softmax of the second, with
+    sched_group_barrier pipelines on top, and with 8 waves)."""
     from omnitokenizer_amd import _lib
     _lib.set_option("attn_h2_variant", request.param)
     yield request.param
@@ -167,10 +168,10 @@ def test_attn_h2_legacy_bias(ops, variant):
 
 @pytest.mark.parametrize("gh,gw", [(16, 16), (32, 32), (8, 16), (16, 8), (16, 12), (64, 32)])
 def test_attn_h2_legacy_bias_grids(ops, variant, gh, gw):
-    """r06: the 64-query kernels (variants 4 - 7) read the legacy relative-position bias (reference attention.py:453-483, 535-583) from
-    a per-head table staged in LDS -- power-of-two grid widths >= 8 with tables up to 32 KiB; other grids (16 x 12: width not a power
-    of two; 64 x 32: 127 x 63 floats > 32 KiB) keep the global gather of variant 3.  Every variant and grid against fp64 with the
-    dense bias of the oracle's ContinuousPositionBias."""
+    """r06: the 64-query kernel (variants 4 - 7) reads the legacy relative-position bias (reference attention.py:453-483, 535-583) from
+    a per-head table staged in LDS -- power-of-two grid widths >= 8 with tables up to 32 KiB (64 x 32: 127 x 63 floats, the largest
+    that fits); other grids (16 x 12: width not a power of two) keep the global gather of the 32-query kernel (variant 3).  Every
+    variant and grid against fp64 with the dense bias of the oracle's ContinuousPositionBias."""
     c = GoldenCase("s1_legacy_r64_img")
     p = "encoder.enc_spatial_transformer.layers.0.1.spatial_rel_pos_bias"
     N = gh * gw

@@ -29,7 +29,7 @@ FAMILIES = {
     # the fp32 epilogue serves FF-out (16 launches, K = 1408) AND the temporal / window q|k|v launches (10, K = 512): one
     # kernel name, so the counters cannot be split per family -- reported under its own key, not as gemm_ff_out
     "gemm_f32_epilogue_mixed": ["gemm_pl_kernel<0,"],
-    "attn_spatial": ["attn_spatial_h2w_kernel", "attn_spatial_h2p_kernel", "attn_spatial_h2x_kernel"],   # r04 default: h2w
+    "attn_spatial": ["attn_spatial_h2w_kernel", "attn_spatial_h2x_kernel"],   # default: h2w
     "attn_temporal": ["attn_temporal_reg"],
     "attn_window": ["attn_window_h2_kernel", "attn_window_kernel"],
     "vq_argmin": ["vq_screen_kernel", "vq_argmin_kernel"],   # r05 default: the screened search
