@@ -32,6 +32,13 @@ class OmnitokLmConfig(Structure):
                 ("n_embd", c_int)]
 
 
+class OmnitokDitConfig(Structure):
+    """omnitok_dit_config (include/omnitok_dit.h)."""
+    _fields_ = [("input_size", c_int), ("patch_size", c_int), ("in_channels", c_int), ("hidden", c_int), ("depth", c_int),
+                ("heads", c_int), ("mlp_hidden", c_int), ("num_classes", c_int), ("class_dropout", c_float),
+                ("learn_sigma", c_int)]
+
+
 class OmnitokPlGemm(Structure):
     """omnitok_pl_gemm (include/omnitok.h): arguments of the plane x plane GEMM."""
     _fields_ = [
@@ -285,6 +292,30 @@ _RESTYPES = {"omnitok_last_error": c_char_p, "omnitok_version": c_char_p,
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)
 
+# include/omnitok_dit.h, bound by load() like the table above
+_DIT_PROTOS = {
+    "omnitok_dit_create": [POINTER(OmnitokDitConfig), POINTER(P)],
+    "omnitok_dit_destroy": [P],
+    "omnitok_dit_set_weight": [P, c_char_p, P, POINTER(I64), c_int, P],
+    "omnitok_dit_missing": [P, c_char_p, c_int],
+    "omnitok_dit_finalize": [P, P],
+    "omnitok_dit_timestep_table": [P, P],
+    "omnitok_dit_set_frequencies": [P, P, c_int],
+    "omnitok_dit_workspace_bytes": [P, c_int],
+    "omnitok_dit_forward": [P, P, P, P, c_int, P, P],
+    "omnitok_dit_forward_cfg": [P, P, P, P, c_int, c_float, P, P],
+    "omnitok_dit_check": [P, P],
+    "omnitok_dit_patch_embed": [P, c_int, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P],
+    "omnitok_dit_ln_modulate": [P, P, P, I64, I64, c_int, c_int, P, P],
+    "omnitok_dit_attn": [P, c_int, c_int, c_int, c_int, P, P],
+    "omnitok_dit_gate_residual": [P, P, P, I64, I64, c_int, c_int, P],
+    "omnitok_dit_gelu_tanh": [P, I64, P],
+    "omnitok_dit_unpatchify": [P, c_int, c_int, c_int, c_int, P, P],
+    "omnitok_dit_p_sample": [P, P, P, P, c_int, P, c_int, c_int, I64, c_int, c_int, P, P, P],
+}
+_RESTYPES.update({"omnitok_dit_destroy": None, "omnitok_dit_workspace_bytes": c_int64})
+DIT_EXPORTED_SYMBOLS = tuple(_DIT_PROTOS)
+
 _lib = None
 
 
@@ -304,7 +335,7 @@ def load():
     # matter what the caller imported before.
     import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
-    for name, argtypes in _PROTOS.items():
+    for name, argtypes in {**_PROTOS, **_DIT_PROTOS}.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch: fail loudly
         fn.argtypes = argtypes
         fn.restype = _RESTYPES.get(name, c_int)

@@ -1,0 +1,34 @@
+// DiT denoiser (include/omnitok_dit.h): the class-conditional diffusion transformer of the reference's image-generation
+// pipeline (Diffusion/DiT/models.py:145-266) and the per-step update of its ancestral sampler
+// (Diffusion/DiT/diffusion/gaussian_diffusion.py:254-417).
+//
+// Which unit holds what:
+//   dit_common.h   the constants the units share and the flag bits of the engine's range word
+//   dit_ops.hip    the small kernels: patch_embed (+ pos_embed), the conditioning's gather / SiLU passes, ln_modulate, gelu_tanh,
+//                  gate_residual, unpatchify, the classifier-free-guidance blend and p_sample, with their exported entry points
+//   dit_attn.hip   dit_attn_kernel: non-causal attention on v_mfma_f32_32x32x2_f32, head_dim 64 and 72 (omnitok_dit_attn)
+//   dit_engine.hip struct omnitok_dit and its exported functions (create .. finalize, forward, forward_cfg)
+// The linears (qkv, proj, fc1, fc2, the conditioning MLP, the modulation GEMM and the final linear) are omnitok_gemm calls.
+#pragma once
+#include "common.h"
+#include "../../include/omnitok_dit.h"
+
+namespace omnitok {
+
+constexpr int DIT_T_STEPS = 1000;  // timesteps of the table: t in [0, 1000)
+constexpr int DIT_T_FREQ = 256;    // frequency_embedding_size of TimestepEmbedder (models.py:31)
+constexpr int DIT_FLAG_T_RANGE = 1;  // bits of the engine's range word (omnitok_dit_check)
+constexpr int DIT_FLAG_Y_RANGE = 2;
+
+// dit_ops.hip: the conditioning's element-wise steps (rows of D floats, one per sample)
+//   temb[b, :] = table[clamp(t[b])][:]                       (DIT_T_FREQ floats; raises DIT_FLAG_T_RANGE)
+//   x = silu(x)                                              in place
+//   c[b, :] = silu(temb2[b, :] + ytable[clamp(y[b])][:])     (raises DIT_FLAG_Y_RANGE)
+int dit_cond_gather(const float *table, const int64_t *t, int B, float *temb, int *flag, hipStream_t stream);
+int dit_silu(float *x, int64_t n, hipStream_t stream);
+int dit_cond_combine(const float *temb2, const float *ytable, int y_rows, const int64_t *y, int B, int D, float *c, int *flag,
+                     hipStream_t stream);
+// out [B, Cout, HW]: channels [0, min(3, Cout)) of both halves <- uncond + s * (cond - uncond), in place
+int dit_cfg_blend(float *out, int B, int Cout, int64_t HW, float s, hipStream_t stream);
+
+}  // namespace omnitok

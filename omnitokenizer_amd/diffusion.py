@@ -1,0 +1,273 @@
+"""The ancestral sampler of the reference's Diffusion/DiT/diffusion package on the MI355X: `create_diffusion` with the reference's
+signature, and of the object it returns what sample.py / sample_ddp.py use -- p_sample_loop, p_sample, timestep_map,
+num_timesteps.
+
+    from omnitokenizer_amd.diffusion import create_diffusion, generate_images
+    diffusion = create_diffusion("250")
+    samples = diffusion.p_sample_loop(model.forward_with_cfg, z.shape, z, clip_denoised=False,
+                                      model_kwargs=dict(y=y, cfg_scale=4.0), device=z.device)
+
+Built: epsilon prediction, LEARNED_RANGE or fixed variances, the linear schedule, space_timesteps with its section form
+("10,15,20").  The coefficient tables are computed on the host in fp64 exactly as the reference's numpy does (respacing
+included) and rounded to fp32 where _extract_into_tensor rounds them (gaussian_diffusion.py:861-874); one step is one model call
+plus ONE element-wise kernel (omnitok_dit_p_sample).  Everything else raises NotImplementedError with the reference line.
+"""
+from __future__ import annotations
+
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import check
+
+_REF = "Diffusion/DiT/diffusion/"
+
+
+def space_timesteps(num_timesteps, section_counts):
+    """respace.py:12-62: the timesteps of the original process to keep, for a count per equally sized section."""
+    if isinstance(section_counts, str):
+        if section_counts.startswith("ddim"):
+            raise NotImplementedError(f"the 'ddimN' striding ({_REF}respace.py:32-39) belongs to the DDIM sampler, which is not built")
+        section_counts = [int(x) for x in section_counts.split(",")]
+    size_per = num_timesteps // len(section_counts)
+    extra = num_timesteps % len(section_counts)
+    start_idx = 0
+    all_steps = []
+    for i, section_count in enumerate(section_counts):
+        size = size_per + (1 if i < extra else 0)
+        if size < section_count:
+            raise ValueError(f"cannot divide section of {size} steps into {section_count}")
+        frac_stride = 1 if section_count <= 1 else (size - 1) / (section_count - 1)
+        cur_idx = 0.0
+        for _ in range(section_count):
+            all_steps.append(start_idx + round(cur_idx))
+            cur_idx += frac_stride
+        start_idx += size
+    return set(all_steps)
+
+
+def linear_betas(num_diffusion_timesteps):
+    """get_named_beta_schedule("linear") (gaussian_diffusion.py:106-115): Ho et al.'s schedule scaled to any step count."""
+    scale = 1000 / num_diffusion_timesteps
+    return np.linspace(scale * 0.0001, scale * 0.02, num_diffusion_timesteps, dtype=np.float64)
+
+
+def _not_built(what, where):
+    raise NotImplementedError(f"{what} is not built ({_REF}{where})")
+
+
+class SpacedDiffusion:
+    """respace.py:65-129 over gaussian_diffusion.py:144-201: the respaced process and its fp64 tables."""
+
+    COEF_NAMES = ("sqrt_recip_alphas_cumprod", "sqrt_recipm1_alphas_cumprod", "posterior_mean_coef1", "posterior_mean_coef2",
+                  "posterior_log_variance_clipped", "log_betas", "fixed_log_variance", "nonzero_mask")
+
+    def __init__(self, use_timesteps, betas, learn_sigma=True, sigma_small=False):
+        self.use_timesteps = set(use_timesteps)
+        self.original_num_steps = len(betas)
+        self.learn_sigma = bool(learn_sigma)
+        self.sigma_small = bool(sigma_small)
+        base_cumprod = np.cumprod(1.0 - np.asarray(betas, dtype=np.float64), axis=0)
+        last = 1.0
+        new_betas, self.timestep_map = [], []
+        for i, ac in enumerate(base_cumprod):
+            if i in self.use_timesteps:
+                new_betas.append(1 - ac / last)
+                last = ac
+                self.timestep_map.append(i)
+        betas = np.array(new_betas, dtype=np.float64)
+        assert betas.ndim == 1 and (betas > 0).all() and (betas <= 1).all()
+        self.betas = betas
+        self.num_timesteps = int(betas.shape[0])
+        alphas = 1.0 - betas
+        self.alphas_cumprod = np.cumprod(alphas, axis=0)
+        self.alphas_cumprod_prev = np.append(1.0, self.alphas_cumprod[:-1])
+        self.sqrt_recip_alphas_cumprod = np.sqrt(1.0 / self.alphas_cumprod)
+        self.sqrt_recipm1_alphas_cumprod = np.sqrt(1.0 / self.alphas_cumprod - 1)
+        self.posterior_variance = betas * (1.0 - self.alphas_cumprod_prev) / (1.0 - self.alphas_cumprod)
+        self.posterior_log_variance_clipped = np.log(np.append(self.posterior_variance[1], self.posterior_variance[1:])) \
+            if len(self.posterior_variance) > 1 else np.array([])
+        self.posterior_mean_coef1 = betas * np.sqrt(self.alphas_cumprod_prev) / (1.0 - self.alphas_cumprod)
+        self.posterior_mean_coef2 = (1.0 - self.alphas_cumprod_prev) * np.sqrt(alphas) / (1.0 - self.alphas_cumprod)
+        if self.num_timesteps < 2:
+            raise ValueError("the sampler needs at least two timesteps (the reference's clipped log variance is empty below)")
+        self._dev_tables = {}
+
+    # ---- the per-timestep scalars of one ancestral step ---------------------------------------------------------------------
+    def coefficient_table(self) -> np.ndarray:
+        """[num_timesteps, 8] fp32, the columns of COEF_NAMES (include/omnitok_dit.h, omnitok_dit_p_sample): each fp64 table
+        rounded to fp32 as _extract_into_tensor's .float() does.  The fixed log variance is FIXED_LARGE's
+        log(append(posterior_variance[1], betas[1:])) or, with sigma_small, the clipped posterior one (gaussian_diffusion.py:295-306)."""
+        fixed = self.posterior_log_variance_clipped if self.sigma_small else \
+            np.log(np.append(self.posterior_variance[1], self.betas[1:]))
+        cols = [self.sqrt_recip_alphas_cumprod, self.sqrt_recipm1_alphas_cumprod, self.posterior_mean_coef1,
+                self.posterior_mean_coef2, self.posterior_log_variance_clipped, np.log(self.betas), fixed,
+                (np.arange(self.num_timesteps) != 0).astype(np.float64)]
+        return np.stack(cols, axis=1).astype(np.float32)
+
+    def _table_on(self, device):
+        key = str(device)
+        if key not in self._dev_tables:
+            self._dev_tables[key] = (torch.from_numpy(self.coefficient_table()).to(device).contiguous(),
+                                     torch.tensor(self.timestep_map, device=device, dtype=torch.int64))
+        return self._dev_tables[key]
+
+    # ---- sampling ---------------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _refuse(denoised_fn=None, cond_fn=None):
+        if denoised_fn is not None:
+            _not_built("denoised_fn", "gaussian_diffusion.py:310-315")
+        if cond_fn is not None:
+            _not_built("cond_fn (classifier guidance)", "gaussian_diffusion.py:346-356, 414-415")
+
+    @torch.no_grad()
+    def p_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None, noise=None):
+        """gaussian_diffusion.py:376-417.  x [N,C,H,W] fp32 on the GPU, t [N] indices of the RESPACED process; the model is called
+        with timestep_map[t] (respace.py:124-129).  noise: this step's normal draw (default torch.randn_like(x)).
+        Returns {"sample", "pred_xstart"}."""
+        self._refuse(denoised_fn, cond_fn)
+        if x.device.type != "cuda":
+            raise RuntimeError(f"x is on {x.device}: the sampler runs on the GPU only")
+        x = x.float().contiguous()
+        B, C = x.shape[:2]
+        t = t.to(device=x.device, dtype=torch.int64).contiguous()
+        if tuple(t.shape) != (B,):
+            raise ValueError(f"t must be [{B}]")
+        coef, tmap = self._table_on(x.device)
+        model_output = model(x, tmap[t], **(model_kwargs or {}))
+        if isinstance(model_output, tuple):
+            model_output = model_output[0]
+        want = (B, C * (2 if self.learn_sigma else 1), *x.shape[2:])
+        if tuple(model_output.shape) != want:
+            raise ValueError(f"model output {tuple(model_output.shape)}, expected {want}")
+        model_output = model_output.float().contiguous()
+        if noise is None:
+            noise = torch.randn_like(x)
+        elif noise.shape != x.shape or noise.device != x.device:
+            raise ValueError("noise must have x's shape and device")
+        noise = noise.float().contiguous()
+        sample, xstart = torch.empty_like(x), torch.empty_like(x)
+        P = ctypes.c_void_p
+        check(_lib.load().omnitok_dit_p_sample(P(model_output.data_ptr()), P(x.data_ptr()), P(noise.data_ptr()), P(coef.data_ptr()),
+                                               self.num_timesteps, P(t.data_ptr()), B, C, x[0, 0].numel(), int(self.learn_sigma),
+                                               int(bool(clip_denoised)), P(sample.data_ptr()), P(xstart.data_ptr()),
+                                               torch.cuda.current_stream().cuda_stream), "dit_p_sample")
+        return {"sample": sample, "pred_xstart": xstart}
+
+    @torch.no_grad()
+    def p_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
+                                  model_kwargs=None, device=None, progress=False, step_noise=None):
+        """gaussian_diffusion.py:464-511.  step_noise: [num_timesteps, *shape] -- row k is the draw of the k-th step taken
+        (timestep num_timesteps - 1 - k) -- or a callable step_noise(k, shape, device); it replaces the per-step torch.randn."""
+        self._refuse(denoised_fn, cond_fn)
+        if device is None:
+            owner = getattr(model, "__self__", model)
+            device = next(owner.parameters()).device
+        device = torch.device(device)
+        assert isinstance(shape, (tuple, list))
+        img = noise if noise is not None else torch.randn(*shape, device=device)
+        if step_noise is not None and not callable(step_noise) and tuple(step_noise.shape) != (self.num_timesteps, *shape):
+            raise ValueError(f"step_noise must be [{self.num_timesteps}, *shape]")
+        owner = getattr(model, "__self__", None)
+        fast = owner is not None and hasattr(owner, "check_range") and getattr(model, "__name__", "") in ("forward", "forward_with_cfg")
+        kwargs = dict(model_kwargs or {})
+        if fast:
+            kwargs["check_range"] = False  # one read-back after the loop instead of a host synchronisation per step
+        indices = list(range(self.num_timesteps))[::-1]
+        if progress:
+            from tqdm.auto import tqdm
+            indices = tqdm(indices)
+        for k, i in enumerate(indices):
+            t = torch.full((shape[0],), i, device=device, dtype=torch.int64)
+            if step_noise is None:
+                eps = None
+            elif callable(step_noise):
+                eps = step_noise(k, tuple(shape), device)
+            else:
+                eps = step_noise[k].to(device)
+            out = self.p_sample(model, img, t, clip_denoised=clip_denoised, model_kwargs=kwargs, noise=eps)
+            yield out
+            img = out["sample"]
+        if fast:
+            owner.check_range()
+
+    def p_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
+                      device=None, progress=False, step_noise=None):
+        """gaussian_diffusion.py:419-462: all rows of the batch, as the reference returns them (with classifier-free guidance the
+        caller `chunk`s the null half away)."""
+        final = None
+        for sample in self.p_sample_loop_progressive(model, shape, noise=noise, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
+                                                     cond_fn=cond_fn, model_kwargs=model_kwargs, device=device, progress=progress,
+                                                     step_noise=step_noise):
+            final = sample
+        return final["sample"]
+
+    # ---- what is not built ----------------------------------------------------------------------------------------------------------
+    def ddim_sample(self, *a, **k):
+        _not_built("DDIM sampling", "gaussian_diffusion.py:513-560")
+
+    def ddim_reverse_sample(self, *a, **k):
+        _not_built("DDIM sampling", "gaussian_diffusion.py:562-598")
+
+    def ddim_sample_loop(self, *a, **k):
+        _not_built("DDIM sampling", "gaussian_diffusion.py:600-631")
+
+    def ddim_sample_loop_progressive(self, *a, **k):
+        _not_built("DDIM sampling", "gaussian_diffusion.py:633-680")
+
+    def training_losses(self, *a, **k):
+        _not_built("training_losses (DiT training)", "gaussian_diffusion.py:715-787")
+
+    def calc_bpd_loop(self, *a, **k):
+        _not_built("calc_bpd_loop", "gaussian_diffusion.py:805-858")
+
+
+def create_diffusion(timestep_respacing, noise_schedule="linear", use_kl=False, sigma_small=False, predict_xstart=False,
+                     learn_sigma=True, rescale_learned_sigmas=False, diffusion_steps=1000):
+    """diffusion/__init__.py:10-46.  use_kl / rescale_learned_sigmas only choose a training loss there and are accepted."""
+    if noise_schedule != "linear":
+        _not_built(f"the {noise_schedule!r} noise schedule", "gaussian_diffusion.py:116-122")
+    if predict_xstart:
+        _not_built("predict_xstart (ModelMeanType.START_X)", "gaussian_diffusion.py:317-318")
+    betas = linear_betas(diffusion_steps)
+    if timestep_respacing is None or timestep_respacing == "":
+        timestep_respacing = [diffusion_steps]
+    return SpacedDiffusion(space_timesteps(diffusion_steps, timestep_respacing), betas, learn_sigma=learn_sigma,
+                           sigma_small=sigma_small)
+
+
+@torch.no_grad()
+def generate_images(dit, diffusion, vae, labels, cfg_scale=1.5, seed=0):
+    """The body of sample_ddp.py:136-163 in one call: labels [n] int64 on the GPU -> uint8 images [n,H,W,3].
+    z ~ N(0, 1) from a generator seeded with `seed` on the model's device; with cfg_scale > 1 the batch is doubled with the null
+    class (num_classes) and run through forward_with_cfg; p_sample_loop with clip_denoised=False; the null half is dropped;
+    vae.decode(samples / 0.18215, is_image=True); frames.pixels_to_frames, this package's uint8 conversion (the script's own is
+    clamp(255 x + 128, 0, 255) truncated: half a grey level above it)."""
+    from .frames import pixels_to_frames
+    if cfg_scale < 1.0:
+        raise ValueError("In almost all cases, cfg_scale be >= 1.0")
+    device = dit.device
+    labels = labels.to(device=device, dtype=torch.int64)
+    n = labels.shape[0]
+    gen = torch.Generator(device=device)
+    gen.manual_seed(int(seed))
+    z = torch.randn(n, dit.in_channels, dit.input_size, dit.input_size, device=device, generator=gen)
+    using_cfg = cfg_scale > 1.0
+    if using_cfg:
+        z = torch.cat([z, z], 0)
+        y = torch.cat([labels, torch.full((n,), dit.num_classes, device=device, dtype=torch.int64)], 0)
+        model_kwargs, sample_fn = dict(y=y, cfg_scale=cfg_scale), dit.forward_with_cfg
+    else:
+        model_kwargs, sample_fn = dict(y=labels), dit.forward
+
+    def draw(k, shape, dev):
+        return torch.randn(*shape, device=dev, generator=gen)
+
+    samples = diffusion.p_sample_loop(sample_fn, z.shape, z, clip_denoised=False, model_kwargs=model_kwargs, device=device,
+                                      step_noise=draw)
+    if using_cfg:
+        samples, _ = samples.chunk(2, dim=0)
+    pixels = vae.decode((samples / 0.18215).contiguous(), is_image=True)
+    return pixels_to_frames(pixels)

@@ -1,0 +1,170 @@
+#!/usr/bin/env python
+"""One denoising step of DiT-XL/2 on the engine against the fp32 PyTorch restatement on the same GPU, in the same session.
+
+    python tools/dit_bench.py --out profiles/dit_bench.json
+
+The workload: DiT-XL/2 at input_size 32, 8 latent channels (the --use_vae tokenizer's), seeded random weights, 8 images with
+classifier-free guidance = 16 streams x 256 tokens = 4096 rows; one step = forward_with_cfg + the p_sample update.  Reported:
+  step_ms            median of >= 20 steps after warm-up, device events around each step
+  torch_step_ms      the same step through tests/dit_ref.py in fp32 by torch on this GPU (what a user would otherwise run)
+  split              each operator alone at the model's shapes through its stand-alone entry point, x its calls per forward; their sum
+                     is not the step (no launch gaps, warm caches): it says where the time goes
+  attention          the attention kernel's useful FLOP (4 B heads N^2 hd: both products, the dead 3/4 of head_dim 72's third output
+                     block not counted) over its time, as a fraction of the fp32-input MFMA peak
+"""
+import argparse
+import ctypes
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+PEAK_F32_MFMA_TFLOPS = 157.3
+
+
+def timed(fn, warmup, steps):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(steps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+    return statistics.median(ms), min(ms), max(ms)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--model", default="DiT-XL/2")
+    ap.add_argument("--images", type=int, default=8)
+    ap.add_argument("--steps", type=int, default=24)
+    ap.add_argument("--warmup", type=int, default=4)
+    ap.add_argument("--torch-steps", type=int, default=20)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("dit_bench needs the GPU: there is nothing to measure without it")
+    from omnitokenizer_amd import _lib
+    from omnitokenizer_amd.dit import DiT_models
+    from omnitokenizer_amd.diffusion import create_diffusion
+    from tests import dit_ref
+
+    m = DiT_models[a.model](input_size=32, in_channels=8, num_classes=1000)
+    cfg = dict(input_size=32, patch_size=m.patch_size, in_channels=8, hidden_size=m.hidden_size, depth=m.depth,
+               num_heads=m.num_heads, mlp_ratio=4.0, class_dropout_prob=0.1, num_classes=1000, learn_sigma=True)
+    w = dit_ref.make_weights(cfg, 1)
+    m.load_state_dict(w, strict=True)
+    m = m.cuda().eval()
+    wd = {k: v.cuda() for k, v in w.items()}
+    n = a.images
+    B = 2 * n
+    g = torch.Generator(device="cuda")
+    g.manual_seed(0)
+    z = torch.randn(n, 8, 32, 32, device="cuda", generator=g)
+    z = torch.cat([z, z])
+    y = torch.cat([torch.arange(n, device="cuda") % 1000, torch.full((n,), 1000, device="cuda")])
+    noise = torch.randn(B, 8, 32, 32, device="cuda", generator=g)
+    d = create_diffusion("250")
+    t = torch.full((B,), 125, device="cuda", dtype=torch.int64)
+    kw = dict(y=y, cfg_scale=4.0, check_range=False)
+
+    def engine_step():
+        return d.p_sample(m.forward_with_cfg, z, t, clip_denoised=False, model_kwargs=kw, noise=noise)["sample"]
+
+    coef = d.coefficient_table()[125]
+    tmap = torch.tensor(d.timestep_map, device="cuda")
+
+    def torch_step():
+        out = dit_ref.forward_with_cfg(wd, cfg, z, tmap[t], y, 4.0)
+        return dit_ref.p_sample(coef, out, z, noise, True, False)[0]
+
+    with torch.no_grad():
+        ours, ref = engine_step(), torch_step()
+        diff = float((ours - ref).abs().max())
+        step = timed(engine_step, a.warmup, a.steps)
+        tstep = timed(torch_step, a.warmup, a.torch_steps)
+
+    # ---- the split: each operator alone at the model's shapes -------------------------------------------------------------------
+    lib = _lib.load()
+    P = ctypes.c_void_p
+    st = torch.cuda.current_stream().cuda_stream
+    D, F, N, H, hd, L = m.hidden_size, m.mlp_hidden, (32 // m.patch_size) ** 2, m.num_heads, m.hidden_size // m.num_heads, m.depth
+    M = B * N
+    modN = L * 6 * D + 2 * D
+    PC = m.patch_size ** 2 * 16
+    buf = lambda *s: torch.randn(*s, device="cuda", generator=g)  # noqa: E731
+    X, Y, QKV, H1, mod = buf(M, D), buf(M, D), buf(M, 3 * D), buf(M, F), buf(B, modN) * 0.1
+    O, O3, OF, OL = torch.empty(M, D, device="cuda"), torch.empty(M, 3 * D, device="cuda"), torch.empty(M, F, device="cuda"), \
+        torch.empty(M, PC, device="cuda")
+    Wqkv, Wp, W1, W2, Wf, bias = buf(3 * D, D), buf(D, D), buf(F, D), buf(D, F), buf(PC, D), buf(max(3 * D, F, modN))  # the widest N
+
+    def gemm(A, W, C, Mr, Nc, K):
+        assert A.numel() >= Mr * K and W.numel() == Nc * K and C.numel() == Mr * Nc and bias.numel() >= Nc, "operand smaller than the GEMM"
+        desc = _lib.OmnitokRowGemm(a=A.data_ptr(), lda=K, w=W.data_ptr(), ldw=K, bias=bias.data_ptr(), c=C.data_ptr(), ldc=Nc, M=Mr,
+                                   N=Nc, K=K, flags=1)
+        return lambda: _lib.check(lib.omnitok_gemm(ctypes.byref(desc), st))
+
+    xin, wpe, pos = buf(B, 8, 32, 32), buf(D, 8, m.patch_size, m.patch_size), buf(N, D)
+    img = torch.empty(B, 16, 32, 32, device="cuda")
+    ops = {
+        "patch_embed": (1, lambda: lib.omnitok_dit_patch_embed(P(xin.data_ptr()), B, P(wpe.data_ptr()), P(bias.data_ptr()), P(pos.data_ptr()),
+                                                               B, 8, 32, m.patch_size, D, P(O.data_ptr()), st)),
+        "ln_modulate": (2 * L + 1, lambda: lib.omnitok_dit_ln_modulate(P(X.data_ptr()), P(mod.data_ptr()), P(mod.data_ptr() + 4 * D), modN,
+                                                                       M, N, D, P(O.data_ptr()), st)),
+        "gemm_qkv": (L, gemm(X, Wqkv, O3, M, 3 * D, D)),
+        "attention": (L, lambda: lib.omnitok_dit_attn(P(QKV.data_ptr()), B, N, H, hd, P(O.data_ptr()), st)),
+        "gemm_proj": (L, gemm(X, Wp, O, M, D, D)),
+        "gate_residual": (2 * L, lambda: lib.omnitok_dit_gate_residual(P(Y.data_ptr()), P(X.data_ptr()), P(mod.data_ptr()), modN, M, N, D, st)),
+        "gemm_fc1": (L, gemm(X, W1, OF, M, F, D)),
+        "gelu_tanh": (L, lambda: lib.omnitok_dit_gelu_tanh(P(H1.data_ptr()), M * F, st)),
+        "gemm_fc2": (L, gemm(H1, W2, O, M, D, F)),
+        "gemm_modulation": (1, gemm(X, buf(modN, D), torch.empty(B, modN, device="cuda"), B, modN, D)),
+        "gemm_final": (1, gemm(X, Wf, OL, M, PC, D)),
+        "unpatchify": (1, lambda: lib.omnitok_dit_unpatchify(P(OL.data_ptr()), B, N, m.patch_size, 16, P(img.data_ptr()), st)),
+    }
+    split = {}
+    for name, (calls, fn) in ops.items():
+        def rep(fn=fn):
+            for _ in range(10):
+                fn()
+        print("split:", name, file=sys.stderr, flush=True)
+        med, _, _ = timed(rep, 2, 10)
+        split[name] = {"ms_per_call": round(med / 10, 5), "calls_per_forward": calls, "ms_per_forward": round(med / 10 * calls, 4)}
+    attn_ms = split["attention"]["ms_per_call"]
+    attn_flop = 4.0 * B * H * N * N * hd
+    gemm_flop = 2.0 * M * D * (3 * D + D + 2 * F) * L
+    gemm_ms = sum(split[k]["ms_per_forward"] for k in ("gemm_qkv", "gemm_proj", "gemm_fc1", "gemm_fc2"))
+    res = {
+        "bench": "dit_step", "model": a.model, "input_size": 32, "in_channels": 8, "images": n, "streams": B, "rows": M,
+        "device": torch.cuda.get_device_name(0), "arithmetic": "fp32 (v_mfma_f32_32x32x2_f32 GEMMs and attention)",
+        "step_ms": round(step[0], 4), "step_ms_min_max": [round(step[1], 4), round(step[2], 4)], "steps_timed": a.steps,
+        "torch_step_ms": round(tstep[0], 4), "torch_step_ms_min_max": [round(tstep[1], 4), round(tstep[2], 4)],
+        "torch_baseline": "tests/dit_ref.py forward_with_cfg + p_sample in fp32 through torch on the same GPU, same session "
+                          f"(allow_tf32 {torch.backends.cuda.matmul.allow_tf32})",
+        "speedup_over_torch": round(tstep[0] / step[0], 3), "max_abs_diff_to_torch_step": diff,
+        "split": split, "split_sum_ms": round(sum(v["ms_per_forward"] for v in split.values()), 4),
+        "attention": {"useful_flop": attn_flop, "tflops": round(attn_flop / (attn_ms * 1e-3) / 1e12, 2),
+                      "frac_of_f32_mfma_peak": round(attn_flop / (attn_ms * 1e-3) / 1e12 / PEAK_F32_MFMA_TFLOPS, 4)},
+        "block_gemms": {"flop": gemm_flop, "tflops": round(gemm_flop / (gemm_ms * 1e-3) / 1e12, 2),
+                        "frac_of_f32_mfma_peak": round(gemm_flop / (gemm_ms * 1e-3) / 1e12 / PEAK_F32_MFMA_TFLOPS, 4)},
+        "peak_f32_mfma_tflops": PEAK_F32_MFMA_TFLOPS,
+    }
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+
+
+if __name__ == "__main__":
+    main()
