@@ -7,6 +7,7 @@
 //   dit_ops.hip    the small kernels: patch_embed (+ pos_embed), the conditioning's gather / SiLU passes, ln_modulate, gelu_tanh,
 //                  gate_residual, unpatchify, the classifier-free-guidance blend and p_sample, with their exported entry points
 //   dit_attn.hip   dit_attn_kernel: non-causal attention on v_mfma_f32_32x32x2_f32, head_dim 64 and 72 (omnitok_dit_attn)
+//   attn_f32_tiled.h  (not the DiT's alone) the body of dit_attn_kernel, shared with the LM's tiled causal prefill attention
 //   dit_engine.hip struct omnitok_dit and its exported functions (create .. finalize, forward, forward_cfg)
 // The linears (qkv, proj, fc1, fc2, the conditioning MLP, the modulation GEMM and the final linear) are omnitok_gemm calls.
 #pragma once

@@ -18,7 +18,7 @@
 //   lm_attn.hip       lm_attn_decode_kernel (flash-decode over the fp32 / bf16 / fp16 K/V cache, chunk partials), lm_attn_merge_kernel
 //                     (fp32 or, for a PF_W16 prefill, 16-bit output), lm_kv_scatter_kernel, lm_kv_read_kernel, omnitok_lm_attn_decode[_kv16]
 //   lm_attn_prefill.hip  the tiled causal attention of the prefill, K/V tiles shared by 128 query rows (omnitok_lm_set_prefill_attention):
-//                     lm_attn_prefill_kernel on the fp32-input MFMA and lm_attn_prefill16_kernel on the bf16 / fp16 MFMA (Q / K / V / P
+//                     lm_attn_prefill_kernel on the fp32-input MFMA (the body it shares with the DiT: attn_f32_tiled.h) and lm_attn_prefill16_kernel on the bf16 / fp16 MFMA (Q / K / V / P
 //                     rounded once to the operand format; omnitok_lm_set_prefill_attention_operands) behind one host side,
 //                     lm_attn_prefill_any; omnitok_lm_attn_prefill, omnitok_lm_attn_prefill16
 //   lm_engine.hip     struct omnitok_lm and its exported functions (create .. finalize, alloc_cache, step, prefill, prefill_loss) and the
