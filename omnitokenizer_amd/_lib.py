@@ -369,3 +369,14 @@ def check(rc: int, what: str = ""):
     if rc == -4:
         raise NotImplementedError(msg)
     raise OmnitokError(f"{what}: {msg} (status {rc})")
+
+
+def ptr(t):
+    """the address of tensor t as a ctypes pointer argument; None (a null pointer) for None"""
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def stream():
+    """the current torch stream as the omnitok_stream_t argument of the entry points"""
+    import torch
+    return torch.cuda.current_stream().cuda_stream

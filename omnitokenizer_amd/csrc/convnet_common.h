@@ -1,6 +1,7 @@
-// What csrc/i3d.hip and csrc/inception.hip share: the implicit-GEMM convolution of I3D's Unit3D (and of Inception V3's
-// BasicConv2d, as T = kt = 1 with explicit padding) and the bilinear source arithmetic of their preprocess kernels.  The
-// design is described at the top of csrc/i3d.hip.
+// What csrc/i3d.hip and csrc/inception.hip share (LPIPS's VGG16 trunk runs on the latter's conv): the implicit-GEMM
+// convolution of I3D's Unit3D (and of Inception V3's BasicConv2d, as T = kt = 1 with explicit padding) with the host side of
+// its two entry points, and the bilinear source arithmetic of their preprocess kernels.  The design is described at the top
+// of csrc/i3d.hip.
 #pragma once
 #include "gemm_common.h"
 
@@ -218,6 +219,46 @@ static int conv_launch(const CvArgs &a, int64_t nbm, hipStream_t stream, const c
     OT_CHECK_ARG(tiles <= 0x7fffffff, "%s: %lld tiles", what, (long long)tiles);
     hipLaunchKernelGGL((conv3d_same_kernel<WMT, WNT, WN>), dim3((unsigned)tiles), dim3(256), lds, stream, p);
     OT_LAUNCH_CHECK(what);
+    return OMNITOK_OK;
+}
+
+// What omnitok_conv3d_same and omnitok_conv2d check and fill alike, for a descriptor D (omnitok_conv3d, omnitok_conv2d_desc)
+// whose sizes, kernel, strides and padding the caller has checked and written to `a` with the output grid and ldw: the
+// channel windows of x, y and y2, then (unless batch == 0: nothing is read, so null pointers are fine, and the caller returns)
+// the pointers, the rest of `a` and the size limit.
+template <class D>
+static int conv_args(const D *c, const char *what, int batch, CvArgs &a) {
+    OT_CHECK_ARG(c->x_off >= 0 && c->x_off % 4 == 0 && c->x_cs % 4 == 0 && c->x_off + c->Cin <= c->x_cs,
+                 "%s: input channels [%d, %d) outside the %lld per position, or not 16-byte groups", what, c->x_off,
+                 c->x_off + c->Cin, (long long)c->x_cs);
+    OT_CHECK_ARG(c->split >= 1 && c->split <= c->Cout, "%s: split %d outside 1..Cout (%d)", what, c->split, c->Cout);
+    OT_CHECK_ARG(c->y_off >= 0 && c->y_off + c->split <= c->y_cs, "%s: output channels [%d, %d) outside the %lld per "
+                 "position", what, c->y_off, c->y_off + c->split, (long long)c->y_cs);
+    if (c->split < c->Cout)
+        OT_CHECK_ARG(c->y2_off >= 0 && c->y2_off + (c->Cout - c->split) <= c->y2_cs, "%s: second output channels [%d, %d) "
+                     "outside the %lld per position", what, c->y2_off, c->y2_off + c->Cout - c->split, (long long)c->y2_cs);
+    if (batch == 0) return OMNITOK_OK;
+    OT_CHECK_ARG(c->x && c->w && c->bias && c->y && (c->split == c->Cout || c->y2), "%s: null pointer", what);
+    OT_CHECK_ARG(aligned16(c->x) && aligned16(c->w), "%s: x and w must be 16-byte aligned", what);
+    a.x = c->x;
+    a.x_cs = c->x_cs;
+    a.x_off = c->x_off;
+    a.Cin = c->Cin;
+    a.w = c->w;
+    a.bias = c->bias;
+    a.N = c->Cout;
+    a.M = (int64_t)batch * a.To * a.Ho * a.Wo;
+    OT_CHECK_ARG((int64_t)batch * a.T * a.H * a.W * c->x_cs < (1ll << 40) && a.M * std::max(c->y_cs, c->y2_cs) < (1ll << 40),
+                 "%s: tensors too large", what);
+    a.nk = (int)(a.ldw / CV_BK);
+    a.y = c->y;
+    a.y_cs = c->y_cs;
+    a.y_off = c->y_off;
+    a.y2 = c->y2;
+    a.y2_cs = c->y2_cs;
+    a.y2_off = c->y2_off;
+    a.split = c->split;
+    a.relu = c->relu;
     return OMNITOK_OK;
 }
 

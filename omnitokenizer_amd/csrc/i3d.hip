@@ -7,7 +7,7 @@
 //     channel 3 = 0.  The source index / lambda arithmetic and the tap order are those of frames.hip's BILINEAR mode, on the
 //     values 0..255 instead of u / 255; where the size does not change the taps are (v, 1, 0) and the result is exact.
 //
-//   conv3d_same_kernel<WMT, WNT, WN> (csrc/i3d_common.h, shared with csrc/inception.hip)   one Unit3D: TF "same" padding (Unit3D.compute_pad: the front gets pad // 2, the back the
+//   conv3d_same_kernel<WMT, WNT, WN> (csrc/convnet_common.h, shared with csrc/inception.hip)   one Unit3D: TF "same" padding (Unit3D.compute_pad: the front gets pad // 2, the back the
 //     rest), conv3d, the folded BatchNorm's bias and an optional ReLU, as an implicit GEMM on v_mfma_f32_32x32x2_f32:
 //       M = output positions (b, t, h, w), N = Cout, K = taps x Cin, k = tap * Cin + ci, tap = (dt * kh + dh) * kw + dw.
 //     A (BM x 32) is gathered from the input on the fly (zeros outside it: the pad); B is the packed weight [Cout][Kpad].
@@ -25,7 +25,7 @@
 //   i3d_head_kernel   AvgPool3d([2, 7, 7], stride 1) (sum of the 98 taps in (t, h, w) order, / 98), the logits 1x1x1 conv
 //     with bias (a k-ordered fma chain over C) and the mean over the pooled time steps (sum in t order, / T'): one block
 //     per (clip, h', w').
-#include "i3d_common.h"
+#include "convnet_common.h"
 
 namespace omnitok {
 
@@ -193,57 +193,23 @@ extern "C" int omnitok_conv3d_same(const omnitok_conv3d *c, omnitok_stream_t str
     OT_CHECK_ARG(c->st >= 1 && c->st <= 4 && c->sh >= 1 && c->sh <= 4 && c->sw >= 1 && c->sw <= 4,
                  "conv3d_same: strides %d x %d x %d outside 1..4", c->st, c->sh, c->sw);
     OT_CHECK_ARG(c->relu == 0 || c->relu == 1, "conv3d_same: relu %d", c->relu);
-    OT_CHECK_ARG(c->x_off >= 0 && c->x_off % 4 == 0 && c->x_cs % 4 == 0 && c->x_off + c->Cin <= c->x_cs,
-                 "conv3d_same: input channels [%d, %d) outside the %lld per position, or not 16-byte groups", c->x_off,
-                 c->x_off + c->Cin, (long long)c->x_cs);
-    OT_CHECK_ARG(c->split >= 1 && c->split <= c->Cout, "conv3d_same: split %d outside 1..Cout (%d)", c->split, c->Cout);
-    OT_CHECK_ARG(c->y_off >= 0 && c->y_off + c->split <= c->y_cs, "conv3d_same: output channels [%d, %d) outside the %lld "
-                 "per position", c->y_off, c->y_off + c->split, (long long)c->y_cs);
-    if (c->split < c->Cout)
-        OT_CHECK_ARG(c->y2_off >= 0 && c->y2_off + (c->Cout - c->split) <= c->y2_cs, "conv3d_same: second output channels "
-                     "[%d, %d) outside the %lld per position", c->y2_off, c->y2_off + c->Cout - c->split,
-                     (long long)c->y2_cs);
-    if (c->B == 0) return OMNITOK_OK;
-    OT_CHECK_ARG(c->x && c->w && c->bias && c->y && (c->split == c->Cout || c->y2), "conv3d_same: null pointer");
-    OT_CHECK_ARG(aligned16(c->x) && aligned16(c->w), "conv3d_same: x and w must be 16-byte aligned");
     CvArgs a{};
-    int To, Ho, Wo;
-    same_pad(c->T, c->kt, c->st, a.pt, To);
-    same_pad(c->H, c->kh, c->sh, a.ph, Ho);
-    same_pad(c->W, c->kw, c->sw, a.pw, Wo);
-    OT_CHECK_ARG(To >= 1 && Ho >= 1 && Wo >= 1, "conv3d_same: empty output");
-    a.x = c->x;
-    a.x_cs = c->x_cs;
-    a.x_off = c->x_off;
     a.T = c->T;
     a.H = c->H;
     a.W = c->W;
-    a.Cin = c->Cin;
-    a.w = c->w;
     a.ldw = ldw;
-    a.bias = c->bias;
-    a.N = c->Cout;
     a.kt = c->kt;
     a.kh = c->kh;
     a.kw = c->kw;
     a.st = c->st;
     a.sh = c->sh;
     a.sw = c->sw;
-    a.To = To;
-    a.Ho = Ho;
-    a.Wo = Wo;
-    a.M = (int64_t)c->B * To * Ho * Wo;
-    OT_CHECK_ARG((int64_t)c->B * c->T * c->H * c->W * c->x_cs < (1ll << 40) && a.M * std::max(c->y_cs, c->y2_cs) < (1ll << 40),
-                 "conv3d_same: tensors too large");
-    a.nk = (int)(ldw / CV_BK);
-    a.y = c->y;
-    a.y_cs = c->y_cs;
-    a.y_off = c->y_off;
-    a.y2 = c->y2;
-    a.y2_cs = c->y2_cs;
-    a.y2_off = c->y2_off;
-    a.split = c->split;
-    a.relu = c->relu;
+    same_pad(c->T, c->kt, c->st, a.pt, a.To);
+    same_pad(c->H, c->kh, c->sh, a.ph, a.Ho);
+    same_pad(c->W, c->kw, c->sw, a.pw, a.Wo);
+    OT_CHECK_ARG(a.To >= 1 && a.Ho >= 1 && a.Wo >= 1, "conv3d_same: empty output");  // "same" padding: never, for sizes >= 1
+    if (int rc = conv_args(c, "conv3d_same", c->B, a)) return rc;
+    if (c->B == 0) return OMNITOK_OK;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     // the tile by Cout alone: 128 columns unless 64 pads less (a clip's results never depend on the tile)
     const int pad128 = (c->Cout + 127) / 128 * 128, pad64 = (c->Cout + 63) / 64 * 64;

@@ -1,5 +1,5 @@
 // Inception V3 (the FID feature net of the reference's evaluation/pytorch-fid, inception.py): its layer set around the
-// implicit-GEMM convolution of csrc/i3d_common.h.  Activations are fp32 and channels-last, [N, H, W, C]; a conv reads a
+// implicit-GEMM convolution of csrc/convnet_common.h.  Activations are fp32 and channels-last, [N, H, W, C]; a conv reads a
 // channel slice of its input and writes channel slices of its outputs (include/omnitok.h "Inception V3").
 //
 //   fid_preprocess_kernel<U8>   uint8 [N, H, W, 3] (rows `ld` bytes apart) or fp32 [N, 3, H, W] -> fp32 [N, R_h, R_w, 4]:
@@ -24,7 +24,7 @@
 //
 //   spatial_mean_kernel   adaptive_avg_pool2d(x, 1) over [N, h, w, C] -> [N, C]: the fp32 sum over positions in (y, x)
 //     order from 0, divided by h * w.
-#include "i3d_common.h"
+#include "convnet_common.h"
 
 namespace omnitok {
 
@@ -225,33 +225,14 @@ extern "C" int omnitok_conv2d(const omnitok_conv2d_desc *c, omnitok_stream_t str
     OT_CHECK_ARG(c->ph >= 0 && c->ph < c->kh && c->pw >= 0 && c->pw < c->kw, "conv2d: padding %d x %d outside 0..kernel - 1",
                  c->ph, c->pw);
     OT_CHECK_ARG(c->relu == 0 || c->relu == 1, "conv2d: relu %d", c->relu);
-    OT_CHECK_ARG(c->x_off >= 0 && c->x_off % 4 == 0 && c->x_cs % 4 == 0 && c->x_off + c->Cin <= c->x_cs,
-                 "conv2d: input channels [%d, %d) outside the %lld per position, or not 16-byte groups", c->x_off,
-                 c->x_off + c->Cin, (long long)c->x_cs);
-    OT_CHECK_ARG(c->split >= 1 && c->split <= c->Cout, "conv2d: split %d outside 1..Cout (%d)", c->split, c->Cout);
-    OT_CHECK_ARG(c->y_off >= 0 && c->y_off + c->split <= c->y_cs, "conv2d: output channels [%d, %d) outside the %lld per "
-                 "position", c->y_off, c->y_off + c->split, (long long)c->y_cs);
-    if (c->split < c->Cout)
-        OT_CHECK_ARG(c->y2_off >= 0 && c->y2_off + (c->Cout - c->split) <= c->y2_cs, "conv2d: second output channels "
-                     "[%d, %d) outside the %lld per position", c->y2_off, c->y2_off + c->Cout - c->split, (long long)c->y2_cs);
     const int Ho = pool_out(c->H, c->kh, c->sh, c->ph), Wo = pool_out(c->W, c->kw, c->sw, c->pw);
     OT_CHECK_ARG(Ho >= 1 && Wo >= 1, "conv2d: empty output (%d x %d input, kernel %d x %d, padding %d x %d)", c->H, c->W,
                  c->kh, c->kw, c->ph, c->pw);
-    if (c->N == 0) return OMNITOK_OK;
-    OT_CHECK_ARG(c->x && c->w && c->bias && c->y && (c->split == c->Cout || c->y2), "conv2d: null pointer");
-    OT_CHECK_ARG(aligned16(c->x) && aligned16(c->w), "conv2d: x and w must be 16-byte aligned");
     CvArgs a{};
-    a.x = c->x;
-    a.x_cs = c->x_cs;
-    a.x_off = c->x_off;
     a.T = 1;
     a.H = c->H;
     a.W = c->W;
-    a.Cin = c->Cin;
-    a.w = c->w;
     a.ldw = ldw;
-    a.bias = c->bias;
-    a.N = c->Cout;
     a.kt = 1;
     a.kh = c->kh;
     a.kw = c->kw;
@@ -264,18 +245,8 @@ extern "C" int omnitok_conv2d(const omnitok_conv2d_desc *c, omnitok_stream_t str
     a.To = 1;
     a.Ho = Ho;
     a.Wo = Wo;
-    a.M = (int64_t)c->N * Ho * Wo;
-    OT_CHECK_ARG((int64_t)c->N * c->H * c->W * c->x_cs < (1ll << 40) && a.M * std::max(c->y_cs, c->y2_cs) < (1ll << 40),
-                 "conv2d: tensors too large");
-    a.nk = (int)(ldw / CV_BK);
-    a.y = c->y;
-    a.y_cs = c->y_cs;
-    a.y_off = c->y_off;
-    a.y2 = c->y2;
-    a.y2_cs = c->y2_cs;
-    a.y2_off = c->y2_off;
-    a.split = c->split;
-    a.relu = c->relu;
+    if (int rc = conv_args(c, "conv2d", c->N, a)) return rc;
+    if (c->N == 0) return OMNITOK_OK;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     // the tile by the layer's shape alone (Cout and the per-image output extent; an image's results never depend on it):
     // 256 x 32 for Cout <= 32; 64 x 64 on maps of at most 17 x 17 (Mixed_6*, Mixed_7*: few rows per image, so larger tiles

@@ -1,5 +1,6 @@
 """InceptionI3d on the device: the reference's fvd/pytorch_i3d.py network (the feature net of FVD), its state_dict and its
-logits, with every layer in csrc/i3d.hip (include/omnitok.h "I3D").
+logits, with every layer in csrc/i3d.hip (include/omnitok.h "I3D").  The conv and pool operators and the weight scaffold are
+convnet.py's, shared with inception.py and lpips.py.
 
     i3d = InceptionI3d(400, in_channels=3)
     i3d.load_state_dict(torch.load("i3d_pretrained_400.pt"))      # strict: the reference's keys and shapes
@@ -17,14 +18,14 @@ Each output element is a fixed-order fp32 sum, so a clip gets the same logits al
 """
 from __future__ import annotations
 
-import ctypes
 from collections import OrderedDict
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import List, Optional, Tuple
 
 import torch
 
-from . import _lib
-from ._lib import OmnitokConv3d, check
+from . import _lib, convnet
+from ._lib import check, ptr, stream
+from .convnet import conv3d_same, maxpool3d_same, pack_conv_weight, same_pad
 
 MAX_CHUNK = 16   # clips per pass through the network (fvd.py MAX_BATCH): bounds the activations to ~0.9 GB at T = 17
 BN_EPS = 1e-5
@@ -89,12 +90,6 @@ def state_spec(num_classes: int = 400) -> "OrderedDict[str, Tuple[Tuple[int, ...
     return spec
 
 
-def same_pad(s: int, k: int, stride: int) -> Tuple[int, int]:
-    """(front pad, output extent) of Unit3D.compute_pad / MaxPool3dSamePadding.compute_pad (include/omnitok.h)"""
-    pad = max(k - (s % stride or stride), 0)
-    return pad // 2, (s + pad - k) // stride + 1
-
-
 def final_grid(T: int, H: int, W: int) -> Tuple[int, int, int]:
     """the extent of Mixed_5c's output (what the [2, 7, 7] average pool sees) for a [T, H, W] input"""
     ext = [T, H, W]
@@ -117,54 +112,20 @@ def check_input_size(T: int, H: int, W: int):
                          "[2, 7, 7] average pool needs 7 x 7)")
 
 
-def _ptr(t: Optional[torch.Tensor]):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-# ---- the four operators -------------------------------------------------------------------------------------------------
+# ---- the two operators of I3D alone (the conv and the pool are convnet.py's) --------------------------------------------
 
 def _preprocess_native(frames: torch.Tensor, R_h: int, R_w: int) -> torch.Tensor:
     B, T, H, W, _ = frames.shape
     out = torch.empty((B, T, R_h, R_w, 4), device=frames.device, dtype=torch.float32)
-    check(_lib.load().omnitok_i3d_preprocess(_ptr(frames), B, T, H, W, R_h, R_w, _ptr(out),
-                                             torch.cuda.current_stream().cuda_stream), "i3d_preprocess")
+    check(_lib.load().omnitok_i3d_preprocess(ptr(frames), B, T, H, W, R_h, R_w, ptr(out), stream()), "i3d_preprocess")
     return out
-
-
-def _conv_native(x, x_off, cin, w, bias, kernel, stride, relu, y, y_off, y2, y2_off, split):
-    d = OmnitokConv3d()
-    d.x, d.x_cs, d.x_off = x.data_ptr(), x.shape[4], x_off
-    d.B, d.T, d.H, d.W, d.Cin = x.shape[0], x.shape[1], x.shape[2], x.shape[3], cin
-    d.w, d.bias, d.Cout = w.data_ptr(), bias.data_ptr(), w.shape[0]
-    d.kt, d.kh, d.kw = kernel
-    d.st, d.sh, d.sw = stride
-    d.relu = int(relu)
-    d.y, d.y_cs, d.y_off = y.data_ptr(), y.shape[4], y_off
-    if y2 is not None:
-        d.y2, d.y2_cs, d.y2_off = y2.data_ptr(), y2.shape[4], y2_off
-    d.split = split
-    check(_lib.load().omnitok_conv3d_same(ctypes.byref(d), torch.cuda.current_stream().cuda_stream), "conv3d_same")
-
-
-def _pool_shape(shape, kernel, stride):
-    B, T, H, W, C = shape
-    return (B,) + tuple(same_pad(e, k, s)[1] for e, k, s in zip((T, H, W), kernel, stride)) + (C,)
-
-
-def _maxpool_native(x: torch.Tensor, kernel, stride) -> torch.Tensor:
-    y = torch.empty(_pool_shape(x.shape, kernel, stride), device=x.device, dtype=torch.float32)
-    B, T, H, W, C = x.shape
-    check(_lib.load().omnitok_maxpool3d_same(_ptr(x), B, T, H, W, C, *kernel, *stride, _ptr(y),
-                                             torch.cuda.current_stream().cuda_stream), "maxpool3d_same")
-    return y
 
 
 def _head_native(x: torch.Tensor, w_t: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
     B, T, H, W, C = x.shape
     ncls = w_t.shape[1]
     out = torch.empty((B, ncls, H - 6, W - 6), device=x.device, dtype=torch.float32)
-    check(_lib.load().omnitok_i3d_head(_ptr(x), B, T, H, W, C, _ptr(w_t), _ptr(bias), ncls, _ptr(out),
-                                       torch.cuda.current_stream().cuda_stream), "i3d_head")
+    check(_lib.load().omnitok_i3d_head(ptr(x), B, T, H, W, C, ptr(w_t), ptr(bias), ncls, ptr(out), stream()), "i3d_head")
     return out
 
 
@@ -181,35 +142,6 @@ def _register_ops():
     @_pre.register_fake
     def _(frames, R_h, R_w):
         return frames.new_empty((frames.shape[0], frames.shape[1], R_h, R_w, 4), dtype=torch.float32)
-
-    @custom_op("omnitok::conv3d_same", mutates_args=("y", "y2"), device_types="cuda")
-    def _conv(x: torch.Tensor, x_off: int, cin: int, w: torch.Tensor, bias: torch.Tensor, kernel: List[int],
-              stride: List[int], relu: bool, y: torch.Tensor, y_off: int, y2: Optional[torch.Tensor], y2_off: int,
-              split: int) -> None:
-        for name, t in (("x", x), ("w", w), ("bias", bias), ("y", y), ("y2", y2)):
-            if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
-                raise ValueError(f"conv3d_same: {name} must be a contiguous float32 tensor")
-        if x.dim() != 5 or y.dim() != 5 or (y2 is not None and y2.dim() != 5):
-            raise ValueError("conv3d_same: x, y and y2 are channels-last [B, T, H, W, C]")
-        want = _pool_shape(x.shape, kernel, stride)[:4]
-        for name, t in (("y", y), ("y2", y2)):
-            if t is not None and tuple(t.shape[:4]) != want:
-                raise ValueError(f"conv3d_same: {name} is {tuple(t.shape)}, the output grid is {want}")
-        _conv_native(x, x_off, cin, w, bias, kernel, stride, relu, y, y_off, y2, y2_off, split)
-
-    @_conv.register_fake
-    def _(x, x_off, cin, w, bias, kernel, stride, relu, y, y_off, y2, y2_off, split):
-        return None
-
-    @custom_op("omnitok::maxpool3d_same", mutates_args=(), device_types="cuda")
-    def _pool(x: torch.Tensor, kernel: List[int], stride: List[int]) -> torch.Tensor:
-        if x.dtype != torch.float32 or x.dim() != 5:
-            raise ValueError(f"maxpool3d_same: x must be float32 [B, T, H, W, C], got {x.dtype} {tuple(x.shape)}")
-        return _maxpool_native(x.contiguous(), kernel, stride)
-
-    @_pool.register_fake
-    def _(x, kernel, stride):
-        return x.new_empty(_pool_shape(x.shape, kernel, stride))
 
     @custom_op("omnitok::i3d_head", mutates_args=(), device_types="cuda")
     def _head(x: torch.Tensor, w_t: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
@@ -231,55 +163,16 @@ def preprocess_frames(frames: torch.Tensor, size: Tuple[int, int] = (224, 224)) 
     return torch.ops.omnitok.i3d_preprocess(frames, int(size[0]), int(size[1]))
 
 
-def conv3d_same(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor, kernel: Sequence[int],
-                stride: Sequence[int] = (1, 1, 1), relu: bool = True, *, cin: Optional[int] = None, x_off: int = 0,
-                out: Optional[torch.Tensor] = None, out_off: int = 0, out2: Optional[torch.Tensor] = None,
-                out2_off: int = 0, split: Optional[int] = None) -> torch.Tensor:
-    """One Unit3D on channels-last x (channels [x_off, x_off + cin)); writes channels [out_off, out_off + split) of `out`
-    (a new [B, To, Ho, Wo, Cout] tensor if None) and the columns past `split` to `out2` at out2_off.  Returns `out`."""
-    cin = x.shape[4] - x_off if cin is None else cin
-    cout = w_packed.shape[0]
-    split = cout if split is None else split
-    if out is None:
-        out = torch.empty(_pool_shape(x.shape, kernel, stride)[:4] + (split,), device=x.device, dtype=torch.float32)
-    torch.ops.omnitok.conv3d_same(x, x_off, cin, w_packed, bias, list(kernel), list(stride), relu, out, out_off, out2,
-                                  out2_off, split)
-    return out
-
-
-def maxpool3d_same(x: torch.Tensor, kernel: Sequence[int], stride: Sequence[int]) -> torch.Tensor:
-    return torch.ops.omnitok.maxpool3d_same(x, list(kernel), list(stride))
-
-
 def i3d_head(x: torch.Tensor, w_t: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
     return torch.ops.omnitok.i3d_head(x, w_t, bias)
 
 
-def pack_conv_weight(w: torch.Tensor) -> torch.Tensor:
-    """[Cout, Cin, kt, kh, kw] -> the packed [Cout, ldw] fp32 of omnitok_conv3d_same: k = tap * Cin4 + ci, Cin4 = Cin
-    rounded up to 4 (zero weights), zeros from K to ldw (a multiple of 32)"""
-    cout, cin, kt, kh, kw = w.shape
-    cin4 = (cin + 3) // 4 * 4
-    ldw = int(_lib.load().omnitok_conv3d_packed_ldw(cin4, kt, kh, kw))
-    if ldw < 0:
-        raise ValueError(f"pack_conv_weight: unsupported shape {tuple(w.shape)}")
-    p = torch.zeros((cout, kt, kh, kw, cin4), dtype=w.dtype)
-    p[..., :cin] = w.detach().cpu().permute(0, 2, 3, 4, 1)
-    out = torch.zeros((cout, ldw), dtype=torch.float32)
-    out[:, :kt * kh * kw * cin4] = p.reshape(cout, -1).float()
-    return out
-
-
 def fold_bn(sd, name: str) -> Tuple[torch.Tensor, torch.Tensor]:
     """(weight, bias) of Unit3D `name` with its BatchNorm folded in, in fp64"""
-    w = sd[f"{name}.conv3d.weight"].double()
-    g, b = sd[f"{name}.bn.weight"].double(), sd[f"{name}.bn.bias"].double()
-    m, v = sd[f"{name}.bn.running_mean"].double(), sd[f"{name}.bn.running_var"].double()
-    scale = g / torch.sqrt(v + BN_EPS)
-    return w * scale.view(-1, 1, 1, 1, 1), b - m * scale
+    return convnet.fold_bn(sd, name, "conv3d", BN_EPS)
 
 
-class InceptionI3d(torch.nn.Module):
+class InceptionI3d(convnet.PackedWeights):
     """The reference's InceptionI3d (fvd/pytorch_i3d.py) for its FVD use: constructor arguments, state_dict keys and
     forward logits as there, on the GPU.  is_coinrun, other final endpoints, spatial_squeeze=False (the reference's forward
     fails on it) and in_channels != 3 are not provided."""
@@ -300,38 +193,15 @@ class InceptionI3d(torch.nn.Module):
             raise NotImplementedError("InceptionI3d: spatial_squeeze=False (the reference's forward fails on it)")
         super().__init__()
         self._num_classes = int(num_classes)
-        self._sd: Optional[Dict[str, torch.Tensor]] = None
-        self._packed: Dict[torch.device, dict] = {}
 
     # -- weights ------------------------------------------------------------------------------------------------------
-    def state_dict(self, *args, **kwargs):
-        if self._sd is None:
-            raise RuntimeError("InceptionI3d: no weights loaded")
-        return OrderedDict((k, v.clone()) for k, v in self._sd.items())
-
-    def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
+    def _held(self, state_dict):
         spec = state_spec(self._num_classes)
-        missing = [k for k in spec if k not in state_dict]
-        unexpected = [k for k in state_dict if k not in spec]
-        if missing or unexpected:
-            # only strict loading is meaningful: every parameter feeds the logits
-            raise RuntimeError(f"Error(s) in loading state_dict for InceptionI3d: missing keys {missing[:8]}"
-                               f"{' ...' if len(missing) > 8 else ''}, unexpected keys {unexpected[:8]}"
-                               f"{' ...' if len(unexpected) > 8 else ''}")
-        for k, (shape, _) in spec.items():
-            if tuple(state_dict[k].shape) != shape:
-                raise RuntimeError(f"Error(s) in loading state_dict for InceptionI3d: size mismatch for {k}: "
-                                   f"copying a param with shape {tuple(state_dict[k].shape)}, the model has {shape}")
-        self._sd = OrderedDict((k, state_dict[k].detach().cpu().clone()) for k in spec)
-        self._packed = {}
-        return torch.nn.modules.module._IncompatibleKeys([], [])
+        convnet.check_state_dict(state_dict, {k: shape for k, (shape, _) in spec.items()}, "InceptionI3d")
+        return OrderedDict((k, state_dict[k].detach().cpu().clone()) for k in spec)
 
-    def _weights(self, device: torch.device) -> dict:
-        if self._sd is None:
-            raise RuntimeError("InceptionI3d: load_state_dict first")
-        if device in self._packed:
-            return self._packed[device]
-        sd, packed = self._sd, {}
+    def _pack(self, sd, device: torch.device) -> dict:
+        packed = {}
 
         def put(name, w64, b64):
             packed[name] = (pack_conv_weight(w64).to(device), b64.float().to(device))
@@ -347,7 +217,6 @@ class InceptionI3d(torch.nn.Module):
                     put(f"{p[1]}.{b}", *u[b])
         w = sd["logits.conv3d.weight"].reshape(self._num_classes, LOGITS_IN)
         packed["logits"] = (w.t().contiguous().float().to(device), sd["logits.conv3d.bias"].float().to(device))
-        self._packed[device] = packed
         return packed
 
     # -- forward ------------------------------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
 """Inception V3 on the device: the reference's evaluation/pytorch-fid InceptionV3 (torchvision's Inception3 with the FID
 patches, the feature net of FID), its state_dicts and its feature blocks, with every layer in csrc/inception.hip
-(include/omnitok.h "Inception V3").
+(include/omnitok.h "Inception V3").  The conv and pool operators and the weight scaffold are convnet.py's, shared with
+i3d.py and lpips.py.
 
     net = InceptionV3([3])                                                  # output_blocks as in the reference
     net.load_state_dict(torch.load("pt_inception-2015-12-05-6726825d.pth"))  # strict: the .pth keys or the wrapper's
@@ -21,15 +22,14 @@ Each output element is a fixed-order fp32 sum, so an image gets the same feature
 """
 from __future__ import annotations
 
-import ctypes
 from collections import OrderedDict
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import List, Optional, Tuple
 
 import torch
 
-from . import _lib
-from ._lib import OmnitokConv2d, check
-from .i3d import pack_conv_weight
+from . import _lib, convnet
+from ._lib import check, ptr, stream
+from .convnet import avgpool2d, conv2d, maxpool2d, out_size, pack_conv_weight, spatial_mean
 
 MAX_CHUNK = 64   # images per pass through the network: bounds the activations to ~0.6 GB at 299 x 299
 BN_EPS = 1e-3
@@ -134,12 +134,6 @@ def state_spec(wrapper: bool = False, last_block: int = 3) -> "OrderedDict[str, 
     return spec
 
 
-def out_size(s: int, k: int, stride: int, pad: int) -> int:
-    """floor((s + 2 pad - k) / stride) + 1, 0 where the window does not fit (omnitok_conv2d_out)"""
-    span = s + 2 * pad - k
-    return span // stride + 1 if span >= 0 else 0
-
-
 def block_extents(H: int, W: int, last_block: int = 3) -> List[Tuple[str, int, int]]:
     """(layer, h, w) of every layer output of the reference's forward on an H x W network input, up to last_block; an
     extent of 0 is where the reference's forward fails"""
@@ -177,15 +171,7 @@ def check_input_size(H: int, W: int, last_block: int):
                              f"at least {need} x {need} is needed, or resize_input=True)")
 
 
-def _ptr(t: Optional[torch.Tensor]):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-# ---- the operators ------------------------------------------------------------------------------------------------------
+# ---- the operator of Inception alone (the conv and the pools are convnet.py's) ------------------------------------------
 
 def _preprocess_native(src: torch.Tensor, resize: bool, normalize: bool, R_h: int, R_w: int) -> torch.Tensor:
     if src.dtype == torch.uint8:
@@ -196,29 +182,9 @@ def _preprocess_native(src: torch.Tensor, resize: bool, normalize: bool, R_h: in
         dtype, ld = FID_F32, 0
     out = torch.empty((N, R_h, R_w, 4), device=src.device, dtype=torch.float32)
     flags = (FLAG_RESIZE if resize else 0) | (FLAG_NORMALIZE if normalize else 0)
-    check(_lib.load().omnitok_fid_preprocess(_ptr(src), dtype, ld, N, H, W, R_h, R_w, flags, _ptr(out), _stream()),
+    check(_lib.load().omnitok_fid_preprocess(ptr(src), dtype, ld, N, H, W, R_h, R_w, flags, ptr(out), stream()),
           "fid_preprocess")
     return out
-
-
-def _conv_native(x, x_off, cin, w, bias, kernel, stride, padding, relu, y, y_off, y2, y2_off, split):
-    d = OmnitokConv2d()
-    d.x, d.x_cs, d.x_off = x.data_ptr(), x.shape[3], x_off
-    d.N, d.H, d.W, d.Cin = x.shape[0], x.shape[1], x.shape[2], cin
-    d.w, d.bias, d.Cout = w.data_ptr(), bias.data_ptr(), w.shape[0]
-    d.kh, d.kw = kernel
-    d.sh, d.sw = stride
-    d.ph, d.pw = padding
-    d.relu = int(relu)
-    d.y, d.y_cs, d.y_off = y.data_ptr(), y.shape[3], y_off
-    if y2 is not None:
-        d.y2, d.y2_cs, d.y2_off = y2.data_ptr(), y2.shape[3], y2_off
-    d.split = split
-    check(_lib.load().omnitok_conv2d(ctypes.byref(d), _stream()), "conv2d")
-
-
-def _out_grid(shape, kernel, stride, padding):
-    return (shape[0],) + tuple(out_size(e, k, s, p) for e, k, s, p in zip(shape[1:3], kernel, stride, padding))
 
 
 def _register_ops():
@@ -243,68 +209,6 @@ def _register_ops():
     def _(src, resize, normalize, R_h, R_w):
         return src.new_empty((src.shape[0], R_h, R_w, 4), dtype=torch.float32)
 
-    @custom_op("omnitok::conv2d", mutates_args=("y", "y2"), device_types="cuda")
-    def _conv2d(x: torch.Tensor, x_off: int, cin: int, w: torch.Tensor, bias: torch.Tensor, kernel: List[int],
-                stride: List[int], padding: List[int], relu: bool, y: torch.Tensor, y_off: int, y2: Optional[torch.Tensor],
-                y2_off: int, split: int) -> None:
-        for name, t in (("x", x), ("w", w), ("bias", bias), ("y", y), ("y2", y2)):
-            if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
-                raise ValueError(f"conv2d: {name} must be a contiguous float32 tensor")
-        if x.dim() != 4 or y.dim() != 4 or (y2 is not None and y2.dim() != 4):
-            raise ValueError("conv2d: x, y and y2 are channels-last [N, H, W, C]")
-        want = _out_grid(x.shape, kernel, stride, padding)
-        for name, t in (("y", y), ("y2", y2)):
-            if t is not None and tuple(t.shape[:3]) != want:
-                raise ValueError(f"conv2d: {name} is {tuple(t.shape)}, the output grid is {want}")
-        _conv_native(x, x_off, cin, w, bias, kernel, stride, padding, relu, y, y_off, y2, y2_off, split)
-
-    @_conv2d.register_fake
-    def _(x, x_off, cin, w, bias, kernel, stride, padding, relu, y, y_off, y2, y2_off, split):
-        return None
-
-    def _pool_check(what, x, k, s, p, y):
-        if x.dtype != torch.float32 or x.dim() != 4 or not x.is_contiguous():
-            raise ValueError(f"{what}: x must be a contiguous float32 [N, H, W, C], got {x.dtype} {tuple(x.shape)}")
-        if y.dtype != torch.float32 or not y.is_contiguous() or tuple(y.shape[:3]) != _out_grid(x.shape, (k, k), (s, s),
-                                                                                                  (p, p)):
-            raise ValueError(f"{what}: y is {tuple(y.shape)}, the output grid is {_out_grid(x.shape, (k, k), (s, s), (p, p))}")
-
-    @custom_op("omnitok::maxpool2d", mutates_args=("y",), device_types="cuda")
-    def _maxpool(x: torch.Tensor, k: int, s: int, p: int, y: torch.Tensor, y_off: int) -> None:
-        _pool_check("maxpool2d", x, k, s, p, y)
-        N, H, W, C = x.shape
-        check(_lib.load().omnitok_maxpool2d(_ptr(x), N, H, W, C, k, s, p, _ptr(y), y.shape[3], y_off, _stream()),
-              "maxpool2d")
-
-    @_maxpool.register_fake
-    def _(x, k, s, p, y, y_off):
-        return None
-
-    @custom_op("omnitok::avgpool2d", mutates_args=("y",), device_types="cuda")
-    def _avgpool(x: torch.Tensor, k: int, s: int, p: int, y: torch.Tensor, y_off: int) -> None:
-        _pool_check("avgpool2d", x, k, s, p, y)
-        N, H, W, C = x.shape
-        check(_lib.load().omnitok_avgpool2d(_ptr(x), N, H, W, C, k, s, p, _ptr(y), y.shape[3], y_off, _stream()),
-              "avgpool2d")
-
-    @_avgpool.register_fake
-    def _(x, k, s, p, y, y_off):
-        return None
-
-    @custom_op("omnitok::spatial_mean", mutates_args=(), device_types="cuda")
-    def _mean(x: torch.Tensor) -> torch.Tensor:
-        if x.dtype != torch.float32 or x.dim() != 4:
-            raise ValueError(f"spatial_mean: x must be float32 [N, H, W, C], got {x.dtype} {tuple(x.shape)}")
-        x = x.contiguous()
-        N, H, W, C = x.shape
-        y = torch.empty((N, C), device=x.device, dtype=torch.float32)
-        check(_lib.load().omnitok_spatial_mean(_ptr(x), N, H, W, C, _ptr(y), _stream()), "spatial_mean")
-        return y
-
-    @_mean.register_fake
-    def _(x):
-        return x.new_empty((x.shape[0], x.shape[3]))
-
 
 _register_ops()
 
@@ -318,53 +222,9 @@ def preprocess_images(images: torch.Tensor, resize: bool = True, normalize: bool
     return torch.ops.omnitok.fid_preprocess(images, bool(resize), bool(normalize), R_h, R_w)
 
 
-def conv2d(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor, kernel: Sequence[int],
-           stride: Sequence[int] = (1, 1), padding: Sequence[int] = (0, 0), relu: bool = True, *, cin: Optional[int] = None,
-           x_off: int = 0, out: Optional[torch.Tensor] = None, out_off: int = 0, out2: Optional[torch.Tensor] = None,
-           out2_off: int = 0, split: Optional[int] = None) -> torch.Tensor:
-    """One BasicConv2d on channels-last x (channels [x_off, x_off + cin)); writes channels [out_off, out_off + split) of
-    `out` (a new [N, Ho, Wo, Cout] tensor if None) and the columns past `split` to `out2` at out2_off.  Returns `out`."""
-    cin = x.shape[3] - x_off if cin is None else cin
-    cout = w_packed.shape[0]
-    split = cout if split is None else split
-    if out is None:
-        out = torch.empty(_out_grid(x.shape, kernel, stride, padding) + (split,), device=x.device, dtype=torch.float32)
-    torch.ops.omnitok.conv2d(x, x_off, cin, w_packed, bias, list(kernel), list(stride), list(padding), relu, out, out_off,
-                             out2, out2_off, split)
-    return out
-
-
-def _pool(op, x, k, s, p, out, out_off):
-    if out is None:
-        out = torch.empty(_out_grid(x.shape, (k, k), (s, s), (p, p)) + (x.shape[3],), device=x.device, dtype=torch.float32)
-    op(x, k, s, p, out, out_off)
-    return out
-
-
-def maxpool2d(x: torch.Tensor, k: int, s: int, p: int = 0, *, out: Optional[torch.Tensor] = None,
-              out_off: int = 0) -> torch.Tensor:
-    """max_pool2d(x, k, s, p) (-inf padding, floor sizing) on channels-last x, into channels [out_off, out_off + C) of out"""
-    return _pool(torch.ops.omnitok.maxpool2d, x, k, s, p, out, out_off)
-
-
-def avgpool2d(x: torch.Tensor, k: int, s: int, p: int = 0, *, out: Optional[torch.Tensor] = None,
-              out_off: int = 0) -> torch.Tensor:
-    """avg_pool2d(x, k, s, p, count_include_pad=False) on channels-last x"""
-    return _pool(torch.ops.omnitok.avgpool2d, x, k, s, p, out, out_off)
-
-
-def spatial_mean(x: torch.Tensor) -> torch.Tensor:
-    """adaptive_avg_pool2d(x, 1) of channels-last [N, h, w, C] -> [N, C]"""
-    return torch.ops.omnitok.spatial_mean(x)
-
-
 def fold_bn(sd, prefix: str) -> Tuple[torch.Tensor, torch.Tensor]:
     """(weight, bias) of BasicConv2d `prefix` with its BatchNorm (eps 1e-3) folded in, in fp64"""
-    w = sd[f"{prefix}.conv.weight"].double()
-    g, b = sd[f"{prefix}.bn.weight"].double(), sd[f"{prefix}.bn.bias"].double()
-    m, v = sd[f"{prefix}.bn.running_mean"].double(), sd[f"{prefix}.bn.running_var"].double()
-    scale = g / torch.sqrt(v + BN_EPS)
-    return w * scale.view(-1, 1, 1, 1), b - m * scale
+    return convnet.fold_bn(sd, prefix, "conv", BN_EPS)
 
 
 # the sibling 1x1 convs of one input that a module runs as one GEMM (the first goes straight to the module output)
@@ -373,7 +233,7 @@ FUSED_1X1 = {"A": ("branch1x1", "branch5x5_1", "branch3x3dbl_1"), "B": ("branch3
              "E1": ("branch1x1", "branch3x3_1", "branch3x3dbl_1"), "E2": ("branch1x1", "branch3x3_1", "branch3x3dbl_1")}
 
 
-class InceptionV3(torch.nn.Module):
+class InceptionV3(convnet.PackedWeights):
     """The reference's pytorch-fid InceptionV3 for its FID use: constructor arguments, BLOCK_INDEX_BY_DIM and the forward
     contract (fp32 [N, 3, H, W] in [0, 1] -> one [N, C, h, w] per requested block, sorted by index) as there, on the GPU.
     The outputs are channels-last views.  use_fid_inception=False (torchvision's ImageNet weights) is not provided."""
@@ -396,35 +256,16 @@ class InceptionV3(torch.nn.Module):
         self.normalize_input = bool(normalize_input)
         self.output_blocks = blocks
         self.last_needed_block = blocks[-1]
-        self._sd: Optional[Dict[str, torch.Tensor]] = None
-        self._packed: Dict[torch.device, dict] = {}
 
     # -- weights ------------------------------------------------------------------------------------------------------
-    def state_dict(self, *args, **kwargs):
-        """the wrapper's own key set (blocks.{i}.{j}.*, up to the last needed block)"""
-        if self._sd is None:
-            raise RuntimeError("InceptionV3: no weights loaded")
-        return OrderedDict((k, v.clone()) for k, v in self._sd.items())
-
-    def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
+    def _held(self, state_dict):
         """Strict: either the .pth key set (torchvision Inception3 names, fc read and ignored) or the wrapper's own
-        (blocks.*).  num_batches_tracked may be absent throughout (torch's BatchNorm accepts checkpoints without it)."""
+        (blocks.*; what state_dict() returns, up to the last needed block).  num_batches_tracked may be absent throughout
+        (torch's BatchNorm accepts checkpoints without it)."""
         wrapper = any(k.startswith("blocks.") for k in state_dict)
         spec = state_spec(wrapper, self.last_needed_block if wrapper else 3)
-        optional = {k for k in spec if k.endswith("num_batches_tracked")}
-        missing = [k for k in spec if k not in state_dict and k not in optional]
-        unexpected = [k for k in state_dict if k not in spec]
-        has_nbt = [k in state_dict for k in optional]
-        if any(has_nbt) and not all(has_nbt):
-            missing += [k for k in optional if k not in state_dict]
-        if missing or unexpected:
-            raise RuntimeError(f"Error(s) in loading state_dict for InceptionV3: missing keys {missing[:8]}"
-                               f"{' ...' if len(missing) > 8 else ''}, unexpected keys {unexpected[:8]}"
-                               f"{' ...' if len(unexpected) > 8 else ''}")
-        for k, (shape, _) in spec.items():
-            if k in state_dict and tuple(state_dict[k].shape) != shape:
-                raise RuntimeError(f"Error(s) in loading state_dict for InceptionV3: size mismatch for {k}: copying a "
-                                   f"param with shape {tuple(state_dict[k].shape)}, the model has {shape}")
+        convnet.check_state_dict(state_dict, {k: shape for k, (shape, _) in spec.items()}, "InceptionV3",
+                                 optional=[k for k in spec if k.endswith("num_batches_tracked")])
         # held under the wrapper's names, as the reference's InceptionV3 holds them
         L = self.last_needed_block
         own = [p for p, _ in _convs_with_keys(True, L)]
@@ -434,16 +275,10 @@ class InceptionV3(torch.nn.Module):
             for s in ("conv.weight",) + tuple(f"bn.{b}" for b in BN_KEYS):
                 if f"{i}.{s}" in state_dict:
                     sd[f"{o}.{s}"] = state_dict[f"{i}.{s}"].detach().cpu().clone()
-        self._sd = sd
-        self._packed = {}
-        return torch.nn.modules.module._IncompatibleKeys([], [])
+        return sd
 
-    def _weights(self, device: torch.device) -> dict:
-        if self._sd is None:
-            raise RuntimeError("InceptionV3: load_state_dict first")
-        if device in self._packed:
-            return self._packed[device]
-        sd, packed = self._sd, {}
+    def _pack(self, sd, device: torch.device) -> dict:
+        packed = {}
 
         def put(key, w64, b64):
             packed[key] = (pack_conv_weight(w64.unsqueeze(2)).to(device), b64.float().to(device))
@@ -465,7 +300,6 @@ class InceptionV3(torch.nn.Module):
             for c in convs:
                 if c[0] not in fused:
                     put(f"{mname}.{c[0]}", *fold_bn(sd, f"{base}.{c[0]}"))
-        self._packed[device] = packed
         return packed
 
     # -- forward ------------------------------------------------------------------------------------------------------

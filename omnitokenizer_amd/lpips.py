@@ -1,6 +1,6 @@
 """LPIPS on the device: the reference's OmniTokenizer/modules/lpips.py (taming's VGG16 LPIPS, the tokenizer's own
 perceptual model: `perceptual_model` of omnitokenizer.py, the `val/perceptual_loss` of validation_step), with its input
-path and heads in csrc/lpips.hip and its VGG16 trunk on omnitok_conv2d / omnitok_maxpool2d (include/omnitok.h "LPIPS").
+path and heads in csrc/lpips.hip and its VGG16 trunk on convnet.py's conv2d / maxpool2d (include/omnitok.h "LPIPS").
 
     model = load_lpips("cuda", "omnitokenizer.ckpt")           # a checkpoint's perceptual_model.* (no download)
     d = model(input, target)                                   # [N, 3, H, W] fp32 -> [N, 1, 1, 1], as the reference
@@ -19,12 +19,13 @@ from __future__ import annotations
 import ctypes
 import os
 from collections import OrderedDict
-from typing import Dict, List, Optional, Tuple
+from typing import List, Optional, Tuple
 
 import torch
 
 from . import _lib
-from ._lib import check
+from ._lib import check, ptr, stream
+from .convnet import PackedWeights, check_state_dict, conv2d, maxpool2d, pack_conv_weight
 
 MIN_SIZE = 16                     # OMNITOK_LPIPS_MIN_SIZE
 FLAG_NORMALIZE = 1                # OMNITOK_LPIPS_NORMALIZE
@@ -64,27 +65,6 @@ def to_torchvision(sd) -> Tuple["OrderedDict[str, torch.Tensor]", "OrderedDict[s
     return vgg, lin
 
 
-def _strict(sd, spec, what: str, ignore=()):
-    missing = [k for k in spec if k not in sd]
-    unexpected = [k for k in sd if k not in spec and not k.startswith(tuple(ignore))]
-    if missing or unexpected:
-        raise RuntimeError(f"Error(s) in loading state_dict for {what}: missing keys {missing[:8]}"
-                           f"{' ...' if len(missing) > 8 else ''}, unexpected keys {unexpected[:8]}"
-                           f"{' ...' if len(unexpected) > 8 else ''}")
-    for k, shape in spec.items():
-        if tuple(sd[k].shape) != tuple(shape):
-            raise RuntimeError(f"Error(s) in loading state_dict for {what}: size mismatch for {k}: copying a param with "
-                               f"shape {tuple(sd[k].shape)}, the model has {tuple(shape)}")
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
 # ---- the operators ------------------------------------------------------------------------------------------------------
 
 def _register_ops():
@@ -106,7 +86,7 @@ def _register_ops():
         sc = (ctypes.c_float * 3)(*scaling_scale)
         d = _operand_desc(src, shift, clamp)
         check(_lib.load().omnitok_lpips_preprocess(ctypes.byref(d), B, F_, H, W, i0, out.shape[0],
-                                                   FLAG_NORMALIZE if normalize else 0, sh, sc, _ptr(out), _stream()),
+                                                   FLAG_NORMALIZE if normalize else 0, sh, sc, ptr(out), stream()),
               "lpips_preprocess")
 
     @_pre.register_fake
@@ -128,8 +108,8 @@ def _register_ops():
         if need < 0:
             raise ValueError(f"lpips_layer: bad shape {tuple(feats.shape)}")
         work = torch.empty(max(need, 8), device=feats.device, dtype=torch.uint8)
-        check(lib.omnitok_lpips_layer(_ptr(feats), N2 // 2, h, w, C, _ptr(lin_w), layer, _ptr(work), need, _ptr(res),
-                                      _stream()), "lpips_layer")
+        check(lib.omnitok_lpips_layer(ptr(feats), N2 // 2, h, w, C, ptr(lin_w), layer, ptr(work), need, ptr(res),
+                                      stream()), "lpips_layer")
 
     @_layer.register_fake
     def _(feats, lin_w, layer, res):
@@ -141,7 +121,7 @@ def _register_ops():
             raise ValueError(f"lpips_finalize: res must be float64 [N, 5], got {res.dtype} {tuple(res.shape)}")
         res = res.contiguous()
         val = torch.empty(res.shape[0], device=res.device, dtype=torch.float32)
-        check(_lib.load().omnitok_lpips_finalize(_ptr(res), res.shape[0], _ptr(val), _stream()), "lpips_finalize")
+        check(_lib.load().omnitok_lpips_finalize(ptr(res), res.shape[0], ptr(val), stream()), "lpips_finalize")
         return val
 
     @_fin.register_fake
@@ -163,45 +143,31 @@ def layer_head(feats: torch.Tensor, lin_w: torch.Tensor, layer: int = 0, res: Op
 
 # ---- the model ----------------------------------------------------------------------------------------------------------
 
-class LPIPS(torch.nn.Module):
+class LPIPS(PackedWeights):
     """The reference's LPIPS (lpips.py, use_dropout=True) for inference: state_dict keys and forward contract as there
     ([N, 3, H, W] fp32 pairs -> [N, 1, 1, 1] fp32), on the GPU.  Weights are given by load_state_dict (strict) or
     load_lpips; they are packed once per device.  There is no CPU path and no training (Dropout is the identity)."""
 
+    NOT_LOADED = "load_state_dict first (or load_lpips)"
+
     def __init__(self, max_pairs: int = 32):
         super().__init__()
         self.max_pairs = int(max_pairs)
-        self._sd: Optional["OrderedDict[str, torch.Tensor]"] = None
-        self._packed: Dict[torch.device, dict] = {}
 
-    def state_dict(self, *args, **kwargs):
-        if self._sd is None:
-            raise RuntimeError("LPIPS: no weights loaded")
-        return OrderedDict((k, v.clone()) for k, v in self._sd.items())
-
-    def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
+    def _held(self, state_dict):
         """Strict: exactly the reference's LPIPS().state_dict() keys and shapes"""
-        _strict(state_dict, state_spec(), "LPIPS")
-        self._sd = OrderedDict((k, state_dict[k].detach().cpu().float().clone()) for k in state_spec())
-        self._packed = {}
-        return torch.nn.modules.module._IncompatibleKeys([], [])
+        check_state_dict(state_dict, state_spec(), "LPIPS")
+        return OrderedDict((k, state_dict[k].detach().cpu().float().clone()) for k in state_spec())
 
-    def _weights(self, device: torch.device) -> dict:
-        if self._sd is None:
-            raise RuntimeError("LPIPS: load_state_dict first (or load_lpips)")
-        if device not in self._packed:
-            from .i3d import pack_conv_weight
-            sd = self._sd
-            convs = []
-            for s, i, _, _ in CONVS:
-                w = sd[f"net.slice{s}.{i}.weight"]
-                convs.append((s, pack_conv_weight(w.unsqueeze(2)).to(device),
-                              sd[f"net.slice{s}.{i}.bias"].contiguous().to(device)))
-            lins = [sd[f"lin{k}.model.1.weight"].reshape(-1).contiguous().to(device) for k in range(len(CHNS))]
-            self._packed[device] = dict(convs=convs, lins=lins,
-                                        shift=[float(v) for v in sd["scaling_layer.shift"].reshape(-1)],
-                                        scale=[float(v) for v in sd["scaling_layer.scale"].reshape(-1)])
-        return self._packed[device]
+    def _pack(self, sd, device: torch.device) -> dict:
+        convs = []
+        for s, i, _, _ in CONVS:
+            w = sd[f"net.slice{s}.{i}.weight"]
+            convs.append((s, pack_conv_weight(w.unsqueeze(2)).to(device),
+                          sd[f"net.slice{s}.{i}.bias"].contiguous().to(device)))
+        lins = [sd[f"lin{k}.model.1.weight"].reshape(-1).contiguous().to(device) for k in range(len(CHNS))]
+        return dict(convs=convs, lins=lins, shift=[float(v) for v in sd["scaling_layer.shift"].reshape(-1)],
+                    scale=[float(v) for v in sd["scaling_layer.scale"].reshape(-1)])
 
     def packed(self, device) -> dict:
         """the packed weights on `device`: convs [(slice, packed weight, bias)], lins [C], shift, scale"""
@@ -209,7 +175,6 @@ class LPIPS(torch.nn.Module):
 
     def trunk(self, x: torch.Tensor, res: torch.Tensor, endpoints: Optional[list] = None) -> torch.Tensor:
         """the VGG16 slices on the preprocessed channels-last x [2N, H, W, 4], each slice's head into res [N, 5]"""
-        from .inception import conv2d, maxpool2d
         pk = self._weights(x.device)
         cur = 1
         for s, w, b in pk["convs"]:
@@ -293,9 +258,9 @@ def load_lpips(device="cuda", source=None, max_pairs: int = 32) -> LPIPS:
         for _, i, cin, cout in CONVS:
             vspec[f"features.{i}.weight"] = (cout, cin, 3, 3)
             vspec[f"features.{i}.bias"] = (cout,)
-        _strict(vgg, vspec, "torchvision vgg16", ignore=("classifier.",))
+        check_state_dict(vgg, vspec, "torchvision vgg16", ignore=("classifier.",))
         lspec = OrderedDict((k, v) for k, v in spec.items() if k.startswith("lin"))
-        _strict(lin, lspec, "vgg.pth")
+        check_state_dict(lin, lspec, "vgg.pth")
         sd = OrderedDict()
         sd["scaling_layer.shift"] = torch.tensor(SCALING_SHIFT, dtype=torch.float32).view(1, 3, 1, 1)
         sd["scaling_layer.scale"] = torch.tensor(SCALING_SCALE, dtype=torch.float32).view(1, 3, 1, 1)

@@ -61,22 +61,61 @@ def _conv(**kw):
     return d
 
 
-@pytest.mark.parametrize("bad", [
-    dict(Cin=3, x_cs=4), dict(Cin=0), dict(kh=8), dict(kw=0), dict(sh=0), dict(sw=5), dict(ph=3), dict(pw=-1),
-    dict(relu=2), dict(x_off=2), dict(x_cs=62), dict(x_off=4), dict(split=0), dict(split=33), dict(y_off=1), dict(y_cs=16),
-    dict(split=16), dict(split=16, y2=FAKE.value, y2_cs=8), dict(split=16, y2=FAKE.value, y2_cs=20, y2_off=8),
-    dict(x=None), dict(w=None), dict(bias=None), dict(y=None), dict(x=FAKE.value + 4), dict(w=FAKE.value + 8), dict(H=0),
-    dict(N=-1), dict(Cout=0), dict(H=2, W=2, ph=0, pw=0)])
-def test_conv_abi_rejects(lib, bad):
+# every bad descriptor with the full omnitok_last_error() text of the commit before the shared host side
+# (conv_args in csrc/convnet_common.h)
+CONV_REJECTS = [
+    (dict(Cin=3, x_cs=4), "conv2d: Cin 3 must be a positive multiple of 4 and the kernel 3 x 3 within 1..7"),
+    (dict(Cin=0), "conv2d: Cin 0 must be a positive multiple of 4 and the kernel 3 x 3 within 1..7"),
+    (dict(kh=8), "conv2d: Cin 64 must be a positive multiple of 4 and the kernel 8 x 3 within 1..7"),
+    (dict(kw=0), "conv2d: Cin 64 must be a positive multiple of 4 and the kernel 3 x 0 within 1..7"),
+    (dict(sh=0), "conv2d: strides 0 x 1 outside 1..4"),
+    (dict(sw=5), "conv2d: strides 1 x 5 outside 1..4"),
+    (dict(ph=3), "conv2d: padding 3 x 1 outside 0..kernel - 1"),
+    (dict(pw=-1), "conv2d: padding 1 x -1 outside 0..kernel - 1"),
+    (dict(relu=2), "conv2d: relu 2"),
+    (dict(x_off=2), "conv2d: input channels [2, 66) outside the 64 per position, or not 16-byte groups"),
+    (dict(x_cs=62), "conv2d: input channels [0, 64) outside the 62 per position, or not 16-byte groups"),
+    (dict(x_off=4), "conv2d: input channels [4, 68) outside the 64 per position, or not 16-byte groups"),
+    (dict(split=0), "conv2d: split 0 outside 1..Cout (32)"),
+    (dict(split=33), "conv2d: split 33 outside 1..Cout (32)"),
+    (dict(y_off=1), "conv2d: output channels [1, 33) outside the 32 per position"),
+    (dict(y_cs=16), "conv2d: output channels [0, 32) outside the 16 per position"),
+    (dict(split=16), "conv2d: second output channels [0, 16) outside the 0 per position"),
+    (dict(split=16, y2=FAKE.value, y2_cs=8), "conv2d: second output channels [0, 16) outside the 8 per position"),
+    (dict(split=16, y2=FAKE.value, y2_cs=20, y2_off=8), "conv2d: second output channels [8, 24) outside the 20 per position"),
+    (dict(x=None), "conv2d: null pointer"),
+    (dict(w=None), "conv2d: null pointer"),
+    (dict(bias=None), "conv2d: null pointer"),
+    (dict(y=None), "conv2d: null pointer"),
+    (dict(x=FAKE.value + 4), "conv2d: x and w must be 16-byte aligned"),
+    (dict(w=FAKE.value + 8), "conv2d: x and w must be 16-byte aligned"),
+    (dict(H=0), "conv2d: bad sizes N 1 H 0 W 35 Cout 32"),
+    (dict(N=-1), "conv2d: bad sizes N -1 H 35 W 35 Cout 32"),
+    (dict(Cout=0), "conv2d: bad sizes N 1 H 35 W 35 Cout 0"),
+    (dict(H=2, W=2, ph=0, pw=0), "conv2d: empty output (2 x 2 input, kernel 3 x 3, padding 0 x 0)"),
+]
+
+
+@pytest.mark.parametrize("bad,text", CONV_REJECTS, ids=[f"bad{i}" for i in range(len(CONV_REJECTS))])
+def test_conv_abi_rejects(lib, bad, text):
     d = _conv(**bad)
     assert lib.omnitok_conv2d(ctypes.byref(d), None) == -1
     assert lib.omnitok_last_error().decode().startswith("conv2d")
+    assert lib.omnitok_last_error().decode() == text
     assert lib.omnitok_conv2d(None, None) == -1
+    assert lib.omnitok_last_error().decode() == "conv2d: null descriptor"
 
 
 def test_conv_abi_accepts_empty_batch(lib):
     d = _conv(N=0, x=None, w=None, bias=None, y=None)
     assert lib.omnitok_conv2d(ctypes.byref(d), None) == 0
+    # the empty-batch return comes after the channel-window checks and after the empty-output check
+    d = _conv(N=0, x=None, w=None, bias=None, y=None, split=0)
+    assert lib.omnitok_conv2d(ctypes.byref(d), None) == -1
+    assert lib.omnitok_last_error().decode() == "conv2d: split 0 outside 1..Cout (32)"
+    d = _conv(N=0, x=None, w=None, bias=None, y=None, H=2, W=2, ph=0, pw=0)
+    assert lib.omnitok_conv2d(ctypes.byref(d), None) == -1
+    assert lib.omnitok_last_error().decode() == "conv2d: empty output (2 x 2 input, kernel 3 x 3, padding 0 x 0)"
 
 
 @pytest.mark.parametrize("args", [
@@ -159,6 +198,24 @@ def test_strict_loading_accepts_both_key_sets():
     inception.InceptionV3([3]).load_state_dict({k: v for k, v in sd.items() if "num_batches_tracked" not in k})
 
 
+# the full texts of the commit before the shared strict check (omnitokenizer_amd/convnet.py)
+_PRE = "Error(s) in loading state_dict for InceptionV3: "
+STRICT_TEXT = {
+    "missing": _PRE + "missing keys ['Mixed_6e.branch7x7dbl_4.bn.running_var'], unexpected keys []",
+    "extra": _PRE + "missing keys [], unexpected keys ['AuxLogits.fc.weight']",
+    "shape": _PRE + (
+        "size mismatch for Mixed_5b.branch_pool.conv.weight: copying a param with shape (64, 192, 1, 1), the model has "
+        "(32, 192, 1, 1)"),
+    "no_fc": _PRE + "missing keys ['fc.weight', 'fc.bias'], unexpected keys []",
+    "wrapper_extra_block": _PRE + (
+        "missing keys [], unexpected keys ['blocks.2.0.branch1x1.conv.weight', 'blocks.2.0.branch1x1.bn.weight', "
+        "'blocks.2.0.branch1x1.bn.bias', 'blocks.2.0.branch1x1.bn.running_mean', "
+        "'blocks.2.0.branch1x1.bn.running_var', 'blocks.2.0.branch1x1.bn.num_batches_tracked', "
+        "'blocks.2.0.branch5x5_1.conv.weight', 'blocks.2.0.branch5x5_1.bn.weight'] ..."),
+    "some_nbt": _PRE + "missing keys ['Conv2d_2a_3x3.bn.num_batches_tracked'], unexpected keys []",
+}
+
+
 @pytest.mark.parametrize("edit", ["missing", "extra", "shape", "no_fc", "wrapper_extra_block", "some_nbt"])
 def test_strict_loading_rejects(edit):
     sd = synth.synth_fid_inception_state_dict(3)
@@ -176,8 +233,9 @@ def test_strict_loading_rejects(edit):
         sd = _wrapper_sd(sd, 2)
     elif edit == "some_nbt":
         del sd["Conv2d_2a_3x3.bn.num_batches_tracked"]
-    with pytest.raises(RuntimeError, match="Error"):
+    with pytest.raises(RuntimeError, match="Error") as e:
         m.load_state_dict(sd)
+    assert str(e.value) == STRICT_TEXT[edit]
 
 
 def test_fixture_blocks_stay_order_one():

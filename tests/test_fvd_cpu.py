@@ -64,17 +64,56 @@ def _conv(**kw):
     return d
 
 
-@pytest.mark.parametrize("bad", [
-    dict(Cin=3, x_cs=4), dict(Cin=0), dict(kt=8), dict(kw=0), dict(st=0), dict(sh=5), dict(relu=2), dict(x_off=2),
-    dict(x_cs=62), dict(x_off=4), dict(split=0), dict(split=33), dict(y_off=1), dict(y_cs=16), dict(split=16),
-    dict(split=16, y2=FAKE.value, y2_cs=8), dict(split=16, y2=FAKE.value, y2_cs=20, y2_off=8), dict(x=None),
-    dict(w=None), dict(bias=None), dict(y=None), dict(x=FAKE.value + 4), dict(w=FAKE.value + 8), dict(T=0), dict(B=-1),
-    dict(Cout=0)])
-def test_conv_abi_rejects(lib, bad):
+# every bad descriptor with the full omnitok_last_error() text of the commit before the shared host side
+# (conv_args in csrc/convnet_common.h)
+CONV_REJECTS = [
+    (dict(Cin=3, x_cs=4), "conv3d_same: Cin 3 must be a positive multiple of 4 and the kernel 3 x 3 x 3 within 1..7"),
+    (dict(Cin=0), "conv3d_same: Cin 0 must be a positive multiple of 4 and the kernel 3 x 3 x 3 within 1..7"),
+    (dict(kt=8), "conv3d_same: Cin 64 must be a positive multiple of 4 and the kernel 8 x 3 x 3 within 1..7"),
+    (dict(kw=0), "conv3d_same: Cin 64 must be a positive multiple of 4 and the kernel 3 x 3 x 0 within 1..7"),
+    (dict(st=0), "conv3d_same: strides 0 x 1 x 1 outside 1..4"),
+    (dict(sh=5), "conv3d_same: strides 1 x 5 x 1 outside 1..4"),
+    (dict(relu=2), "conv3d_same: relu 2"),
+    (dict(x_off=2), "conv3d_same: input channels [2, 66) outside the 64 per position, or not 16-byte groups"),
+    (dict(x_cs=62), "conv3d_same: input channels [0, 64) outside the 62 per position, or not 16-byte groups"),
+    (dict(x_off=4), "conv3d_same: input channels [4, 68) outside the 64 per position, or not 16-byte groups"),
+    (dict(split=0), "conv3d_same: split 0 outside 1..Cout (32)"),
+    (dict(split=33), "conv3d_same: split 33 outside 1..Cout (32)"),
+    (dict(y_off=1), "conv3d_same: output channels [1, 33) outside the 32 per position"),
+    (dict(y_cs=16), "conv3d_same: output channels [0, 32) outside the 16 per position"),
+    (dict(split=16), "conv3d_same: second output channels [0, 16) outside the 0 per position"),
+    (dict(split=16, y2=FAKE.value, y2_cs=8), "conv3d_same: second output channels [0, 16) outside the 8 per position"),
+    (dict(split=16, y2=FAKE.value, y2_cs=20, y2_off=8),
+     "conv3d_same: second output channels [8, 24) outside the 20 per position"),
+    (dict(x=None), "conv3d_same: null pointer"),
+    (dict(w=None), "conv3d_same: null pointer"),
+    (dict(bias=None), "conv3d_same: null pointer"),
+    (dict(y=None), "conv3d_same: null pointer"),
+    (dict(x=FAKE.value + 4), "conv3d_same: x and w must be 16-byte aligned"),
+    (dict(w=FAKE.value + 8), "conv3d_same: x and w must be 16-byte aligned"),
+    (dict(T=0), "conv3d_same: bad sizes B 1 T 0 H 28 W 28 Cout 32"),
+    (dict(B=-1), "conv3d_same: bad sizes B -1 T 9 H 28 W 28 Cout 32"),
+    (dict(Cout=0), "conv3d_same: bad sizes B 1 T 9 H 28 W 28 Cout 0"),
+]
+
+
+@pytest.mark.parametrize("bad,text", CONV_REJECTS, ids=[f"bad{i}" for i in range(len(CONV_REJECTS))])
+def test_conv_abi_rejects(lib, bad, text):
     d = _conv(**bad)
     assert lib.omnitok_conv3d_same(ctypes.byref(d), None) == -1
     assert lib.omnitok_last_error().decode().startswith("conv3d_same")
+    assert lib.omnitok_last_error().decode() == text
     assert lib.omnitok_conv3d_same(None, None) == -1
+    assert lib.omnitok_last_error().decode() == "conv3d_same: null descriptor"
+
+
+def test_conv_abi_accepts_empty_batch(lib):
+    d = _conv(B=0, x=None, w=None, bias=None, y=None)
+    assert lib.omnitok_conv3d_same(ctypes.byref(d), None) == 0
+    # the empty-batch return comes after the channel-window checks
+    d = _conv(B=0, x=None, w=None, bias=None, y=None, split=0)
+    assert lib.omnitok_conv3d_same(ctypes.byref(d), None) == -1
+    assert lib.omnitok_last_error().decode() == "conv3d_same: split 0 outside 1..Cout (32)"
 
 
 def test_packed_ldw(lib):
@@ -178,6 +217,45 @@ def test_model_rejects_unsupported_configurations():
         i3d.InceptionI3d(400).load_state_dict(sd)
     with pytest.raises(RuntimeError, match="GPU"):
         m(torch.zeros(1, 3, 9, 224, 224))
+
+
+# the full texts of the commit before the shared strict check and weight holder (omnitokenizer_amd/convnet.py)
+_PRE = "Error(s) in loading state_dict for InceptionI3d: "
+STRICT_TEXT = {
+    "missing": _PRE + "missing keys ['Mixed_4f.b1b.bn.running_var'], unexpected keys []",
+    "extra": _PRE + "missing keys [], unexpected keys ['Mixed_5c.b3b.conv3d.bias']",
+    "shape": _PRE + (
+        "size mismatch for Mixed_3b.b1b.conv3d.weight: copying a param with shape (128, 96, 1, 3, 3), the model has "
+        "(128, 96, 3, 3, 3)"),
+    "truncated": _PRE + ("missing keys ['Mixed_5c.b3b.conv3d.weight', 'Mixed_5c.b3b.bn.weight', 'Mixed_5c.b3b.bn.bias', "
+        "'Mixed_5c.b3b.bn.running_mean', 'Mixed_5c.b3b.bn.running_var', 'Mixed_5c.b3b.bn.num_batches_tracked'], "
+        "unexpected keys ['extra.0', 'extra.1', 'extra.2', 'extra.3', 'extra.4', 'extra.5', 'extra.6', 'extra.7'] ..."),
+}
+
+
+@pytest.mark.parametrize("edit", list(STRICT_TEXT))
+def test_strict_loading_rejects(edit):
+    sd = synth.synth_i3d_state_dict(1)
+    if edit == "missing":
+        del sd["Mixed_4f.b1b.bn.running_var"]
+    elif edit == "extra":
+        sd["Mixed_5c.b3b.conv3d.bias"] = torch.zeros(128)
+    elif edit == "shape":
+        sd["Mixed_3b.b1b.conv3d.weight"] = torch.zeros(128, 96, 1, 3, 3)
+    else:   # more than 8 unexpected keys: the first 8, then " ..."
+        for k in [k for k in sd if k.startswith("Mixed_5c.b3b.")]:
+            del sd[k]
+        sd.update({f"extra.{j}": torch.zeros(1) for j in range(9)})
+    m = i3d.InceptionI3d(400)
+    with pytest.raises(RuntimeError) as e:
+        m.load_state_dict(sd)
+    assert str(e.value) == STRICT_TEXT[edit]
+    with pytest.raises(RuntimeError) as e:
+        m.state_dict()
+    assert str(e.value) == "InceptionI3d: no weights loaded"
+    with pytest.raises(RuntimeError) as e:
+        m._weights(torch.device("cpu"))
+    assert str(e.value) == "InceptionI3d: load_state_dict first"
 
 
 def test_input_checks():

@@ -30,7 +30,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from omnitokenizer_amd import fid, i3d, inception, synth
+from omnitokenizer_amd import fid, i3d, inception, lpips, synth
 
 pytestmark = pytest.mark.gpu
 
@@ -423,3 +423,53 @@ I3D_DIGESTS = {"conv3d_4-64_k7s2": "a8065e1a95892765", "conv3d_64-176_k1s1": "80
 
 def test_i3d_bits_unchanged_by_the_shared_conv():
     assert i3d_digests() == I3D_DIGESTS
+
+
+# ---- Inception V3 and LPIPS after their operators and weight scaffold moved to one module -------------------------------
+
+def _sha(*tensors):
+    h = hashlib.sha256()
+    for t in tensors:
+        h.update(t.contiguous().cpu().numpy().tobytes())
+    return h.hexdigest()[:16]
+
+
+def inception_digests():
+    """sha256 of all four block outputs of 2 seeded images, at the least input that reaches block 3 without the resize and
+    from 64 x 64 with it: every module kind, every fused 1x1 split and every channel-slice offset of InceptionV3"""
+    from tests.golden.make_golden_fid import WEIGHT_SEED
+    sd, out = synth.synth_fid_inception_state_dict(WEIGHT_SEED), {}
+    for tag, resize, size in (("native", False, inception.min_input_size(3)), ("resized", True, 64)):
+        m = inception.InceptionV3((0, 1, 2, 3), resize_input=resize)
+        m.load_state_dict(sd)
+        x = torch.rand((2, 3, size, size), generator=torch.Generator().manual_seed(size))
+        for blk, o in zip(m.output_blocks, m.cuda().eval()(x.cuda())):
+            out[f"inception_{tag}_block{blk}"] = _sha(o)
+    return out
+
+
+def lpips_digests():
+    """sha256 of the LPIPS distances of 2 seeded pairs at the least frame size and at 32 x 48: the VGG16 trunk's 13 convs
+    and 4 pools, the heads and the ScalingLayer constants"""
+    m, out = lpips.load_lpips("cuda", synth.synth_lpips_state_dict(7)), {}
+    for H, W in ((lpips.MIN_SIZE, lpips.MIN_SIZE), (32, 48)):
+        g = torch.Generator().manual_seed(H * W)
+        a, b = (torch.rand((2, 3, H, W), generator=g) - 0.5 for _ in range(2))
+        out[f"lpips_{H}x{W}"] = _sha(m(a.cuda(), b.cuda()))
+    return out
+
+
+# recorded on an MI355X with the library and the Python of the commit before omnitokenizer_amd/convnet.py
+INCEPTION_DIGESTS = {"inception_native_block0": "3328f1e55918f8d9", "inception_native_block1": "8c01f2b873080d76",
+                     "inception_native_block2": "64f513b612c2c9eb", "inception_native_block3": "83ab1aec0be55dac",
+                     "inception_resized_block0": "1788cf9f17e1471e", "inception_resized_block1": "3a4a4c55429a5158",
+                     "inception_resized_block2": "820e12734c78a8cc", "inception_resized_block3": "389fb158df0b8aae"}
+LPIPS_DIGESTS = {"lpips_16x16": "5a96543106042317", "lpips_32x48": "dd0099ed48a32cbf"}
+
+
+def test_inception_bits_unchanged_by_the_shared_module():
+    assert inception_digests() == INCEPTION_DIGESTS
+
+
+def test_lpips_bits_unchanged_by_the_shared_module():
+    assert lpips_digests() == LPIPS_DIGESTS

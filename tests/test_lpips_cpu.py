@@ -152,6 +152,16 @@ def test_load_lpips_sources_agree(lib, tmp_path):
     assert w0.shape[0] == 64 and w0.shape[1] >= 36 and (w0[:, 3:36:4] == 0).all() and (w0[:, 0:36:4] != 0).any()
 
 
+# the full texts of the commit before the shared strict check (omnitokenizer_amd/convnet.py)
+STRICT_TEXT = {
+    "missing": "Error(s) in loading state_dict for LPIPS: missing keys ['lin3.model.1.weight'], unexpected keys []",
+    "extra": "Error(s) in loading state_dict for LPIPS: missing keys [], unexpected keys ['net.slice5.30.weight']",
+    "shape": ("Error(s) in loading state_dict for LPIPS: size mismatch for net.slice2.5.weight: copying a param with shape "
+        "(128, 64, 1, 1), the model has (128, 64, 3, 3)"),
+    "vgg16": "Error(s) in loading state_dict for torchvision vgg16: missing keys ['features.28.bias'], unexpected keys []",
+}
+
+
 @pytest.mark.parametrize("edit", ["missing", "extra", "shape"])
 def test_load_lpips_is_strict(lib, edit):
     sd = dict(synth.synth_lpips_state_dict(7))
@@ -161,12 +171,19 @@ def test_load_lpips_is_strict(lib, edit):
         sd["net.slice5.30.weight"] = torch.zeros(1)
     else:
         sd["net.slice2.5.weight"] = torch.zeros(128, 64, 1, 1)
-    with pytest.raises(RuntimeError, match="loading state_dict"):
+    with pytest.raises(RuntimeError, match="loading state_dict") as e:
         lpips.load_lpips("cpu", sd)
+    assert str(e.value) == STRICT_TEXT[edit]
     vgg, lin = lpips.to_torchvision(synth.synth_lpips_state_dict(7))
     del vgg["features.28.bias"]
-    with pytest.raises(RuntimeError, match="vgg16"):
+    with pytest.raises(RuntimeError, match="vgg16") as e:
         lpips.load_lpips("cpu", (vgg, lin))
+    assert str(e.value) == STRICT_TEXT["vgg16"]
+    for call, text in ((lpips.LPIPS().state_dict, "LPIPS: no weights loaded"),
+                       (lambda: lpips.LPIPS().packed("cpu"), "LPIPS: load_state_dict first (or load_lpips)")):
+        with pytest.raises(RuntimeError) as e:
+            call()
+        assert str(e.value) == text
 
 
 def test_fixture_slices_stay_order_one():
