@@ -11,6 +11,7 @@
     from omnitokenizer_amd import resize_frames, images_to_pixels, center_crop_arr   # Pillow-exact resize (omnitokenizer_amd.frames)
     from omnitokenizer_amd import DiT, DiT_models, load_dit                           # DiT denoiser (omnitokenizer_amd.dit)
     from omnitokenizer_amd import create_diffusion, generate_images                  # its sampler (omnitokenizer_amd.diffusion)
+    from omnitokenizer_amd import Latte, Latte_models, load_latte, generate_videos   # Latte video denoiser (omnitokenizer_amd.latte)
 """
 from .config import OmniTokConfig, make_args  # noqa: F401
 
@@ -23,7 +24,8 @@ __all__ = ["OmniTokenizer_VQGAN", "GPT", "OmniTokConfig", "make_args", "psnr_ssi
            "InceptionI3d", "load_fvd_model", "get_fvd_logits", "frechet_distance", "compute_fvd",
            "InceptionV3"] + list(_FID_NAMES) + ["LPIPS", "load_lpips", "lpips_frames", "reconstruction_losses",
                                            "token_cross_entropy", "resize_frames", "images_to_pixels", "center_crop_arr",
-                                           "DiT", "DiT_models", "load_dit", "create_diffusion", "generate_images"]
+                                           "DiT", "DiT_models", "load_dit", "create_diffusion", "generate_images",
+                                           "Latte", "Latte_models", "load_latte", "get_1d_sincos_temp_embed", "generate_videos"]
 
 
 def __getattr__(name):
@@ -63,7 +65,10 @@ def __getattr__(name):
     if name in ("DiT", "DiT_models", "load_dit"):
         from . import dit
         return getattr(dit, name)
-    if name in ("create_diffusion", "generate_images"):
+    if name in ("Latte", "Latte_models", "load_latte", "get_1d_sincos_temp_embed"):
+        from . import latte
+        return getattr(latte, name)
+    if name in ("create_diffusion", "generate_images", "generate_videos"):
         from . import diffusion
         return getattr(diffusion, name)
     raise AttributeError(name)

@@ -39,6 +39,11 @@ class OmnitokDitConfig(Structure):
                 ("learn_sigma", c_int)]
 
 
+class OmnitokLatteConfig(Structure):
+    """omnitok_latte_config (include/omnitok_latte.h): the DiT's fields, then num_frames and extras."""
+    _fields_ = OmnitokDitConfig._fields_ + [("num_frames", c_int), ("extras", c_int)]
+
+
 class OmnitokPlGemm(Structure):
     """omnitok_pl_gemm (include/omnitok.h): arguments of the plane x plane GEMM."""
     _fields_ = [
@@ -316,6 +321,25 @@ _DIT_PROTOS = {
 _RESTYPES.update({"omnitok_dit_destroy": None, "omnitok_dit_workspace_bytes": c_int64})
 DIT_EXPORTED_SYMBOLS = tuple(_DIT_PROTOS)
 
+# include/omnitok_latte.h
+_LATTE_PROTOS = {
+    "omnitok_latte_create": [POINTER(OmnitokLatteConfig), POINTER(P)],
+    "omnitok_latte_destroy": [P],
+    "omnitok_latte_set_weight": [P, c_char_p, P, POINTER(I64), c_int, P],
+    "omnitok_latte_missing": [P, c_char_p, c_int],
+    "omnitok_latte_finalize": [P, P],
+    "omnitok_latte_set_frequencies": [P, P, c_int],
+    "omnitok_latte_workspace_bytes": [P, c_int],
+    "omnitok_latte_forward": [P, P, P, P, c_int, P, P],
+    "omnitok_latte_forward_cfg": [P, P, P, P, c_int, c_float, P, P],
+    "omnitok_latte_check": [P, P],
+    "omnitok_latte_attn_temporal": [P, c_int, c_int, c_int, c_int, c_int, P, P],
+    "omnitok_latte_add_temp_embed": [P, P, c_int, c_int, c_int, c_int, P],
+    "omnitok_latte_cfg_blend": [P, c_int, c_int, c_int, I64, c_float, P],
+}
+_RESTYPES.update({"omnitok_latte_destroy": None, "omnitok_latte_workspace_bytes": c_int64})
+LATTE_EXPORTED_SYMBOLS = tuple(_LATTE_PROTOS)
+
 _lib = None
 
 
@@ -335,7 +359,7 @@ def load():
     # matter what the caller imported before.
     import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
-    for name, argtypes in {**_PROTOS, **_DIT_PROTOS}.items():
+    for name, argtypes in {**_PROTOS, **_DIT_PROTOS, **_LATTE_PROTOS}.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch: fail loudly
         fn.argtypes = argtypes
         fn.restype = _RESTYPES.get(name, c_int)

@@ -9,6 +9,8 @@
 //   dit_attn.hip   dit_attn_kernel: non-causal attention on v_mfma_f32_32x32x2_f32, head_dim 64 and 72 (omnitok_dit_attn)
 //   attn_f32_tiled.h  (not the DiT's alone) the body of dit_attn_kernel, shared with the LM's tiled causal prefill attention
 //   dit_engine.hip struct omnitok_dit and its exported functions (create .. finalize, forward, forward_cfg)
+//   dit_scaffold.h the engine's host-side scaffold (weight slots, timestep table, workspace, one block, the conditioning), shared
+//                  with the Latte video denoiser (latte_engine.hip, index: latte_common.h)
 // The linears (qkv, proj, fc1, fc2, the conditioning MLP, the modulation GEMM and the final linear) are omnitok_gemm calls.
 #pragma once
 #include "common.h"
@@ -24,12 +26,14 @@ constexpr int DIT_FLAG_Y_RANGE = 2;
 // dit_ops.hip: the conditioning's element-wise steps (rows of D floats, one per sample)
 //   temb[b, :] = table[clamp(t[b])][:]                       (DIT_T_FREQ floats; raises DIT_FLAG_T_RANGE)
 //   x = silu(x)                                              in place
-//   c[b, :] = silu(temb2[b, :] + ytable[clamp(y[b])][:])     (raises DIT_FLAG_Y_RANGE)
+//   c[b, :] = silu(temb2[b, :] + ytable[clamp(y[b])][:])     (raises DIT_FLAG_Y_RANGE); ytable == nullptr (a model without labels,
+//                                                            Latte's extras == 1): c[b, :] = silu(temb2[b, :]), y is not read
 int dit_cond_gather(const float *table, const int64_t *t, int B, float *temb, int *flag, hipStream_t stream);
 int dit_silu(float *x, int64_t n, hipStream_t stream);
 int dit_cond_combine(const float *temb2, const float *ytable, int y_rows, const int64_t *y, int B, int D, float *c, int *flag,
                      hipStream_t stream);
-// out [B, Cout, HW]: channels [0, min(3, Cout)) of both halves <- uncond + s * (cond - uncond), in place
-int dit_cfg_blend(float *out, int B, int Cout, int64_t HW, float s, hipStream_t stream);
+// out [B, Cout, HW]: channels [0, min(channels, Cout)) of both halves <- uncond + s * (cond - uncond), in place (the DiT guides 3
+// channels, Latte 4 of every frame: the literals of models.py:262 and latte.py:399)
+int dit_cfg_blend(float *out, int B, int Cout, int channels, int64_t HW, float s, hipStream_t stream);
 
 }  // namespace omnitok

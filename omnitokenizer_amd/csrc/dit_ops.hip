@@ -75,6 +75,10 @@ __global__ void dit_cond_combine_kernel(const float *__restrict__ temb2, const f
                                         const int64_t *__restrict__ y, int B, int D, float *__restrict__ c, int *__restrict__ flag) {
     const int b = blockIdx.x;
     if (b >= B) return;
+    if (!ytable) {  // no labels: c = silu(t_emb)
+        for (int d = threadIdx.x; d < D; d += blockDim.x) c[(int64_t)b * D + d] = dit_silu_f(temb2[(int64_t)b * D + d]);
+        return;
+    }
     int64_t yv = y[b];
     if (yv < 0 || yv >= y_rows) {
         if (threadIdx.x == 0) atomicOr(flag, DIT_FLAG_Y_RANGE);
@@ -220,8 +224,8 @@ int dit_cond_combine(const float *temb2, const float *ytable, int y_rows, const 
     return OMNITOK_OK;
 }
 
-int dit_cfg_blend(float *out, int B, int Cout, int64_t HW, float s, hipStream_t stream) {
-    const int half = B / 2, nc = Cout < 3 ? Cout : 3;
+int dit_cfg_blend(float *out, int B, int Cout, int channels, int64_t HW, float s, hipStream_t stream) {
+    const int half = B / 2, nc = Cout < channels ? Cout : channels;
     hipLaunchKernelGGL(dit_cfg_blend_kernel, dim3(blocks_for((int64_t)half * nc * HW, 256)), dim3(256), 0, stream, out, half, Cout, nc, HW, s);
     OT_LAUNCH_CHECK("dit_cfg_blend");
     return OMNITOK_OK;

@@ -1,6 +1,6 @@
 """The ancestral sampler of the reference's Diffusion/DiT/diffusion package on the MI355X: `create_diffusion` with the reference's
 signature, and of the object it returns what sample.py / sample_ddp.py use -- p_sample_loop, p_sample, timestep_map,
-num_timesteps.
+num_timesteps.  Diffusion/Latte/diffusion is the same package with 5-D video latents [N,F,C,H,W]; p_sample takes both.
 
     from omnitokenizer_amd.diffusion import create_diffusion, generate_images
     diffusion = create_diffusion("250")
@@ -126,12 +126,17 @@ class SpacedDiffusion:
     def p_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None, noise=None):
         """gaussian_diffusion.py:376-417.  x [N,C,H,W] fp32 on the GPU, t [N] indices of the RESPACED process; the model is called
         with timestep_map[t] (respace.py:124-129).  noise: this step's normal draw (default torch.randn_like(x)).
+        Video latents x [N,F,C,H,W] (Diffusion/Latte/diffusion/gaussian_diffusion.py:277-291): the model returns [N,F,2C | C,H,W],
+        split on dim 2, and the update runs over the N F frames with each sample's t repeated F times.
         Returns {"sample", "pred_xstart"}."""
         self._refuse(denoised_fn, cond_fn)
         if x.device.type != "cuda":
             raise RuntimeError(f"x is on {x.device}: the sampler runs on the GPU only")
+        if x.dim() not in (4, 5):
+            raise ValueError(f"x must be [N,C,H,W] or [N,F,C,H,W], got {tuple(x.shape)}")
         x = x.float().contiguous()
-        B, C = x.shape[:2]
+        video = x.dim() == 5
+        B, frames, C = x.shape[0], (x.shape[1] if video else 1), x.shape[-3]
         t = t.to(device=x.device, dtype=torch.int64).contiguous()
         if tuple(t.shape) != (B,):
             raise ValueError(f"t must be [{B}]")
@@ -139,7 +144,7 @@ class SpacedDiffusion:
         model_output = model(x, tmap[t], **(model_kwargs or {}))
         if isinstance(model_output, tuple):
             model_output = model_output[0]
-        want = (B, C * (2 if self.learn_sigma else 1), *x.shape[2:])
+        want = (*x.shape[:-3], C * (2 if self.learn_sigma else 1), *x.shape[-2:])
         if tuple(model_output.shape) != want:
             raise ValueError(f"model output {tuple(model_output.shape)}, expected {want}")
         model_output = model_output.float().contiguous()
@@ -149,9 +154,12 @@ class SpacedDiffusion:
             raise ValueError("noise must have x's shape and device")
         noise = noise.float().contiguous()
         sample, xstart = torch.empty_like(x), torch.empty_like(x)
+        if video:
+            t = t.repeat_interleave(frames)
         P = ctypes.c_void_p
         check(_lib.load().omnitok_dit_p_sample(P(model_output.data_ptr()), P(x.data_ptr()), P(noise.data_ptr()), P(coef.data_ptr()),
-                                               self.num_timesteps, P(t.data_ptr()), B, C, x[0, 0].numel(), int(self.learn_sigma),
+                                               self.num_timesteps, P(t.data_ptr()), B * frames, C, x.shape[-2] * x.shape[-1],
+                                               int(self.learn_sigma),
                                                int(bool(clip_denoised)), P(sample.data_ptr()), P(xstart.data_ptr()),
                                                torch.cuda.current_stream().cuda_stream), "dit_p_sample")
         return {"sample": sample, "pred_xstart": xstart}
@@ -270,4 +278,48 @@ def generate_images(dit, diffusion, vae, labels, cfg_scale=1.5, seed=0):
     if using_cfg:
         samples, _ = samples.chunk(2, dim=0)
     pixels = vae.decode((samples / 0.18215).contiguous(), is_image=True)
+    return pixels_to_frames(pixels)
+
+
+@torch.no_grad()
+def generate_videos(latte, diffusion, vae, labels, cfg_scale=7.0, seed=0):
+    """The loop body of Diffusion/Latte/sample/sample_ddp.py:148-211 in one call: labels [n] int64 on the GPU (an int n, or None
+    with n = 1, for a model without labels, extras == 1) -> uint8 videos [n,F_pixels,H,W,3].
+    z ~ N(0, 1) of shape [n, latte.num_frames, in_channels, s, s] from a generator seeded with `seed` on the model's device; with
+    cfg_scale > 1 the batch is doubled with the null class (num_classes: the script's literal 101 is UCF-101's) and run through
+    forward_with_cfg; p_sample_loop with clip_denoised=False; the null half is dropped; the latents go channel-last
+    ("b f c h w -> b f h w c", :202) into vae.decode(samples / 0.18215, is_image=False); frames.pixels_to_frames, which is the
+    script's own uint8 conversion (:207)."""
+    from .frames import pixels_to_frames
+    if cfg_scale < 1.0:
+        raise ValueError("In almost all cases, cfg_scale be >= 1.0")
+    device = latte.device
+    conditional = latte.extras == 2
+    if conditional:
+        if labels is None:
+            raise ValueError("labels are required: the model has extras == 2")
+        labels = labels.to(device=device, dtype=torch.int64)
+        n = labels.shape[0]
+    else:
+        n = 1 if labels is None else (int(labels) if isinstance(labels, int) else labels.shape[0])
+        labels = None
+    gen = torch.Generator(device=device)
+    gen.manual_seed(int(seed))
+    z = torch.randn(n, latte.num_frames, latte.in_channels, latte.input_size, latte.input_size, device=device, generator=gen)
+    using_cfg = cfg_scale > 1.0
+    if using_cfg:
+        z = torch.cat([z, z], 0)
+        y = torch.cat([labels, torch.full((n,), latte.num_classes, device=device, dtype=torch.int64)], 0) if conditional else None
+        model_kwargs, sample_fn = dict(y=y, cfg_scale=cfg_scale), latte.forward_with_cfg
+    else:
+        model_kwargs, sample_fn = dict(y=labels), latte.forward
+
+    def draw(k, shape, dev):
+        return torch.randn(*shape, device=dev, generator=gen)
+
+    samples = diffusion.p_sample_loop(sample_fn, z.shape, z, clip_denoised=False, model_kwargs=model_kwargs, device=device,
+                                      step_noise=draw)
+    if using_cfg:
+        samples, _ = samples.chunk(2, dim=0)
+    pixels = vae.decode((samples / 0.18215).permute(0, 1, 3, 4, 2).contiguous(), is_image=False)
     return pixels_to_frames(pixels)

@@ -73,27 +73,40 @@ def timestep_frequencies() -> torch.Tensor:
 class DiT(nn.Module):
     """models.py:145-266, inference only.  Same constructor, same state_dict keys, same forward / forward_with_cfg."""
 
+    _API = "dit"  # the engine's C prefix: omnitok_dit_create, ... (the Latte subclass of omnitokenizer_amd.latte runs omnitok_latte_*)
+    _TOKEN_DROP_REF = "models.py:78-94"
+
     def __init__(self, input_size=32, patch_size=2, in_channels=4, hidden_size=1152, depth=28, num_heads=16, mlp_ratio=4.0,
                  class_dropout_prob=0.1, num_classes=1000, learn_sigma=True):
         super().__init__()
-        self.learn_sigma = learn_sigma
+        mlp_hidden = int(hidden_size * mlp_ratio)
+        cfg = OmnitokDitConfig(input_size, patch_size, in_channels, hidden_size, depth, num_heads, mlp_hidden, num_classes,
+                               float(class_dropout_prob), int(bool(learn_sigma)))
+        self._build(cfg, label_rows=num_classes + (1 if class_dropout_prob > 0 else 0))
+
+    def _fn(self, name):
+        return getattr(_lib.load(), f"omnitok_{self._API}_{name}")
+
+    def _build(self, cfg, label_rows):
+        """The attributes and parameter holders of the reference's module from the engine's config struct; label_rows None: a
+        model without y_embedder."""
+        self._cfg = cfg
+        input_size, patch_size, in_channels, D, depth = cfg.input_size, cfg.patch_size, cfg.in_channels, cfg.hidden, cfg.depth
+        self.learn_sigma = bool(cfg.learn_sigma)
         self.in_channels = in_channels
-        self.out_channels = in_channels * 2 if learn_sigma else in_channels
+        self.out_channels = in_channels * 2 if self.learn_sigma else in_channels
         self.patch_size = patch_size
-        self.num_heads = num_heads
+        self.num_heads = cfg.heads
         self.input_size = input_size
-        self.hidden_size = hidden_size
+        self.hidden_size = D
         self.depth = depth
-        self.mlp_hidden = int(hidden_size * mlp_ratio)
-        self.num_classes = num_classes
-        self.class_dropout_prob = float(class_dropout_prob)
-        D = hidden_size
-        self._cfg = OmnitokDitConfig(input_size, patch_size, in_channels, D, depth, num_heads, self.mlp_hidden, num_classes,
-                                     self.class_dropout_prob, int(bool(learn_sigma)))
+        self.mlp_hidden = cfg.mlp_hidden
+        self.num_classes = cfg.num_classes
+        self.class_dropout_prob = float(cfg.class_dropout)
         # the configuration is checked where the engine checks it (no GPU needed): an unsupported model fails here
         probe = ctypes.c_void_p()
-        check(_lib.load().omnitok_dit_create(ctypes.byref(self._cfg), ctypes.byref(probe)), "dit_create")
-        _lib.load().omnitok_dit_destroy(probe)
+        check(self._fn("create")(ctypes.byref(self._cfg), ctypes.byref(probe)), f"{self._API}_create")
+        self._fn("destroy")(probe)
         n_tok = (input_size // patch_size) ** 2
 
         self.x_embedder = _Holder()
@@ -102,10 +115,10 @@ class DiT(nn.Module):
         self.x_embedder.proj.bias = nn.Parameter(torch.zeros(D), requires_grad=False)
         self.t_embedder = _Holder()
         self.t_embedder.mlp = _seq(_Lin(D, FREQUENCY_EMBEDDING_SIZE), None, _Lin(D, D))
-        self.y_embedder = _Holder()
-        self.y_embedder.embedding_table = _Holder()
-        self.y_embedder.embedding_table.weight = nn.Parameter(
-            torch.zeros(num_classes + (1 if class_dropout_prob > 0 else 0), D), requires_grad=False)
+        if label_rows is not None:
+            self.y_embedder = _Holder()
+            self.y_embedder.embedding_table = _Holder()
+            self.y_embedder.embedding_table.weight = nn.Parameter(torch.zeros(label_rows, D), requires_grad=False)
         self.pos_embed = nn.Parameter(torch.from_numpy(get_2d_sincos_pos_embed(D, input_size // patch_size)).float().unsqueeze(0),
                                       requires_grad=False)
         assert self.pos_embed.shape == (1, n_tok, D)
@@ -124,7 +137,7 @@ class DiT(nn.Module):
         self.final_layer.adaLN_modulation = _seq(None, _Lin(2 * D, D))
         self._engine = None
         self._engine_sig = None
-        super().train(False)
+        nn.Module.train(self, False)
 
     # ---- plumbing ---------------------------------------------------------------------------------
     @property
@@ -133,32 +146,31 @@ class DiT(nn.Module):
 
     def train(self, mode: bool = True):
         if mode:
-            raise NotImplementedError("omnitokenizer_amd DiT is inference-only: training and the label dropout of "
-                                      "LabelEmbedder.token_drop (models.py:78-94) are not built")
+            raise NotImplementedError(f"omnitokenizer_amd {type(self).__name__} is inference-only: training and the label dropout "
+                                      f"of LabelEmbedder.token_drop ({self._TOKEN_DROP_REF}) are not built")
         return super().train(False)
 
     def __del__(self):
         try:
             if self._engine is not None:
-                _lib.load().omnitok_dit_destroy(self._engine)
+                self._fn("destroy")(self._engine)
         except Exception:
             pass
 
     def engine_missing(self):
         """The state_dict keys the engine of this configuration still waits for (all of them before the first forward)."""
-        lib = _lib.load()
         h = self._engine
         own = h is None
         if own:
             h = ctypes.c_void_p()
-            check(lib.omnitok_dit_create(ctypes.byref(self._cfg), ctypes.byref(h)), "dit_create")
+            check(self._fn("create")(ctypes.byref(self._cfg), ctypes.byref(h)), f"{self._API}_create")
         try:
             buf = ctypes.create_string_buffer(1 << 20)
-            n = check(lib.omnitok_dit_missing(h, buf, len(buf)), "dit_missing")
+            n = check(self._fn("missing")(h, buf, len(buf)), f"{self._API}_missing")
             names = buf.value.decode().split("\n") if n else []
         finally:
             if own:
-                lib.omnitok_dit_destroy(h)
+                self._fn("destroy")(h)
         return names
 
     def _signature(self):
@@ -167,28 +179,28 @@ class DiT(nn.Module):
     def _sync_engine(self):
         dev = self.device
         if dev.type != "cuda":
-            raise RuntimeError(f"DiT is on {dev}: move it to the GPU (.to('cuda')). The MI355X HIP path is the only "
+            raise RuntimeError(f"{type(self).__name__} is on {dev}: move it to the GPU (.to('cuda')). The MI355X HIP path is the only "
                                "implementation; there is no CPU fallback.")
         sig = self._signature()
         if self._engine is not None and sig == self._engine_sig:
             return
-        lib = _lib.load()
+        api = self._API
         stream = torch.cuda.current_stream().cuda_stream
         if self._engine is None:
             h = ctypes.c_void_p()
-            check(lib.omnitok_dit_create(ctypes.byref(self._cfg), ctypes.byref(h)), "dit_create")
+            check(self._fn("create")(ctypes.byref(self._cfg), ctypes.byref(h)), f"{api}_create")
             self._engine = h
             fr = timestep_frequencies().contiguous()
-            check(lib.omnitok_dit_set_frequencies(self._engine, ctypes.c_void_p(fr.data_ptr()), fr.numel()), "dit_set_frequencies")
+            check(self._fn("set_frequencies")(self._engine, ctypes.c_void_p(fr.data_ptr()), fr.numel()), f"{api}_set_frequencies")
         for name, t in self.state_dict(keep_vars=True).items():
             t = t.detach()
             if t.dtype != torch.float32:
                 raise TypeError(f"{name}: parameters must be float32 (the path computes in fp32)")
             t = t.contiguous()
             shape = (ctypes.c_int64 * max(t.dim(), 1))(*t.shape)
-            check(lib.omnitok_dit_set_weight(self._engine, name.encode(), ctypes.c_void_p(t.data_ptr()), shape, t.dim(), stream),
-                  f"dit_set_weight({name})")
-        check(lib.omnitok_dit_finalize(self._engine, stream), "dit_finalize")
+            check(self._fn("set_weight")(self._engine, name.encode(), ctypes.c_void_p(t.data_ptr()), shape, t.dim(), stream),
+                  f"{api}_set_weight({name})")
+        check(self._fn("finalize")(self._engine, stream), f"{api}_finalize")
         torch.cuda.current_stream().synchronize()
         self._engine_sig = sig
 
@@ -209,16 +221,16 @@ class DiT(nn.Module):
         x, t, y = self._inputs(x, t, y)
         self._sync_engine()
         B = x.shape[0]
-        out = torch.empty(B, self.out_channels, self.input_size, self.input_size, device=x.device, dtype=torch.float32)
-        lib = _lib.load()
+        out = torch.empty(*x.shape[:-3], self.out_channels, self.input_size, self.input_size, device=x.device, dtype=torch.float32)
         stream = torch.cuda.current_stream().cuda_stream
         P = ctypes.c_void_p
+        yp = P(y.data_ptr()) if y is not None else None
         if cfg_scale is None:
-            check(lib.omnitok_dit_forward(self._engine, P(x.data_ptr()), P(t.data_ptr()), P(y.data_ptr()), B, P(out.data_ptr()),
-                                          stream), "dit_forward")
+            check(self._fn("forward")(self._engine, P(x.data_ptr()), P(t.data_ptr()), yp, B, P(out.data_ptr()), stream),
+                  f"{self._API}_forward")
         else:
-            check(lib.omnitok_dit_forward_cfg(self._engine, P(x.data_ptr()), P(t.data_ptr()), P(y.data_ptr()), B, float(cfg_scale),
-                                              P(out.data_ptr()), stream), "dit_forward_cfg")
+            check(self._fn("forward_cfg")(self._engine, P(x.data_ptr()), P(t.data_ptr()), yp, B, float(cfg_scale), P(out.data_ptr()),
+                                          stream), f"{self._API}_forward_cfg")
         if check_range:
             self.check_range()
         return out
@@ -226,7 +238,7 @@ class DiT(nn.Module):
     def check_range(self):
         """Raises ValueError if a forward since the last check saw a timestep outside [0, 1000) or a label outside the embedding
         table (one int read-back: a host synchronisation)."""
-        check(_lib.load().omnitok_dit_check(self._engine, torch.cuda.current_stream().cuda_stream), "dit_check")
+        check(self._fn("check")(self._engine, torch.cuda.current_stream().cuda_stream), f"{self._API}_check")
 
     # ---- the reference's two entry points ------------------------------------------------------------
     @torch.no_grad()

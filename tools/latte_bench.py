@@ -1,0 +1,176 @@
+#!/usr/bin/env python
+"""One guided denoising step of Latte on the engine, and its temporal-attention kernel alone against the rearranging alternative.
+
+    python tools/latte_bench.py --out profiles/latte_bench.json
+
+Two shapes, seeded random weights, B = 2 (one video and its null-class twin), 256 tokens per frame:
+  omnitokenizer   Latte-XL/2-omnitokenizer: 8 latent channels, F = 5 latent frames (17 pixel frames through the tokenizer's VAE)
+  sd1.4           Latte-XL/2: 4 latent channels, F = 16
+Reported per shape:
+  step_ms         median of the timed steps after warm-up, device events around each; one step = forward_with_cfg + the p_sample
+                  update over the B F frames
+  temporal_attn   omnitok_latte_attn_temporal alone at the model's shape (qkv [B F N, 3 D] in (b f) n order): median ms per call
+                  over batches of calls, and the achieved bytes/s against ONE read of qkv plus ONE write of out
+  rearranged      what the kernel replaces: the copy '(b f) n d -> (b n) f d' of qkv, omnitok_dit_attn with N = F on it, and the copy
+                  of its output back -- the three together and each alone -- with the max abs difference of the two results
+  clock / power   the shader clock and board power sampled over the timed windows (tools/gpu_power.py)
+"""
+import argparse
+import ctypes
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+SHAPES = {
+    "omnitokenizer": dict(model="Latte-XL/2-omnitokenizer", num_frames=5, in_channels=8),
+    "sd1.4": dict(model="Latte-XL/2", num_frames=16, in_channels=4),
+}
+
+
+def timed(fn, warmup, steps):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(steps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+    return statistics.median(ms), min(ms), max(ms)
+
+
+def per_call(fn, calls, warmup, steps):
+    """median / min / max ms of ONE call, from timed batches of `calls` back-to-back calls"""
+    def batch():
+        for _ in range(calls):
+            fn()
+    return [round(v / calls, 5) for v in timed(batch, warmup, steps)]
+
+
+def bench_shape(name, spec, a, lib):
+    from omnitokenizer_amd import _lib
+    from omnitokenizer_amd.diffusion import create_diffusion
+    from omnitokenizer_amd.latte import Latte_models
+    P = ctypes.c_void_p
+    st = torch.cuda.current_stream().cuda_stream
+    g = torch.Generator(device="cuda")
+    g.manual_seed(0)
+    B, F, C = 2, spec["num_frames"], spec["in_channels"]
+    m = Latte_models[spec["model"]](input_size=32, num_frames=F, num_classes=101, extras=2,
+                                    **({} if "omnitokenizer" in spec["model"] else {"in_channels": C})).cuda().eval()
+    for k, v in m.state_dict(keep_vars=True).items():  # every block contributes; the values do not change the time
+        if k not in ("pos_embed", "temp_embed"):
+            v.data.copy_(torch.randn(v.shape, device="cuda", generator=g) * 0.02)
+    z = torch.randn(B // 2, F, C, 32, 32, device="cuda", generator=g)
+    z = torch.cat([z, z])
+    y = torch.tensor([7, 101], device="cuda")
+    noise = torch.randn(B, F, C, 32, 32, device="cuda", generator=g)
+    d = create_diffusion("250")
+    t = torch.full((B,), 125, device="cuda", dtype=torch.int64)
+    kw = dict(y=y, cfg_scale=7.0, check_range=False)
+
+    def step():
+        return d.p_sample(m.forward_with_cfg, z, t, clip_denoised=False, model_kwargs=kw, noise=noise)["sample"]
+
+    with torch.no_grad():
+        assert torch.isfinite(step()).all()
+        m.check_range()
+        step_ms = timed(step, a.warmup, a.steps)
+
+    # ---- the temporal attention alone, and the rearranging alternative ------------------------------------------------------------
+    D, heads, N = m.hidden_size, m.num_heads, (32 // m.patch_size) ** 2
+    hd, rows = D // heads, B * F * N
+    qkv = torch.randn(rows, 3 * D, device="cuda", generator=g)
+    out = torch.empty(rows, D, device="cuda")
+    qkv_t, out_t, out2 = torch.empty(rows, 3 * D, device="cuda"), torch.empty(rows, D, device="cuda"), torch.empty(rows, D, device="cuda")
+
+    def strided():
+        _lib.check(lib.omnitok_latte_attn_temporal(P(qkv.data_ptr()), B, F, N, heads, hd, P(out.data_ptr()), st))
+
+    def copy_in():   # '(b f) n d -> (b n) f d'
+        qkv_t.view(B, N, F, 3 * D).copy_(qkv.view(B, F, N, 3 * D).transpose(1, 2))
+
+    def tiled():
+        _lib.check(lib.omnitok_dit_attn(P(qkv_t.data_ptr()), B * N, F, heads, hd, P(out_t.data_ptr()), st))
+
+    def copy_out():  # '(b n) f d -> (b f) n d'
+        out2.view(B, F, N, D).copy_(out_t.view(B, N, F, D).transpose(1, 2))
+
+    def rearranged():
+        copy_in()
+        tiled()
+        copy_out()
+
+    strided()
+    rearranged()
+    torch.cuda.synchronize()
+    diff = float((out - out2).abs().max())
+    calls = a.calls
+    res_strided = per_call(strided, calls, 2, a.steps)
+    res_re = per_call(rearranged, calls, 2, a.steps)
+    parts = {k: per_call(f, calls, 2, a.steps)[0] for k, f in (("copy_in", copy_in), ("dit_attn_N_eq_F", tiled), ("copy_out", copy_out))}
+    nbytes = rows * 4 * D * 4   # one read of qkv [rows, 3 D] + one write of out [rows, D], fp32
+    return {
+        "model": spec["model"], "B": B, "frames": F, "tokens": N, "in_channels": C, "rows": rows, "hidden": D, "heads": heads,
+        "head_dim": hd, "step_ms": round(step_ms[0], 4), "step_ms_min_max": [round(step_ms[1], 4), round(step_ms[2], 4)],
+        "steps_timed": a.steps,
+        "temporal_attn": {"ms_per_call": res_strided[0], "ms_min_max": res_strided[1:], "calls_per_forward": m.depth // 2,
+                          "bytes_one_read_one_write": nbytes, "achieved_GBps": round(nbytes / (res_strided[0] * 1e-3) / 1e9, 1),
+                          "sequences": B * N * heads},
+        "rearranged": {"ms_per_call": res_re[0], "ms_min_max": res_re[1:], "parts_ms": parts,
+                       "max_abs_diff_to_strided": diff},
+        "strided_speedup_over_rearranged": round(res_re[0] / res_strided[0], 3),
+    }
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shapes", default="omnitokenizer,sd1.4")
+    ap.add_argument("--steps", type=int, default=15)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--calls", type=int, default=50, help="kernel calls per timed batch")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("latte_bench needs the GPU: there is nothing to measure without it")
+    from omnitokenizer_amd import _lib
+    from tools import gpu_power
+    lib = _lib.load()
+    idle = gpu_power.snapshot()
+    x = torch.randn(8192, 8192, device="cuda")
+    for _ in range(20):
+        x @ x
+    busy = gpu_power.snapshot()
+    torch.cuda.synchronize()
+    del x
+    files, hw = gpu_power.pick_hwmon(idle, busy, pci=gpu_power.pci_address(torch.cuda.current_device()))
+    res = {"bench": "latte_step", "device": torch.cuda.get_device_name(0), "arithmetic": "fp32", "shapes": {}}
+    for name in a.shapes.split(","):
+        smp = gpu_power.Sampler(files) if files else None
+        if smp:
+            smp.start()
+        res["shapes"][name] = bench_shape(name, SHAPES[name], a, lib)
+        if smp:
+            smp.stop()
+            res["shapes"][name]["clock_power"] = smp.summary()
+        torch.cuda.empty_cache()
+    res["hwmon"] = hw if hw else "not readable: clock and power not measured"
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+
+
+if __name__ == "__main__":
+    main()
