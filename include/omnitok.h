@@ -79,8 +79,7 @@ const char *omnitok_version(void);
  * full rounds of 256x256 tiles + the last round's rows on thin tiles in a second launch | 0 one launch), "sp_small_blocks" (0 default:
  * omnitok_stats_pack in 16-row workgroups at every size | n: only below n 64-row blocks), "attn_h2_variant" (6 default: omnitok_attn_spatial_h2
  * on the 64-queries-per-wave kernel | 3 the 32-queries-per-wave kernel, which also takes every legacy bias table outside the LDS form | 4, 5, 7
- * measurement arms of the first; the entry point refuses any other value), "vq_split", "vq_screen" (1 default: omnitok_encode uses the screened search omnitok_vq_argmin_screened | 0 the exact sweep), "vq_screen_split", "vq_variant" (1 default: distance finished on the matrix pipe | 0 VALU epilogue | 2 codebook
- * staged in LDS; all bit-exact, profiles/r03_vq_variants.txt), "pl_stagger" (start delay step of persistent GEMM workgroups in
+ * measurement arms of the first; the entry point refuses any other value), "vq_split", "vq_screen" (1 default: omnitok_encode uses the screened search omnitok_vq_argmin_screened | 0 the exact sweep), "vq_screen_split", "pl_stagger" (start delay step of persistent GEMM workgroups in
  * ~1 us units, 0 = off: a measured no-gain knob), "peg_variant" (1 default: LDS-tiled -- the 64-channel kernel of peg_wide.h for
  * 2..8 planes on grids with W % 16 == 0, H % 4 == 0, D % 64 == 0, its one-plane form (9 taps, four workgroups per CU) for images,
  * else the 32-channel time ring | 2 the 64-channel walk kernel whenever the grid allows | 3 time ring only (1, 2, 3 bit-identical)

@@ -59,7 +59,6 @@ int current_device_cus(int *n_cu) {
     X(gemm_gn, false, INT_MIN)          \
     X(gemm_small, false, INT_MIN)       \
     X(vq_split, false, INT_MIN)         \
-    X(vq_variant, false, INT_MIN)       \
     X(vq_screen, false, INT_MIN)        \
     X(vq_screen_split, false, INT_MIN)  \
     X(x3_tile, false, INT_MIN)          \

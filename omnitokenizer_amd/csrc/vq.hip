@@ -21,14 +21,10 @@ namespace omnitok {
 constexpr int VQ_ROWS_PER_WAVE = 64;
 constexpr int VQ_ROWS_PER_BLOCK = 256;
 int g_vq_split = 0;  // 0 = automatic
-// "vq_variant" (VQ_CODEBOOK mode; A/B record in profiles/r03_vq_variants.txt):
-//   0  dot on the matrix pipe, (xx - dot) + ee on the VALU, codebook fragments from L2            (rounds 1-2)
-//   1  fifth MFMA step: the chain runs on -2z (exactly -dot), then k = 8: 1 * xx, k = 9: ee * 1 -- the accumulator
-//      ends in fl(fl(xx - dot) + ee), the reference's distance bit for bit, and the epilogue is the min tree alone
-//      (default: 0.268 vs 0.284 ms at C3)
-//   2  like 0 with the split's codebook fragments staged in LDS once per workgroup (1 KiB per 32 codes): 0.32 ms, the
-//      L2-resident fragments (one coalesced 16-byte load per lane and tile, prefetched two tiles ahead) were never the limit
-int g_vq_variant = 1;
+// The VQ_CODEBOOK sweep finishes the distance on the matrix pipe with a fifth MFMA step: the chain runs on -2z (exactly -dot), then
+// k = 8: 1 * xx, k = 9: ee * 1 -- the accumulator ends in fl(fl(xx - dot) + ee), the reference's distance bit for bit, and the
+// epilogue is the min tree alone.  Retired arms of the "vq_variant" option (the VALU epilogue for this mode, the codebook
+// fragments staged in LDS): profiles/r03_vq_variants.txt; last tree with the arms: 3751f52.
 // "vq_screen" 1 (default): omnitok_encode's nearest-code search is the screened form (vq_screen_kernel below: same ids,
 // a fifth of the matrix work) | 0: the exact sweep for every code.  "vq_screen_split": 0 = automatic, else forced.
 int g_vq_screen = 1;
@@ -73,33 +69,112 @@ __device__ __forceinline__ unsigned order_key(float d) {
 //                (distinct squared distances can round to the same root -> tie -> lowest index)
 enum { VQ_CODEBOOK = 0, VQ_COS = 1, VQ_EUCLID = 2 };
 
-template <bool SPLIT, int MODE = VQ_CODEBOOK, int VAR = 0>
-__global__ __launch_bounds__(256, VAR == 2 ? 1 : 2) void vq_argmin_kernel(const float *__restrict__ z,
-                                                           const float *__restrict__ packed,
+// ---- the pieces vq_argmin_kernel and vq_screen_kernel share ---------------------------------------------------------------------
+
+// The code tiles [t0, t1) of this workgroup (SPLIT: its share of gridDim.y; else all) and c0 = 32 t0, its first code; stages
+// ee[c0 .. 32 t1) into ee_s for the workgroup (HAS_EE: VQ_COS has none).  false: the share is empty, the kernel returns.
+template <bool SPLIT, bool HAS_EE>
+__device__ __forceinline__ bool vq_split_prologue(int n_codes, const float *__restrict__ ee_g, float *ee_s, int &t0, int &t1,
+                                                  int &c0) {
+    const int ntiles_all = n_codes >> 5;
+    const int tiles_per = (ntiles_all + (int)gridDim.y - 1) / (int)gridDim.y;
+    t0 = SPLIT ? (int)blockIdx.y * tiles_per : 0;
+    t1 = SPLIT ? (t0 + tiles_per < ntiles_all ? t0 + tiles_per : ntiles_all) : ntiles_all;
+    if (t0 >= t1) return false;
+    c0 = t0 * 32;
+    if (HAS_EE) {
+        for (int i = (int)threadIdx.x * 4; i < (t1 - t0) * 32; i += 256 * 4)
+            *reinterpret_cast<f32x4 *>(ee_s + i) = *reinterpret_cast<const f32x4 *>(ee_g + c0 + i);
+        __syncthreads();
+    }
+    return true;
+}
+
+// Row min(row, n - 1) of z: 2 z (exact) in zlo | zhi, returns xx = |z|^2 as the reference sums it (k-ordered, unfused)
+__device__ __forceinline__ float vq_load_row(const float *__restrict__ z, int64_t row, int64_t n, f32x4 &zlo, f32x4 &zhi) {
+    if (row > n - 1) row = n - 1;
+    const f32x4 lo = *reinterpret_cast<const f32x4 *>(z + row * 8);
+    const f32x4 hi4 = *reinterpret_cast<const f32x4 *>(z + row * 8 + 4);
+    float acc = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) acc = __fadd_rn(acc, __fmul_rn(lo[k], lo[k]));
+#pragma unroll
+    for (int k = 0; k < 4; ++k) acc = __fadd_rn(acc, __fmul_rn(hi4[k], hi4[k]));
+    zlo = lo * 2.0f;
+    zhi = hi4 * 2.0f;
+    return acc;
+}
+
+// the distance of MODE from the dot of 2 z with the code (the MODE table above)
+template <int MODE>
+__device__ __forceinline__ float vq_dist(float xx, float dot, float ee) {
+    if (MODE == VQ_EUCLID)  // + 0.0f: sqrt(-0.0) = -0.0 must not order below +0.0 in the split key
+        return __fadd_rn(__fsqrt_rn(fmaxf(__fsub_rn(__fadd_rn(xx, ee), dot), 0.0f)), 0.0f);
+    return __fadd_rn(__fsub_rn(xx, dot), ee);
+}
+
+// Exact scan of tile t: the half-wave's 16 codes of the tile (hi: which half), with the sweep's own arithmetic -- the fp32 MFMA is
+// bitwise the k-ordered fmaf chain from 0 (oracle/vq_argmin.c), so the scalar chain reproduces its distances -- in increasing code
+// order with a strict '<': (best, bidx) ends as the first minimum of what it was and these codes.  Callers scan tiles in increasing
+// order.  zlo | zhi: 2 z of the lane's row; ee_s holds ee[c0 ..).
+template <int MODE>
+__device__ __forceinline__ void vq_scan_tile(const float *__restrict__ packed, const float *ee_s, int c0, int t, int hi,
+                                             const f32x4 &zlo, const f32x4 &zhi, float xx, float &best, int &bidx) {
+    const float *pt = packed + (int64_t)t * 256;  // float index of code r (half hh) step s: (hh*32 + r)*4 + s
+    const float zz[8] = {zlo[0], zlo[1], zlo[2], zlo[3], zhi[0], zhi[1], zhi[2], zhi[3]};
+    float bd = best;  // the running pair in values of its own: updated through the references, it is carried twice
+    int bi = bidx;
+#pragma unroll 4
+    for (int qe = 0; qe < 16; ++qe) {
+        const int r = 8 * (qe >> 2) + (qe & 3) + 4 * hi;  // row of accumulator register qe inside the tile
+        const f32x4 ev = *reinterpret_cast<const f32x4 *>(pt + r * 4);        // k = 0, 2, 4, 6
+        const f32x4 od = *reinterpret_cast<const f32x4 *>(pt + (32 + r) * 4);  // k = 1, 3, 5, 7
+        float dot = 0.0f;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            dot = __fmaf_rn(ev[s], zz[2 * s], dot);
+            dot = __fmaf_rn(od[s], zz[2 * s + 1], dot);
+        }
+        const float d = vq_dist<MODE>(xx, dot, MODE == VQ_COS ? 0.0f : ee_s[t * 32 + r - c0]);
+        if (d < bd) {
+            bd = d;
+            bi = t * 32 + r;
+        }
+    }
+    best = bd;
+    bidx = bi;
+}
+
+// Merges the two half-waves' (distance, index) lexicographically -- each scanned the other 16 codes of the same tiles -- and
+// writes the row's result: SPLIT, the 64-bit atomicMin of (order_key << 32 | index) (above); else the index itself.
+template <bool SPLIT>
+__device__ __forceinline__ void vq_merge_store(float best, int bidx, int hi, int64_t row, int64_t n, int64_t *__restrict__ ids) {
+    const float od = swap32(best);
+    const int oi = __shfl_xor(bidx, 32);
+    if (od < best || (od == best && oi < bidx)) {
+        best = od;
+        bidx = oi;
+    }
+    if (hi == 0 && row < n) {
+        if (SPLIT)
+            atomicMin(reinterpret_cast<unsigned long long *>(ids + row),
+                      ((unsigned long long)order_key(best) << 32) | (unsigned)bidx);
+        else
+            ids[row] = (int64_t)bidx;
+    }
+}
+
+template <bool SPLIT, int MODE = VQ_CODEBOOK>
+__global__ __launch_bounds__(256, 2) void vq_argmin_kernel(const float *__restrict__ z, const float *__restrict__ packed,
                                                            const float *__restrict__ ee_g, int64_t n, int n_codes,
                                                            int64_t *__restrict__ ids) {
     extern __shared__ __attribute__((aligned(16))) float ee_s[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r32 = lane & 31, hi = lane >> 5;
-    const int ntiles_all = n_codes >> 5;
-    const int tiles_per = (ntiles_all + (int)gridDim.y - 1) / (int)gridDim.y;
-    const int t0 = SPLIT ? (int)blockIdx.y * tiles_per : 0;
-    const int t1 = SPLIT ? (t0 + tiles_per < ntiles_all ? t0 + tiles_per : ntiles_all) : ntiles_all;
-    if (t0 >= t1) return;
-    const int c0 = t0 * 32;  // first code of this split; ee_s holds ee[c0 .. t1*32)
-    constexpr bool FIFTH = VAR == 1 && MODE == VQ_CODEBOOK;
-    constexpr bool CB_LDS = VAR == 2;
-    // LDS: ee[c0 .. t1 * 32) and, for VAR 2, the codebook fragments of the same codes behind them
-    f32x4 *cb_s = reinterpret_cast<f32x4 *>(ee_s + (MODE != VQ_COS ? ((t1 - t0) * 32 + 3) / 4 * 4 : 0));
-    if (MODE != VQ_COS) {
-        for (int i = tid * 4; i < (t1 - t0) * 32; i += 256 * 4)
-            *reinterpret_cast<f32x4 *>(ee_s + i) = *reinterpret_cast<const f32x4 *>(ee_g + c0 + i);
-    }
-    if (CB_LDS) {
-        const f32x4 *src = reinterpret_cast<const f32x4 *>(packed) + (int64_t)t0 * 64;
-        for (int i = tid; i < (t1 - t0) * 64; i += 256) cb_s[i] = src[i];
-    }
-    if (MODE != VQ_COS || CB_LDS) __syncthreads();
+    int t0, t1, c0;
+    if (!vq_split_prologue<SPLIT, MODE != VQ_COS>(n_codes, ee_g, ee_s, t0, t1, c0)) return;
+    // the distance finished by a fifth MFMA step (the file header); the external modes finish it on the VALU
+    constexpr bool FIFTH = MODE == VQ_CODEBOOK;
 
     const int64_t row_base = (int64_t)blockIdx.x * VQ_ROWS_PER_BLOCK + wave * VQ_ROWS_PER_WAVE;
     float xb[2][4], xx[2], best[2];
@@ -107,18 +182,8 @@ __global__ __launch_bounds__(256, VAR == 2 ? 1 : 2) void vq_argmin_kernel(const 
     int btile[2];
 #pragma unroll
     for (int g = 0; g < 2; ++g) {
-        int64_t row = row_base + g * 32 + r32;
-        if (row > n - 1) row = n - 1;
-        const f32x4 lo = *reinterpret_cast<const f32x4 *>(z + row * 8);
-        const f32x4 hi4 = *reinterpret_cast<const f32x4 *>(z + row * 8 + 4);
-        float acc = 0.0f;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) acc = __fadd_rn(acc, __fmul_rn(lo[k], lo[k]));
-#pragma unroll
-        for (int k = 0; k < 4; ++k) acc = __fadd_rn(acc, __fmul_rn(hi4[k], hi4[k]));
+        const float acc = vq_load_row(z, row_base + g * 32 + r32, n, zlo[g], zhi[g]);
         xx[g] = MODE == VQ_COS ? 0.0f : acc;
-        zlo[g] = lo * 2.0f;  // exact
-        zhi[g] = hi4 * 2.0f;
         // k = 2s + hi for MFMA step s.  FIFTH: the chain runs on -2z -- every step is fl(a * (-b) + c) = -fl(a * b - c),
         // round-to-nearest is sign-symmetric, so the accumulator is exactly -dot
         const float sg = FIFTH ? -1.0f : 1.0f;
@@ -134,18 +199,13 @@ __global__ __launch_bounds__(256, VAR == 2 ? 1 : 2) void vq_argmin_kernel(const 
 #pragma unroll
     for (int g = 0; g < 2; ++g) xb5[g] = hi ? 1.0f : xx[g];
     auto a5_of = [&](int t) { return hi ? ee_s[t * 32 + r32 - c0] : 1.0f; };
-    auto dist = [&](float xxg, float dot, float ee) {
-        if (MODE == VQ_EUCLID)  // + 0.0f: sqrt(-0.0) = -0.0 must not order below +0.0 in the split key
-            return __fadd_rn(__fsqrt_rn(fmaxf(__fsub_rn(__fadd_rn(xxg, ee), dot), 0.0f)), 0.0f);
-        return __fadd_rn(__fsub_rn(xxg, dot), ee);
-    };
 
     // Sweep: per 32-code tile only the lane's minimum distance (v_min3 tree, ~2.5 VALU per element instead of
     // the 5 of a running (value, index) pair) and the tile that holds it; strict '<' keeps the FIRST tile of a tie.
     // Software pipeline: the 8 MFMAs of tile t + 1 are issued with the epilogue of tile t (two accumulator sets),
     // so a wave's VALU work sits beside its own matrix instructions instead of after them.
     const f32x4 *pk = reinterpret_cast<const f32x4 *>(packed) + lane;
-    auto ld_a = [&](int t) -> f32x4 { return CB_LDS ? cb_s[(t - t0) * 64 + lane] : pk[(int64_t)t * 64]; };
+    auto ld_a = [&](int t) -> f32x4 { return pk[(int64_t)t * 64]; };
     auto dots = [&](const f32x4 &a, float a5, f32x16 (&acc)[2]) {
 #pragma unroll
         for (int g = 0; g < 2; ++g) {
@@ -167,18 +227,9 @@ __global__ __launch_bounds__(256, VAR == 2 ? 1 : 2) void vq_argmin_kernel(const 
             float d0, d1, d2, d3;
             if constexpr (FIFTH) {  // the accumulators ARE the distances
                 d0 = acc[g][q * 4 + 0]; d1 = acc[g][q * 4 + 1]; d2 = acc[g][q * 4 + 2]; d3 = acc[g][q * 4 + 3];
-            } else if constexpr (MODE == VQ_EUCLID) {
-                d0 = dist(xx[g], acc[g][q * 4 + 0], e4[0]); d1 = dist(xx[g], acc[g][q * 4 + 1], e4[1]);
-                d2 = dist(xx[g], acc[g][q * 4 + 2], e4[2]); d3 = dist(xx[g], acc[g][q * 4 + 3], e4[3]);
             } else {
-                // (xx - dot) + ee on register pairs: v_pk_add_f32 rounds each half like the scalar add
-                // (IEEE, no contraction), so the distances are bit-identical at half the issue slots
-                typedef float f32x2 __attribute__((ext_vector_type(2)));
-                const f32x2 x2 = {xx[g], xx[g]};
-                const f32x2 a01 = {acc[g][q * 4 + 0], acc[g][q * 4 + 1]}, a23 = {acc[g][q * 4 + 2], acc[g][q * 4 + 3]};
-                const f32x2 e01 = {e4[0], e4[1]}, e23 = {e4[2], e4[3]};
-                const f32x2 r01 = (x2 - a01) + e01, r23 = (x2 - a23) + e23;
-                d0 = r01[0]; d1 = r01[1]; d2 = r23[0]; d3 = r23[1];
+                d0 = vq_dist<MODE>(xx[g], acc[g][q * 4 + 0], e4[0]); d1 = vq_dist<MODE>(xx[g], acc[g][q * 4 + 1], e4[1]);
+                d2 = vq_dist<MODE>(xx[g], acc[g][q * 4 + 2], e4[2]); d3 = vq_dist<MODE>(xx[g], acc[g][q * 4 + 3], e4[3]);
             }
             tmin[g] = fminf(fminf(tmin[g], d0), d1);
             tmin[g] = fminf(fminf(tmin[g], d2), d3);
@@ -239,59 +290,20 @@ __global__ __launch_bounds__(256, VAR == 2 ? 1 : 2) void vq_argmin_kernel(const 
     } else {
         epilogue(t, accA);
     }
-    // Resolve the index: redo the lane's 16 codes of its winning tile with the same arithmetic -- the fp32 MFMA is
-    // bitwise the k-ordered fmaf chain from 0 (oracle/vq_argmin.c), so the scalar chain reproduces the distances --
-    // in increasing code order with a strict '<' (first minimum inside the tile).
+    // Resolve the index: the sweep kept the lane's minimum and its tile, the exact scan of that tile finds the code
     int bidx[2];
 #pragma unroll
     for (int g = 0; g < 2; ++g) {
-        const int t = btile[g];
-        const float *pt = packed + (int64_t)t * 256;  // float index of code r (half hh) step s: (hh*32 + r)*4 + s
-        float bd = INFINITY;
-        int bi = t * 32 + 4 * hi;
-        const float zz[8] = {zlo[g][0], zlo[g][1], zlo[g][2], zlo[g][3], zhi[g][0], zhi[g][1], zhi[g][2], zhi[g][3]};
-#pragma unroll 4
-        for (int qe = 0; qe < 16; ++qe) {
-            const int r = 8 * (qe >> 2) + (qe & 3) + 4 * hi;  // row of accumulator register qe inside the tile
-            const f32x4 ev = *reinterpret_cast<const f32x4 *>(pt + r * 4);        // k = 0, 2, 4, 6
-            const f32x4 od = *reinterpret_cast<const f32x4 *>(pt + (32 + r) * 4);  // k = 1, 3, 5, 7
-            float dot = 0.0f;
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                dot = __fmaf_rn(ev[s], zz[2 * s], dot);
-                dot = __fmaf_rn(od[s], zz[2 * s + 1], dot);
-            }
-            const float ee = MODE == VQ_COS ? 0.0f : ee_s[t * 32 + r - c0];
-            const float d = dist(xx[g], dot, ee);
-            if (d < bd) {
-                bd = d;
-                bi = t * 32 + r;
-            }
-        }
-        best[g] = bd;
-        bidx[g] = bi;
+        best[g] = INFINITY;
+        bidx[g] = btile[g] * 32 + 4 * hi;
+        vq_scan_tile<MODE>(packed, ee_s, c0, btile[g], hi, zlo[g], zhi[g], xx[g], best[g], bidx[g]);
     }
 #pragma unroll
-    for (int g = 0; g < 2; ++g) {
-        const float od = swap32(best[g]);
-        const int oi = __shfl_xor(bidx[g], 32);
-        if (od < best[g] || (od == best[g] && oi < bidx[g])) {
-            best[g] = od;
-            bidx[g] = oi;
-        }
-        const int64_t row = row_base + g * 32 + r32;
-        if (hi == 0 && row < n) {
-            if (SPLIT)
-                atomicMin(reinterpret_cast<unsigned long long *>(ids + row),
-                          ((unsigned long long)order_key(best[g]) << 32) | (unsigned)bidx[g]);
-            else
-                ids[row] = (int64_t)bidx[g];
-        }
-    }
+    for (int g = 0; g < 2; ++g) vq_merge_store<SPLIT>(best[g], bidx[g], hi, row_base + g * 32 + r32, n, ids);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// SCREENED nearest-code search ("vq_variant" 3, VQ_CODEBOOK distance; reference modules/codebook.py:82-86): the same ids as
+// SCREENED nearest-code search (VQ_CODEBOOK distance; reference modules/codebook.py:82-86): the same ids as
 // vq_argmin_kernel, bit for bit, at a fraction of its matrix work.
 //
 // The exact search spends five fp32-input MFMAs (320 matrix cycles) per 32 codes x 32 rows because the distance must be
@@ -314,7 +326,7 @@ __global__ __launch_bounds__(256, VAR == 2 ? 1 : 2) void vq_argmin_kernel(const 
 //     s'[c*] <= d[c*] - xx + delta + eps <= d[c_m] - xx + delta + eps <= s'[c_m] + 2 (delta + eps),
 // i.e. c* -- and every code tied with it in fp32 -- lies within tau = 2 (eps + delta) of the screen's minimum.
 // Pass 1 sweeps all codes for min s' (per row); pass 2 sweeps again and RECORDS the tiles holding a code within tau of it
-// (almost always exactly one); the recorded tiles are then re-evaluated with the exact fmaf chain of the kernel above, in
+// (almost always exactly one); the recorded tiles are then re-evaluated with the exact scan the kernel above ends in (vq_scan_tile), in
 // increasing code order with a strict '<'.  Rows whose inputs leave fp16's range or are not finite, and rows with more than
 // SCR_CAP candidate tiles (a codebook full of duplicates), re-evaluate every tile: slow, never wrong.
 constexpr int SCR_CAP = 4;
@@ -360,15 +372,8 @@ __global__ __launch_bounds__(256, 2) void vq_screen_kernel(const float *__restri
     extern __shared__ __attribute__((aligned(16))) float ee_s[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r32 = lane & 31, hi = lane >> 5;
-    const int ntiles_all = n_codes >> 5;
-    const int tiles_per = (ntiles_all + (int)gridDim.y - 1) / (int)gridDim.y;
-    const int t0 = SPLIT ? (int)blockIdx.y * tiles_per : 0;
-    const int t1 = SPLIT ? (t0 + tiles_per < ntiles_all ? t0 + tiles_per : ntiles_all) : ntiles_all;
-    if (t0 >= t1) return;
-    const int c0 = t0 * 32;
-    for (int i = tid * 4; i < (t1 - t0) * 32; i += 256 * 4)
-        *reinterpret_cast<f32x4 *>(ee_s + i) = *reinterpret_cast<const f32x4 *>(ee_g + c0 + i);
-    __syncthreads();
+    int t0, t1, c0;
+    if (!vq_split_prologue<SPLIT, true>(n_codes, ee_g, ee_s, t0, t1, c0)) return;
 
     const float nE = consts[0], nEE = consts[1], nAbs = consts[2];
     const bool cb_ok = nAbs <= 60000.0f && nEE <= 60000.0f && nE <= 60000.0f;  // false for inf / NaN too
@@ -379,22 +384,12 @@ __global__ __launch_bounds__(256, 2) void vq_screen_kernel(const float *__restri
     bool all_tiles[2];
 #pragma unroll
     for (int g = 0; g < 2; ++g) {
-        int64_t row = row_base + g * 32 + r32;
-        if (row > n - 1) row = n - 1;
-        const f32x4 lo = *reinterpret_cast<const f32x4 *>(z + row * 8);
-        const f32x4 hi4 = *reinterpret_cast<const f32x4 *>(z + row * 8 + 4);
-        float acc = 0.0f, amax = 0.0f;
+        const float acc = xx[g] = vq_load_row(z, row_base + g * 32 + r32, n, zlo[g], zhi[g]);
+        float amax = 0.0f;  // of |2 z|
 #pragma unroll
-        for (int k = 0; k < 4; ++k) acc = __fadd_rn(acc, __fmul_rn(lo[k], lo[k]));
-#pragma unroll
-        for (int k = 0; k < 4; ++k) acc = __fadd_rn(acc, __fmul_rn(hi4[k], hi4[k]));
-#pragma unroll
-        for (int k = 0; k < 4; ++k) amax = fmaxf(amax, fmaxf(fabsf(lo[k]), fabsf(hi4[k])));
-        xx[g] = acc;
-        zlo[g] = lo * 2.0f;  // exact
-        zhi[g] = hi4 * 2.0f;
-        // fp16 range of 2 z, finiteness (fmaxf drops NaN, so xx is tested too)
-        all_tiles[g] = !(cb_ok && amax <= 30000.0f && acc <= 1e9f);
+        for (int k = 0; k < 4; ++k) amax = fmaxf(amax, fmaxf(fabsf(zlo[g][k]), fabsf(zhi[g][k])));
+        // fp16 range of 2 z (the doubling is exact: the same rows as |z| <= 30000), finiteness (fmaxf drops NaN, so xx is tested too)
+        all_tiles[g] = !(cb_ok && amax <= 60000.0f && acc <= 1e9f);
         if (hi == 0)
             bf[g] = f16x8{(_Float16)(-zlo[g][0]), (_Float16)(-zlo[g][1]), (_Float16)(-zlo[g][2]), (_Float16)(-zlo[g][3]),
                           (_Float16)(-zhi[g][0]), (_Float16)(-zhi[g][1]), (_Float16)(-zhi[g][2]), (_Float16)(-zhi[g][3])};
@@ -481,7 +476,7 @@ __global__ __launch_bounds__(256, 2) void vq_screen_kernel(const float *__restri
             if (t + 3 < t1) step(D, t + 3);
         }
     }
-    // ---- exact re-evaluation of the recorded tiles (the arithmetic of vq_argmin_kernel's index resolution) ----------
+    // ---- exact re-evaluation of the recorded tiles, in increasing order ----------------------------------------------
     float best[2];
     int bidx[2];
 #pragma unroll
@@ -491,9 +486,8 @@ __global__ __launch_bounds__(256, 2) void vq_screen_kernel(const float *__restri
         // both half-waves must scan the same tiles for the merge to see every candidate: a tile recorded by one half only
         // is simply absent from the other half's list -- its codes there are above the threshold, hence not the answer
         const int nt = every ? t1 - t0 : cnt[g];
-        float bd = INFINITY;
-        int bi = t0 * 32 + 4 * hi;
-        const float zz[8] = {zlo[g][0], zlo[g][1], zlo[g][2], zlo[g][3], zhi[g][0], zhi[g][1], zhi[g][2], zhi[g][3]};
+        best[g] = INFINITY;
+        bidx[g] = t0 * 32 + 4 * hi;
         for (int i = 0; __builtin_amdgcn_ballot_w64(i < nt) != 0; ++i) {
             if (i < nt) {
                 int t = t0 + i;
@@ -503,46 +497,12 @@ __global__ __launch_bounds__(256, 2) void vq_screen_kernel(const float *__restri
                     for (int j = 1; j < SCR_CAP; ++j)
                         if (i == j) t = ct[g][j];
                 }
-                const float *pt = packed + (int64_t)t * 256;
-#pragma unroll 4
-                for (int qe = 0; qe < 16; ++qe) {
-                    const int r = 8 * (qe >> 2) + (qe & 3) + 4 * hi;
-                    const f32x4 ev = *reinterpret_cast<const f32x4 *>(pt + r * 4);
-                    const f32x4 od = *reinterpret_cast<const f32x4 *>(pt + (32 + r) * 4);
-                    float dot = 0.0f;
-#pragma unroll
-                    for (int s = 0; s < 4; ++s) {
-                        dot = __fmaf_rn(ev[s], zz[2 * s], dot);
-                        dot = __fmaf_rn(od[s], zz[2 * s + 1], dot);
-                    }
-                    const float d = __fadd_rn(__fsub_rn(xx[g], dot), ee_s[t * 32 + r - c0]);
-                    if (d < bd) {  // tiles and codes in increasing order: strict '<' keeps the first minimum
-                        bd = d;
-                        bi = t * 32 + r;
-                    }
-                }
+                vq_scan_tile<VQ_CODEBOOK>(packed, ee_s, c0, t, hi, zlo[g], zhi[g], xx[g], best[g], bidx[g]);
             }
         }
-        best[g] = bd;
-        bidx[g] = bi;
     }
 #pragma unroll
-    for (int g = 0; g < 2; ++g) {
-        const float od = swap32(best[g]);
-        const int oi = __shfl_xor(bidx[g], 32);
-        if (od < best[g] || (od == best[g] && oi < bidx[g])) {
-            best[g] = od;
-            bidx[g] = oi;
-        }
-        const int64_t row = row_base + g * 32 + r32;
-        if (hi == 0 && row < n) {
-            if (SPLIT)
-                atomicMin(reinterpret_cast<unsigned long long *>(ids + row),
-                          ((unsigned long long)order_key(best[g]) << 32) | (unsigned)bidx[g]);
-            else
-                ids[row] = (int64_t)bidx[g];
-        }
-    }
+    for (int g = 0; g < 2; ++g) vq_merge_store<SPLIT>(best[g], bidx[g], hi, row_base + g * 32 + r32, n, ids);
 }
 
 __global__ __launch_bounds__(256) void vq_finalize_kernel(int64_t *__restrict__ ids, int64_t n) {
@@ -827,71 +787,92 @@ extern "C" int omnitok_vq_prepare(const float *codebook, int n_codes, int cdim, 
     return OMNITOK_OK;
 }
 
-template <int MODE, int VAR>
-static int launch_vq_var(const float *z, const float *packed, const float *ee, int64_t n, int n_codes, int64_t *ids,
-                         hipStream_t stream) {
-    constexpr bool cosine = MODE == VQ_COS;
-    const int64_t blocks = (n + VQ_ROWS_PER_BLOCK - 1) / VQ_ROWS_PER_BLOCK;
-    // Code-range splits.  Measured at the BASELINE sizes (profiles/r04_vq_split_sweep.txt: C3 640 row blocks x 256 tiles,
-    // C2 256 x 256, C5 272 x 512, 8 C5 clips 2176 x 512, one clip 20 x 256, one image 4 x 256): an unsplit launch is the
-    // slowest arm at every size but the smallest (one tail round of long workgroups), and past the point where the
-    // chip's 512 slots see a few rounds more splits only add prologues and atomics.  The rule minimises
-    //     (rounds + 1/2) * (tiles per workgroup + 10),   rounds = row blocks * splits / 512
-    // over splits in {1, 2, 4, 8, 16} with at least 16 tiles each -- it picks 4 / 4 / 8 / 2 / 16 / 16 there: the best
-    // measured arm at five of the six sizes (one clip: 16 instead of 8, 26.8 vs 25.6 us).
-    const int ntiles = n_codes >> 5;
+// ---- host side of the four nearest-code entry points ----------------------------------------------------------------------------
+
+// the argument checks of entry `name`: inputs are the read-only device pointers (all 16-byte aligned), ids the output
+static int vq_search_check(const char *name, std::initializer_list<const void *> inputs, const int64_t *ids, int n_codes) {
+    bool nonnull = ids != nullptr, aligned = true;
+    for (const void *p : inputs) {
+        nonnull = nonnull && p != nullptr;
+        aligned = aligned && aligned16(p);
+    }
+    OT_CHECK_ARG(nonnull, "%s: null pointer", name);
+    OT_CHECK_ARG(n_codes % 32 == 0 && n_codes > 0 && n_codes <= 32768, "%s: n_codes=%d unsupported", name, n_codes);
+    OT_CHECK_ARG(aligned, "%s: unaligned", name);
+    return OMNITOK_OK;
+}
+
+static int64_t vq_row_blocks(int64_t n) { return (n + VQ_ROWS_PER_BLOCK - 1) / VQ_ROWS_PER_BLOCK; }
+
+// Code-range splits of vq_argmin_kernel.  Measured at the BASELINE sizes (profiles/r04_vq_split_sweep.txt: C3 640 row blocks x 256
+// tiles, C2 256 x 256, C5 272 x 512, 8 C5 clips 2176 x 512, one clip 20 x 256, one image 4 x 256): an unsplit launch is the
+// slowest arm at every size but the smallest (one tail round of long workgroups), and past the point where the
+// chip's 512 slots see a few rounds more splits only add prologues and atomics.  The rule minimises
+//     (rounds + 1/2) * (tiles per workgroup + 10),   rounds = row blocks * splits / 512
+// over splits in {1, 2, 4, 8, 16} with at least 16 tiles each -- it picks 4 / 4 / 8 / 2 / 16 / 16 there: the best
+// measured arm at five of the six sizes (one clip: 16 instead of 8, 26.8 vs 25.6 us).
+static int vq_sweep_splits(int64_t blocks, int ntiles) {
     int nsplit = 1;
-    {
-        double best = 1e300;
-        for (int s = 1; s <= 16; s *= 2) {
-            if (s > 1 && ntiles / s < 16) break;
-            const double cost = ((double)blocks * s / 512.0 + 0.5) * ((double)(ntiles + s - 1) / s + 10.0);
-            if (cost < best) { best = cost; nsplit = s; }
-        }
+    double best = 1e300;
+    for (int s = 1; s <= 16; s *= 2) {
+        if (s > 1 && ntiles / s < 16) break;
+        const double cost = ((double)blocks * s / 512.0 + 0.5) * ((double)(ntiles + s - 1) / s + 10.0);
+        if (cost < best) { best = cost; nsplit = s; }
     }
     if (g_vq_split >= 1) nsplit = g_vq_split;  // "vq_split" option: force (tests / A-B)
-    if (nsplit > ntiles) nsplit = ntiles;
-    if (VAR == 2)  // the staged fragments (1 KiB per tile) + ee must fit the CU's LDS
-        while ((ntiles + nsplit - 1) / nsplit * (1024 + 128) + 64 > 160 * 1024) nsplit *= 2;
-    const int tiles_per = (ntiles + nsplit - 1) / nsplit;
-    const int lds = (cosine ? 0 : (tiles_per * 32 + 3) / 4 * 4 * 4) + (VAR == 2 ? tiles_per * 1024 : 0);
+    return nsplit < ntiles ? nsplit : ntiles;
+}
+
+// Code-range splits of vq_screen_kernel, from the sweep in profiles/r05_vq_screen.txt (C3 163 840 x 8192: 378 / 222 / 130 / 168 /
+// 243 us at 1 / 2 / 4 / 8 / 16 splits; C5 69 632 x 16 384: best at 4-8; one clip / one image: best at 16): about 64 tiles per
+// workgroup, more splits only while the launch has fewer than 1024 workgroups and a split keeps >= 16 tiles
+static int vq_screen_splits(int64_t blocks, int ntiles) {
+    int nsplit = 1;
+    while (ntiles / nsplit > 64 && nsplit < 16) nsplit *= 2;
+    while (blocks * nsplit < 1024 && nsplit < 16 && ntiles / (nsplit * 2) >= 16) nsplit *= 2;
+    if (g_vq_screen_split >= 1) nsplit = g_vq_screen_split;  // "vq_screen_split" option
+    return nsplit < ntiles ? nsplit : ntiles;
+}
+
+// bytes of ee_s: the ee of one split's share of ntiles tiles
+static int vq_ee_lds(int ntiles, int nsplit) { return (ntiles + nsplit - 1) / nsplit * 32 * (int)sizeof(float); }
+
+// One search launch over n rows: KERNEL_1 on the whole code range writes ids itself; nsplit > 1: ids preset to all ones,
+// KERNEL_SPLIT merges its nsplit shares into them, vq_finalize_kernel strips the keys.  args: the kernels' arguments.
+template <auto KERNEL_1, auto KERNEL_SPLIT, typename... Args>
+static int vq_launch(const char *name, int nsplit, int lds, int64_t n, int64_t *ids, hipStream_t stream, Args... args) {
     if (lds > 65536) {
-        if (int rc = set_max_dynamic_lds(reinterpret_cast<const void *>(vq_argmin_kernel<false, MODE, VAR>), lds)) return rc;
-        if (int rc = set_max_dynamic_lds(reinterpret_cast<const void *>(vq_argmin_kernel<true, MODE, VAR>), lds)) return rc;
+        if (int rc = set_max_dynamic_lds(reinterpret_cast<const void *>(KERNEL_1), lds)) return rc;
+        if (int rc = set_max_dynamic_lds(reinterpret_cast<const void *>(KERNEL_SPLIT), lds)) return rc;
     }
-    const dim3 grid((unsigned)blocks, nsplit);
+    const dim3 grid((unsigned)vq_row_blocks(n), nsplit);
     if (nsplit == 1) {
-        hipLaunchKernelGGL((vq_argmin_kernel<false, MODE, VAR>), grid, dim3(256), lds, stream, z, packed, ee, n, n_codes, ids);
-        OT_LAUNCH_CHECK("vq_argmin");
+        hipLaunchKernelGGL(KERNEL_1, grid, dim3(256), lds, stream, args...);
+        OT_LAUNCH_CHECK(name);
         return OMNITOK_OK;
     }
     if (int rc = device_fill_u32(ids, 0xFFFFFFFFu, n * 2, stream)) return rc;
-    hipLaunchKernelGGL((vq_argmin_kernel<true, MODE, VAR>), grid, dim3(256), lds, stream, z, packed, ee, n, n_codes, ids);
-    OT_LAUNCH_CHECK("vq_argmin");
+    hipLaunchKernelGGL(KERNEL_SPLIT, grid, dim3(256), lds, stream, args...);
+    OT_LAUNCH_CHECK(name);
     hipLaunchKernelGGL(vq_finalize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, ids, n);
     OT_LAUNCH_CHECK("vq_finalize");
     return OMNITOK_OK;
 }
 
+// the exact sweep of MODE (ee: nullptr for VQ_COS)
 template <int MODE>
-static int launch_vq(const float *z, const float *packed, const float *ee, int64_t n, int n_codes, int64_t *ids,
-                     hipStream_t stream) {
-    if constexpr (MODE == VQ_CODEBOOK) {
-        if (g_vq_variant == 0) return launch_vq_var<MODE, 0>(z, packed, ee, n, n_codes, ids, stream);
-        if (g_vq_variant == 2) return launch_vq_var<MODE, 2>(z, packed, ee, n, n_codes, ids, stream);
-        return launch_vq_var<MODE, 1>(z, packed, ee, n, n_codes, ids, stream);
-    }
-    return launch_vq_var<MODE, 0>(z, packed, ee, n, n_codes, ids, stream);
+static int vq_sweep(const float *z, const float *packed, const float *ee, int64_t n, int n_codes, int64_t *ids,
+                    hipStream_t stream) {
+    const int ntiles = n_codes >> 5, nsplit = vq_sweep_splits(vq_row_blocks(n), ntiles);
+    return vq_launch<vq_argmin_kernel<false, MODE>, vq_argmin_kernel<true, MODE>>(
+        "vq_argmin", nsplit, MODE == VQ_COS ? 0 : vq_ee_lds(ntiles, nsplit), n, ids, stream, z, packed, ee, n, n_codes, ids);
 }
 
 extern "C" int omnitok_vq_argmin(const float *z, const float *packed, const float *ee, int64_t n, int n_codes,
                                  int64_t *ids, omnitok_stream_t stream_) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (n == 0) return OMNITOK_OK;
-    OT_CHECK_ARG(z && packed && ee && ids, "vq_argmin: null pointer");
-    OT_CHECK_ARG(n_codes % 32 == 0 && n_codes > 0 && n_codes <= 32768, "vq_argmin: n_codes=%d unsupported", n_codes);
-    OT_CHECK_ARG(aligned16(z) && aligned16(packed) && aligned16(ee), "vq_argmin: unaligned");
-    return launch_vq<VQ_CODEBOOK>(z, packed, ee, n, n_codes, ids, stream);
+    if (int rc = vq_search_check("vq_argmin", {z, packed, ee}, ids, n_codes)) return rc;
+    return vq_sweep<VQ_CODEBOOK>(z, packed, ee, n, n_codes, ids, static_cast<hipStream_t>(stream_));
 }
 
 // screen[n_codes * 8 + 4] floats: 32 bytes per code of fp16 screening fragments (per tile of 32 codes 64 lanes x 16 B in MFMA
@@ -912,62 +893,28 @@ extern "C" int omnitok_vq_screen_prepare(const float *codebook, const float *ee,
 
 extern "C" int omnitok_vq_argmin_screened(const float *z, const float *packed, const float *ee, const float *screen, int64_t n,
                                           int n_codes, int64_t *ids, omnitok_stream_t stream_) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (n == 0) return OMNITOK_OK;
-    OT_CHECK_ARG(z && packed && ee && screen && ids, "vq_argmin_screened: null pointer");
-    OT_CHECK_ARG(n_codes % 32 == 0 && n_codes > 0 && n_codes <= 32768, "vq_argmin_screened: n_codes=%d unsupported", n_codes);
-    OT_CHECK_ARG(aligned16(z) && aligned16(packed) && aligned16(ee) && aligned16(screen), "vq_argmin_screened: unaligned");
-    const int64_t blocks = (n + VQ_ROWS_PER_BLOCK - 1) / VQ_ROWS_PER_BLOCK;
-    const int ntiles = n_codes >> 5;
-    // splits of the code range, from the sweep in profiles/r05_vq_screen.txt (C3 163 840 x 8192: 378 / 222 / 130 / 168 / 243 us
-    // at 1 / 2 / 4 / 8 / 16 splits; C5 69 632 x 16 384: best at 4-8; one clip / one image: best at 16): about 64 tiles per
-    // workgroup, more splits only while the launch has fewer than 1024 workgroups and a split keeps >= 16 tiles
-    int nsplit = 1;
-    while (ntiles / nsplit > 64 && nsplit < 16) nsplit *= 2;
-    while (blocks * nsplit < 1024 && nsplit < 16 && ntiles / (nsplit * 2) >= 16) nsplit *= 2;
-    if (g_vq_screen_split >= 1) nsplit = g_vq_screen_split;
-    if (nsplit > ntiles) nsplit = ntiles;
-    const int tiles_per = (ntiles + nsplit - 1) / nsplit;
-    const int lds = (tiles_per * 32 + 3) / 4 * 4 * 4;
-    if (lds > 65536) {
-        if (int rc = set_max_dynamic_lds(reinterpret_cast<const void *>(vq_screen_kernel<false>), lds)) return rc;
-        if (int rc = set_max_dynamic_lds(reinterpret_cast<const void *>(vq_screen_kernel<true>), lds)) return rc;
-    }
+    if (int rc = vq_search_check("vq_argmin_screened", {z, packed, ee, screen}, ids, n_codes)) return rc;
+    const int ntiles = n_codes >> 5, nsplit = vq_screen_splits(vq_row_blocks(n), ntiles);
     const u32x4 *frag = reinterpret_cast<const u32x4 *>(screen);
     const float *consts = screen + (int64_t)n_codes * 8;
-    const dim3 grid((unsigned)blocks, nsplit);
-    if (nsplit == 1) {
-        hipLaunchKernelGGL((vq_screen_kernel<false>), grid, dim3(256), lds, stream, z, packed, ee, frag, consts, n, n_codes, ids);
-        OT_LAUNCH_CHECK("vq_screen");
-        return OMNITOK_OK;
-    }
-    if (int rc = device_fill_u32(ids, 0xFFFFFFFFu, n * 2, stream)) return rc;
-    hipLaunchKernelGGL((vq_screen_kernel<true>), grid, dim3(256), lds, stream, z, packed, ee, frag, consts, n, n_codes, ids);
-    OT_LAUNCH_CHECK("vq_screen");
-    hipLaunchKernelGGL(vq_finalize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, ids, n);
-    OT_LAUNCH_CHECK("vq_finalize");
-    return OMNITOK_OK;
+    return vq_launch<vq_screen_kernel<false>, vq_screen_kernel<true>>("vq_screen", nsplit, vq_ee_lds(ntiles, nsplit), n, ids,
+                                                                      static_cast<hipStream_t>(stream_), z, packed, ee, frag,
+                                                                      consts, n, n_codes, ids);
 }
 
 extern "C" int omnitok_vq_argmax_cos(const float *z, const float *packed, int64_t n, int n_codes, int64_t *ids,
                                      omnitok_stream_t stream_) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (n == 0) return OMNITOK_OK;
-    OT_CHECK_ARG(z && packed && ids, "vq_argmax_cos: null pointer");
-    OT_CHECK_ARG(n_codes % 32 == 0 && n_codes > 0 && n_codes <= 32768, "vq_argmax_cos: n_codes=%d unsupported", n_codes);
-    OT_CHECK_ARG(aligned16(z) && aligned16(packed), "vq_argmax_cos: unaligned");
-    return launch_vq<VQ_COS>(z, packed, nullptr, n, n_codes, ids, stream);
+    if (int rc = vq_search_check("vq_argmax_cos", {z, packed}, ids, n_codes)) return rc;
+    return vq_sweep<VQ_COS>(z, packed, nullptr, n, n_codes, ids, static_cast<hipStream_t>(stream_));
 }
 
 extern "C" int omnitok_vq_argmin_cdist(const float *z, const float *packed, const float *ee, int64_t n, int n_codes,
                                        int64_t *ids, omnitok_stream_t stream_) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (n == 0) return OMNITOK_OK;
-    OT_CHECK_ARG(z && packed && ee && ids, "vq_argmin_cdist: null pointer");
-    OT_CHECK_ARG(n_codes % 32 == 0 && n_codes > 0 && n_codes <= 32768, "vq_argmin_cdist: n_codes=%d unsupported",
-                 n_codes);
-    OT_CHECK_ARG(aligned16(z) && aligned16(packed) && aligned16(ee), "vq_argmin_cdist: unaligned");
-    return launch_vq<VQ_EUCLID>(z, packed, ee, n, n_codes, ids, stream);
+    if (int rc = vq_search_check("vq_argmin_cdist", {z, packed, ee}, ids, n_codes)) return rc;
+    return vq_sweep<VQ_EUCLID>(z, packed, ee, n, n_codes, ids, static_cast<hipStream_t>(stream_));
 }
 
 extern "C" int omnitok_dequant_table(const float *codebook, int n_codes, int cdim, const float *w, const float *b,

@@ -282,6 +282,58 @@ def test_new_entry_points_validate_arguments_without_gpu(lib):
     assert lib.omnitok_engine_set_option(None, b"gemm_mode", 1) == -1
 
 
+# the nearest-code entry points of csrc/vq.hip: argument names in call order (the stream, always last, is passed as NULL)
+VQ_ENTRIES = {
+    "omnitok_vq_argmin": "z packed ee n n_codes ids",
+    "omnitok_vq_argmin_screened": "z packed ee screen n n_codes ids",
+    "omnitok_vq_argmax_cos": "z packed n n_codes ids",
+    "omnitok_vq_argmin_cdist": "z packed ee n n_codes ids",
+    "omnitok_vq_prepare": "codebook n_codes cdim packed ee",
+    "omnitok_vq_screen_prepare": "codebook ee n_codes cdim screen",
+}
+_VQ_SIZES = dict(n=64, n_codes=8192, cdim=8)
+_VQ_PREPARE = " need cdim == 8, n_codes % 32 == 0"
+# pointers whose 16-byte alignment the entry checks (ids and the arguments of omnitok_vq_prepare are not among them: a misaligned
+# one passes every check and would reach the kernel)
+_VQ_ALIGNED = {"omnitok_vq_argmin": "z packed ee", "omnitok_vq_argmin_screened": "z packed ee screen",
+               "omnitok_vq_argmax_cos": "z packed", "omnitok_vq_argmin_cdist": "z packed ee", "omnitok_vq_prepare": "",
+               "omnitok_vq_screen_prepare": "screen"}
+
+
+def _vq_call(lib, name, **over):
+    """(status, message) of `name` on sizes that pass every check and pointers 256 (non-null, 16-byte aligned, never
+    dereferenced: each case below fails a check, and the checks come before the first HIP call), with `over` replaced."""
+    args = [over.get(k, _VQ_SIZES.get(k, 256)) for k in VQ_ENTRIES[name].split()]
+    return getattr(lib, name)(*args, None), lib.omnitok_last_error().decode()
+
+
+@pytest.mark.parametrize("name", sorted(VQ_ENTRIES))
+def test_vq_entry_points_host_checks(lib, name):
+    """Status and omnitok_last_error() text of every host check of the four search entries and the two prepare entries, as
+    commit 3751f52 (the last with one copy of the checks per entry) returned them: a null pointer in each position, n_codes 0 /
+    33 / 32800, cdim 4, a pointer at address 8, and n == 0 ahead of every check.  n_codes 32800 is left out for the two prepare
+    entries: they have no upper bound, so the call passes its checks and launches on the fake addresses."""
+    short = name[len("omnitok_"):]
+    prepare = name.endswith("prepare")
+    pointers = [p for p in VQ_ENTRIES[name].split() if p not in _VQ_SIZES]
+    for p in pointers:
+        assert _vq_call(lib, name, **{p: None}) == (-1, f"{short}: null pointer"), p
+    for n_codes in (0, 33) if prepare else (0, 33, 32800):
+        want = f"{short}:{_VQ_PREPARE}" if prepare else f"{short}: n_codes={n_codes} unsupported"
+        assert _vq_call(lib, name, n_codes=n_codes) == (-1, want), n_codes
+    if prepare:
+        assert _vq_call(lib, name, cdim=4) == (-1, f"{short}:{_VQ_PREPARE}")
+    for p in _VQ_ALIGNED[name].split():
+        want = f"{short}:{_VQ_PREPARE}" if prepare else f"{short}: unaligned"
+        assert _vq_call(lib, name, **{p: 8}) == (-1, want), p
+    if not prepare:   # an empty batch is done before anything is looked at
+        assert _vq_call(lib, name, n=0, n_codes=33, **{p: None for p in pointers})[0] == 0
+    # order of the checks: null pointer, then the sizes, then alignment
+    assert _vq_call(lib, name, **{pointers[0]: None}, n_codes=33)[1] == f"{short}: null pointer"
+    if not prepare:
+        assert _vq_call(lib, name, z=8, n_codes=33)[1] == f"{short}: n_codes=33 unsupported"
+
+
 ROW_GEMMS = ("omnitok_gemm", "omnitok_gemm_x3", "omnitok_gemm_h2")
 
 
@@ -504,7 +556,8 @@ def test_option_table_settable_readable_and_retired_names(lib):
     v = ctypes.c_int()
     assert lib.omnitok_get_option(b"lm_loss_chunk_rows", ctypes.byref(v)) == 0 and v.value == rows.value
 
-    for name in b"h2_dbg x3_dbg attn_h2_dbg no_such_option".split():   # the three retired switches and a made-up name
+    # the three retired switches, the retired arm selector of the VQ search and a made-up name
+    for name in b"h2_dbg x3_dbg attn_h2_dbg vq_variant no_such_option".split():
         assert lib.omnitok_set_option(name, 1) == -1, name
         assert b"unknown option " + name in lib.omnitok_last_error(), name
 

@@ -470,47 +470,35 @@ def test_vae_sample_and_post_vq(ops):
                   want) < 1e-5
 
 
-VQ_VARIANTS = pytest.mark.parametrize("variant", [0, 1, 2], ids=["valu_epilogue", "fifth_mfma_step", "lds_codebook"])
-
-
-@VQ_VARIANTS
 @pytest.mark.parametrize("n_codes", [8192, 16384])
-def test_vq_argmin_bit_exact_vs_reference_kat(ops, n_codes, variant):
+def test_vq_argmin_bit_exact_vs_reference_kat(ops, n_codes):
     """ids bit-exact against the reference's own Codebook.forward outputs (golden KAT), including
-    duplicated code rows (ties -> lowest index) and scaled / exact-code inputs -- for every arm of the search
-    kernel (csrc/vq.hip "vq_variant": the default, the fifth-MFMA-step chain, the LDS-staged codebook)."""
-    from omnitokenizer_amd import _lib
+    duplicated code rows (ties -> lowest index) and scaled / exact-code inputs (csrc/vq.hip, the exact sweep)."""
     g = np.load(os.path.join(GOLDEN, f"vq_kat_{n_codes}.npz"))
     z, E, ids_ref = torch.from_numpy(g["z"]), torch.from_numpy(g["codebook"]), g["ids"].astype(np.int64)
-    _lib.set_option("vq_variant", variant)
-    try:
-        ids = ops.vq_argmin(dev(z), dev(E)).cpu().numpy()
-        assert np.array_equal(ids, ids_ref), f"{(ids != ids_ref).sum()} of {ids.size} ids differ"
-        assert (ids[4096:4160] == 17).all() and (ids[4160:4200] == 3).all()
-        # ragged sizes (not a multiple of the 256-row workgroup) and the empty input
-        for n in (1, 31, 257, 1000):
-            assert np.array_equal(ops.vq_argmin(dev(z[:n]), dev(E)).cpu().numpy(), ids_ref[:n])
-        assert ops.vq_argmin(dev(z[:0]), dev(E)).numel() == 0
-        # un-normalised inputs (|xx - dot| far from the unit sphere's range) against the C oracle
-        rng = np.random.default_rng(11)
-        zz = (rng.standard_normal((3000, 8)) * 3.0).astype(np.float32)
-        EE = rng.standard_normal((2048, 8)).astype(np.float32)
-        got = ops.vq_argmin(dev(torch.from_numpy(zz)), dev(torch.from_numpy(EE))).cpu().numpy()
-        assert np.array_equal(got, c_oracle.vq_argmin(zz, EE))
-    finally:
-        _lib.set_option("vq_variant", 1)  # the default
+    ids = ops.vq_argmin(dev(z), dev(E)).cpu().numpy()
+    assert np.array_equal(ids, ids_ref), f"{(ids != ids_ref).sum()} of {ids.size} ids differ"
+    assert (ids[4096:4160] == 17).all() and (ids[4160:4200] == 3).all()
+    # ragged sizes (not a multiple of the 256-row workgroup) and the empty input
+    for n in (1, 31, 257, 1000):
+        assert np.array_equal(ops.vq_argmin(dev(z[:n]), dev(E)).cpu().numpy(), ids_ref[:n])
+    assert ops.vq_argmin(dev(z[:0]), dev(E)).numel() == 0
+    # un-normalised inputs (|xx - dot| far from the unit sphere's range) against the C oracle
+    rng = np.random.default_rng(11)
+    zz = (rng.standard_normal((3000, 8)) * 3.0).astype(np.float32)
+    EE = rng.standard_normal((2048, 8)).astype(np.float32)
+    got = ops.vq_argmin(dev(torch.from_numpy(zz)), dev(torch.from_numpy(EE))).cpu().numpy()
+    assert np.array_equal(got, c_oracle.vq_argmin(zz, EE))
 
 
-@VQ_VARIANTS
 @pytest.mark.parametrize("split", [1, 2, 4, 16, 3])
-def test_vq_argmin_code_range_splits(ops, split, variant):
+def test_vq_argmin_code_range_splits(ops, split):
     """The load-balancing code-range split (64-bit atomicMin merge of distance key | index) returns
     the same first-minimum ids whatever the number of splits, ties included."""
     from omnitokenizer_amd import _lib
     g = np.load(os.path.join(GOLDEN, "vq_kat_8192.npz"))
     z, E, ids_ref = torch.from_numpy(g["z"]), torch.from_numpy(g["codebook"]), g["ids"].astype(np.int64)
     _lib.set_option("vq_split", split)
-    _lib.set_option("vq_variant", variant)
     try:
         for n in (6144, 1000, 31):
             ids = ops.vq_argmin(dev(z[:n]), dev(E)).cpu().numpy()
@@ -522,7 +510,6 @@ def test_vq_argmin_code_range_splits(ops, split, variant):
         assert ops.vq_argmin(dev(zz), dev(E2)).cpu().tolist() == [100, 100, 100]
     finally:
         _lib.set_option("vq_split", 0)
-        _lib.set_option("vq_variant", 1)
 
 
 @pytest.mark.parametrize("split", [0, 1, 4])
@@ -623,15 +610,46 @@ def test_vq_screened_search_is_bit_identical(ops, split):
         zb[5, 0] = float("nan")
         zb[6] = float("-inf")
         E1 = torch.from_numpy(g["codebook"])
-        assert torch.equal(ops.vq_argmin_screened(dev(zb), dev(E1)).cpu(), ops.vq_argmin(dev(zb), dev(E1)).cpu())
+        got = ops.vq_argmin_screened(dev(zb), dev(E1)).cpu()
+        assert torch.equal(got, ops.vq_argmin(dev(zb), dev(E1)).cpu())
+        # the two sides share their exact scan and merge, so equality alone no longer pins these rows: the ids of commit 3751f52
+        # (its library on an MI355X, every split; a row whose distances are all inf or NaN passes no strict '<': the first code)
+        assert got[:8].tolist() == [5957, 3973, 3762, 3762, 0, 0, 0, 1182]
         # a codebook outside fp16's range / with a non-finite entry: every row takes the exact evaluation
         for bad in (7e4, float("inf"), float("nan")):
             Eb = E1.clone()
             Eb[5000, 2] = bad
             zq = torch.from_numpy(g["z"][:300])
-            assert torch.equal(ops.vq_argmin_screened(dev(zq), dev(Eb)).cpu(), ops.vq_argmin(dev(zq), dev(Eb)).cpu())
+            got = ops.vq_argmin_screened(dev(zq), dev(Eb)).cpu()
+            assert torch.equal(got, ops.vq_argmin(dev(zq), dev(Eb)).cpu())
+            assert int(got[0]) == 4282   # as 3751f52
     finally:
         _lib.set_option("vq_screen_split", 0)
+
+
+def test_vq_search_above_64k_of_dynamic_lds(ops):
+    """32 768 codes in one split: 131 072 bytes of ee in LDS, the launcher's raised dynamic-LDS limit (the 16 384-code KAT
+    needs exactly 65 536 and stays below it).  Exact sweep and screened search against the scalar C oracle; commit 3751f52
+    passes it too.  vq_prepare / vq_screen_prepare have no such upper bound: 32 800 codes are accepted, as there."""
+    from omnitokenizer_amd import _lib
+    rng = np.random.default_rng(11)
+    zz = (rng.standard_normal((300, 8)) * 3.0).astype(np.float32)
+    EE = rng.standard_normal((32768, 8)).astype(np.float32)
+    want = c_oracle.vq_argmin(zz, EE)
+    _lib.set_option("vq_split", 1)
+    _lib.set_option("vq_screen_split", 1)
+    try:
+        assert np.array_equal(ops.vq_argmin(dev(torch.from_numpy(zz)), dev(torch.from_numpy(EE))).cpu().numpy(), want)
+        assert np.array_equal(ops.vq_argmin_screened(dev(torch.from_numpy(zz)), dev(torch.from_numpy(EE))).cpu().numpy(), want)
+    finally:
+        _lib.set_option("vq_split", 0)
+        _lib.set_option("vq_screen_split", 0)
+    E2 = dev(torch.from_numpy(rng.standard_normal((32800, 8)).astype(np.float32)))
+    packed, ee = ops.vq_prepare(E2)
+    assert ops.vq_screen_prepare(E2, ee).numel() == 32800 * 8 + 4
+    # 8 fp32 products summed in fp32, at most 8 roundings on any term: within (1 + 2^-24)^8 - 1 < 9 * 2^-24 of the exact sum
+    ref = (E2.cpu().double() ** 2).sum(1)
+    assert ((ee.cpu().double() - ref).abs() <= 9 * 2.0 ** -24 * ref).all() and packed.numel() == 32800 * 8
 
 
 def test_vq_screened_large_random_vs_exact(ops):
