@@ -9,7 +9,8 @@
  * Same conventions as omnitok_lm.h: device pointers, fp32 (timesteps and labels int64), row-major, every launch on the given
  * stream, 0 = OK, argument errors are returned before any HIP call, omnitok_last_error holds the message.
  *
- * Arithmetic is fp32 throughout: the linears run on the fp32-in row GEMM of omnitok.h (fp32 accumulate on v_mfma_f32_32x32x2_f32), the
+ * Arithmetic is fp32 throughout (the default; omnitok_dit_set_linear_format below opts the block linears into 16-bit operands):
+ * the linears run on the fp32-in row GEMM of omnitok.h (fp32 accumulate on v_mfma_f32_32x32x2_f32), the
  * attention on the same instruction, everything else on the VALU.  Results do not depend on the batch: sample i of a call
  * with B samples has the bits of a call with that sample alone.
  */
@@ -78,6 +79,24 @@ int omnitok_dit_forward_cfg(omnitok_dit *e, const float *x, const int64_t *t, co
  * (t outside [0, 1000) / y outside [0, table rows)), else 0.  Clears the bits. */
 int omnitok_dit_check(omnitok_dit *e, omnitok_stream_t stream);
 
+/* ---- opt-in 16-bit block linears ------------------------------------------------------------------------------------ */
+#define OMNITOK_DIT_LIN_FP32 0 /* the default: everything above as written */
+#define OMNITOK_DIT_LIN_BF16 1
+#define OMNITOK_DIT_LIN_FP16 2
+/* The format of the four linears of every block (attn.qkv, attn.proj, mlp.fc1, mlp.fc2).  Under a 16-bit format they run on
+ * v_mfma_f32_32x32x16_{bf16,f16} (omnitok_dit_gemm16): both operands rounded ONCE to the format, to nearest even (the bits of
+ * tensor.to(torch.bfloat16 / torch.float16)) -- the weights at the next finalize into a packed image beside the fp32 originals
+ * (weight memory 1.5 x; switching back needs a finalize only), the activations where they are produced (the modulated LayerNorm rows,
+ * the attention output, the GELU output) -- products exact, accumulators fp32.  Everything else stays fp32: the patch embedding, the
+ * conditioning, the adaLN GEMM, the final layer, every bias, the residual stream, LayerNorm statistics and modulation, attention,
+ * guidance, unpatchify, p_sample.  Batch invariance holds as before.
+ * -1 before any HIP call for a null engine, an unknown format or sizes the 16-bit GEMM cannot take (hidden and mlp_hidden must be
+ * multiples of 32); a refused value changes nothing.  Setting a format clears `finalized`.  fp16: a weight that rounds to +-inf makes
+ * finalize fail with OMNITOK_ERR_INVALID naming the tensor (set another format and finalize again); an activation that does raises a
+ * bit that omnitok_dit_check reports ("fp16"). */
+int omnitok_dit_set_linear_format(omnitok_dit *e, int fmt);
+int omnitok_dit_linear_format(omnitok_dit *e); /* -1: null engine */
+
 /* ---- the operators of the forward, each usable without an engine ---------------------------------------------------- */
 
 /* PatchEmbed (a stride-p conv = a [p*p*C -> D] linear per token) + pos_embed: x [x_batch,C,H,W], w [D,C,p,p], bias [D],
@@ -96,6 +115,25 @@ int omnitok_dit_gate_residual(float *x, const float *y, const float *gate, int64
                               omnitok_stream_t stream);
 /* nn.GELU(approximate="tanh") in place over n floats. */
 int omnitok_dit_gelu_tanh(float *x, int64_t n, omnitok_stream_t stream);
+/* omnitok_dit_ln_modulate with its result rounded once to fmt (OMNITOK_DIT_LIN_BF16 | _FP16) into the packed out16 [rows, D].
+ * fp16: a finite value that rounds to +-inf ORs 4 into *flag (an int on the device; may be NULL for bf16). */
+int omnitok_dit_ln_modulate16(const float *x, const float *shift, const float *scale, int64_t ld_mod, int64_t rows, int n_tokens,
+                              int D, int fmt, void *out16, int *flag, omnitok_stream_t stream);
+/* dst16[i] = src[i] rounded to fmt, n % 4 == 0: the pass behind the attention, and the weight images.  flag as above. */
+int omnitok_dit_round16(const float *src, int fmt, void *dst16, int64_t n, int *flag, omnitok_stream_t stream);
+/* The GEMM of a 16-bit linear format: a16 [M, K] . w16 [N, K]^T, both packed in fmt and row-major, fp32 accumulators, K % 32 == 0,
+ * M <= 2^24, and then one of three epilogues in fp32 on the accumulators (bias [N] is required): */
+#define OMNITOK_DIT_EPI_BIAS 0          /* y32 [M, N] = acc + bias                                                              */
+#define OMNITOK_DIT_EPI_GELU16 1        /* y16 [M, N] = gelu_tanh(acc + bias) (omnitok_dit_gelu_tanh's arithmetic) rounded to fmt;  */
+                                        /* flag as above                                                                         */
+#define OMNITOK_DIT_EPI_GATE_RESIDUAL 2 /* x [M, N] += gate[m / n_tokens, :] * (acc + bias): omnitok_dit_gate_residual's arithmetic; */
+                                        /* gate rows ld_gate floats apart, ceil(M / n_tokens) of them                            */
+/* Exactly the outputs of the epilogue are non-NULL (y32 | y16 | gate and x).  Row m of the result depends on row m of a16, on
+ * x[m, :] and on its sample's gate row only; the order of a dot product's partial sums is fixed by K.  -1 before any HIP call for
+ * null or non-16-byte-aligned pointers, sizes outside the contract, an unknown fmt or epilogue, or outputs that do not match it. */
+int omnitok_dit_gemm16(const void *a16, const void *w16, int fmt, const float *bias, int epilogue, float *y32, void *y16,
+                       const float *gate, int64_t ld_gate, int n_tokens, float *x, int64_t M, int N, int K, int *flag,
+                       omnitok_stream_t stream);
 /* models.py:218-231: lin [B*N, p*p*Cout] -> out [B,Cout,H,H] (nhwpqc -> nchpwq), H = sqrt(N) * p. */
 int omnitok_dit_unpatchify(const float *lin, int B, int N, int p, int Cout, float *out, omnitok_stream_t stream);
 /* One ancestral step, gaussian_diffusion.py:254-417 with epsilon prediction: model_out [B, 2C | C, HW], x, noise [B,C,HW],

@@ -310,11 +310,16 @@ _DIT_PROTOS = {
     "omnitok_dit_forward": [P, P, P, P, c_int, P, P],
     "omnitok_dit_forward_cfg": [P, P, P, P, c_int, c_float, P, P],
     "omnitok_dit_check": [P, P],
+    "omnitok_dit_set_linear_format": [P, c_int],
+    "omnitok_dit_linear_format": [P],
     "omnitok_dit_patch_embed": [P, c_int, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P],
     "omnitok_dit_ln_modulate": [P, P, P, I64, I64, c_int, c_int, P, P],
     "omnitok_dit_attn": [P, c_int, c_int, c_int, c_int, P, P],
     "omnitok_dit_gate_residual": [P, P, P, I64, I64, c_int, c_int, P],
     "omnitok_dit_gelu_tanh": [P, I64, P],
+    "omnitok_dit_ln_modulate16": [P, P, P, I64, I64, c_int, c_int, c_int, P, P, P],
+    "omnitok_dit_round16": [P, c_int, P, I64, P, P],
+    "omnitok_dit_gemm16": [P, P, c_int, P, c_int, P, P, P, I64, c_int, P, I64, c_int, c_int, P, P],
     "omnitok_dit_unpatchify": [P, c_int, c_int, c_int, c_int, P, P],
     "omnitok_dit_p_sample": [P, P, P, P, c_int, P, c_int, c_int, I64, c_int, c_int, P, P, P],
 }
@@ -340,6 +345,13 @@ _LATTE_PROTOS = {
 _RESTYPES.update({"omnitok_latte_destroy": None, "omnitok_latte_workspace_bytes": c_int64})
 LATTE_EXPORTED_SYMBOLS = tuple(_LATTE_PROTOS)
 
+# include/omnitok_latte_linear.h (the part of omnitok_latte.h that holds the engine's linear format)
+_LATTE_LINEAR_PROTOS = {
+    "omnitok_latte_set_linear_format": [P, c_int],
+    "omnitok_latte_linear_format": [P],
+}
+LATTE_LINEAR_EXPORTED_SYMBOLS = tuple(_LATTE_LINEAR_PROTOS)
+
 _lib = None
 
 
@@ -359,7 +371,7 @@ def load():
     # matter what the caller imported before.
     import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
-    for name, argtypes in {**_PROTOS, **_DIT_PROTOS, **_LATTE_PROTOS}.items():
+    for name, argtypes in {**_PROTOS, **_DIT_PROTOS, **_LATTE_PROTOS, **_LATTE_LINEAR_PROTOS}.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch: fail loudly
         fn.argtypes = argtypes
         fn.restype = _RESTYPES.get(name, c_int)

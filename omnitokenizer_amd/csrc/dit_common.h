@@ -8,12 +8,17 @@
 //                  gate_residual, unpatchify, the classifier-free-guidance blend and p_sample, with their exported entry points
 //   dit_attn.hip   dit_attn_kernel: non-causal attention on v_mfma_f32_32x32x2_f32, head_dim 64 and 72 (omnitok_dit_attn)
 //   attn_f32_tiled.h  (not the DiT's alone) the body of dit_attn_kernel, shared with the LM's tiled causal prefill attention
+//   dit_gemm16.hip dit_gemm16_kernel: the block linears of a 16-bit linear format (omnitok_dit_set_linear_format) on
+//                  v_mfma_f32_32x32x16_{bf16,f16}, the K loop of csrc/gemm16_tile.h with the DiT's three epilogues (omnitok_dit_gemm16)
 //   dit_engine.hip struct omnitok_dit and its exported functions (create .. finalize, forward, forward_cfg)
 //   dit_scaffold.h the engine's host-side scaffold (weight slots, timestep table, workspace, one block, the conditioning), shared
 //                  with the Latte video denoiser (latte_engine.hip, index: latte_common.h)
-// The linears (qkv, proj, fc1, fc2, the conditioning MLP, the modulation GEMM and the final linear) are omnitok_gemm calls.
+// The linears (qkv, proj, fc1, fc2, the conditioning MLP, the modulation GEMM and the final linear) are omnitok_gemm calls; under a
+// 16-bit linear format the four of a block are omnitok_dit_gemm16 calls on operands rounded once where they are produced
+// (omnitok_dit_ln_modulate16, omnitok_dit_round16 behind the attention, the fc1 epilogue).
 #pragma once
 #include "common.h"
+#include "lm_common.h"  // lm_bf16, lm_fp16, lm_round16: the 16-bit element types and their one conversion
 #include "../../include/omnitok_dit.h"
 
 namespace omnitok {
@@ -22,6 +27,33 @@ constexpr int DIT_T_STEPS = 1000;  // timesteps of the table: t in [0, 1000)
 constexpr int DIT_T_FREQ = 256;    // frequency_embedding_size of TimestepEmbedder (models.py:31)
 constexpr int DIT_FLAG_T_RANGE = 1;  // bits of the engine's range word (omnitok_dit_check)
 constexpr int DIT_FLAG_Y_RANGE = 2;
+constexpr int DIT_FLAG_F16_RANGE = 4;  // an activation of an fp16 linear format rounded from a finite value to +-inf
+
+#ifdef __HIPCC__
+// nn.GELU(approximate="tanh"): 0.5 x (1 + tanh(sqrt(2 / pi) (x + 0.044715 x^3))) -- dit_gelu_tanh_kernel and the fc1 epilogue of
+// dit_gemm16_kernel
+__device__ __forceinline__ float dit_gelu_tanh_f(float v) {
+    const float inner = 0.7978845608028654f * (v + 0.044715f * v * v * v);
+    return 0.5f * v * (1.0f + tanhf(inner));
+}
+
+// One value / four consecutive values rounded to OT = lm_bf16 | lm_fp16 (lm_round16: the bits of tensor.to(dtype)); `inf` records a
+// FINITE value that became +-inf, which only fp16 can do.
+template <typename OT> __device__ __forceinline__ unsigned short dit_round16(float f, bool &inf) {
+    const unsigned short h = lm_round16<OT>(f);
+    if constexpr (__is_same(OT, lm_fp16)) inf = inf || (lm_f16_is_inf(h) && fabsf(f) <= 3.402823466e38f);
+    return h;
+}
+template <typename OT> __device__ __forceinline__ u32x2 dit_round16x4(const f32x4 &v, bool &inf) {
+    unsigned short h[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const float f = v[e];
+        h[e] = dit_round16<OT>(f, inf);
+    }
+    return u32x2{(unsigned)h[0] | ((unsigned)h[1] << 16), (unsigned)h[2] | ((unsigned)h[3] << 16)};
+}
+#endif
 
 // dit_ops.hip: the conditioning's element-wise steps (rows of D floats, one per sample)
 //   temb[b, :] = table[clamp(t[b])][:]                       (DIT_T_FREQ floats; raises DIT_FLAG_T_RANGE)

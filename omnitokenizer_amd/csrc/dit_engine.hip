@@ -8,7 +8,8 @@
 //   per block: ln_modulate -> qkv GEMM -> attention -> proj GEMM -> gate_residual -> ln_modulate -> fc1 GEMM -> GELU-tanh -> fc2 GEMM
 //              -> gate_residual
 //   ln_modulate -> final linear -> unpatchify                       -> out [B, Cout, H, W]
-// Every GEMM is omnitok_gemm with OMNITOK_GEMM_BIAS.
+// Every GEMM is omnitok_gemm with OMNITOK_GEMM_BIAS.  Under a 16-bit linear format (omnitok_dit_set_linear_format, DitLinear in
+// dit_scaffold.h) the four GEMMs of a block are omnitok_dit_gemm16 calls with gate_residual and GELU in their epilogues (dit_block).
 #include "dit_scaffold.h"
 
 using namespace omnitok;
@@ -21,6 +22,7 @@ struct omnitok_dit {
     std::vector<DitBlock> blocks;
     float *w_patch = nullptr, *b_patch = nullptr, *pos = nullptr, *w_t0 = nullptr, *b_t0 = nullptr, *w_t2 = nullptr, *b_t2 = nullptr,
           *ytable = nullptr, *w_mod = nullptr, *b_mod = nullptr, *w_final = nullptr, *b_final = nullptr;
+    DitLinear lin;  // omnitok_dit_set_linear_format
     DitTables tb;  // omnitok_dit_set_frequencies; no frequencies: the built-in chain
     void *work = nullptr;
     int64_t work_bytes = 0;
@@ -75,6 +77,7 @@ extern "C" void omnitok_dit_destroy(omnitok_dit *e) {
     if (!e) return;
     e->w.free_all();
     e->tb.free_all();
+    e->lin.free_all();
     if (e->work) (void)hipFree(e->work);
     delete e;
 }
@@ -128,6 +131,7 @@ extern "C" int omnitok_dit_finalize(omnitok_dit *e, omnitok_stream_t stream) {
     OT_CHECK_ARG(e, "dit_finalize: null engine");
     if (int rc = e->w.require_all("dit")) return rc;
     if (int rc = e->tb.finalize(static_cast<hipStream_t>(stream))) return rc;
+    if (int rc = e->lin.finalize("dit", e->w, e->blocks, e->cfg.hidden, e->cfg.mlp_hidden, static_cast<hipStream_t>(stream))) return rc;
     e->finalized = true;
     return OMNITOK_OK;
 }
@@ -137,7 +141,20 @@ extern "C" int64_t omnitok_dit_workspace_bytes(omnitok_dit *e, int B) {
         set_error("dit_workspace_bytes: null engine or B %d (B * tokens <= 2^24)", B);
         return -1;
     }
-    return dit_work_floats((int64_t)B * e->N, B, e->cfg.hidden, e->cfg.mlp_hidden, dit_patch_out(e), e->modN) * 4;
+    return dit_work_floats((int64_t)B * e->N, B, e->cfg.hidden, e->cfg.mlp_hidden, dit_patch_out(e), e->modN,
+                           e->lin.fmt != OMNITOK_DIT_LIN_FP32) * 4;
+}
+
+extern "C" int omnitok_dit_set_linear_format(omnitok_dit *e, int fmt) {
+    OT_CHECK_ARG(e, "dit_set_linear_format: null engine");
+    if (int rc = e->lin.set("dit", fmt, e->cfg.hidden, e->cfg.mlp_hidden)) return rc;
+    e->finalized = false;
+    return OMNITOK_OK;
+}
+
+extern "C" int omnitok_dit_linear_format(omnitok_dit *e) {
+    OT_CHECK_ARG(e, "dit_linear_format: null engine");
+    return e->lin.fmt;
 }
 
 static int dit_forward_any(const char *who, omnitok_dit *e, const float *x, const int64_t *t, const int64_t *y, int B, bool cfg,
@@ -154,8 +171,10 @@ static int dit_forward_any(const char *who, omnitok_dit *e, const float *x, cons
     const omnitok_dit_config &c = e->cfg;
     const int D = c.hidden, F = c.mlp_hidden, N = e->N, PC = (int)dit_patch_out(e);
     const int64_t M = (int64_t)B * N, modN = e->modN;
-    if (int rc = dit_grow(&e->work, &e->work_bytes, dit_work_floats(M, B, D, F, PC, modN) * 4)) return rc;
-    const DitWork w(e->work, M, B, D, F, PC);
+    const int fmt = e->lin.fmt;
+    const bool lin16 = fmt != OMNITOK_DIT_LIN_FP32;
+    if (int rc = dit_grow(&e->work, &e->work_bytes, dit_work_floats(M, B, D, F, PC, modN, lin16) * 4)) return rc;
+    const DitWork w(e->work, M, B, D, F, PC, lin16);
 #define DIT_RUN(call) \
     if (int rc_ = (call)) return rc_
     DIT_RUN(omnitok_dit_patch_embed(x, cfg ? B / 2 : B, e->w_patch, e->b_patch, e->pos, B, c.in_channels, c.input_size, c.patch_size, D, w.X,
@@ -164,7 +183,8 @@ static int dit_forward_any(const char *who, omnitok_dit *e, const float *x, cons
                              stream));
     for (int i = 0; i < c.depth; ++i)
         DIT_RUN(dit_block(e->blocks[i], w, w.mod + (int64_t)i * 6 * D, modN, M, N, D, F,
-                          [&](const float *qkv, float *a) { return omnitok_dit_attn(qkv, B, N, c.heads, e->hd, a, stream); }, stream));
+                          [&](const float *qkv, float *a) { return omnitok_dit_attn(qkv, B, N, c.heads, e->hd, a, stream); }, fmt,
+                          e->tb.flag, stream));
     const float *mf = w.mod + (int64_t)c.depth * 6 * D;  // shift | scale
     DIT_RUN(omnitok_dit_ln_modulate(w.X, mf, mf + D, modN, M, N, D, w.Xn, stream));
     DIT_RUN(dit_linear(w.Xn, e->w_final, e->b_final, w.LIN, M, PC, D, stream));

@@ -89,9 +89,12 @@ __global__ void dit_cond_combine_kernel(const float *__restrict__ temb2, const f
 
 // ---- LayerNorm (eps 1e-6, no affine) * (1 + scale[b]) + shift[b] -------------------------------------------------------------------
 // One wave per row: pass 1 the mean, pass 2 the variance around it, pass 3 the store (the row stays in L1 / L2 between them).
+// OT = float: the fp32 row.  OT = lm_bf16 / lm_fp16 (omnitok_dit_ln_modulate16): the same values rounded once into a packed row, the A
+// operand of dit_gemm16_kernel; a finite value that leaves the fp16 range raises DIT_FLAG_F16_RANGE in *flag.
+template <typename OT>
 __global__ __launch_bounds__(256) void dit_ln_modulate_kernel(const float *__restrict__ x, const float *__restrict__ shift,
                                                               const float *__restrict__ scale, int64_t ld_mod, int64_t rows, int n_tokens,
-                                                              int D, float *__restrict__ out) {
+                                                              int D, void *__restrict__ out_, int *__restrict__ flag) {
     const int lane = threadIdx.x & 63;
     const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= rows) return;  // wave-uniform
@@ -116,14 +119,30 @@ __global__ __launch_bounds__(256) void dit_ln_modulate_kernel(const float *__res
     const float rstd = 1.0f / sqrtf(wave_allsum(q) / (float)D + 1e-6f);
     const f32x4 *sh = reinterpret_cast<const f32x4 *>(shift + b * ld_mod);
     const f32x4 *sc = reinterpret_cast<const f32x4 *>(scale + b * ld_mod);
-    f32x4 *o = reinterpret_cast<f32x4 *>(out + r * D);
+    bool inf = false;
     for (int i = lane; i < n4; i += 64) {
         const f32x4 v = xr[i], a = sc[i], c = sh[i];
         f32x4 y;
 #pragma unroll
         for (int e = 0; e < 4; ++e) y[e] = fmaf((v[e] - mean) * rstd, 1.0f + a[e], c[e]);
-        o[i] = y;
+        if constexpr (__is_same(OT, float))
+            reinterpret_cast<f32x4 *>(static_cast<float *>(out_) + r * D)[i] = y;
+        else
+            reinterpret_cast<u32x2 *>(static_cast<unsigned short *>(out_) + r * D)[i] = dit_round16x4<OT>(y, inf);
     }
+    if constexpr (__is_same(OT, lm_fp16))
+        if (inf) atomicOr(flag, DIT_FLAG_F16_RANGE);
+}
+
+// ---- fp32 -> packed 16-bit, round to nearest even (the attention output in front of proj; the weight images at finalize) ---------------
+template <typename OT>
+__global__ void dit_round16_kernel(const float *__restrict__ src, unsigned short *__restrict__ dst, int64_t n4, int *__restrict__ flag) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n4) return;
+    bool inf = false;
+    reinterpret_cast<u32x2 *>(dst)[i] = dit_round16x4<OT>(reinterpret_cast<const f32x4 *>(src)[i], inf);
+    if constexpr (__is_same(OT, lm_fp16))
+        if (inf) atomicOr(flag, DIT_FLAG_F16_RANGE);
 }
 
 // ---- x += gate[b] * y ---------------------------------------------------------------------------------------------------------------
@@ -142,13 +161,11 @@ __global__ void dit_gate_residual_kernel(float *__restrict__ x, const float *__r
     reinterpret_cast<f32x4 *>(x)[id] = xv;
 }
 
-// ---- GELU, tanh form: 0.5 x (1 + tanh(sqrt(2 / pi) (x + 0.044715 x^3))) -----------------------------------------------------------------
+// ---- GELU, tanh form (dit_common.h) ----------------------------------------------------------------------------------------------------
 __global__ void dit_gelu_tanh_kernel(float *__restrict__ x, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const float v = x[i];
-    const float inner = 0.7978845608028654f * (v + 0.044715f * v * v * v);
-    x[i] = 0.5f * v * (1.0f + tanhf(inner));
+    x[i] = dit_gelu_tanh_f(x[i]);
 }
 
 // ---- unpatchify: lin[(b, hp, wp)][(i, j, c)] -> out[b][c][hp p + i][wp p + j] -------------------------------------------------------------
@@ -262,9 +279,46 @@ extern "C" int omnitok_dit_ln_modulate(const float *x, const float *shift, const
                  (long long)ld_mod);
     OT_CHECK_ARG(aligned16(x) && aligned16(shift) && aligned16(scale) && aligned16(out), "dit_ln_modulate: unaligned pointer (16 bytes)");
     DIT_CHECK_GRID("dit_ln_modulate", rows * 64);
-    hipLaunchKernelGGL(dit_ln_modulate_kernel, dim3(blocks_for(rows, 4)), dim3(256), 0, static_cast<hipStream_t>(stream), x, shift, scale,
-                       ld_mod, rows, n_tokens, D, out);
+    hipLaunchKernelGGL(dit_ln_modulate_kernel<float>, dim3(blocks_for(rows, 4)), dim3(256), 0, static_cast<hipStream_t>(stream), x, shift,
+                       scale, ld_mod, rows, n_tokens, D, out, nullptr);
     OT_LAUNCH_CHECK("dit_ln_modulate");
+    return OMNITOK_OK;
+}
+
+extern "C" int omnitok_dit_ln_modulate16(const float *x, const float *shift, const float *scale, int64_t ld_mod, int64_t rows,
+                                         int n_tokens, int D, int fmt, void *out16, int *flag, omnitok_stream_t stream) {
+    OT_CHECK_ARG(fmt == OMNITOK_DIT_LIN_BF16 || fmt == OMNITOK_DIT_LIN_FP16, "dit_ln_modulate16: fmt %d (OMNITOK_DIT_LIN_BF16 | _FP16)", fmt);
+    OT_CHECK_ARG(x && shift && scale && out16 && (flag || fmt != OMNITOK_DIT_LIN_FP16), "dit_ln_modulate16: null pointer");
+    OT_CHECK_ARG(rows >= 1 && n_tokens >= 1 && D >= 4 && D % 4 == 0 && ld_mod % 4 == 0 && ld_mod >= 0,
+                 "dit_ln_modulate16: rows %lld, n_tokens %d, D %d (%% 4 == 0), ld_mod %lld (%% 4 == 0)", (long long)rows, n_tokens, D,
+                 (long long)ld_mod);
+    OT_CHECK_ARG(aligned16(x) && aligned16(shift) && aligned16(scale) && aligned16(out16) && (reinterpret_cast<uintptr_t>(flag) & 3) == 0,
+                 "dit_ln_modulate16: unaligned pointer (16 bytes)");
+    DIT_CHECK_GRID("dit_ln_modulate16", rows * 64);
+    if (fmt == OMNITOK_DIT_LIN_BF16)
+        hipLaunchKernelGGL(dit_ln_modulate_kernel<lm_bf16>, dim3(blocks_for(rows, 4)), dim3(256), 0, static_cast<hipStream_t>(stream), x,
+                           shift, scale, ld_mod, rows, n_tokens, D, out16, flag);
+    else
+        hipLaunchKernelGGL(dit_ln_modulate_kernel<lm_fp16>, dim3(blocks_for(rows, 4)), dim3(256), 0, static_cast<hipStream_t>(stream), x,
+                           shift, scale, ld_mod, rows, n_tokens, D, out16, flag);
+    OT_LAUNCH_CHECK("dit_ln_modulate16");
+    return OMNITOK_OK;
+}
+
+extern "C" int omnitok_dit_round16(const float *src, int fmt, void *dst16, int64_t n, int *flag, omnitok_stream_t stream) {
+    OT_CHECK_ARG(fmt == OMNITOK_DIT_LIN_BF16 || fmt == OMNITOK_DIT_LIN_FP16, "dit_round16: fmt %d (OMNITOK_DIT_LIN_BF16 | _FP16)", fmt);
+    OT_CHECK_ARG(src && dst16 && (flag || fmt != OMNITOK_DIT_LIN_FP16), "dit_round16: null pointer");
+    OT_CHECK_ARG(n >= 4 && n % 4 == 0, "dit_round16: n %lld (%% 4 == 0)", (long long)n);
+    OT_CHECK_ARG(aligned16(src) && aligned16(dst16) && (reinterpret_cast<uintptr_t>(flag) & 3) == 0, "dit_round16: unaligned pointer (16 bytes)");
+    DIT_CHECK_GRID("dit_round16", n / 4);
+    unsigned short *dst = static_cast<unsigned short *>(dst16);
+    if (fmt == OMNITOK_DIT_LIN_BF16)
+        hipLaunchKernelGGL(dit_round16_kernel<lm_bf16>, dim3(blocks_for(n / 4, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), src, dst,
+                           n / 4, flag);
+    else
+        hipLaunchKernelGGL(dit_round16_kernel<lm_fp16>, dim3(blocks_for(n / 4, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), src, dst,
+                           n / 4, flag);
+    OT_LAUNCH_CHECK("dit_round16");
     return OMNITOK_OK;
 }
 

@@ -22,11 +22,13 @@ struct DitSlot {
 struct DitBlock {
     float *wqkv = nullptr, *bqkv = nullptr, *wproj = nullptr, *bproj = nullptr, *wfc1 = nullptr, *bfc1 = nullptr, *wfc2 = nullptr,
           *bfc2 = nullptr;
+    unsigned short *w16qkv = nullptr, *w16proj = nullptr, *w16fc1 = nullptr, *w16fc2 = nullptr;  // inside DitLinear::image
 };
 
 struct DitSlots {
     std::map<std::string, DitSlot> slots;
     std::vector<std::string> order;  // the state_dict's order, for missing()
+    bool changed = true;             // a weight was set since DitLinear built its image
 
     void add(const std::string &name, std::vector<int64_t> shape, float **dst, int64_t offset = 0, int64_t alloc = 0) {
         int64_t n = 1;
@@ -84,6 +86,7 @@ struct DitSlots {
         if (!*s.dst) OT_HIP(hipMalloc(reinterpret_cast<void **>(s.dst), (size_t)s.alloc * 4));
         OT_HIP(hipMemcpyAsync(*s.dst + s.offset, dev_ptr, (size_t)n * 4, hipMemcpyDeviceToDevice, stream));
         s.set = true;
+        changed = true;
         return OMNITOK_OK;
     }
 
@@ -155,15 +158,83 @@ struct DitTables {
         OT_HIP(hipStreamSynchronize(stream));
         if (!bits) return OMNITOK_OK;
         if (int rc = device_fill_u32(flag, 0, 1, stream)) return rc;
-        set_error("%s_forward: %s%s%s", who, bits & DIT_FLAG_T_RANGE ? "a timestep outside [0, 1000)" : "",
+        const bool ty = bits & (DIT_FLAG_T_RANGE | DIT_FLAG_Y_RANGE);
+        set_error("%s_forward: %s%s%s%s%s", who, bits & DIT_FLAG_T_RANGE ? "a timestep outside [0, 1000)" : "",
                   (bits & DIT_FLAG_T_RANGE) && (bits & DIT_FLAG_Y_RANGE) ? " and " : "",
-                  bits & DIT_FLAG_Y_RANGE ? "a label outside the embedding table" : "");
+                  bits & DIT_FLAG_Y_RANGE ? "a label outside the embedding table" : "", ty && (bits & DIT_FLAG_F16_RANGE) ? " and " : "",
+                  bits & DIT_FLAG_F16_RANGE ? "an activation outside the fp16 range (linear format fp16: use bf16 or fp32)" : "");
         return OMNITOK_ERR_INVALID;
     }
 
     void free_all() {
         if (t_table) (void)hipFree(t_table);
         if (flag) (void)hipFree(flag);
+    }
+};
+
+// The linear format of an engine (omnitok_dit_set_linear_format) and, under a 16-bit one, the packed image of the four matrices of
+// every block: attn.qkv | attn.proj | mlp.fc1 | mlp.fc2, block after block, rounded on the device by omnitok_dit_round16.  The fp32
+// originals stay where DitSlots put them.
+struct DitLinear {
+    int fmt = OMNITOK_DIT_LIN_FP32;
+    int built = OMNITOK_DIT_LIN_FP32;  // the format `image` holds; -1: none that can be used
+    unsigned short *image = nullptr;
+    int *wflags = nullptr;  // one range word per matrix
+
+    int set(const char *who, int f, int D, int F) {
+        OT_CHECK_ARG(f == OMNITOK_DIT_LIN_FP32 || f == OMNITOK_DIT_LIN_BF16 || f == OMNITOK_DIT_LIN_FP16,
+                     "%s_set_linear_format: format %d (OMNITOK_DIT_LIN_FP32 | _BF16 | _FP16)", who, f);
+        OT_CHECK_ARG(f == OMNITOK_DIT_LIN_FP32 || (D % 32 == 0 && F % 32 == 0),
+                     "%s_set_linear_format: the 16-bit GEMM needs K %% 32 == 0, hidden is %d and mlp_hidden %d", who, D, F);
+        fmt = f;
+        return OMNITOK_OK;
+    }
+
+    int finalize(const char *who, DitSlots &slots, std::vector<DitBlock> &blocks, int64_t D, int64_t F, hipStream_t stream) {
+        if (fmt == OMNITOK_DIT_LIN_FP32) {
+            free_all();  // (hipFree synchronises: no earlier forward still reads the image)
+            for (DitBlock &L : blocks) L.w16qkv = L.w16proj = L.w16fc1 = L.w16fc2 = nullptr;
+            built = fmt;
+            return OMNITOK_OK;
+        }
+        if (image && built == fmt && !slots.changed) return OMNITOK_OK;
+        built = -1;
+        const int64_t per = 4 * D * D + 2 * F * D;
+        const int n = 4 * (int)blocks.size();
+        if (!image) OT_HIP(hipMalloc(reinterpret_cast<void **>(&image), (size_t)per * blocks.size() * 2));
+        if (!wflags) OT_HIP(hipMalloc(reinterpret_cast<void **>(&wflags), (size_t)n * 4));
+        if (int rc = device_fill_u32(wflags, 0, n, stream)) return rc;
+        for (size_t i = 0; i < blocks.size(); ++i) {
+            DitBlock &L = blocks[i];
+            L.w16qkv = image + (int64_t)i * per;
+            L.w16proj = L.w16qkv + 3 * D * D;
+            L.w16fc1 = L.w16proj + D * D;
+            L.w16fc2 = L.w16fc1 + F * D;
+            const float *src[4] = {L.wqkv, L.wproj, L.wfc1, L.wfc2};
+            unsigned short *dst[4] = {L.w16qkv, L.w16proj, L.w16fc1, L.w16fc2};
+            const int64_t count[4] = {3 * D * D, D * D, F * D, D * F};
+            for (int k = 0; k < 4; ++k)
+                if (int rc = omnitok_dit_round16(src[k], fmt, dst[k], count[k], wflags + 4 * i + k, stream)) return rc;
+        }
+        if (fmt == OMNITOK_DIT_LIN_FP16) {
+            std::vector<int> host(n);
+            OT_HIP(hipMemcpyAsync(host.data(), wflags, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
+            OT_HIP(hipStreamSynchronize(stream));
+            static const char *const names[4] = {"attn.qkv.weight", "attn.proj.weight", "mlp.fc1.weight", "mlp.fc2.weight"};
+            for (int k = 0; k < n; ++k)
+                OT_CHECK_ARG(!host[k], "%s_finalize: blocks.%d.%s has an element outside the fp16 range (linear format fp16: use bf16 or fp32)",
+                             who, k / 4, names[k % 4]);
+        }
+        built = fmt;
+        slots.changed = false;
+        return OMNITOK_OK;
+    }
+
+    void free_all() {
+        if (image) (void)hipFree(image);
+        if (wflags) (void)hipFree(wflags);
+        image = nullptr;
+        wflags = nullptr;
     }
 };
 
@@ -186,23 +257,31 @@ inline int dit_linear(const float *a, const float *w, const float *bias, float *
 }
 
 // floats of one forward's workspace over M token rows of B samples (D hidden, F mlp hidden, lin_floats the final linear's output
-// rounded up to whole f32x4):  X, Xn, Y, A | qkv | fc1 | final linear | temb, h1, h2, c | mod
+// rounded up to whole f32x4):  X, Xn, Y, A | qkv | fc1 | final linear | temb, h1, h2, c | mod.  Under a 16-bit linear format
+// (lin16) there is no Y -- its M D floats hold the packed Xn16 | A16 -- and fc1's output is the packed H16, half the bytes.
 inline int64_t dit_lin_floats(int64_t M, int64_t patch_out) { return (M * patch_out + 3) / 4 * 4; }
-inline int64_t dit_work_floats(int64_t M, int64_t B, int64_t D, int64_t F, int64_t patch_out, int64_t modN) {
-    return 4 * M * D + 3 * M * D + M * F + dit_lin_floats(M, patch_out) + B * (DIT_T_FREQ + 3 * D) + B * modN;
+inline int64_t dit_work_floats(int64_t M, int64_t B, int64_t D, int64_t F, int64_t patch_out, int64_t modN, bool lin16) {
+    return 4 * M * D + 3 * M * D + M * F / (lin16 ? 2 : 1) + dit_lin_floats(M, patch_out) + B * (DIT_T_FREQ + 3 * D) + B * modN;
 }
 
 // the pointers of that workspace
 struct DitWork {
     float *X, *Xn, *Y, *A, *QKV, *H1, *LIN, *temb, *h1, *h2, *cs, *mod;
-    DitWork(void *base, int64_t M, int64_t B, int64_t D, int64_t F, int64_t patch_out) {
+    unsigned short *Xn16 = nullptr, *A16 = nullptr, *H16 = nullptr;
+    DitWork(void *base, int64_t M, int64_t B, int64_t D, int64_t F, int64_t patch_out, bool lin16) {
         X = static_cast<float *>(base);
         Xn = X + M * D;
         Y = Xn + M * D;
         A = Y + M * D;
         QKV = A + M * D;
         H1 = QKV + 3 * M * D;
-        LIN = H1 + M * F;
+        LIN = H1 + M * F / (lin16 ? 2 : 1);
+        if (lin16) {
+            Xn16 = reinterpret_cast<unsigned short *>(Y);
+            A16 = Xn16 + M * D;
+            H16 = reinterpret_cast<unsigned short *>(H1);
+            Y = H1 = nullptr;
+        }
         temb = LIN + dit_lin_floats(M, patch_out);
         h1 = temb + B * DIT_T_FREQ;
         h2 = h1 + B * D;
@@ -213,11 +292,28 @@ struct DitWork {
 
 // One transformer block in place on X [M, D] (M rows, n_tokens of them per sample), m = the block's 6 D modulation columns of `mod`
 // (shift_msa | scale_msa | gate_msa | shift_mlp | scale_mlp | gate_mlp, rows modN apart); attn(QKV, A) is the caller's attention.
+// fmt: the engine's linear format; under a 16-bit one the four linears are omnitok_dit_gemm16 calls on the packed images L.w16*, each
+// A operand rounded once where it is produced, gate_residual and GELU inside the epilogues; `flag` is the engine's range word.
 template <typename Attn>
 inline int dit_block(const DitBlock &L, const DitWork &w, const float *m, int64_t modN, int64_t M, int n_tokens, int D, int F, Attn attn,
-                     hipStream_t stream) {
+                     int fmt, int *flag, hipStream_t stream) {
 #define DIT_RUN(call) \
     if (int rc_ = (call)) return rc_
+    if (fmt != OMNITOK_DIT_LIN_FP32) {
+        DIT_RUN(omnitok_dit_ln_modulate16(w.X, m, m + D, modN, M, n_tokens, D, fmt, w.Xn16, flag, stream));
+        DIT_RUN(omnitok_dit_gemm16(w.Xn16, L.w16qkv, fmt, L.bqkv, OMNITOK_DIT_EPI_BIAS, w.QKV, nullptr, nullptr, 0, 0, nullptr, M, 3 * D, D,
+                                   flag, stream));
+        DIT_RUN(attn(w.QKV, w.A));
+        DIT_RUN(omnitok_dit_round16(w.A, fmt, w.A16, M * D, flag, stream));
+        DIT_RUN(omnitok_dit_gemm16(w.A16, L.w16proj, fmt, L.bproj, OMNITOK_DIT_EPI_GATE_RESIDUAL, nullptr, nullptr, m + 2 * D, modN,
+                                   n_tokens, w.X, M, D, D, flag, stream));
+        DIT_RUN(omnitok_dit_ln_modulate16(w.X, m + 3 * D, m + 4 * D, modN, M, n_tokens, D, fmt, w.Xn16, flag, stream));
+        DIT_RUN(omnitok_dit_gemm16(w.Xn16, L.w16fc1, fmt, L.bfc1, OMNITOK_DIT_EPI_GELU16, nullptr, w.H16, nullptr, 0, 0, nullptr, M, F, D,
+                                   flag, stream));
+        DIT_RUN(omnitok_dit_gemm16(w.H16, L.w16fc2, fmt, L.bfc2, OMNITOK_DIT_EPI_GATE_RESIDUAL, nullptr, nullptr, m + 5 * D, modN, n_tokens,
+                                   w.X, M, D, F, flag, stream));
+        return OMNITOK_OK;
+    }
     DIT_RUN(omnitok_dit_ln_modulate(w.X, m, m + D, modN, M, n_tokens, D, w.Xn, stream));
     DIT_RUN(dit_linear(w.Xn, L.wqkv, L.bqkv, w.QKV, M, 3 * D, D, stream));
     DIT_RUN(attn(w.QKV, w.A));

@@ -23,6 +23,7 @@ struct omnitok_latte {
     std::vector<DitBlock> blocks;
     float *w_patch = nullptr, *b_patch = nullptr, *pos = nullptr, *temp = nullptr, *w_t0 = nullptr, *b_t0 = nullptr, *w_t2 = nullptr,
           *b_t2 = nullptr, *ytable = nullptr, *w_mod = nullptr, *b_mod = nullptr, *w_final = nullptr, *b_final = nullptr;
+    DitLinear lin;  // omnitok_latte_set_linear_format
     DitTables tb;
     void *work = nullptr;
     int64_t work_bytes = 0;
@@ -83,6 +84,7 @@ extern "C" void omnitok_latte_destroy(omnitok_latte *e) {
     if (!e) return;
     e->w.free_all();
     e->tb.free_all();
+    e->lin.free_all();
     if (e->work) (void)hipFree(e->work);
     delete e;
 }
@@ -109,6 +111,7 @@ extern "C" int omnitok_latte_finalize(omnitok_latte *e, omnitok_stream_t stream)
     OT_CHECK_ARG(e, "latte_finalize: null engine");
     if (int rc = e->w.require_all("latte")) return rc;
     if (int rc = e->tb.finalize(static_cast<hipStream_t>(stream))) return rc;
+    if (int rc = e->lin.finalize("latte", e->w, e->blocks, e->cfg.hidden, e->cfg.mlp_hidden, static_cast<hipStream_t>(stream))) return rc;
     e->finalized = true;
     return OMNITOK_OK;
 }
@@ -118,7 +121,20 @@ extern "C" int64_t omnitok_latte_workspace_bytes(omnitok_latte *e, int B) {
         set_error("latte_workspace_bytes: null engine or B %d (B * frames * tokens <= 2^24)", B);
         return -1;
     }
-    return dit_work_floats(latte_rows(e, B), B, e->cfg.hidden, e->cfg.mlp_hidden, latte_patch_out(e), e->modN) * 4;
+    return dit_work_floats(latte_rows(e, B), B, e->cfg.hidden, e->cfg.mlp_hidden, latte_patch_out(e), e->modN,
+                           e->lin.fmt != OMNITOK_DIT_LIN_FP32) * 4;
+}
+
+extern "C" int omnitok_latte_set_linear_format(omnitok_latte *e, int fmt) {
+    OT_CHECK_ARG(e, "latte_set_linear_format: null engine");
+    if (int rc = e->lin.set("latte", fmt, e->cfg.hidden, e->cfg.mlp_hidden)) return rc;
+    e->finalized = false;
+    return OMNITOK_OK;
+}
+
+extern "C" int omnitok_latte_linear_format(omnitok_latte *e) {
+    OT_CHECK_ARG(e, "latte_linear_format: null engine");
+    return e->lin.fmt;
 }
 
 static int latte_forward_any(const char *who, omnitok_latte *e, const float *x, const int64_t *t, const int64_t *y, int B, bool cfg,
@@ -136,8 +152,10 @@ static int latte_forward_any(const char *who, omnitok_latte *e, const float *x, 
     const omnitok_latte_config &c = e->cfg;
     const int D = c.hidden, F = c.mlp_hidden, N = e->N, NF = c.num_frames, PC = (int)latte_patch_out(e), BF = B * NF;
     const int64_t M = latte_rows(e, B), modN = e->modN;
-    if (int rc = dit_grow(&e->work, &e->work_bytes, dit_work_floats(M, B, D, F, PC, modN) * 4)) return rc;
-    const DitWork w(e->work, M, B, D, F, PC);
+    const int fmt = e->lin.fmt;
+    const bool lin16 = fmt != OMNITOK_DIT_LIN_FP32;
+    if (int rc = dit_grow(&e->work, &e->work_bytes, dit_work_floats(M, B, D, F, PC, modN, lin16) * 4)) return rc;
+    const DitWork w(e->work, M, B, D, F, PC, lin16);
 #define LATTE_RUN(call) \
     if (int rc_ = (call)) return rc_
     LATTE_RUN(omnitok_dit_patch_embed(x, cfg ? BF / 2 : BF, e->w_patch, e->b_patch, e->pos, BF, c.in_channels, c.input_size, c.patch_size, D,
@@ -146,11 +164,12 @@ static int latte_forward_any(const char *who, omnitok_latte *e, const float *x, 
                                stream));
     for (int i = 0; i < c.depth; i += 2) {
         LATTE_RUN(dit_block(e->blocks[i], w, w.mod + (int64_t)i * 6 * D, modN, M, NF * N, D, F,
-                            [&](const float *qkv, float *a) { return omnitok_dit_attn(qkv, BF, N, c.heads, e->hd, a, stream); }, stream));
+                            [&](const float *qkv, float *a) { return omnitok_dit_attn(qkv, BF, N, c.heads, e->hd, a, stream); }, fmt,
+                            e->tb.flag, stream));
         if (i == 0) LATTE_RUN(omnitok_latte_add_temp_embed(w.X, e->temp, B, NF, N, D, stream));
         LATTE_RUN(dit_block(e->blocks[i + 1], w, w.mod + (int64_t)(i + 1) * 6 * D, modN, M, NF * N, D, F,
                             [&](const float *qkv, float *a) { return omnitok_latte_attn_temporal(qkv, B, NF, N, c.heads, e->hd, a, stream); },
-                            stream));
+                            fmt, e->tb.flag, stream));
     }
     const float *mf = w.mod + (int64_t)c.depth * 6 * D;  // shift | scale
     LATTE_RUN(omnitok_dit_ln_modulate(w.X, mf, mf + D, modN, M, NF * N, D, w.Xn, stream));

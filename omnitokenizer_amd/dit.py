@@ -7,7 +7,9 @@
     eps_sigma = model.forward_with_cfg(x, t, y, cfg_scale=4.0)
 
 The module holds the reference's parameter names, so its checkpoints load unchanged; the forward pass runs on the library's
-engine (fp32 throughout; there is no PyTorch fallback).  Training, label dropout and fractional timesteps are not built.
+engine (fp32 throughout by default; there is no PyTorch fallback).  Training, label dropout and fractional timesteps are not built.
+
+    model.set_linear_format("bf16")     # opt-in: the four linears of every block on the 16-bit MFMA ("fp32" | "bf16" | "fp16")
 """
 from __future__ import annotations
 
@@ -21,6 +23,7 @@ import torch.nn as nn
 from . import _lib
 from ._lib import OmnitokDitConfig, check
 
+LINEAR_FORMATS = {"fp32": 0, "bf16": 1, "fp16": 2}  # OMNITOK_DIT_LIN_* (include/omnitok_dit.h)
 FREQUENCY_EMBEDDING_SIZE = 256  # TimestepEmbedder's default (models.py:31), the only one the reference uses
 
 
@@ -137,12 +140,31 @@ class DiT(nn.Module):
         self.final_layer.adaLN_modulation = _seq(None, _Lin(2 * D, D))
         self._engine = None
         self._engine_sig = None
+        self._linear_format = "fp32"
         nn.Module.train(self, False)
 
     # ---- plumbing ---------------------------------------------------------------------------------
     @property
     def device(self):
         return self.pos_embed.device
+
+    @property
+    def linear_format(self) -> str:
+        """The format of the block linears: "fp32" (the default), "bf16" or "fp16" (set_linear_format)."""
+        return self._linear_format
+
+    def set_linear_format(self, fmt: str):
+        """Runs attn.qkv, attn.proj, mlp.fc1 and mlp.fc2 of every block on the 16-bit MFMA: weights and the linears' inputs rounded
+        once to `fmt`, exact products, fp32 accumulators; everything else stays fp32 (omnitok_dit_set_linear_format).  This is not
+        the reference's use_fp16, which casts the whole module.  Takes effect at the next forward; "fp32" restores the default
+        bit for bit.  Under "fp16" a weight outside the fp16 range fails the next forward and an activation outside it fails
+        check_range()."""
+        if fmt not in LINEAR_FORMATS:
+            raise ValueError(f"linear format {fmt!r}: one of {', '.join(LINEAR_FORMATS)}")
+        if fmt != self._linear_format:
+            self._linear_format = fmt
+            self._engine_sig = None  # the next forward re-finalizes
+        return self
 
     def train(self, mode: bool = True):
         if mode:
@@ -200,6 +222,7 @@ class DiT(nn.Module):
             shape = (ctypes.c_int64 * max(t.dim(), 1))(*t.shape)
             check(self._fn("set_weight")(self._engine, name.encode(), ctypes.c_void_p(t.data_ptr()), shape, t.dim(), stream),
                   f"{api}_set_weight({name})")
+        check(self._fn("set_linear_format")(self._engine, LINEAR_FORMATS[self._linear_format]), f"{api}_set_linear_format")
         check(self._fn("finalize")(self._engine, stream), f"{api}_finalize")
         torch.cuda.current_stream().synchronize()
         self._engine_sig = sig
@@ -236,8 +259,8 @@ class DiT(nn.Module):
         return out
 
     def check_range(self):
-        """Raises ValueError if a forward since the last check saw a timestep outside [0, 1000) or a label outside the embedding
-        table (one int read-back: a host synchronisation)."""
+        """Raises ValueError if a forward since the last check saw a timestep outside [0, 1000), a label outside the embedding
+        table or, under the "fp16" linear format, an activation outside the fp16 range (one int read-back: a host synchronisation)."""
         check(self._fn("check")(self._engine, torch.cuda.current_stream().cuda_stream), f"{self._API}_check")
 
     # ---- the reference's two entry points ------------------------------------------------------------

@@ -9,6 +9,9 @@ classifier-free guidance = 16 streams x 256 tokens = 4096 rows; one step = forwa
   torch_step_ms      the same step through tests/dit_ref.py in fp32 by torch on this GPU (what a user would otherwise run)
   split              each operator alone at the model's shapes through its stand-alone entry point, x its calls per forward; their sum
                      is not the step (no launch gaps, warm caches): it says where the time goes
+  --linear-format    bf16 | fp16: the block linears on the 16-bit MFMA (DiT.set_linear_format).  step_ms is then the 16-bit step and
+                     fp32_step_ms the default format's, timed first in the same session; the split times omnitok_dit_gemm16 per
+                     epilogue and the producers of its packed operands, and block_gemms is held against the 16-bit MFMA peak
   attention          the attention kernel's useful FLOP (4 B heads N^2 hd: both products, the dead 3/4 of head_dim 72's third output
                      block not counted) over its time, as a fraction of the fp32-input MFMA peak
 """
@@ -25,6 +28,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 PEAK_F32_MFMA_TFLOPS = 157.3
+PEAK_16BIT_MFMA_TFLOPS = 2500.0
 
 
 def timed(fn, warmup, steps):
@@ -49,8 +53,10 @@ def main():
     ap.add_argument("--steps", type=int, default=24)
     ap.add_argument("--warmup", type=int, default=4)
     ap.add_argument("--torch-steps", type=int, default=20)
+    ap.add_argument("--linear-format", default="fp32", choices=["fp32", "bf16", "fp16"])
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    lin16 = a.linear_format != "fp32"
     if not torch.cuda.is_available():
         raise SystemExit("dit_bench needs the GPU: there is nothing to measure without it")
     from omnitokenizer_amd import _lib
@@ -90,7 +96,11 @@ def main():
     with torch.no_grad():
         ours, ref = engine_step(), torch_step()
         diff = float((ours - ref).abs().max())
-        step = timed(engine_step, a.warmup, a.steps)
+        step = fp32_step = timed(engine_step, a.warmup, a.steps)
+        if lin16:
+            m.set_linear_format(a.linear_format)
+            diff16 = float((engine_step() - ours).abs().max())
+            step = timed(engine_step, a.warmup, a.steps)
         tstep = timed(torch_step, a.warmup, a.torch_steps)
 
     # ---- the split: each operator alone at the model's shapes -------------------------------------------------------------------
@@ -131,6 +141,31 @@ def main():
         "gemm_final": (1, gemm(X, Wf, OL, M, PC, D)),
         "unpatchify": (1, lambda: lib.omnitok_dit_unpatchify(P(OL.data_ptr()), B, N, m.patch_size, 16, P(img.data_ptr()), st)),
     }
+    if lin16:  # the block's four GEMMs with their epilogues, and the passes that round their A operands
+        code, dt = {"bf16": (1, torch.bfloat16), "fp16": (2, torch.float16)}[a.linear_format]
+        X16, H16, O16 = (buf(M, D) * 0.5).to(dt), (buf(M, F) * 0.5).to(dt), torch.empty(M, F, device="cuda", dtype=dt)
+        W16 = {k: (v * 0.02).to(dt) for k, v in (("qkv", Wqkv), ("proj", Wp), ("fc1", W1), ("fc2", W2))}
+        flag = torch.zeros(1, dtype=torch.int32, device="cuda")
+        gate = P(mod.data_ptr() + 8 * D)
+
+        def gemm16(A, W, epi, y32, y16, Nc, K):
+            gated = epi == 2
+            return lambda: _lib.check(lib.omnitok_dit_gemm16(P(A.data_ptr()), P(W.data_ptr()), code, P(bias.data_ptr()), epi, y32, y16,
+                                                             gate if gated else None, modN if gated else 0, N if gated else 0,
+                                                             P(Y.data_ptr()) if gated else None, M, Nc, K, P(flag.data_ptr()), st))
+
+        for k in ("gemm_qkv", "gemm_proj", "gate_residual", "gemm_fc1", "gelu_tanh", "gemm_fc2"):
+            del ops[k]
+        ops.update({
+            "ln_modulate16": (2 * L, lambda: lib.omnitok_dit_ln_modulate16(P(X.data_ptr()), P(mod.data_ptr()), P(mod.data_ptr() + 4 * D), modN,
+                                                                           M, N, D, code, P(O16.data_ptr()), P(flag.data_ptr()), st)),
+            "round16_attention": (L, lambda: lib.omnitok_dit_round16(P(X.data_ptr()), code, P(O16.data_ptr()), M * D, P(flag.data_ptr()), st)),
+            "gemm16_qkv_bias": (L, gemm16(X16, W16["qkv"], 0, P(O3.data_ptr()), None, 3 * D, D)),
+            "gemm16_proj_gate_residual": (L, gemm16(X16, W16["proj"], 2, None, None, D, D)),
+            "gemm16_fc1_gelu16": (L, gemm16(X16, W16["fc1"], 1, None, P(O16.data_ptr()), F, D)),
+            "gemm16_fc2_gate_residual": (L, gemm16(H16, W16["fc2"], 2, None, None, D, F)),
+        })
+        ops["ln_modulate"] = (1, ops["ln_modulate"][1])  # the final layer's
     split = {}
     for name, (calls, fn) in ops.items():
         def rep(fn=fn):
@@ -142,10 +177,14 @@ def main():
     attn_ms = split["attention"]["ms_per_call"]
     attn_flop = 4.0 * B * H * N * N * hd
     gemm_flop = 2.0 * M * D * (3 * D + D + 2 * F) * L
-    gemm_ms = sum(split[k]["ms_per_forward"] for k in ("gemm_qkv", "gemm_proj", "gemm_fc1", "gemm_fc2"))
+    gemm_ms = sum(v["ms_per_forward"] for k, v in split.items() if k.startswith("gemm16_" if lin16 else ("gemm_qkv", "gemm_proj", "gemm_fc")))
+    peak = PEAK_16BIT_MFMA_TFLOPS if lin16 else PEAK_F32_MFMA_TFLOPS
+    tiles = {k: ((M + 127) // 128) * ((nc + 127) // 128) for k, nc in (("qkv", 3 * D), ("proj", D), ("fc1", F), ("fc2", D))}
     res = {
         "bench": "dit_step", "model": a.model, "input_size": 32, "in_channels": 8, "images": n, "streams": B, "rows": M,
-        "device": torch.cuda.get_device_name(0), "arithmetic": "fp32 (v_mfma_f32_32x32x2_f32 GEMMs and attention)",
+        "device": torch.cuda.get_device_name(0), "linear_format": a.linear_format,
+        "arithmetic": (f"block linears {a.linear_format} operands on v_mfma_f32_32x32x16, fp32 accumulate; everything else fp32" if lin16
+                       else "fp32 (v_mfma_f32_32x32x2_f32 GEMMs and attention)"),
         "step_ms": round(step[0], 4), "step_ms_min_max": [round(step[1], 4), round(step[2], 4)], "steps_timed": a.steps,
         "torch_step_ms": round(tstep[0], 4), "torch_step_ms_min_max": [round(tstep[1], 4), round(tstep[2], 4)],
         "torch_baseline": "tests/dit_ref.py forward_with_cfg + p_sample in fp32 through torch on the same GPU, same session "
@@ -154,10 +193,14 @@ def main():
         "split": split, "split_sum_ms": round(sum(v["ms_per_forward"] for v in split.values()), 4),
         "attention": {"useful_flop": attn_flop, "tflops": round(attn_flop / (attn_ms * 1e-3) / 1e12, 2),
                       "frac_of_f32_mfma_peak": round(attn_flop / (attn_ms * 1e-3) / 1e12 / PEAK_F32_MFMA_TFLOPS, 4)},
-        "block_gemms": {"flop": gemm_flop, "tflops": round(gemm_flop / (gemm_ms * 1e-3) / 1e12, 2),
-                        "frac_of_f32_mfma_peak": round(gemm_flop / (gemm_ms * 1e-3) / 1e12 / PEAK_F32_MFMA_TFLOPS, 4)},
+        "block_gemms": {"flop": gemm_flop, "ms_per_forward": round(gemm_ms, 4), "tflops": round(gemm_flop / (gemm_ms * 1e-3) / 1e12, 2),
+                        ("frac_of_16bit_mfma_peak" if lin16 else "frac_of_f32_mfma_peak"): round(gemm_flop / (gemm_ms * 1e-3) / 1e12 / peak, 4)},
         "peak_f32_mfma_tflops": PEAK_F32_MFMA_TFLOPS,
     }
+    if lin16:
+        res.update({"fp32_step_ms": round(fp32_step[0], 4), "fp32_step_ms_min_max": [round(fp32_step[1], 4), round(fp32_step[2], 4)],
+                    "speedup_over_fp32_step": round(fp32_step[0] / step[0], 3), "max_abs_diff_to_fp32_step": diff16,
+                    "peak_16bit_mfma_tflops": PEAK_16BIT_MFMA_TFLOPS, "gemm16_tiles_128x128": tiles, "compute_units": 256})
     line = json.dumps(res)
     print(line)
     if a.out:

@@ -9,6 +9,8 @@ Two shapes, seeded random weights, B = 2 (one video and its null-class twin), 25
 Reported per shape:
   step_ms         median of the timed steps after warm-up, device events around each; one step = forward_with_cfg + the p_sample
                   update over the B F frames
+  --linear-format bf16 | fp16: the block linears of both kinds of block on the 16-bit MFMA (Latte.set_linear_format); step_ms is then
+                  the 16-bit step and fp32_step_ms the default format's, timed first in the same session on the same model
   temporal_attn   omnitok_latte_attn_temporal alone at the model's shape (qkv [B F N, 3 D] in (b f) n order): median ms per call
                   over batches of calls, and the achieved bytes/s against ONE read of qkv plus ONE write of out
   rearranged      what the kernel replaces: the copy '(b f) n d -> (b n) f d' of qkv, omnitok_dit_attn with N = F on it, and the copy
@@ -84,7 +86,13 @@ def bench_shape(name, spec, a, lib):
     with torch.no_grad():
         assert torch.isfinite(step()).all()
         m.check_range()
-        step_ms = timed(step, a.warmup, a.steps)
+        step_ms = fp32_ms = timed(step, a.warmup, a.steps)
+        if a.linear_format != "fp32":
+            ref = step()
+            m.set_linear_format(a.linear_format)
+            diff16 = float((step() - ref).abs().max())
+            m.check_range()
+            step_ms = timed(step, a.warmup, a.steps)
 
     # ---- the temporal attention alone, and the rearranging alternative ------------------------------------------------------------
     D, heads, N = m.hidden_size, m.num_heads, (32 // m.patch_size) ** 2
@@ -119,7 +127,11 @@ def bench_shape(name, spec, a, lib):
     res_re = per_call(rearranged, calls, 2, a.steps)
     parts = {k: per_call(f, calls, 2, a.steps)[0] for k, f in (("copy_in", copy_in), ("dit_attn_N_eq_F", tiled), ("copy_out", copy_out))}
     nbytes = rows * 4 * D * 4   # one read of qkv [rows, 3 D] + one write of out [rows, D], fp32
+    extra = {} if a.linear_format == "fp32" else {
+        "fp32_step_ms": round(fp32_ms[0], 4), "fp32_step_ms_min_max": [round(fp32_ms[1], 4), round(fp32_ms[2], 4)],
+        "speedup_over_fp32_step": round(fp32_ms[0] / step_ms[0], 3), "max_abs_diff_to_fp32_step": diff16}
     return {
+        **extra, "linear_format": a.linear_format,
         "model": spec["model"], "B": B, "frames": F, "tokens": N, "in_channels": C, "rows": rows, "hidden": D, "heads": heads,
         "head_dim": hd, "step_ms": round(step_ms[0], 4), "step_ms_min_max": [round(step_ms[1], 4), round(step_ms[2], 4)],
         "steps_timed": a.steps,
@@ -138,6 +150,7 @@ def main():
     ap.add_argument("--steps", type=int, default=15)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--calls", type=int, default=50, help="kernel calls per timed batch")
+    ap.add_argument("--linear-format", default="fp32", choices=["fp32", "bf16", "fp16"])
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -153,7 +166,9 @@ def main():
     torch.cuda.synchronize()
     del x
     files, hw = gpu_power.pick_hwmon(idle, busy, pci=gpu_power.pci_address(torch.cuda.current_device()))
-    res = {"bench": "latte_step", "device": torch.cuda.get_device_name(0), "arithmetic": "fp32", "shapes": {}}
+    res = {"bench": "latte_step", "device": torch.cuda.get_device_name(0), "shapes": {},
+           "arithmetic": "fp32" if a.linear_format == "fp32" else
+           f"block linears {a.linear_format} operands on v_mfma_f32_32x32x16, fp32 accumulate; everything else fp32"}
     for name in a.shapes.split(","):
         smp = gpu_power.Sampler(files) if files else None
         if smp:
