@@ -9,7 +9,8 @@
  * Same conventions as omnitok_lm.h: device pointers, fp32 (timesteps and labels int64), row-major, every launch on the given
  * stream, 0 = OK, argument errors are returned before any HIP call, omnitok_last_error holds the message.
  *
- * Arithmetic is fp32 throughout (the default; omnitok_dit_set_linear_format below opts the block linears into 16-bit operands):
+ * Arithmetic is fp32 throughout (the default; omnitok_dit_set_linear_format below opts the block linears into 16-bit operands,
+ * omnitok_dit_set_attention_format the attention):
  * the linears run on the fp32-in row GEMM of omnitok.h (fp32 accumulate on v_mfma_f32_32x32x2_f32), the
  * attention on the same instruction, everything else on the VALU.  Results do not depend on the batch: sample i of a call
  * with B samples has the bits of a call with that sample alone.
@@ -76,7 +77,8 @@ int omnitok_dit_forward(omnitok_dit *e, const float *x, const int64_t *t, const 
 int omnitok_dit_forward_cfg(omnitok_dit *e, const float *x, const int64_t *t, const int64_t *y, int B, float cfg_scale,
                             float *out, omnitok_stream_t stream);
 /* Synchronises the stream and reads the range bits of the forwards since the last check: OMNITOK_ERR_INVALID with the reason
- * (t outside [0, 1000) / y outside [0, table rows)), else 0.  Clears the bits. */
+ * (t outside [0, 1000) / y outside [0, table rows) / under an fp16 linear or attention format a value outside the fp16 range), else 0.
+ * Clears the bits. */
 int omnitok_dit_check(omnitok_dit *e, omnitok_stream_t stream);
 
 /* ---- opt-in 16-bit block linears ------------------------------------------------------------------------------------ */
@@ -88,14 +90,30 @@ int omnitok_dit_check(omnitok_dit *e, omnitok_stream_t stream);
  * tensor.to(torch.bfloat16 / torch.float16)) -- the weights at the next finalize into a packed image beside the fp32 originals
  * (weight memory 1.5 x; switching back needs a finalize only), the activations where they are produced (the modulated LayerNorm rows,
  * the attention output, the GELU output) -- products exact, accumulators fp32.  Everything else stays fp32: the patch embedding, the
- * conditioning, the adaLN GEMM, the final layer, every bias, the residual stream, LayerNorm statistics and modulation, attention,
- * guidance, unpatchify, p_sample.  Batch invariance holds as before.
+ * conditioning, the adaLN GEMM, the final layer, every bias, the residual stream, LayerNorm statistics and modulation, attention
+ * (its own switch: omnitok_dit_set_attention_format), guidance, unpatchify, p_sample.  Batch invariance holds as before.
  * -1 before any HIP call for a null engine, an unknown format or sizes the 16-bit GEMM cannot take (hidden and mlp_hidden must be
  * multiples of 32); a refused value changes nothing.  Setting a format clears `finalized`.  fp16: a weight that rounds to +-inf makes
  * finalize fail with OMNITOK_ERR_INVALID naming the tensor (set another format and finalize again); an activation that does raises a
  * bit that omnitok_dit_check reports ("fp16"). */
 int omnitok_dit_set_linear_format(omnitok_dit *e, int fmt);
 int omnitok_dit_linear_format(omnitok_dit *e); /* -1: null engine */
+
+/* ---- opt-in 16-bit attention operands -------------------------------------------------------------------------------- */
+/* The OMNITOK_DIT_LIN_* values under a second name: one set of format codes, so that omnitok_dit_attn16 can write the packed
+ * operand of attn.proj in the linear format without a translation. */
+#define OMNITOK_DIT_ATTN_FP32 OMNITOK_DIT_LIN_FP32 /* the default: omnitok_dit_attn */
+#define OMNITOK_DIT_ATTN_BF16 OMNITOK_DIT_LIN_BF16
+#define OMNITOK_DIT_ATTN_FP16 OMNITOK_DIT_LIN_FP16
+/* The format of the operands of every block's attention.  Under a 16-bit format it runs on omnitok_dit_attn16 (below: the arithmetic
+ * contract and the fp16 range rules).  Independent of the linear format: all nine combinations are legal.  Where both are 16-bit the
+ * attention writes the packed operand of attn.proj itself, in the linear format, and the omnitok_dit_round16 pass behind it is not
+ * launched; its bits are those of that pass over the fp32 result.  With OMNITOK_DIT_ATTN_FP32 every launch is as before.
+ * -1 before any HIP call for a null engine or an unknown format; a refused value changes nothing.  No weight image depends on the
+ * format, so setting it does NOT clear `finalized`: it takes effect at the next forward.  fp16: a q, k or v that rounds from a finite
+ * value to +-inf raises a bit that omnitok_dit_check reports ("attention format fp16"). */
+int omnitok_dit_set_attention_format(omnitok_dit *e, int fmt);
+int omnitok_dit_attention_format(omnitok_dit *e); /* -1: null engine */
 
 /* ---- the operators of the forward, each usable without an engine ---------------------------------------------------- */
 
@@ -110,6 +128,25 @@ int omnitok_dit_ln_modulate(const float *x, const float *shift, const float *sca
 /* Non-causal attention over [B, heads, N, hd] read straight from the qkv rows [B*N, 3*heads*hd] (timm's
  * reshape(B, N, 3, heads, hd)), scale hd^-0.5, hd 64 or 72 -> out [B*N, heads*hd]. */
 int omnitok_dit_attn(const float *qkv, int B, int N, int heads, int head_dim, float *out, omnitok_stream_t stream);
+/* omnitok_dit_attn with Q . K^T and P . V on v_mfma_f32_32x32x16_{bf16,f16}: op_fmt OMNITOK_DIT_LIN_BF16 | _FP16; the result goes to
+ * exactly one of out32 [B*N, heads*hd] (fp32) and out16 (the same, rounded once more to out_fmt, a 16-bit format, and packed).
+ *   - Q, K, V are each rounded ONCE to op_fmt, to nearest even (the bits of tensor.to(dtype)), where the kernel stages them: there
+ *     is no packed copy of qkv and no workspace.
+ *   - Products are exact.  A score is accumulated in fp32 and the finished dot multiplied by fl(log2(e) / sqrt(hd)), one constant
+ *     rounded once from fp64: hd^-0.5 with the exponential's base change folded in.  At hd 72 the last half k-step multiplies zeros,
+ *     never what lies behind column 71.
+ *   - Online softmax over key tiles of 32, ascending; max, sum and rescale in fp32; the weights are v_exp_f32 of the base-2 score
+ *     differences; l sums the weights BEFORE their rounding; P is rounded once to op_fmt on its way into P . V; O is accumulated in
+ *     fp32; out = O / l, one division.
+ *   - No atomics on the result, no split over keys, no partials.
+ *   - Row (b, t) depends on rows b*N .. b*N + N - 1 of qkv only: not on B or on another sample.
+ * flag (an int on the device, may be NULL): op_fmt fp16, a FINITE element of Q, K or V that rounds to +-inf ORs 8 into it; out_fmt
+ * fp16, an output that rounds from a finite value to +-inf ORs 4, so out16 is bit for bit omnitok_dit_round16 of the out32 result, the
+ * flag included.  bf16 sets neither.
+ * -1 before any HIP call: null or non-16-byte-aligned pointers, both or neither output, op_fmt / out_fmt (with out16) not a 16-bit
+ * format, head_dim not 64 | 72, sizes outside omnitok_dit_attn's. */
+int omnitok_dit_attn16(const float *qkv, int B, int N, int heads, int head_dim, int op_fmt, float *out32, void *out16, int out_fmt,
+                       int *flag, omnitok_stream_t stream);
 /* x[r,:] += gate[b,:] * y[r,:], b = r / n_tokens; gate rows are ld_gate floats apart.  D % 4 == 0. */
 int omnitok_dit_gate_residual(float *x, const float *y, const float *gate, int64_t ld_gate, int64_t rows, int n_tokens, int D,
                               omnitok_stream_t stream);

@@ -65,7 +65,8 @@ int omnitok_latte_forward(omnitok_latte *e, const float *x, const int64_t *t, co
 int omnitok_latte_forward_cfg(omnitok_latte *e, const float *x, const int64_t *t, const int64_t *y, int B, float cfg_scale,
                               float *out, omnitok_stream_t stream);
 int omnitok_latte_check(omnitok_latte *e, omnitok_stream_t stream);
-/* The opt-in 16-bit block linears of omnitok_dit.h under this engine's name: declared in omnitok_latte_linear.h, included below. */
+/* The opt-in 16-bit block linears of omnitok_dit.h under this engine's name: declared in omnitok_latte_linear.h, included below.
+ * The opt-in 16-bit operands of the spatial attention likewise: omnitok_latte_attention.h. */
 
 /* ---- the operators Latte adds to those of omnitok_dit.h, each usable without an engine -------------------------------- */
 
@@ -85,5 +86,6 @@ int omnitok_latte_cfg_blend(float *out, int images, int Cout, int channels, int6
 #endif
 
 #include "omnitok_latte_linear.h"
+#include "omnitok_latte_attention.h"
 
 #endif /* OMNITOK_LATTE_H */

@@ -1,8 +1,9 @@
 /* omnitok_latte_linear.h -- the linear format of the Latte engine; part of omnitok_latte.h, which includes it.
  *
  * The DiT engine's switch (OMNITOK_DIT_LIN_FP32 | _BF16 | _FP16, omnitok_dit.h: what is rounded and where, what stays fp32, the
- * return values, the fp16 range rules) under this engine's name.  It covers the four linears of BOTH kinds of block; the spatial
- * and the temporal attention stay fp32 and their output is rounded once in front of attn.proj.
+ * return values, the fp16 range rules) under this engine's name.  It covers the four linears of BOTH kinds of block; under the
+ * default attention format the spatial and the temporal attention stay fp32 and their output is rounded once in front of attn.proj.
+ * (omnitok_latte_attention.h: the attention format, under which the spatial attention writes that operand itself.)
  */
 #ifndef OMNITOK_LATTE_LINEAR_H
 #define OMNITOK_LATTE_LINEAR_H

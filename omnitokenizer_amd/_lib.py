@@ -312,9 +312,12 @@ _DIT_PROTOS = {
     "omnitok_dit_check": [P, P],
     "omnitok_dit_set_linear_format": [P, c_int],
     "omnitok_dit_linear_format": [P],
+    "omnitok_dit_set_attention_format": [P, c_int],
+    "omnitok_dit_attention_format": [P],
     "omnitok_dit_patch_embed": [P, c_int, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P],
     "omnitok_dit_ln_modulate": [P, P, P, I64, I64, c_int, c_int, P, P],
     "omnitok_dit_attn": [P, c_int, c_int, c_int, c_int, P, P],
+    "omnitok_dit_attn16": [P, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P, P],
     "omnitok_dit_gate_residual": [P, P, P, I64, I64, c_int, c_int, P],
     "omnitok_dit_gelu_tanh": [P, I64, P],
     "omnitok_dit_ln_modulate16": [P, P, P, I64, I64, c_int, c_int, c_int, P, P, P],
@@ -352,6 +355,13 @@ _LATTE_LINEAR_PROTOS = {
 }
 LATTE_LINEAR_EXPORTED_SYMBOLS = tuple(_LATTE_LINEAR_PROTOS)
 
+# include/omnitok_latte_attention.h (the part of omnitok_latte.h that holds the engine's attention format)
+_LATTE_ATTENTION_PROTOS = {
+    "omnitok_latte_set_attention_format": [P, c_int],
+    "omnitok_latte_attention_format": [P],
+}
+LATTE_ATTENTION_EXPORTED_SYMBOLS = tuple(_LATTE_ATTENTION_PROTOS)
+
 _lib = None
 
 
@@ -371,7 +381,7 @@ def load():
     # matter what the caller imported before.
     import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
-    for name, argtypes in {**_PROTOS, **_DIT_PROTOS, **_LATTE_PROTOS, **_LATTE_LINEAR_PROTOS}.items():
+    for name, argtypes in {**_PROTOS, **_DIT_PROTOS, **_LATTE_PROTOS, **_LATTE_LINEAR_PROTOS, **_LATTE_ATTENTION_PROTOS}.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch: fail loudly
         fn.argtypes = argtypes
         fn.restype = _RESTYPES.get(name, c_int)

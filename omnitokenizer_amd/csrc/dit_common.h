@@ -6,8 +6,11 @@
 //   dit_common.h   the constants the units share and the flag bits of the engine's range word
 //   dit_ops.hip    the small kernels: patch_embed (+ pos_embed), the conditioning's gather / SiLU passes, ln_modulate, gelu_tanh,
 //                  gate_residual, unpatchify, the classifier-free-guidance blend and p_sample, with their exported entry points
-//   dit_attn.hip   dit_attn_kernel: non-causal attention on v_mfma_f32_32x32x2_f32, head_dim 64 and 72 (omnitok_dit_attn)
+//   dit_attn.hip   dit_attn_kernel: non-causal attention on v_mfma_f32_32x32x2_f32, head_dim 64 and 72 (omnitok_dit_attn);
+//                  dit_attn16_kernel: the same with bf16 / fp16 operands on v_mfma_f32_32x32x16_{bf16,f16}, fp32 or packed 16-bit output
+//                  (omnitok_dit_attn16; the engines' attention format, omnitok_dit_set_attention_format)
 //   attn_f32_tiled.h  (not the DiT's alone) the body of dit_attn_kernel, shared with the LM's tiled causal prefill attention
+//   attn16_tiled.h    the body of dit_attn16_kernel, and the pa16_* helpers it shares with the LM's 16-bit prefill attention
 //   dit_gemm16.hip dit_gemm16_kernel: the block linears of a 16-bit linear format (omnitok_dit_set_linear_format) on
 //                  v_mfma_f32_32x32x16_{bf16,f16}, the K loop of csrc/gemm16_tile.h with the DiT's three epilogues (omnitok_dit_gemm16)
 //   dit_engine.hip struct omnitok_dit and its exported functions (create .. finalize, forward, forward_cfg)
@@ -15,7 +18,8 @@
 //                  with the Latte video denoiser (latte_engine.hip, index: latte_common.h)
 // The linears (qkv, proj, fc1, fc2, the conditioning MLP, the modulation GEMM and the final linear) are omnitok_gemm calls; under a
 // 16-bit linear format the four of a block are omnitok_dit_gemm16 calls on operands rounded once where they are produced
-// (omnitok_dit_ln_modulate16, omnitok_dit_round16 behind the attention, the fc1 epilogue).
+// (omnitok_dit_ln_modulate16, omnitok_dit_round16 behind the attention, the fc1 epilogue).  Under a 16-bit attention format the
+// spatial attention is omnitok_dit_attn16; with both it writes the packed operand of attn.proj itself and the round16 pass is not run.
 #pragma once
 #include "common.h"
 #include "lm_common.h"  // lm_bf16, lm_fp16, lm_round16: the 16-bit element types and their one conversion
@@ -28,6 +32,7 @@ constexpr int DIT_T_FREQ = 256;    // frequency_embedding_size of TimestepEmbedd
 constexpr int DIT_FLAG_T_RANGE = 1;  // bits of the engine's range word (omnitok_dit_check)
 constexpr int DIT_FLAG_Y_RANGE = 2;
 constexpr int DIT_FLAG_F16_RANGE = 4;  // an activation of an fp16 linear format rounded from a finite value to +-inf
+constexpr int DIT_FLAG_ATTN16_RANGE = 8;  // a q, k or v of an fp16 attention format rounded from a finite value to +-inf
 
 #ifdef __HIPCC__
 // nn.GELU(approximate="tanh"): 0.5 x (1 + tanh(sqrt(2 / pi) (x + 0.044715 x^3))) -- dit_gelu_tanh_kernel and the fc1 epilogue of

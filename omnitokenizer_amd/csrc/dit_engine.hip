@@ -10,6 +10,7 @@
 //   ln_modulate -> final linear -> unpatchify                       -> out [B, Cout, H, W]
 // Every GEMM is omnitok_gemm with OMNITOK_GEMM_BIAS.  Under a 16-bit linear format (omnitok_dit_set_linear_format, DitLinear in
 // dit_scaffold.h) the four GEMMs of a block are omnitok_dit_gemm16 calls with gate_residual and GELU in their epilogues (dit_block).
+// Under a 16-bit attention format (omnitok_dit_set_attention_format) the attention is omnitok_dit_attn16 (dit_spatial_attn).
 #include "dit_scaffold.h"
 
 using namespace omnitok;
@@ -23,6 +24,7 @@ struct omnitok_dit {
     float *w_patch = nullptr, *b_patch = nullptr, *pos = nullptr, *w_t0 = nullptr, *b_t0 = nullptr, *w_t2 = nullptr, *b_t2 = nullptr,
           *ytable = nullptr, *w_mod = nullptr, *b_mod = nullptr, *w_final = nullptr, *b_final = nullptr;
     DitLinear lin;  // omnitok_dit_set_linear_format
+    int attn_fmt = OMNITOK_DIT_ATTN_FP32;  // omnitok_dit_set_attention_format
     DitTables tb;  // omnitok_dit_set_frequencies; no frequencies: the built-in chain
     void *work = nullptr;
     int64_t work_bytes = 0;
@@ -157,6 +159,16 @@ extern "C" int omnitok_dit_linear_format(omnitok_dit *e) {
     return e->lin.fmt;
 }
 
+extern "C" int omnitok_dit_set_attention_format(omnitok_dit *e, int fmt) {
+    OT_CHECK_ARG(e, "dit_set_attention_format: null engine");
+    return dit_set_attention_format("dit", &e->attn_fmt, fmt);
+}
+
+extern "C" int omnitok_dit_attention_format(omnitok_dit *e) {
+    OT_CHECK_ARG(e, "dit_attention_format: null engine");
+    return e->attn_fmt;
+}
+
 static int dit_forward_any(const char *who, omnitok_dit *e, const float *x, const int64_t *t, const int64_t *y, int B, bool cfg,
                            float cfg_scale, float *out, hipStream_t stream) {
     OT_CHECK_ARG(e && x && t && y && out, "%s: null pointer", who);
@@ -173,6 +185,7 @@ static int dit_forward_any(const char *who, omnitok_dit *e, const float *x, cons
     const int64_t M = (int64_t)B * N, modN = e->modN;
     const int fmt = e->lin.fmt;
     const bool lin16 = fmt != OMNITOK_DIT_LIN_FP32;
+    const int afmt = e->attn_fmt;
     if (int rc = dit_grow(&e->work, &e->work_bytes, dit_work_floats(M, B, D, F, PC, modN, lin16) * 4)) return rc;
     const DitWork w(e->work, M, B, D, F, PC, lin16);
 #define DIT_RUN(call) \
@@ -183,8 +196,10 @@ static int dit_forward_any(const char *who, omnitok_dit *e, const float *x, cons
                              stream));
     for (int i = 0; i < c.depth; ++i)
         DIT_RUN(dit_block(e->blocks[i], w, w.mod + (int64_t)i * 6 * D, modN, M, N, D, F,
-                          [&](const float *qkv, float *a) { return omnitok_dit_attn(qkv, B, N, c.heads, e->hd, a, stream); }, fmt,
-                          e->tb.flag, stream));
+                          [&](const float *qkv, float *a32, unsigned short *a16) {
+                              return dit_spatial_attn(qkv, B, N, c.heads, e->hd, afmt, fmt, a32, a16, e->tb.flag, stream);
+                          },
+                          afmt != OMNITOK_DIT_ATTN_FP32, fmt, e->tb.flag, stream));
     const float *mf = w.mod + (int64_t)c.depth * 6 * D;  // shift | scale
     DIT_RUN(omnitok_dit_ln_modulate(w.X, mf, mf + D, modN, M, N, D, w.Xn, stream));
     DIT_RUN(dit_linear(w.Xn, e->w_final, e->b_final, w.LIN, M, PC, D, stream));

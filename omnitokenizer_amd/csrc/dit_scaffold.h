@@ -158,11 +158,15 @@ struct DitTables {
         OT_HIP(hipStreamSynchronize(stream));
         if (!bits) return OMNITOK_OK;
         if (int rc = device_fill_u32(flag, 0, 1, stream)) return rc;
-        const bool ty = bits & (DIT_FLAG_T_RANGE | DIT_FLAG_Y_RANGE);
-        set_error("%s_forward: %s%s%s%s%s", who, bits & DIT_FLAG_T_RANGE ? "a timestep outside [0, 1000)" : "",
-                  (bits & DIT_FLAG_T_RANGE) && (bits & DIT_FLAG_Y_RANGE) ? " and " : "",
-                  bits & DIT_FLAG_Y_RANGE ? "a label outside the embedding table" : "", ty && (bits & DIT_FLAG_F16_RANGE) ? " and " : "",
-                  bits & DIT_FLAG_F16_RANGE ? "an activation outside the fp16 range (linear format fp16: use bf16 or fp32)" : "");
+        static const struct { int bit; const char *what; } clauses[] = {
+            {DIT_FLAG_T_RANGE, "a timestep outside [0, 1000)"},
+            {DIT_FLAG_Y_RANGE, "a label outside the embedding table"},
+            {DIT_FLAG_F16_RANGE, "an activation outside the fp16 range (linear format fp16: use bf16 or fp32)"},
+            {DIT_FLAG_ATTN16_RANGE, "a q, k or v outside the fp16 range (attention format fp16: use bf16 or fp32)"}};
+        std::string msg;
+        for (const auto &c : clauses)
+            if (bits & c.bit) msg += (msg.empty() ? "" : " and ") + std::string(c.what);
+        set_error("%s_forward: %s", who, msg.c_str());
         return OMNITOK_ERR_INVALID;
     }
 
@@ -290,21 +294,46 @@ struct DitWork {
     }
 };
 
+// The attention format of an engine (omnitok_dit_set_attention_format): the operands of the SPATIAL attention.  No weight image
+// depends on it, so setting it does not touch `finalized`.
+inline int dit_set_attention_format(const char *who, int *afmt, int f) {
+    OT_CHECK_ARG(f == OMNITOK_DIT_ATTN_FP32 || f == OMNITOK_DIT_ATTN_BF16 || f == OMNITOK_DIT_ATTN_FP16,
+                 "%s_set_attention_format: format %d (OMNITOK_DIT_ATTN_FP32 | _BF16 | _FP16)", who, f);
+    *afmt = f;
+    return OMNITOK_OK;
+}
+
+// The spatial attention of both engines over B sequences of N tokens, the callback dit_block takes: attention format fp32 is
+// omnitok_dit_attn (a16 is never asked for: attn_packs is false); a 16-bit one omnitok_dit_attn16 into a32, or into a16 packed in
+// the linear format lin_fmt.
+inline int dit_spatial_attn(const float *qkv, int B, int N, int heads, int hd, int afmt, int lin_fmt, float *a32, unsigned short *a16,
+                            int *flag, hipStream_t stream) {
+    if (afmt == OMNITOK_DIT_ATTN_FP32) return omnitok_dit_attn(qkv, B, N, heads, hd, a32, stream);
+    return omnitok_dit_attn16(qkv, B, N, heads, hd, afmt, a32, a16, lin_fmt, flag, stream);
+}
+
 // One transformer block in place on X [M, D] (M rows, n_tokens of them per sample), m = the block's 6 D modulation columns of `mod`
-// (shift_msa | scale_msa | gate_msa | shift_mlp | scale_mlp | gate_mlp, rows modN apart); attn(QKV, A) is the caller's attention.
+// (shift_msa | scale_msa | gate_msa | shift_mlp | scale_mlp | gate_mlp, rows modN apart); attn(QKV, a32, a16) is the caller's attention
+// into exactly one of a32 (fp32) / a16 (packed in fmt).
 // fmt: the engine's linear format; under a 16-bit one the four linears are omnitok_dit_gemm16 calls on the packed images L.w16*, each
 // A operand rounded once where it is produced, gate_residual and GELU inside the epilogues; `flag` is the engine's range word.
+// attn_packs (read under a 16-bit fmt only): the attention writes the packed A16 itself (dit_spatial_attn under a 16-bit attention
+// format); else it writes fp32 and omnitok_dit_round16 runs behind it.
 template <typename Attn>
 inline int dit_block(const DitBlock &L, const DitWork &w, const float *m, int64_t modN, int64_t M, int n_tokens, int D, int F, Attn attn,
-                     int fmt, int *flag, hipStream_t stream) {
+                     bool attn_packs, int fmt, int *flag, hipStream_t stream) {
 #define DIT_RUN(call) \
     if (int rc_ = (call)) return rc_
     if (fmt != OMNITOK_DIT_LIN_FP32) {
         DIT_RUN(omnitok_dit_ln_modulate16(w.X, m, m + D, modN, M, n_tokens, D, fmt, w.Xn16, flag, stream));
         DIT_RUN(omnitok_dit_gemm16(w.Xn16, L.w16qkv, fmt, L.bqkv, OMNITOK_DIT_EPI_BIAS, w.QKV, nullptr, nullptr, 0, 0, nullptr, M, 3 * D, D,
                                    flag, stream));
-        DIT_RUN(attn(w.QKV, w.A));
-        DIT_RUN(omnitok_dit_round16(w.A, fmt, w.A16, M * D, flag, stream));
+        if (attn_packs) {
+            DIT_RUN(attn(w.QKV, nullptr, w.A16));
+        } else {
+            DIT_RUN(attn(w.QKV, w.A, nullptr));
+            DIT_RUN(omnitok_dit_round16(w.A, fmt, w.A16, M * D, flag, stream));
+        }
         DIT_RUN(omnitok_dit_gemm16(w.A16, L.w16proj, fmt, L.bproj, OMNITOK_DIT_EPI_GATE_RESIDUAL, nullptr, nullptr, m + 2 * D, modN,
                                    n_tokens, w.X, M, D, D, flag, stream));
         DIT_RUN(omnitok_dit_ln_modulate16(w.X, m + 3 * D, m + 4 * D, modN, M, n_tokens, D, fmt, w.Xn16, flag, stream));
@@ -316,7 +345,7 @@ inline int dit_block(const DitBlock &L, const DitWork &w, const float *m, int64_
     }
     DIT_RUN(omnitok_dit_ln_modulate(w.X, m, m + D, modN, M, n_tokens, D, w.Xn, stream));
     DIT_RUN(dit_linear(w.Xn, L.wqkv, L.bqkv, w.QKV, M, 3 * D, D, stream));
-    DIT_RUN(attn(w.QKV, w.A));
+    DIT_RUN(attn(w.QKV, w.A, nullptr));
     DIT_RUN(dit_linear(w.A, L.wproj, L.bproj, w.Y, M, D, D, stream));
     DIT_RUN(omnitok_dit_gate_residual(w.X, w.Y, m + 2 * D, modN, M, n_tokens, D, stream));
     DIT_RUN(omnitok_dit_ln_modulate(w.X, m + 3 * D, m + 4 * D, modN, M, n_tokens, D, w.Xn, stream));

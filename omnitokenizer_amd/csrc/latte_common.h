@@ -7,7 +7,8 @@
 //   latte_attn.hip    latte_attn_temporal_kernel: attention over the F <= 32 frames of every (sample, position, head), read from
 //                     and written to rows N apart -- nothing is rearranged (omnitok_latte_attn_temporal)
 //   latte_ops.hip     the temp_embed add and the exported form of the guidance blend with a channel count
-//   latte_engine.hip  struct omnitok_latte and its exported functions (create .. finalize, forward, forward_cfg)
+//   latte_engine.hip  struct omnitok_latte and its exported functions (create .. finalize, forward, forward_cfg, the linear format
+//                     and the attention format: the latter covers the spatial blocks only, the temporal attention stays fp32)
 // Everything else is the DiT's (index: dit_common.h): its operators serve both kinds of block with n_tokens = F N rows per sample,
 // its spatial attention runs over B F "samples" of N tokens, and dit_scaffold.h is the host-side scaffold of both engines.
 #pragma once

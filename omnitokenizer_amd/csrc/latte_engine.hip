@@ -6,7 +6,7 @@
 //                                                                        spatial blocks and per position for the temporal ones: the
 //                                                                        same row of c for every row of sample b, so n_tokens = F N)
 //   ONE GEMM over the concatenated adaLN_modulation.1 weights          -> mod [B, depth * 6 D + 2 D]
-//   per pair: the DiT block with omnitok_dit_attn over B F sequences of N tokens; after the FIRST pair's spatial block the temp_embed
+//   per pair: the DiT block with omnitok_dit_attn (omnitok_dit_attn16 under a 16-bit attention format) over B F sequences of N tokens; after the FIRST pair's spatial block the temp_embed
 //             add; the DiT block with omnitok_latte_attn_temporal over the B N positions' F frames.  Nothing is rearranged.
 //   ln_modulate -> final linear -> unpatchify of B F images             -> out [B, F, Cout, H, W]
 // forward_cfg (latte.py:384-403): patch_embed reads the first B / 2 samples twice; the blend guides channels [0, 4) of every frame.
@@ -24,6 +24,7 @@ struct omnitok_latte {
     float *w_patch = nullptr, *b_patch = nullptr, *pos = nullptr, *temp = nullptr, *w_t0 = nullptr, *b_t0 = nullptr, *w_t2 = nullptr,
           *b_t2 = nullptr, *ytable = nullptr, *w_mod = nullptr, *b_mod = nullptr, *w_final = nullptr, *b_final = nullptr;
     DitLinear lin;  // omnitok_latte_set_linear_format
+    int attn_fmt = OMNITOK_DIT_ATTN_FP32;  // omnitok_latte_set_attention_format: the spatial blocks' attention
     DitTables tb;
     void *work = nullptr;
     int64_t work_bytes = 0;
@@ -137,6 +138,16 @@ extern "C" int omnitok_latte_linear_format(omnitok_latte *e) {
     return e->lin.fmt;
 }
 
+extern "C" int omnitok_latte_set_attention_format(omnitok_latte *e, int fmt) {
+    OT_CHECK_ARG(e, "latte_set_attention_format: null engine");
+    return dit_set_attention_format("latte", &e->attn_fmt, fmt);
+}
+
+extern "C" int omnitok_latte_attention_format(omnitok_latte *e) {
+    OT_CHECK_ARG(e, "latte_attention_format: null engine");
+    return e->attn_fmt;
+}
+
 static int latte_forward_any(const char *who, omnitok_latte *e, const float *x, const int64_t *t, const int64_t *y, int B, bool cfg,
                              float cfg_scale, float *out, hipStream_t stream) {
     OT_CHECK_ARG(e && x && t && out, "%s: null pointer", who);
@@ -154,6 +165,7 @@ static int latte_forward_any(const char *who, omnitok_latte *e, const float *x, 
     const int64_t M = latte_rows(e, B), modN = e->modN;
     const int fmt = e->lin.fmt;
     const bool lin16 = fmt != OMNITOK_DIT_LIN_FP32;
+    const int afmt = e->attn_fmt;
     if (int rc = dit_grow(&e->work, &e->work_bytes, dit_work_floats(M, B, D, F, PC, modN, lin16) * 4)) return rc;
     const DitWork w(e->work, M, B, D, F, PC, lin16);
 #define LATTE_RUN(call) \
@@ -164,12 +176,16 @@ static int latte_forward_any(const char *who, omnitok_latte *e, const float *x, 
                                stream));
     for (int i = 0; i < c.depth; i += 2) {
         LATTE_RUN(dit_block(e->blocks[i], w, w.mod + (int64_t)i * 6 * D, modN, M, NF * N, D, F,
-                            [&](const float *qkv, float *a) { return omnitok_dit_attn(qkv, BF, N, c.heads, e->hd, a, stream); }, fmt,
-                            e->tb.flag, stream));
+                            [&](const float *qkv, float *a32, unsigned short *a16) {
+                                return dit_spatial_attn(qkv, BF, N, c.heads, e->hd, afmt, fmt, a32, a16, e->tb.flag, stream);
+                            },
+                            afmt != OMNITOK_DIT_ATTN_FP32, fmt, e->tb.flag, stream));
         if (i == 0) LATTE_RUN(omnitok_latte_add_temp_embed(w.X, e->temp, B, NF, N, D, stream));
         LATTE_RUN(dit_block(e->blocks[i + 1], w, w.mod + (int64_t)(i + 1) * 6 * D, modN, M, NF * N, D, F,
-                            [&](const float *qkv, float *a) { return omnitok_latte_attn_temporal(qkv, B, NF, N, c.heads, e->hd, a, stream); },
-                            fmt, e->tb.flag, stream));
+                            [&](const float *qkv, float *a32, unsigned short *) {  // fp32 only: the round pass runs behind it
+                                return omnitok_latte_attn_temporal(qkv, B, NF, N, c.heads, e->hd, a32, stream);
+                            },
+                            false, fmt, e->tb.flag, stream));
     }
     const float *mf = w.mod + (int64_t)c.depth * 6 * D;  // shift | scale
     LATTE_RUN(omnitok_dit_ln_modulate(w.X, mf, mf + D, modN, M, NF * N, D, w.Xn, stream));

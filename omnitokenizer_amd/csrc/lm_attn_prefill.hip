@@ -7,6 +7,7 @@
 // the MFMA.  The fp32 kernel is the CAUSAL form of attn_f32_tiled (csrc/attn_f32_tiled.h: the operand layout, the order of every sum,
 // what a row depends on and the non-finite-V limit of a masked key are written down there; the rows kernel skips such a key).  What is
 // the LM's own: the longest query blocks are launched first, scale = 1 / sqrtf(hd) as in lm_attn_decode_kernel, and the output format.
+#include "attn16_tiled.h"
 #include "attn_f32_tiled.h"
 #include "lm_common.h"
 
@@ -58,36 +59,7 @@ __global__ __launch_bounds__(256, 2) void lm_attn_prefill_kernel(const float *__
 // limit (a non-finite V in a masked key of the diagonal tile), are the fp32 kernel's (the head of this file).
 // Flags: an fp16 operand (an element of Q, K or V) that rounds to +-inf ORs LM_FLAG_AOP16_RANGE into *flag; an fp16 OUTPUT of +-inf
 // LM_FLAG_PF16_RANGE, as the fp32 kernel.  bf16 sets neither.
-constexpr int PA16_LDT = 36;  // row stride of the transposed V image in 16-bit elements
-
-typedef unsigned pa16_u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 pa16_bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 pa16_f16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 pa16_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float pa16_f32x2 __attribute__((ext_vector_type(2)));
-
-template <typename OP>
-__device__ __forceinline__ f32x16 pa16_mfma(const pa16_u32x4 &a, const pa16_u32x4 &b, const f32x16 &c) {
-    if constexpr (__is_same(OP, lm_bf16))
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(pa16_bf16x8, a), __builtin_bit_cast(pa16_bf16x8, b), c, 0, 0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(pa16_f16x8, a), __builtin_bit_cast(pa16_f16x8, b), c, 0, 0, 0);
-}
-
-// Two fp32 values rounded to OP, packed low | high; inf: an fp16 result of +-inf.  bf16: one v_cvt_pk_bf16_f32 (the compiler's
-// conversion of a float pair) instead of two integer roundings of 5 instructions each.  Its bits equal lm_round16<lm_bf16>'s for every
-// non-NaN input -- compared over all 2^32 patterns in both halves of the pair on an MI355X, subnormals included; a NaN keeps its
-// payload where lm_round16 gives 0x7FC0 (NaN either way).
-template <typename OP>
-__device__ __forceinline__ unsigned pa16_pack2(float lo, float hi, bool &inf) {
-    if constexpr (__is_same(OP, lm_bf16)) {
-        return __builtin_bit_cast(unsigned, __builtin_convertvector(pa16_f32x2{lo, hi}, pa16_bf16x2));
-    } else {
-        const unsigned short a = lm_round16<OP>(lo), b = lm_round16<OP>(hi);
-        inf = inf || lm_f16_is_inf(a) || lm_f16_is_inf(b);
-        return (unsigned)a | ((unsigned)b << 16);
-    }
-}
+// PA16_LDT, the pa16_* vector types, pa16_mfma and pa16_pack2: csrc/attn16_tiled.h, shared with the DiT's 16-bit attention body.
 
 template <int HD, typename OP, typename OT>
 __global__ __launch_bounds__(256, 2) void lm_attn_prefill16_kernel(const float *__restrict__ qkv, int T, int n_head, OT *__restrict__ out,

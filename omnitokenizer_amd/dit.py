@@ -10,6 +10,7 @@ The module holds the reference's parameter names, so its checkpoints load unchan
 engine (fp32 throughout by default; there is no PyTorch fallback).  Training, label dropout and fractional timesteps are not built.
 
     model.set_linear_format("bf16")     # opt-in: the four linears of every block on the 16-bit MFMA ("fp32" | "bf16" | "fp16")
+    model.set_attention_format("bf16")  # opt-in: Q . K^T and P . V of every block's attention on the 16-bit MFMA (the same three)
 """
 from __future__ import annotations
 
@@ -24,6 +25,7 @@ from . import _lib
 from ._lib import OmnitokDitConfig, check
 
 LINEAR_FORMATS = {"fp32": 0, "bf16": 1, "fp16": 2}  # OMNITOK_DIT_LIN_* (include/omnitok_dit.h)
+ATTENTION_FORMATS = LINEAR_FORMATS  # OMNITOK_DIT_ATTN_*: the same codes under a second name
 FREQUENCY_EMBEDDING_SIZE = 256  # TimestepEmbedder's default (models.py:31), the only one the reference uses
 
 
@@ -141,6 +143,7 @@ class DiT(nn.Module):
         self._engine = None
         self._engine_sig = None
         self._linear_format = "fp32"
+        self._attention_format = "fp32"
         nn.Module.train(self, False)
 
     # ---- plumbing ---------------------------------------------------------------------------------
@@ -164,6 +167,25 @@ class DiT(nn.Module):
         if fmt != self._linear_format:
             self._linear_format = fmt
             self._engine_sig = None  # the next forward re-finalizes
+        return self
+
+    @property
+    def attention_format(self) -> str:
+        """The format of the attention's operands: "fp32" (the default), "bf16" or "fp16" (set_attention_format)."""
+        return self._attention_format
+
+    def set_attention_format(self, fmt: str):
+        """Runs Q . K^T and P . V of every block's attention (Latte: of the spatial blocks; the temporal attention stays fp32) on the
+        16-bit MFMA: q, k, v and the softmax weights rounded once to `fmt`, exact products, fp32 accumulators, softmax statistics in
+        fp32 (omnitok_dit_set_attention_format).  Independent of the linear format; with both 16-bit the attention writes attn.proj's
+        packed operand itself.  These are the operands of one kernel, not the reference's use_fp16.  No weight depends on it: an
+        existing engine takes it at once, without a re-upload; "fp32" restores the default bit for bit.  Under "fp16" a q, k or v
+        outside the fp16 range fails check_range()."""
+        if fmt not in ATTENTION_FORMATS:
+            raise ValueError(f"attention format {fmt!r}: one of {', '.join(ATTENTION_FORMATS)}")
+        self._attention_format = fmt
+        if self._engine is not None:
+            check(self._fn("set_attention_format")(self._engine, ATTENTION_FORMATS[fmt]), f"{self._API}_set_attention_format")
         return self
 
     def train(self, mode: bool = True):
@@ -223,6 +245,7 @@ class DiT(nn.Module):
             check(self._fn("set_weight")(self._engine, name.encode(), ctypes.c_void_p(t.data_ptr()), shape, t.dim(), stream),
                   f"{api}_set_weight({name})")
         check(self._fn("set_linear_format")(self._engine, LINEAR_FORMATS[self._linear_format]), f"{api}_set_linear_format")
+        check(self._fn("set_attention_format")(self._engine, ATTENTION_FORMATS[self._attention_format]), f"{api}_set_attention_format")
         check(self._fn("finalize")(self._engine, stream), f"{api}_finalize")
         torch.cuda.current_stream().synchronize()
         self._engine_sig = sig
@@ -260,7 +283,8 @@ class DiT(nn.Module):
 
     def check_range(self):
         """Raises ValueError if a forward since the last check saw a timestep outside [0, 1000), a label outside the embedding
-        table or, under the "fp16" linear format, an activation outside the fp16 range (one int read-back: a host synchronisation)."""
+        table or, under the "fp16" linear / attention format, an activation / a q, k or v outside the fp16 range (one int read-back:
+        a host synchronisation)."""
         check(self._fn("check")(self._engine, torch.cuda.current_stream().cuda_stream), f"{self._API}_check")
 
     # ---- the reference's two entry points ------------------------------------------------------------

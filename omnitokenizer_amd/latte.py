@@ -7,7 +7,8 @@
     eps_sigma = model.forward_with_cfg(x, t, y, cfg_scale=7.0)   # x [B,F,C,H,W] -> [B,F,2C,H,W]
 
 The module holds the reference's parameter names, so its checkpoints load unchanged; the forward pass runs on the library's engine
-(fp32 throughout by default, DiT.set_linear_format for 16-bit block linears; there is no PyTorch fallback).  Built: extras 1 (unconditional) and 2 (class labels).  Not built: extras 78 (text
+(fp32 throughout by default, DiT.set_linear_format for 16-bit block linears and DiT.set_attention_format for 16-bit operands of
+the spatial attention; there is no PyTorch fallback).  Built: extras 1 (unconditional) and 2 (class labels).  Not built: extras 78 (text
 embeddings), use_fp16, training, fractional timesteps.
 """
 from __future__ import annotations

@@ -12,6 +12,11 @@ classifier-free guidance = 16 streams x 256 tokens = 4096 rows; one step = forwa
   --linear-format    bf16 | fp16: the block linears on the 16-bit MFMA (DiT.set_linear_format).  step_ms is then the 16-bit step and
                      fp32_step_ms the default format's, timed first in the same session; the split times omnitok_dit_gemm16 per
                      epilogue and the producers of its packed operands, and block_gemms is held against the 16-bit MFMA peak
+  --attention-format bf16 | fp16: the attention's operands on the 16-bit MFMA (DiT.set_attention_format).  step_ms is then the step
+                     with that attention and fp32_attention_step_ms the same linear format's step with the fp32 attention, timed just
+                     before it in the same session; the split times omnitok_dit_attn16 (`attention16`, writing what the engine has it
+                     write: the packed operand of attn.proj under a 16-bit linear format, which drops `round16_attention`), and
+                     attention_fp32 holds omnitok_dit_attn's time in the same session
   attention          the attention kernel's useful FLOP (4 B heads N^2 hd: both products, the dead 3/4 of head_dim 72's third output
                      block not counted) over its time, as a fraction of the fp32-input MFMA peak
 """
@@ -54,9 +59,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=4)
     ap.add_argument("--torch-steps", type=int, default=20)
     ap.add_argument("--linear-format", default="fp32", choices=["fp32", "bf16", "fp16"])
+    ap.add_argument("--attention-format", default="fp32", choices=["fp32", "bf16", "fp16"])
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     lin16 = a.linear_format != "fp32"
+    attn16 = a.attention_format != "fp32"
     if not torch.cuda.is_available():
         raise SystemExit("dit_bench needs the GPU: there is nothing to measure without it")
     from omnitokenizer_amd import _lib
@@ -100,6 +107,11 @@ def main():
         if lin16:
             m.set_linear_format(a.linear_format)
             diff16 = float((engine_step() - ours).abs().max())
+            step = timed(engine_step, a.warmup, a.steps)
+        if attn16:
+            before, a32_step = engine_step(), step
+            m.set_attention_format(a.attention_format)
+            diff_a16 = float((engine_step() - before).abs().max())
             step = timed(engine_step, a.warmup, a.steps)
         tstep = timed(torch_step, a.warmup, a.torch_steps)
 
@@ -166,6 +178,16 @@ def main():
             "gemm16_fc2_gate_residual": (L, gemm16(H16, W16["fc2"], 2, None, None, D, F)),
         })
         ops["ln_modulate"] = (1, ops["ln_modulate"][1])  # the final layer's
+    if attn16:  # what the engine launches: into the packed A16 under a 16-bit linear format (no round pass), else fp32
+        acode = {"bf16": 1, "fp16": 2}[a.attention_format]
+        aflag = torch.zeros(1, dtype=torch.int32, device="cuda")
+        A16 = torch.empty(M, D, device="cuda", dtype=torch.int16)
+        o32, o16, ofmt = (None, P(A16.data_ptr()), {"bf16": 1, "fp16": 2}[a.linear_format]) if lin16 else (P(O.data_ptr()), None, 0)
+        attn_fp32 = ops.pop("attention")[1]
+        ops.pop("round16_attention", None)
+        ops["attention16"] = (L, lambda: lib.omnitok_dit_attn16(P(QKV.data_ptr()), B, N, H, hd, acode, o32, o16, ofmt, P(aflag.data_ptr()),
+                                                                st))
+        ops["attention_fp32"] = (0, attn_fp32)  # not part of this forward: the yardstick, timed in the same session
     split = {}
     for name, (calls, fn) in ops.items():
         def rep(fn=fn):
@@ -174,7 +196,7 @@ def main():
         print("split:", name, file=sys.stderr, flush=True)
         med, _, _ = timed(rep, 2, 10)
         split[name] = {"ms_per_call": round(med / 10, 5), "calls_per_forward": calls, "ms_per_forward": round(med / 10 * calls, 4)}
-    attn_ms = split["attention"]["ms_per_call"]
+    attn_ms = split["attention16" if attn16 else "attention"]["ms_per_call"]
     attn_flop = 4.0 * B * H * N * N * hd
     gemm_flop = 2.0 * M * D * (3 * D + D + 2 * F) * L
     gemm_ms = sum(v["ms_per_forward"] for k, v in split.items() if k.startswith("gemm16_" if lin16 else ("gemm_qkv", "gemm_proj", "gemm_fc")))
@@ -182,7 +204,7 @@ def main():
     tiles = {k: ((M + 127) // 128) * ((nc + 127) // 128) for k, nc in (("qkv", 3 * D), ("proj", D), ("fc1", F), ("fc2", D))}
     res = {
         "bench": "dit_step", "model": a.model, "input_size": 32, "in_channels": 8, "images": n, "streams": B, "rows": M,
-        "device": torch.cuda.get_device_name(0), "linear_format": a.linear_format,
+        "device": torch.cuda.get_device_name(0), "linear_format": a.linear_format, "attention_format": a.attention_format,
         "arithmetic": (f"block linears {a.linear_format} operands on v_mfma_f32_32x32x16, fp32 accumulate; everything else fp32" if lin16
                        else "fp32 (v_mfma_f32_32x32x2_f32 GEMMs and attention)"),
         "step_ms": round(step[0], 4), "step_ms_min_max": [round(step[1], 4), round(step[2], 4)], "steps_timed": a.steps,
@@ -201,6 +223,17 @@ def main():
         res.update({"fp32_step_ms": round(fp32_step[0], 4), "fp32_step_ms_min_max": [round(fp32_step[1], 4), round(fp32_step[2], 4)],
                     "speedup_over_fp32_step": round(fp32_step[0] / step[0], 3), "max_abs_diff_to_fp32_step": diff16,
                     "peak_16bit_mfma_tflops": PEAK_16BIT_MFMA_TFLOPS, "gemm16_tiles_128x128": tiles, "compute_units": 256})
+    if attn16:
+        a32 = split.pop("attention_fp32")["ms_per_call"]
+        res["split_sum_ms"] = round(sum(v["ms_per_forward"] for v in split.values()), 4)
+        res["arithmetic"] += f"; attention operands {a.attention_format} on v_mfma_f32_32x32x16, fp32 softmax and accumulate"
+        res["attention"]["frac_of_16bit_mfma_peak"] = round(attn_flop / (attn_ms * 1e-3) / 1e12 / PEAK_16BIT_MFMA_TFLOPS, 4)
+        res.update({"attention_fp32": {"ms_per_call": a32, "ms_per_forward": round(a32 * L, 4), "kernel": "omnitok_dit_attn, same session"},
+                    "attention16_speedup_over_fp32_kernel": round(a32 / attn_ms, 3),
+                    "fp32_attention_step_ms": round(a32_step[0], 4),
+                    "fp32_attention_step_ms_min_max": [round(a32_step[1], 4), round(a32_step[2], 4)],
+                    "speedup_over_fp32_attention_step": round(a32_step[0] / step[0], 3), "max_abs_diff_to_fp32_attention_step": diff_a16,
+                    "peak_16bit_mfma_tflops": PEAK_16BIT_MFMA_TFLOPS})
     line = json.dumps(res)
     print(line)
     if a.out:

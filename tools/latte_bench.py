@@ -11,6 +11,11 @@ Reported per shape:
                   update over the B F frames
   --linear-format bf16 | fp16: the block linears of both kinds of block on the 16-bit MFMA (Latte.set_linear_format); step_ms is then
                   the 16-bit step and fp32_step_ms the default format's, timed first in the same session on the same model
+  --attention-format bf16 | fp16: the spatial blocks' attention operands on the 16-bit MFMA (Latte.set_attention_format); step_ms is
+                  then the step with that attention and fp32_attention_step_ms the same linear format's step with the fp32 attention,
+                  timed just before it in the same session.  `split` then holds attention16 (omnitok_dit_attn16 over the B F frames,
+                  writing what the engine has it write), attention_fp32 (omnitok_dit_attn at the same shape, same session) and, under
+                  a 16-bit linear format, round16_attention with the calls it still has (the temporal blocks')
   temporal_attn   omnitok_latte_attn_temporal alone at the model's shape (qkv [B F N, 3 D] in (b f) n order): median ms per call
                   over batches of calls, and the achieved bytes/s against ONE read of qkv plus ONE write of out
   rearranged      what the kernel replaces: the copy '(b f) n d -> (b n) f d' of qkv, omnitok_dit_attn with N = F on it, and the copy
@@ -93,6 +98,12 @@ def bench_shape(name, spec, a, lib):
             diff16 = float((step() - ref).abs().max())
             m.check_range()
             step_ms = timed(step, a.warmup, a.steps)
+        if a.attention_format != "fp32":
+            ref, a32_ms = step(), step_ms
+            m.set_attention_format(a.attention_format)
+            diff_a16 = float((step() - ref).abs().max())
+            m.check_range()
+            step_ms = timed(step, a.warmup, a.steps)
 
     # ---- the temporal attention alone, and the rearranging alternative ------------------------------------------------------------
     D, heads, N = m.hidden_size, m.num_heads, (32 // m.patch_size) ** 2
@@ -130,8 +141,39 @@ def bench_shape(name, spec, a, lib):
     extra = {} if a.linear_format == "fp32" else {
         "fp32_step_ms": round(fp32_ms[0], 4), "fp32_step_ms_min_max": [round(fp32_ms[1], 4), round(fp32_ms[2], 4)],
         "speedup_over_fp32_step": round(fp32_ms[0] / step_ms[0], 3), "max_abs_diff_to_fp32_step": diff16}
+    if a.attention_format != "fp32":   # the spatial attention alone: B F sequences of N tokens, both kernels in this session
+        codes = {"bf16": 1, "fp16": 2}
+        lin16 = a.linear_format != "fp32"
+        flag = torch.zeros(1, dtype=torch.int32, device="cuda")
+        a16 = torch.empty(rows, D, device="cuda", dtype=torch.int16)
+        o32, o16, ofmt = (None, P(a16.data_ptr()), codes[a.linear_format]) if lin16 else (P(out.data_ptr()), None, 0)
+
+        def spatial16():
+            _lib.check(lib.omnitok_dit_attn16(P(qkv.data_ptr()), B * F, N, heads, hd, codes[a.attention_format], o32, o16, ofmt,
+                                              P(flag.data_ptr()), st))
+
+        def spatial32():
+            _lib.check(lib.omnitok_dit_attn(P(qkv.data_ptr()), B * F, N, heads, hd, P(out.data_ptr()), st))
+
+        def round16():
+            _lib.check(lib.omnitok_dit_round16(P(out.data_ptr()), codes[a.linear_format], P(a16.data_ptr()), rows * D, P(flag.data_ptr()), st))
+
+        r16, r32 = per_call(spatial16, calls, 2, a.steps), per_call(spatial32, calls, 2, a.steps)
+        split = {"attention16": {"ms_per_call": r16[0], "ms_min_max": r16[1:], "calls_per_forward": m.depth // 2,
+                                 "writes": "the packed operand of attn.proj" if lin16 else "fp32"},
+                 "attention_fp32": {"ms_per_call": r32[0], "ms_min_max": r32[1:], "calls_per_forward": 0,
+                                    "kernel": "omnitok_dit_attn at the same shape, same session"}}
+        if lin16:
+            rr = per_call(round16, calls, 2, a.steps)
+            split["round16_attention"] = {"ms_per_call": rr[0], "ms_min_max": rr[1:], "calls_per_forward": m.depth // 2,
+                                          "note": "behind the temporal attention only; the spatial blocks' pass is not launched"}
+        extra.update({"split": split, "attention16_speedup_over_fp32_kernel": round(r32[0] / r16[0], 3),
+                      "fp32_attention_step_ms": round(a32_ms[0], 4),
+                      "fp32_attention_step_ms_min_max": [round(a32_ms[1], 4), round(a32_ms[2], 4)],
+                      "speedup_over_fp32_attention_step": round(a32_ms[0] / step_ms[0], 3),
+                      "max_abs_diff_to_fp32_attention_step": diff_a16})
     return {
-        **extra, "linear_format": a.linear_format,
+        **extra, "linear_format": a.linear_format, "attention_format": a.attention_format,
         "model": spec["model"], "B": B, "frames": F, "tokens": N, "in_channels": C, "rows": rows, "hidden": D, "heads": heads,
         "head_dim": hd, "step_ms": round(step_ms[0], 4), "step_ms_min_max": [round(step_ms[1], 4), round(step_ms[2], 4)],
         "steps_timed": a.steps,
@@ -151,6 +193,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--calls", type=int, default=50, help="kernel calls per timed batch")
     ap.add_argument("--linear-format", default="fp32", choices=["fp32", "bf16", "fp16"])
+    ap.add_argument("--attention-format", default="fp32", choices=["fp32", "bf16", "fp16"])
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -169,6 +212,9 @@ def main():
     res = {"bench": "latte_step", "device": torch.cuda.get_device_name(0), "shapes": {},
            "arithmetic": "fp32" if a.linear_format == "fp32" else
            f"block linears {a.linear_format} operands on v_mfma_f32_32x32x16, fp32 accumulate; everything else fp32"}
+    if a.attention_format != "fp32":
+        res["arithmetic"] += (f"; spatial attention operands {a.attention_format} on v_mfma_f32_32x32x16, fp32 softmax and accumulate "
+                              "(the temporal attention stays fp32)")
     for name in a.shapes.split(","):
         smp = gpu_power.Sampler(files) if files else None
         if smp:
