@@ -112,6 +112,35 @@ int omnitok_lm_cache_format(omnitok_lm *lm); /* -1: null engine */
 int omnitok_lm_set_max_streams(omnitok_lm *lm, int n);
 int omnitok_lm_max_streams(omnitok_lm *lm); /* -1: null engine */
 
+/* How a many-stream decode step runs its GEMMs -- per engine, default OMNITOK_LM_SF_FP32 (nothing below applies then: a default engine
+ * issues exactly the launches it issued before the switch existed).  The many-stream step (B >= option "lm_streams_min" streams, above)
+ * multiplies fp32 activations on the fp32-input MFMA even when the engine holds packed 16-bit weight images, widening every weight in
+ * registers; at 64 and 128 streams it is bound by that instruction, which runs at 1/16 of the matrix cores' 16-bit rate.
+ * OMNITOK_LM_SF_W16 runs the step's four linears per block and the head on the bf16 / fp16 MFMA instead (omnitok_lm_gemm_streams16 below)
+ * over the packed images:
+ *   Needs a 16-bit weight format: with OMNITOK_LM_W_FP32 in force omnitok_lm_step / _step_ex return OMNITOK_ERR_STATE and name both
+ *     switches in omnitok_last_error(), whatever B is -- there is no fallback.
+ *   Only the many-stream step: a step of fewer than "lm_streams_min" streams (default 17) runs the <= 16-stream kernels exactly as before,
+ *     and the switch has no effect on it ("lm_streams_min" 1 sends every B to the 16-bit kernel, as it sends it to the fp32-MFMA one
+ *     today).  The prefill has its own switch (omnitok_lm_set_prefill_format) and is unaffected.
+ *   What is rounded: the A operand of each GEMM, ONCE, to the engine's weight format (lm_round16, round to nearest even) -- the rounding
+ *     points of an OMNITOK_LM_PF_W16 prefill: the LayerNorm rows (ln1, ln2, ln_f), the merged attention output and FC1's GELU output (in
+ *     its GEMM's fp32 epilogue).  Products are exact in fp32, accumulation is fp32 in an order fixed by (N, K) alone, no atomics: a
+ *     stream's logits do not depend on B, on its slot or on what the other streams hold, and two calls give equal bits.
+ *   Everything else stays fp32: the embeddings, the residual stream, the LayerNorm statistics, qkv and what goes into the K/V cache (in
+ *     the cache's own format), the flash-decode attention and its partials, biases and the logits.
+ *   The step is then no longer the fp32 step's arithmetic: its logits differ from the OMNITOK_LM_SF_FP32 step's by the activation rounding
+ *     (tests/test_gpu_lm_streams16.py holds them to the bar of tests/lm_prefill16_ref.py, the restatement of these rounding points).
+ *   fp16 range: an activation that rounds to +-inf raises bit 16 of the engine's flag word (omnitok_lm_overflowed).  bf16 has fp32's
+ *     range and never does.
+ * omnitok_lm_set_streams_format: -1 for a null engine or an unknown format (a refused format changes nothing); it touches neither
+ * `finalized`, the weights nor the cache, is independent of the cache format, the three prefill switches and max_streams, and applies
+ * from the next step on (a captured graph keeps the launches it was captured with). */
+#define OMNITOK_LM_SF_FP32 0
+#define OMNITOK_LM_SF_W16 1
+int omnitok_lm_set_streams_format(omnitok_lm *lm, int fmt);
+int omnitok_lm_streams_format(omnitok_lm *lm); /* -1: null engine */
+
 /* How the batched prefill runs its GEMMs -- per engine, default OMNITOK_LM_PF_FP32 (nothing below applies then).  The prefill
  * (omnitok_lm_prefill, _prefill_ex, _prefill_loss) is bound by its five nn.Linear GEMMs per block and the head GEMM, which run on the
  * fp32-input MFMA (omnitok_gemm) at 1/16 of the matrix cores' 16-bit rate; under the reference's precision="bf16" its nn.Linears see
@@ -234,7 +263,10 @@ int omnitok_lm_step_ex(omnitok_lm *lm, const int64_t *idx, const float *emb, con
  *      the default prefill format or a bf16 engine.
  *   8: a Q, K or V element of a prefill attention with OMNITOK_LM_AOP_FP16 operands left the fp16 range and entered its MFMA as
  *      +-inf: that prefill's logits are invalid (the cache rows are stored unrounded and are not).  Never set by fp32 or bf16
- *      operands. */
+ *      operands.
+ *  16: an activation of an OMNITOK_LM_SF_W16 many-stream step on an fp16 engine (a LayerNorm row, a merged attention row or FC1's GELU
+ *      output) left the fp16 range and entered its GEMM as +-inf: the logits from there on are invalid (a non-finite K/V row may sit
+ *      in the cache).  Never set by the default streams format or a bf16 engine. */
 int omnitok_lm_overflowed(omnitok_lm *lm, omnitok_stream_t stream);
 
 /* Batched prefill of a conditioning prefix into EMPTY streams (GPT.forward / the first
@@ -323,6 +355,20 @@ int omnitok_lm_gemv_w16(const float *x, const void *w16, int fmt, const float *b
 int omnitok_lm_gemm_streams(const float *x, const void *w, int fmt, const float *bias, const float *residual,
                             const float *ln_gamma, const float *ln_beta, float *y, int B, int N, int K, int act,
                             omnitok_stream_t stream);
+/* The GEMM of an OMNITOK_LM_SF_W16 many-stream step: y[B, N] = act(a16[B, K] . w16[N, K]^T + bias) (+ residual) for 1 <= B <= 128 in
+ * one pass over w16, with a16 and w16 packed bf16 or fp16 (fmt = OMNITOK_LM_W_BF16 | OMNITOK_LM_W_FP16), row-major, on
+ * v_mfma_f32_32x32x16_{bf16,f16}: exact products, fp32 accumulators.  N >= 1, K % 64 == 0.  Always this kernel: no routing to the
+ * <= 16-stream kernels, no dependence on "lm_streams_min".  The partial sums of a dot product are joined in an order fixed by (N, K):
+ * row b of y depends on row b of a16 only -- its bits do not change with B, with the row's slot or with the other rows' contents (NaN /
+ * Inf included) -- and two calls give equal bits.  Epilogue in fp32: + bias [N] (optional), exact-erf GELU if act == 1, then
+ *   y32 != NULL: + residual [B, N] (optional, may alias y32), stored as fp32; or
+ *   y16 != NULL: rounded to fmt (round to nearest even) into a packed [B, N]; no residual in this form.  An fp16 element that rounds to
+ *     +-inf ORs 16 into *flag (flag may be NULL; bf16 never sets it).
+ * Exactly one of y32 / y16.  -1 before any HIP call for null or non-16-byte-aligned pointers, sizes outside the above, an unknown fmt or
+ * act, both or neither output, or a residual with y16.  Uses a process-wide grow-only scratch (may hipMalloc): calls on different
+ * streams must not overlap. */
+int omnitok_lm_gemm_streams16(const void *a16, const void *w16, int fmt, const float *bias, const float *residual,
+                              float *y32, void *y16, int B, int N, int K, int act, int *flag, omnitok_stream_t stream);
 /* The GEMM of an OMNITOK_LM_PF_W16 prefill: y[M, N] = act(a16[M, K] . w16[N, K]^T + bias) (+ residual) with a16 and w16 packed bf16 or
  * fp16 (fmt = OMNITOK_LM_W_BF16 | OMNITOK_LM_W_FP16), row-major, 16-byte aligned, on v_mfma_f32_32x32x16_{bf16,f16}: exact products,
  * fp32 accumulators.  1 <= M <= 65535, N >= 1, K % 32 == 0.  The partial sums of a dot product are joined in k order, an order fixed

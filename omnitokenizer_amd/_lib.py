@@ -228,6 +228,8 @@ _PROTOS = {
     "omnitok_lm_step_weight_bytes": [P],
     "omnitok_lm_set_cache_format": [P, c_int],
     "omnitok_lm_cache_format": [P],
+    "omnitok_lm_set_streams_format": [P, c_int],
+    "omnitok_lm_streams_format": [P],
     "omnitok_lm_set_prefill_format": [P, c_int],
     "omnitok_lm_prefill_format": [P],
     "omnitok_lm_set_prefill_attention": [P, c_int],
@@ -252,6 +254,7 @@ _PROTOS = {
     "omnitok_lm_gemv": [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P],
     "omnitok_lm_gemv_w16": [P, P, c_int, P, P, P, P, P, c_int, c_int, c_int, c_int, P],
     "omnitok_lm_gemm_streams": [P, P, c_int, P, P, P, P, P, c_int, c_int, c_int, c_int, P],
+    "omnitok_lm_gemm_streams16": [P, P, c_int, P, P, P, P, c_int, c_int, c_int, c_int, P, P],
     "omnitok_lm_gemm16": [P, P, c_int, P, P, P, P, I64, c_int, c_int, c_int, P, P],
     "omnitok_lm_layernorm16": [P, P, P, P, c_int, I64, c_int, P, P],
     "omnitok_lm_attn_decode": [P, P, P, P, c_int, c_int, c_int, c_int, P, P, P],

@@ -174,10 +174,11 @@ __global__ __launch_bounds__(NWV * 64) void lm_attn_decode_kernel(const float *_
 }
 
 // OT = float: out [rows][n_head * HD] fp32 | lm_bf16 / lm_fp16: the same value rounded once (lm_round16) into a packed 16-bit row, the
-// proj GEMM's operand of a PF_W16 prefill; an fp16 result of +-inf raises LM_FLAG_PF16_RANGE in *flag
+// proj GEMM's operand of a PF_W16 prefill or an SF_W16 step; an fp16 result of +-inf raises flag_bit in *flag
 template <typename OT>
 __global__ void lm_attn_merge_kernel(const float *__restrict__ part, const int32_t *__restrict__ cache_len, int n_head,
-                                     int HD, int nchunk, int prefill_T, OT *__restrict__ out, int chunk, int *__restrict__ flag) {
+                                     int HD, int nchunk, int prefill_T, OT *__restrict__ out, int chunk, int *__restrict__ flag,
+                                     int flag_bit) {
     const int h = blockIdx.x, b = blockIdx.y, d = threadIdx.x;  // b: query row
     if (d >= HD) return;
     const int total = (prefill_T > 0 ? b % prefill_T : cache_len[b]) + 1;
@@ -197,7 +198,7 @@ __global__ void lm_attn_merge_kernel(const float *__restrict__ part, const int32
     } else {
         bool inf = false;
         out[((int64_t)b * n_head + h) * HD + d] = LmKV<OT>::store(O / L, inf);
-        if (inf && flag) atomicOr(flag, LM_FLAG_PF16_RANGE);
+        if (inf && flag) atomicOr(flag, flag_bit);
     }
 }
 
@@ -268,11 +269,12 @@ int lm_attn_partials(const LmAttnArgs &a, hipStream_t stream) {
 }
 
 void lm_attn_merge(const float *part, const int32_t *cache_len, int n_head, int hd, int nchunk, int prefill_T, float *out32, void *out16,
-                   int fmt, int64_t rows, int *flag, int chunk, hipStream_t stream) {
+                   int fmt, int64_t rows, int *flag, int chunk, hipStream_t stream, int flag_bit) {
     const dim3 grid(n_head, (unsigned)rows);
     auto launch = [&](auto *out, int *fl) {
         typedef std::remove_pointer_t<decltype(out)> OT;
-        hipLaunchKernelGGL(lm_attn_merge_kernel<OT>, grid, dim3(128), 0, stream, part, cache_len, n_head, hd, nchunk, prefill_T, out, chunk, fl);
+        hipLaunchKernelGGL(lm_attn_merge_kernel<OT>, grid, dim3(128), 0, stream, part, cache_len, n_head, hd, nchunk, prefill_T, out, chunk, fl,
+                           flag_bit);
     };
     if (out32) launch(out32, static_cast<int *>(nullptr));
     else if (fmt == OMNITOK_LM_W_BF16) launch(static_cast<lm_bf16 *>(out16), flag);

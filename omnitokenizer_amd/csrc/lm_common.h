@@ -14,6 +14,8 @@
 //   lm_gemv_ks.hip    lm_gemv_ks_kernel (the K-sliced GEMV of K in {1536, 2048, 6144, 8192}) behind lm_gemv_ks_try; LM_TRACE
 //   lm_gemm_mfma.hip  lm_gemm4_kernel (4 .. 8 streams on the matrix cores, "lm_mfma" 1) behind lm_gemm4_try; lm_gemm_streams_kernel and
 //                     lm_streams_reduce_kernel (17 .. 128 streams, omnitok_lm_set_max_streams), omnitok_lm_gemm_streams
+//   lm_gemm_streams16.hip  lm_gemm_streams16_kernel and lm_streams16_reduce_kernel (17 .. 128 streams on the 16-bit MFMA over packed
+//                     activations and weights, omnitok_lm_set_streams_format), omnitok_lm_gemm_streams16
 //   lm_gemm16.hip     lm_gemm16_kernel (the 16-bit MFMA GEMM of a PF_W16 prefill, omnitok_lm_set_prefill_format), omnitok_lm_gemm16
 //   lm_attn.hip       lm_attn_decode_kernel (flash-decode over the fp32 / bf16 / fp16 K/V cache, chunk partials), lm_attn_merge_kernel
 //                     (fp32 or, for a PF_W16 prefill, 16-bit output), lm_kv_scatter_kernel, lm_kv_read_kernel, omnitok_lm_attn_decode[_kv16]
@@ -124,6 +126,7 @@ constexpr int LM_FLAG_PAST_CACHE = 1;  // bits of the engine's flag word (omnito
 constexpr int LM_FLAG_FP16_RANGE = 2;
 constexpr int LM_FLAG_PF16_RANGE = 4;  // an activation of an fp16 PF_W16 prefill rounded to +-inf
 constexpr int LM_FLAG_AOP16_RANGE = 8;  // a Q / K / V element of a prefill attention with fp16 operands rounded to +-inf
+constexpr int LM_FLAG_SF16_RANGE = 16;  // an activation of an fp16 SF_W16 many-stream step rounded to +-inf
 
 struct LmMerge {
     const float *part;         // [B][n_head][nchunk][2 + hd]
@@ -202,6 +205,12 @@ void lm_trace_reset();
 // the normalised activations (needed when c.ln_g), part: scratch of lm_streams_part_floats(B, N, K) floats.
 int lm_gemm_streams_any(const LmLinear &c, float *xn, float *part, hipStream_t stream);
 int64_t lm_streams_part_floats(int B, int N, int K);
+// lm_gemm_streams16.hip.  y = act(a16 [B, K] . w16 [N, K]^T + bias) (+ residual) for 1 <= B <= 128 streams on lm_gemm_streams16_kernel into
+// y32 or (rounded to fmt, no residual) y16: the contract of omnitok_lm_gemm_streams16 without its argument checks.  part: scratch of
+// lm_streams16_part_floats(B, N, K) floats; an fp16 +-inf raises LM_FLAG_SF16_RANGE in *flag
+int lm_gemm_streams16(const void *a16, const void *w16, int fmt, const float *bias, const float *residual, float *y32, void *y16, int B,
+                      int N, int K, int act, float *part, int *flag, hipStream_t stream);
+int64_t lm_streams16_part_floats(int B, int N, int K);
 // lm_attn.hip.  chunk partials only (the engine merges them inside the proj GEMV)
 // prefill_T > 0: B * prefill_T query rows (row = b * T + t, keys 0..t), chunks sized for T keys
 struct LmAttnArgs {
@@ -218,9 +227,9 @@ struct LmAttnArgs {
 int lm_attn_partials(const LmAttnArgs &a, hipStream_t stream);
 // the one launch of lm_attn_merge_kernel from the partials of `rows` query rows (the caller checks the launch) into out32 [rows][n_head * hd]
 // or, rounded to fmt (OMNITOK_LM_W_BF16 | _FP16), out16: the proj GEMM's operand of a PF_W16 prefill; an fp16 +-inf raises
-// LM_FLAG_PF16_RANGE in *flag.  Exactly one of out32 / out16.  The decode step passes cache_len and its chunk, the prefill prefill_T and LM_CHUNK
+// flag_bit (LM_FLAG_PF16_RANGE | LM_FLAG_SF16_RANGE) in *flag.  Exactly one of out32 / out16.  The decode step passes cache_len and its chunk, the prefill prefill_T and LM_CHUNK
 void lm_attn_merge(const float *part, const int32_t *cache_len, int n_head, int hd, int nchunk, int prefill_T, float *out32, void *out16,
-                   int fmt, int64_t rows, int *flag, int chunk, hipStream_t stream);
+                   int fmt, int64_t rows, int *flag, int chunk, hipStream_t stream, int flag_bit = LM_FLAG_PF16_RANGE);
 // qkv [B * T, 3C] -> cache rows 0 .. T - 1 of every stream | rows t0 .. t0 + n - 1 of one stream's slabs -> fp32
 int lm_kv_scatter(const float *qkv, void *kc, void *vc, int kvfmt, int64_t rows, int T, int n_head, int hd, int max_len,
                   int *err_flag, hipStream_t stream);
@@ -233,9 +242,9 @@ int lm_kv_read(const void *kc, const void *vc, int kvfmt, int t0, int n, int n_h
 int lm_attn_prefill_any(const char *who, const float *qkv, int B, int T, int n_head, int head_dim, int op_fmt, float *out32, void *out16,
                         int out_fmt, int *flag, hipStream_t stream);
 // lm_engine.hip.  nn.LayerNorm(x) over `rows` rows of K floats into y32 or, each value rounded to fmt (OMNITOK_LM_W_BF16 | _FP16), y16; an
-// fp16 +-inf raises LM_FLAG_PF16_RANGE in *flag.  Exactly one of y32 / y16
+// fp16 +-inf raises flag_bit (LM_FLAG_PF16_RANGE | LM_FLAG_SF16_RANGE) in *flag.  Exactly one of y32 / y16
 int lm_layernorm_rows(const float *x, const float *g, const float *beta, float *y32, void *y16, int fmt, int64_t rows, int K, int *flag,
-                      hipStream_t stream);
+                      hipStream_t stream, int flag_bit = LM_FLAG_PF16_RANGE);
 // lm_gemm16.hip.  y = act(a16 [M, K] . w16 [N, K]^T + bias) (+ residual) on the 16-bit MFMA into y32 or (rounded to fmt) y16: the
 // contract of omnitok_lm_gemm16, its argument checks included
 int lm_gemm16(const void *a16, const void *w16, int fmt, const float *bias, const float *residual, float *y32, void *y16, int64_t M,

@@ -63,12 +63,12 @@ __global__ __launch_bounds__(256) void lm_embed_seq_kernel(const int64_t *__rest
 }
 
 // nn.LayerNorm over rows of any width (two-pass, eps 1e-5): one wave per row.  OT = float: y fp32 | lm_bf16 / lm_fp16: the same
-// values rounded once (lm_round16) into packed 16-bit rows, the GEMM operand of a PF_W16 prefill; an fp16 result of +-inf raises
-// LM_FLAG_PF16_RANGE in *flag
+// values rounded once (lm_round16) into packed 16-bit rows, the GEMM operand of a PF_W16 prefill or an SF_W16 step; an fp16 result of
+// +-inf raises flag_bit in *flag
 template <typename OT>
 __global__ __launch_bounds__(256) void lm_layernorm_rows_kernel(const float *__restrict__ x, const float *__restrict__ g,
                                                                 const float *__restrict__ beta, OT *__restrict__ y,
-                                                                int64_t rows, int K, int *__restrict__ flag) {
+                                                                int64_t rows, int K, int *__restrict__ flag, int flag_bit) {
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
@@ -96,7 +96,7 @@ __global__ __launch_bounds__(256) void lm_layernorm_rows_kernel(const float *__r
         } else {
             bool inf = false;
             *reinterpret_cast<u32x2 *>(y + row * K + k) = LmKV<OT>::store4(v, inf);
-            if (inf && flag) atomicOr(flag, LM_FLAG_PF16_RANGE);
+            if (inf && flag) atomicOr(flag, flag_bit);
         }
     }
 }
@@ -163,10 +163,11 @@ __global__ __launch_bounds__(256) void lm_round_w16_kernel(float *__restrict__ w
 }
 
 int lm_layernorm_rows(const float *x, const float *g, const float *beta, float *y32, void *y16, int fmt, int64_t rows, int K, int *flag,
-                      hipStream_t stream) {
+                      hipStream_t stream, int flag_bit) {
     auto launch = [&](auto *y, int *fl) {
         typedef std::remove_pointer_t<decltype(y)> OT;
-        hipLaunchKernelGGL(lm_layernorm_rows_kernel<OT>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, x, g, beta, y, rows, K, fl);
+        hipLaunchKernelGGL(lm_layernorm_rows_kernel<OT>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, x, g, beta, y, rows, K, fl,
+                           flag_bit);
     };
     if (y32) launch(y32, static_cast<int *>(nullptr));
     else if (fmt == OMNITOK_LM_W_BF16) launch(static_cast<lm_bf16 *>(y16), flag);
@@ -203,6 +204,7 @@ struct omnitok_lm {
     int prefill_format = OMNITOK_LM_PF_FP32;  // how the batched prefill runs its GEMMs (omnitok_lm_set_prefill_format)
     int prefill_attention = OMNITOK_LM_PA_ROWS;  // how the batched prefill runs its attention (omnitok_lm_set_prefill_attention)
     int prefill_attention_operands = OMNITOK_LM_AOP_FP32;  // operand format of the tiled attention (omnitok_lm_set_prefill_attention_operands)
+    int streams_format = OMNITOK_LM_SF_FP32;  // how a many-stream step runs its GEMMs (omnitok_lm_set_streams_format)
     LmMat head = {nullptr, nullptr, OMNITOK_LM_W_FP32};  // head.weight
     // cache + workspaces
     void *kv = nullptr;                       // [n_layer][2][max_batch][n_head][max_len][head_dim] elements of cache_format
@@ -213,7 +215,8 @@ struct omnitok_lm {
     int *err_flag = nullptr;  // LM_FLAG_PAST_CACHE: the attention kernel met a stream past max_len | LM_FLAG_FP16_RANGE: a K/V value
                               // stored into an fp16 cache rounded to +-inf (the append, the prefill's scatter)
     float *x = nullptr, *qkv = nullptr, *att = nullptr, *hid = nullptr, *part = nullptr;
-    float *gs = nullptr;  // K-split partials of lm_gemm_streams_kernel (the many-stream step)
+    float *gs = nullptr;  // K-split partials of lm_gemm_streams_kernel / lm_gemm_streams16_kernel (the many-stream step)
+    unsigned short *x16 = nullptr, *h16 = nullptr;  // packed GEMM operands of an SF_W16 step: [max_batch, C] | [max_batch, 4 C] (one allocation)
     int64_t cache_bytes = 0;
     // grow-only prefill workspace (rows = B * T)
     float *pf = nullptr;
@@ -280,6 +283,8 @@ static void lm_free_cache(omnitok_lm *lm) {
             (void)hipFree(*p);
             *p = nullptr;
         }
+    if (lm->x16) (void)hipFree(lm->x16);
+    lm->x16 = lm->h16 = nullptr;
     if (lm->kv) (void)hipFree(lm->kv);
     lm->kv = nullptr;
     lm->cache_bytes = 0;
@@ -367,6 +372,18 @@ extern "C" int omnitok_lm_set_prefill_attention_operands(omnitok_lm *lm, int fmt
 extern "C" int omnitok_lm_prefill_attention_operands(omnitok_lm *lm) {
     OT_CHECK_ARG(lm, "lm_prefill_attention_operands: null engine");
     return lm->prefill_attention_operands;
+}
+
+extern "C" int omnitok_lm_set_streams_format(omnitok_lm *lm, int fmt) {
+    OT_CHECK_ARG(lm, "lm_set_streams_format: null engine");
+    OT_CHECK_ARG(fmt == OMNITOK_LM_SF_FP32 || fmt == OMNITOK_LM_SF_W16, "lm_set_streams_format: unknown format %d", fmt);
+    lm->streams_format = fmt;  // read at the next step: the weights, `finalized` and the cache are left alone
+    return OMNITOK_OK;
+}
+
+extern "C" int omnitok_lm_streams_format(omnitok_lm *lm) {
+    OT_CHECK_ARG(lm, "lm_streams_format: null engine");
+    return lm->streams_format;
 }
 
 extern "C" int omnitok_lm_set_cache_format(omnitok_lm *lm, int fmt) {
@@ -534,7 +551,8 @@ extern "C" int omnitok_lm_alloc_cache(omnitok_lm *lm, int max_batch, int max_len
     // split partials of the many-stream GEMMs of a step: the largest of its five shapes
     int64_t gs = 0;
     const int shapes[5][2] = {{(int)(3 * C), (int)C}, {(int)C, (int)C}, {(int)(4 * C), (int)C}, {(int)C, (int)(4 * C)}, {c.vocab_size, (int)C}};
-    for (const auto &nk : shapes) gs = std::max(gs, lm_streams_part_floats(max_batch, nk[0], nk[1]));
+    for (const auto &nk : shapes)  // (both streams formats: the switch may change after the cache exists)
+        gs = std::max({gs, lm_streams_part_floats(max_batch, nk[0], nk[1]), lm_streams16_part_floats(max_batch, nk[0], nk[1])});
     // a failed allocation (193 GB of fp32 cache for 128 streams of the reference's model do not fit one device) returns its
     // error and leaves the engine without a cache
     auto alloc = [lm](void **p, int64_t bytes) {
@@ -552,8 +570,10 @@ extern "C" int omnitok_lm_alloc_cache(omnitok_lm *lm, int max_batch, int max_len
         !alloc(reinterpret_cast<void **>(&lm->att), max_batch * C * 4) ||
         !alloc(reinterpret_cast<void **>(&lm->hid), max_batch * 4 * C * 4) ||
         !alloc(reinterpret_cast<void **>(&lm->part), (int64_t)max_batch * c.n_head * nchunk * (2 + hd) * 4) ||
-        (gs > 0 && !alloc(reinterpret_cast<void **>(&lm->gs), gs * 4)))
+        (gs > 0 && !alloc(reinterpret_cast<void **>(&lm->gs), gs * 4)) ||
+        !alloc(reinterpret_cast<void **>(&lm->x16), max_batch * 5 * C * 2))
         return OMNITOK_ERR_HIP;
+    lm->h16 = lm->x16 + max_batch * C;
     lm->max_batch = max_batch;
     lm->max_len = max_len;
     lm->cache_bytes = kv_bytes;
@@ -573,7 +593,7 @@ extern "C" int omnitok_lm_overflowed(omnitok_lm *lm, omnitok_stream_t stream_) {
     OT_HIP(hipStreamSynchronize(stream));
     if (h)
         if (int rc = device_fill_u32(lm->err_flag, 0u, 1, stream)) return rc;
-    return h & (LM_FLAG_PAST_CACHE | LM_FLAG_FP16_RANGE | LM_FLAG_PF16_RANGE | LM_FLAG_AOP16_RANGE);
+    return h & (LM_FLAG_PAST_CACHE | LM_FLAG_FP16_RANGE | LM_FLAG_PF16_RANGE | LM_FLAG_AOP16_RANGE | LM_FLAG_SF16_RANGE);
 }
 
 extern "C" int omnitok_lm_cache_read(omnitok_lm *lm, int layer, int b, int t0, int n, float *k_out, float *v_out,
@@ -608,8 +628,28 @@ extern "C" int omnitok_lm_step(omnitok_lm *lm, const int64_t *idx, int32_t *pos,
 // happens inside the projection's prologue: c.x == nullptr).  From there on the many-stream GEMM does (lm_gemm_streams_kernel): one pass
 // over the matrix for the whole batch; LayerNorm is a pass of its own into `att`, and the chunk partials are merged into `att` as a
 // tensor (free again by then), which then feeds the projection.
+// With OMNITOK_LM_SF_W16 the many-stream GEMM is lm_gemm_streams16_kernel over the packed weight image, and its operand is rounded once
+// to the weight format where it is produced, the rounding points of a PF_W16 prefill: LayerNorm rows and the merged partials by their
+// kernels' 16-bit form into x16, FC1's GELU output in its GEMM's epilogue into h16 -- which the one linear without LayerNorm or merge,
+// FC2, reads.  An fp16 +-inf raises LM_FLAG_SF16_RANGE.
 static int lm_step_linear(omnitok_lm *lm, LmLinear c, const LmMerge *mg, hipStream_t stream) {
     if (c.B < g_lm_streams_min) return lm_gemv_any(c, mg, stream);
+    if (lm->streams_format == OMNITOK_LM_SF_W16) {
+        const int fmt = c.w.fmt;
+        const void *a16 = lm->h16;
+        if (mg) {
+            lm_attn_merge(mg->part, mg->cache_len, mg->n_head, mg->hd, mg->nchunk, 0, nullptr, lm->x16, fmt, c.B, lm->err_flag, mg->chunk,
+                          stream, LM_FLAG_SF16_RANGE);
+            OT_LAUNCH_CHECK("lm_attn_merge16");
+            a16 = lm->x16;
+        } else if (c.ln_g) {
+            if (int rc = lm_layernorm_rows(c.x, c.ln_g, c.ln_b, nullptr, lm->x16, fmt, c.B, c.K, lm->err_flag, stream, LM_FLAG_SF16_RANGE))
+                return rc;
+            a16 = lm->x16;
+        }
+        return lm_gemm_streams16(a16, c.w.w16, fmt, c.bias, c.residual, c.act ? nullptr : c.y, c.act ? lm->h16 : nullptr, c.B, c.N, c.K,
+                                 c.act, lm->gs, lm->err_flag, stream);
+    }
     if (mg) {
         lm_attn_merge(mg->part, mg->cache_len, mg->n_head, mg->hd, mg->nchunk, 0, lm->att, nullptr, 0, c.B, nullptr, mg->chunk, stream);
         OT_LAUNCH_CHECK("lm_attn_merge");
@@ -627,6 +667,12 @@ extern "C" int omnitok_lm_step_ex(omnitok_lm *lm, const int64_t *idx, const floa
     OT_CHECK_ARG((idx || emb) && pos && cache_len, "lm_step: null pointer");
     if (!lm->finalized) {
         set_error("lm_step: engine not finalised (load the weights first)");
+        return OMNITOK_ERR_STATE;
+    }
+    if (lm->streams_format == OMNITOK_LM_SF_W16 && (lm->weight_format == OMNITOK_LM_W_FP32 || !lm->head.w16)) {
+        set_error("lm_step: streams format OMNITOK_LM_SF_W16 (omnitok_lm_set_streams_format) needs the packed 16-bit weight images: set "
+                  "omnitok_lm_set_weight_format to OMNITOK_LM_W_BF16 or OMNITOK_LM_W_FP16 (it is OMNITOK_LM_W_FP32), or the streams format "
+                  "back to OMNITOK_LM_SF_FP32");
         return OMNITOK_ERR_STATE;
     }
     if (!lm->kv || B > lm->max_batch) {

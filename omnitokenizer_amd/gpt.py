@@ -31,6 +31,7 @@ WEIGHT_FORMATS = {"fp32": 0, "bf16": 1, "fp16": 2}  # OMNITOK_LM_W_* of include/
 KV_FORMATS = {"fp32": 0, "bf16": 1, "fp16": 2}      # OMNITOK_LM_KV_*
 PREFILL_FORMATS = {"fp32": 0, "w16": 1}             # OMNITOK_LM_PF_*
 PREFILL_ATTENTIONS = {"rows": 0, "tiled": 1}        # OMNITOK_LM_PA_*
+STREAMS_FORMATS = {"fp32": 0, "w16": 1}             # OMNITOK_LM_SF_*
 PREFILL_ATTENTION_OPERANDS = {"fp32": 0, "bf16": 1, "fp16": 2}  # OMNITOK_LM_AOP_*
 
 
@@ -49,6 +50,8 @@ class _PastHandle:
 
 
 class GPT(nn.Module):
+    STREAMS_FORMATS = STREAMS_FORMATS
+
     def __init__(self, args, vocab_size, block_size, n_layer=12, n_head=8, n_embd=256, embd_pdrop=0.,
                  resid_pdrop=0., attn_pdrop=0., n_unmasked=0, vtokens_pos=False):
         """Same signature as the reference (gpt.py:172).  Dropouts are inference no-ops; vtokens_pos adds the
@@ -107,6 +110,7 @@ class GPT(nn.Module):
         self._cache_format = "fp32"
         self._prefill_format = "fp32"
         self._prefill_attention = "rows"
+        self._streams_format = "fp32"
         self._prefill_attention_operands = "fp32"
         self._max_streams = 16
         self._generation = 0
@@ -201,6 +205,26 @@ class GPT(nn.Module):
         self._prefill_format = fmt
         if self._engine is not None:
             check(_lib.load().omnitok_lm_set_prefill_format(self._engine, PREFILL_FORMATS[fmt]), "lm_set_prefill_format")
+        return self
+
+    @property
+    def streams_format(self) -> str:
+        return self._streams_format
+
+    def set_streams_format(self, fmt: str):
+        """How a decode step of more than 16 streams (set_max_streams; option "lm_streams_min") runs its GEMMs (include/omnitok_lm.h,
+        omnitok_lm_set_streams_format): "fp32" (default: the fp32-input MFMA over fp32 activations, unchanged) or "w16": the bf16 / fp16
+        MFMA over the packed weight images of a 16-bit weight format, with the activations entering each GEMM rounded once to that
+        format -- the rounding points of the "w16" prefill; fp32 accumulation, residual stream, LayerNorm statistics, K/V, attention
+        and logits.  "w16" needs set_weight_format("bf16" | "fp16"): with fp32 weights a step raises, it never falls back.  Steps of up
+        to 16 streams run what they ran before.  The captured graphs are dropped (the launches change); the weights, the cache and
+        state_dict() are left alone.  With fp16, check_overflow() raises if an activation left the fp16 range."""
+        if fmt not in STREAMS_FORMATS:
+            raise ValueError(f"streams format {fmt!r}: expected one of {sorted(STREAMS_FORMATS)}")
+        self._streams_format = fmt
+        self._graphs = {}
+        if self._engine is not None:
+            check(_lib.load().omnitok_lm_set_streams_format(self._engine, STREAMS_FORMATS[fmt]), "lm_set_streams_format")
         return self
 
     @property
@@ -307,6 +331,7 @@ class GPT(nn.Module):
             check(lib.omnitok_lm_set_max_streams(self._engine, self._max_streams), "lm_set_max_streams")
         check(lib.omnitok_lm_set_weight_format(self._engine, WEIGHT_FORMATS[self._weight_format]), "lm_set_weight_format")
         check(lib.omnitok_lm_set_prefill_format(self._engine, PREFILL_FORMATS[self._prefill_format]), "lm_set_prefill_format")
+        check(lib.omnitok_lm_set_streams_format(self._engine, STREAMS_FORMATS[self._streams_format]), "lm_set_streams_format")
         check(lib.omnitok_lm_set_prefill_attention(self._engine, PREFILL_ATTENTIONS[self._prefill_attention]), "lm_set_prefill_attention")
         check(lib.omnitok_lm_set_prefill_attention_operands(self._engine, PREFILL_ATTENTION_OPERANDS[self._prefill_attention_operands]),
               "lm_set_prefill_attention_operands")
@@ -355,7 +380,7 @@ class GPT(nn.Module):
     def check_overflow(self):
         """Raises if a decode step since the last check ran past the allocated K/V cache, or stored a K/V value outside the
         fp16 range into an fp16 cache, or a "w16" prefill on fp16 weights rounded an activation to inf, or a prefill attention with
-        fp16 operands rounded an element of Q, K or V to inf (the logits are invalid in each case); one host synchronisation -- the sampling loops call it once at their end."""
+        fp16 operands rounded an element of Q, K or V to inf, or a "w16" many-stream step on fp16 weights rounded an activation to inf (the logits are invalid in each case); one host synchronisation -- the sampling loops call it once at their end."""
         if not self._engine:
             return
         rc = _lib.load().omnitok_lm_overflowed(self._engine, torch.cuda.current_stream().cuda_stream)
@@ -372,6 +397,9 @@ class GPT(nn.Module):
         if rc & 8:
             raise RuntimeError("a Q, K or V element of a prefill attention with fp16 operands left the fp16 range and entered its "
                                "product as inf: use set_prefill_attention_operands('bf16') (fp32's range) for this model")
+        if rc & 16:
+            raise RuntimeError("an activation of a 'w16' many-stream step left the fp16 range and entered its GEMM as inf: use "
+                               "set_weight_format('bf16') (fp32's range) or set_streams_format('fp32') for this model")
 
     @staticmethod
     def _fp(t):

@@ -121,6 +121,8 @@ class Net2NetTransformer(nn.Module):
         self.transformer.set_prefill_attention_operands(_get(args, "lm_prefill_attention_operands", "fp32"))
         # streams per engine (GPT.set_max_streams: 16 by default, up to 128; classifier-free guidance takes two per sample)
         self.transformer.set_max_streams(int(_get(args, "lm_max_streams", 16)))
+        # GEMMs of a step of more than 16 streams ("fp32" | "w16", GPT.set_streams_format; "w16" needs a 16-bit lm_weight_format)
+        self.transformer.set_streams_format(_get(args, "lm_streams_format", "fp32"))
         if ckpt_path is not None:
             self.init_from_ckpt(ckpt_path, ignore_keys=ignore_keys)
 

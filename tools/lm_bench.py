@@ -5,11 +5,16 @@ LM shape by default (scripts/lm_train/train_k600.sh: vocab 8192, block 5120, 24 
 sequence, the HBM roofline of a step (weight bytes + K/V bytes read) and a CPU baseline (the oracle's
 KV-cached step on the host, bounded sample).
     python tools/lm_bench.py [--batch 1] [--steps 512] [--ctx 0] [--weights fp32|bf16|fp16] [--kv fp32|bf16|fp16] [--also 8] [--no-cpu-baseline]
-                             [--max-streams 16]
+                             [--max-streams 16] [--streams-format fp32|w16]
 --streams-session OUT.json: the many-stream record instead (GPT.set_max_streams; profiles/lm_streams_bench.json): the bare decode step
 (graph replay) of B in --session-batches streams at --session-ctx cached tokens, fp32 weights + fp32 cache first, then bf16 + bf16,
 and of 8 and 16 streams once more with "lm_streams_min" 1 (the many-stream kernel below its default threshold).  The cache lengths
 are set on the device, nothing is prefilled: a step's time depends on how many rows it reads, not on what they hold.
+With --streams-format w16 the session is the record of GPT.set_streams_format instead (profiles/lm_streams16_bench.json): bf16 weights +
+bf16 cache only; per context the "fp32" streams format first (every batch, and the 8 / 16-stream cells as above: the yardstick, the
+path as it was), then "w16" at the batches of 17 and more streams, then "fp32" once more at those batches (the end of the session);
+and the bare GEMMs at the model's five shapes and B = 32, 64, 128: omnitok_lm_gemm_streams (fp32-input MFMA over bf16 weights), then
+omnitok_lm_gemm16 at M = B (the prefill kernel), then omnitok_lm_gemm_streams16, 10 back-to-back launches per timed call.
 --prefill-session OUT.json: the batched-prefill record (GPT.set_prefill_format; profiles/lm_prefill16_bench.json): per weight format
 bf16 then fp16, GPT.forward and GPT.token_losses at (B, T) in --prefill-shapes with the fp32 prefill first and the "w16" prefill after
 it, and the bare omnitok_lm_gemm16 at the model's five GEMM shapes with M = the largest B * T.  --prefill-attention rows,tiled adds the
@@ -71,7 +76,9 @@ def streams_session(a, m, dims):
         rounds = sorted(one_round(nrep) for _ in range(5))
         return rounds[2], [round(rounds[0], 4), round(rounds[-1], 4)], nrep
 
-    for fmt in ("fp32", "bf16"):     # the fp32 arm first
+    sf16 = a.streams_format == "w16"
+    fmts = ("bf16",) if sf16 else ("fp32", "bf16")     # the fp32 arm first
+    for fmt in fmts:
         m.set_weight_format(fmt).set_cache_format(fmt)
         weight_bytes = float(m.step_weight_bytes())
         kv_elem = 4.0 if fmt == "fp32" else 2.0
@@ -84,10 +91,13 @@ def streams_session(a, m, dims):
             except Exception as exc:     # a cache the device cannot hold: recorded, not fatal
                 cells.append({"weights": fmt, "kv": fmt, "ctx": ctx, "skipped": f"cache for {NB} streams x {ctx + 64} tokens: {exc}"})
                 continue
-            arms = [(B, default_min) for B in batches] + [(B, 1) for B in (8, 16) if B in batches and B < default_min]
-            for B, smin in arms:
+            arms = [(B, default_min, "fp32") for B in batches] + [(B, 1, "fp32") for B in (8, 16) if B in batches and B < default_min]
+            if sf16:
+                many = [B for B in batches if B >= default_min]
+                arms += [(B, default_min, "w16") for B in many] + [(B, default_min, "fp32 again") for B in many]
+            for B, smin, sf in arms:
                 _lib.set_option("lm_streams_min", smin)
-                m._graphs = {}       # the kernels are chosen when the step is captured
+                m.set_streams_format(sf.split()[0])     # (drops the graphs: the kernels are chosen when the step is captured)
                 try:
                     ms, spread, nrep = time_cell(B, ctx)
                 finally:
@@ -96,7 +106,8 @@ def streams_session(a, m, dims):
                 m.check_overflow()
                 kv_bytes = 2.0 * L * B * H * (ctx + 1) * hd * kv_elem
                 cells.append({"weights": fmt, "kv": fmt, "ctx": ctx, "streams": B, "lm_streams_min": smin,
-                              "path": "many-stream MFMA GEMM" if B >= smin else "VALU GEMV, groups of 8",
+                              **({"streams_format": sf} if sf16 else {}),
+                              "path": "many-stream 16-bit MFMA GEMM" if sf == "w16" else "many-stream MFMA GEMM" if B >= smin else "VALU GEMV, groups of 8",
                               "max_len": m._cache_shape[1], "step_ms": round(ms, 4), "step_ms_min_max": spread,
                               "replays_per_round": nrep,
                               "tokens_s": round(B / (ms * 1e-3), 1), "weight_bytes": weight_bytes, "kv_bytes": kv_bytes,
@@ -105,13 +116,21 @@ def streams_session(a, m, dims):
                               # included) against the f32-MFMA peak: a rate of the step, not of the GEMM kernels
                               "step_gemm_flops_over_f32_mfma_peak": round(B * flop_per_stream / (ms * 1e-3) / 1e12 / PEAK_F32_MFMA_TFLOPS, 4)})
                 print(json.dumps(cells[-1]), flush=True)
+    m.set_streams_format("fp32")
     # the yardstick: a B-stream step against B / 16 steps of 16 streams (the <= 16-stream path, untouched)
-    verdict = []
-    for fmt in ("fp32", "bf16"):
+    verdict, sf_verdict = [], []
+    for fmt in fmts:
         for ctx in ctxs:
-            def cell(B, smin=default_min):
+            def cell(B, smin=default_min, sf="fp32"):
                 return next((c for c in cells if c.get("weights") == fmt and c.get("ctx") == ctx and c.get("streams") == B
-                             and c.get("lm_streams_min") == smin), None)
+                             and c.get("lm_streams_min") == smin and c.get("streams_format", "fp32") == sf), None)
+            for B in (batches if sf16 else []):
+                first, w16, again = cell(B), cell(B, sf="w16"), cell(B, sf="fp32 again")
+                if first and w16 and again:
+                    sf_verdict.append({"weights": fmt, "ctx": ctx, "streams": B, "fp32_first_ms": first["step_ms"],
+                                       "w16_ms": w16["step_ms"], "fp32_again_ms": again["step_ms"],
+                                       "speedup": round(min(first["step_ms"], again["step_ms"]) / w16["step_ms"], 3),
+                                       "w16_faster": bool(w16["step_ms"] < min(first["step_ms"], again["step_ms"]))})
             base = cell(16)
             for B in batches:
                 c = cell(B)
@@ -119,7 +138,8 @@ def streams_session(a, m, dims):
                     verdict.append({"weights": fmt, "ctx": ctx, "streams": B, "step_ms": c["step_ms"],
                                     "steps_of_16_ms": round(base["step_ms"] * B / 16, 4),
                                     "speedup": round(base["step_ms"] * B / 16 / c["step_ms"], 3)})
-    return {"metric": "LM decode step (graph replay), many streams per engine", "unit": "ms per step",
+    extra = {"w16_vs_fp32": sf_verdict, "gemms": streams_gemms(a, dims), "device": device_state()} if sf16 else {}
+    return {**extra, "metric": "LM decode step (graph replay), many streams per engine", "unit": "ms per step",
             "config": {"workload": f"GPT {L}x{C} ({H} heads, head_dim {hd}), vocab {V}, block {BS}", "max_streams": NB,
                        "peak_hbm_gbs": PEAK_HBM_GBS, "peak_f32_mfma_tflops": PEAK_F32_MFMA_TFLOPS,
                        "protocol": "graph replay, pos / cache_len reset before every replay, 1 dropped + 5 timed rounds, median; "
@@ -130,6 +150,64 @@ def streams_session(a, m, dims):
                        "step_gemm_flops_over_f32_mfma_peak": "2 B (12 C^2 L + V C) FLOP / WHOLE step time / peak: a rate of the step, "
                                                              "attention and LayerNorm launches included, not of the GEMM kernels"},
             "cells": cells, "vs_steps_of_16": verdict}
+
+
+def device_state():
+    """clock and power of the device as rocm-smi reports them after the session, or the reason they could not be read"""
+    import subprocess
+    try:
+        r = subprocess.run(["rocm-smi", "--showclocks", "--showpower", "--json"], capture_output=True, text=True, timeout=60)
+        return json.loads(r.stdout) if r.returncode == 0 else {"not_readable": f"rocm-smi exit {r.returncode}: {r.stderr.strip()[:200]}"}
+    except Exception as exc:
+        return {"not_readable": f"{type(exc).__name__}: {exc}"}
+
+
+def streams_gemms(a, dims):
+    """The bare many-stream GEMMs at the model's five shapes, bf16: see the module docstring.  Returns the cells."""
+    import ctypes
+    from omnitokenizer_amd import _lib
+    V, BS, L, H, C = dims
+    lib = _lib.load()
+    stream = torch.cuda.current_stream().cuda_stream
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    P = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    default_min = _lib.get_option("lm_streams_min")
+    fmt = og.WEIGHT_FORMATS["bf16"]
+    cells = []
+    for what, N, K, act in (("qkv", 3 * C, C, 0), ("proj", C, C, 0), ("fc1 (GELU)", 4 * C, C, 1), ("fc2", C, 4 * C, 0), ("head", V, C, 0)):
+        w = ((torch.rand(N, K, device="cuda") * 2 - 1) * 0.02).to(torch.bfloat16)
+        bias = torch.zeros(N, device="cuda")
+        for B in (32, 64, 128):
+            x32 = torch.rand(B, K, device="cuda") * 2 - 1
+            x16 = x32.to(torch.bfloat16)
+            y32 = torch.empty(B, N, device="cuda")
+            y16 = torch.empty(B, N, device="cuda", dtype=torch.bfloat16)
+            o32, o16 = (None, y16) if act else (y32, None)      # FC1 writes the 16-bit operand of FC2 in both 16-bit kernels
+            calls = {"gemm_streams (fp32 MFMA)": lambda: lib.omnitok_lm_gemm_streams(P(x32), P(w), fmt, P(bias), None, None, None, P(y32), B, N, K,
+                                                                                     act, stream),
+                     "gemm16 (M = B)": lambda: lib.omnitok_lm_gemm16(P(x16), P(w), fmt, P(bias), None, P(o32), P(o16), B, N, K, act, None, stream),
+                     "gemm_streams16": lambda: lib.omnitok_lm_gemm_streams16(P(x16), P(w), fmt, P(bias), None, P(o32), P(o16), B, N, K, act, None,
+                                                                            stream)}
+            cell = {"gemm": what, "B": B, "N": N, "K": K, "weight_mb": round(N * K * 2 / 1e6, 2), "gflop": round(2.0 * B * N * K / 1e9, 3)}
+            for name, fn in calls.items():
+                ms = []
+                for _ in range(6):
+                    e0.record()
+                    for _ in range(10):
+                        _lib.check(fn(), name)
+                    e1.record()
+                    torch.cuda.synchronize()
+                    ms.append(e0.elapsed_time(e1) / 10)
+                last = sorted(ms[1:])
+                cell[name + " us"] = round(last[2] * 1e3, 2)
+                cell[name + " us_min_max"] = [round(last[0] * 1e3, 2), round(last[-1] * 1e3, 2)]
+            cell["streams16_over_fp32_mfma"] = round(cell["gemm_streams (fp32 MFMA) us"] / cell["gemm_streams16 us"], 2)
+            cell["streams16_over_gemm16"] = round(cell["gemm16 (M = B) us"] / cell["gemm_streams16 us"], 2)
+            cells.append(cell)
+            print(json.dumps(cell), flush=True)
+        del w
+    assert _lib.get_option("lm_streams_min") == default_min
+    return cells
 
 
 def attn_kernel_session(a):
@@ -325,6 +403,9 @@ def main():
     ap.add_argument("--kv", choices=("fp32", "bf16", "fp16"), default="fp32", help="format of the K/V cache (GPT.set_cache_format)")
     ap.add_argument("--max-streams", type=int, default=16, help="streams per engine (GPT.set_max_streams, up to 128): the limit of "
                                                                  "--batch and of every --also count")
+    ap.add_argument("--streams-format", choices=("fp32", "w16"), default="fp32",
+                    help="GEMMs of a step of more than 16 streams (GPT.set_streams_format; w16 needs --weights bf16|fp16); with "
+                         "--streams-session: the record of the w16 format against the fp32 one")
     ap.add_argument("--streams-session", metavar="OUT.json", help="write the many-stream record (see above) and exit")
     ap.add_argument("--session-batches", default="8,16,32,64,128")
     ap.add_argument("--session-ctx", default="0,4608")
@@ -365,8 +446,9 @@ def main():
         with open(a.streams_session, "w") as f:
             json.dump(rec, f, indent=1)
             f.write("\n")
-        print(json.dumps({"written": a.streams_session, "vs_steps_of_16": rec["vs_steps_of_16"]}), flush=True)
+        print(json.dumps({"written": a.streams_session, "vs_steps_of_16": rec["vs_steps_of_16"], **({"w16_vs_fp32": rec["w16_vs_fp32"]} if "w16_vs_fp32" in rec else {})}), flush=True)
         return
+    m.set_streams_format(a.streams_format)
     B = a.batch
     g = torch.Generator().manual_seed(1)
     cond = torch.randint(0, V, (B, 1 + a.ctx), generator=g).cuda()
@@ -414,7 +496,7 @@ def main():
         "metric": "LM sampled tokens/sec (sample_with_past, top-k 2048 / top-p 0.9)",
         "value": round(B * a.steps / dt_sample, 1), "unit": "tokens/s", "n_gpus": 1, "batch_streams": B,
         "steps": a.steps, "ctx": a.ctx, "ms_per_token_step": round(dt_sample / a.steps * 1e3, 4),
-        "dtype": "f32", "weights": a.weights, "kv": a.kv, "data": "synthetic",
+        "dtype": "f32", "weights": a.weights, "kv": a.kv, "streams_format": a.streams_format, "data": "synthetic",
         "config": {"workload": f"GPT {L}x{C} ({H} heads, head_dim {hd}), vocab {V}, block {BS}; B={B} streams, "
                                f"{a.ctx} cached tokens + {a.steps} sampled"},
         "roofline": {"kernel": "decode step (graph replay) at the final context", "bound": "hbm",
