@@ -66,6 +66,38 @@ int omnitok_lm_weight_format(omnitok_lm *lm); /* -1: null engine */
  * (12 * n_embd^2 * n_layer + vocab_size * n_embd) * sizeof(element).  Needs no GPU; 0 for a null engine. */
 int64_t omnitok_lm_step_weight_bytes(omnitok_lm *lm);
 
+/* Weight-only fp8 for the decode step -- per engine, default OMNITOK_LM_DQ_NONE (nothing below applies then: a default engine issues
+ * exactly the launches and computes exactly the bits it did before the switch existed).  It is NOT a weight format: the weight
+ * format keeps deciding what every other path reads.  With OMNITOK_LM_DQ_FP8 omnitok_lm_finalize additionally makes, for each of
+ * the five matrix families a step streams (wqkv, attn.proj, mlp.0, mlp.2 of every block and head.weight), an OCP e4m3fn image of one
+ * byte per weight and one fp32 scale per output row, and a decode step of fewer than "lm_streams_min" (default 17) streams reads
+ * those instead of the fp32 / 16-bit image: a quarter / half of the bytes.
+ *   Scale: s[n] = 2^e with e the smallest integer such that amax_n * 2^-e <= 448 (e4m3fn's largest value).  Exactly, with
+ *     amax_n = m * 2^x, m in [0.5, 1) (frexp): e = x - 9 if m <= 0.875, else x - 8; an all-zero row has s[n] = 1; e is clamped to
+ *     [-126, 127] so that s is a normal fp32.
+ *   Weight: q[n, k] = e4m3fn(w[n, k] * 2^-e) -- the scaling is exact, the conversion ONE round to nearest even with subnormal results
+ *     kept: the bits of torch's CPU tensor.to(torch.float8_e4m3fn).  No value exceeds 448 after the scaling, so nothing saturates.
+ *     Always quantised from the fp32 values that were set, also when the weight format rounds the other images to 16 bits.
+ *   A step then computes y = act(s[n] * sum_k x[k] * q[n, k] + bias) (+ residual): s * q is exact in fp32 and so is the scaling of
+ *     the sum, i.e. an fp32 dot product of the fp32 activations with the exact fp32 values s * q in some order -- the fp32 step's
+ *     arithmetic on other weight values, as with the 16-bit formats.  Activations, accumulation, LayerNorm, attention and the K/V
+ *     cache are untouched.  e4m3 has 3 mantissa bits: relative weight error up to 2^-4 above the subnormal range of a row.
+ *   Scope: ONLY that decode step.  The batched prefill, omnitok_lm_prefill_loss and a step of "lm_streams_min" or more streams keep
+ *     running on the weight format's images, bit for bit as without the switch; option "lm_mfma" 1 does not take fp8 matrices.  So
+ *     "same arithmetic as T decode steps" does NOT hold under OMNITOK_LM_DQ_FP8: prefill and stepping compute on different weight
+ *     values (as they compute on different activations under OMNITOK_LM_PF_W16).
+ *   Non-finite weights: a NaN or an infinity in one of these matrices makes omnitok_lm_finalize fail with OMNITOK_ERR_INVALID and
+ *     the tensor's name in omnitok_last_error(); set all weights again.
+ *   Memory: the images add a quarter of the fp32 weights' bytes.  omnitok_lm_step_weight_bytes under OMNITOK_LM_DQ_FP8 is
+ *     (12 * n_embd^2 * n_layer + vocab_size * n_embd) * 1 + (12 * n_embd * n_layer + vocab_size) * 4: the scales are counted.
+ * omnitok_lm_set_decode_quant: -1 for a null engine or an unknown value (a refused value changes nothing).  Like
+ * omnitok_lm_set_weight_format it clears `finalized`: set ALL weights again, then finalize.  Independent of the weight, cache,
+ * prefill and streams formats and of max_streams. */
+#define OMNITOK_LM_DQ_NONE 0
+#define OMNITOK_LM_DQ_FP8 1
+int omnitok_lm_set_decode_quant(omnitok_lm *lm, int q);
+int omnitok_lm_decode_quant(omnitok_lm *lm); /* -1: null engine */
+
 /* Format of the K/V cache -- per engine, default OMNITOK_LM_KV_FP32 (nothing below applies then), independent of the weight format
  * (all 3 x 3 combinations work).  At long contexts the cache is the other half of a decode step's traffic (24 layers x 2 x 4608 rows
  * x 1536 x 4 B = 1.36 GB per stream and step at the reference's context), and under the reference's precision="bf16" its own
@@ -343,6 +375,19 @@ int omnitok_lm_gemv(const float *x, const float *w, const float *bias, const flo
 int omnitok_lm_gemv_w16(const float *x, const void *w16, int fmt, const float *bias, const float *residual,
                         const float *ln_gamma, const float *ln_beta, float *y, int B, int N, int K, int act,
                         omnitok_stream_t stream);
+/* omnitok_lm_gemv over an fp8 weight matrix q8 [N, K] (e4m3fn bytes, 16-byte aligned) with one fp32 scale per output row, scale [N]
+ * (powers of two, as omnitok_lm_quantize_fp8 writes them): y[b, n] = act(scale[n] * sum_k x[b, k] * float(q8[n, k]) + bias[n])
+ * (+ residual[b, n]).  Each byte is widened to fp32 in registers (exact, subnormals and +-0 included), then the same fmaf chains into
+ * fp32 accumulators; the scale multiplies the finished sum once, in front of the bias (exact for a power of two).  Same contract and
+ * argument checks otherwise (null pointers -- scale included --, unaligned x / q8, K % 256, B <= 16: -1 before any HIP call). */
+int omnitok_lm_gemv_fp8(const float *x, const void *q8, const float *scale, const float *bias, const float *residual,
+                        const float *ln_gamma, const float *ln_beta, float *y, int B, int N, int K, int act,
+                        omnitok_stream_t stream);
+/* The quantiser of omnitok_lm_set_decode_quant alone: w [N, K] fp32 -> q8 [N, K] e4m3fn bytes and scale [N] by the rule stated
+ * there.  K % 4 == 0; w and q8 16-byte aligned; -1 for null pointers (flag may be NULL), sizes outside these or unaligned pointers,
+ * before any HIP call.  *flag (an int on the device) is SET to 1 if w holds a NaN or an infinity and left alone otherwise; what q8
+ * and scale hold for the rows of such an element is not specified. */
+int omnitok_lm_quantize_fp8(const float *w, void *q8, float *scale, int N, int K, int *flag, omnitok_stream_t stream);
 /* The many-stream form: y[B, N] = act(LN(x)[B, K] . w[N, K]^T + bias) (+ residual) for 1 <= B <= 128 in one pass over w, which is
  * fp32, bf16 or fp16 (fmt = OMNITOK_LM_W_FP32 | _BF16 | _FP16; 16-byte aligned like x and y).  N >= 1, K % 256 == 0; -1 for null
  * pointers, unaligned pointers, sizes outside these or an unknown fmt, before any HIP call.  Every product is an fp32 product of an

@@ -226,6 +226,8 @@ _PROTOS = {
     "omnitok_lm_set_weight_format": [P, c_int],
     "omnitok_lm_weight_format": [P],
     "omnitok_lm_step_weight_bytes": [P],
+    "omnitok_lm_set_decode_quant": [P, c_int],
+    "omnitok_lm_decode_quant": [P],
     "omnitok_lm_set_cache_format": [P, c_int],
     "omnitok_lm_cache_format": [P],
     "omnitok_lm_set_streams_format": [P, c_int],
@@ -253,6 +255,8 @@ _PROTOS = {
     "omnitok_lm_select": [P, P, c_int, c_int, c_float, c_float, c_float, c_int, c_float, c_int, P, P, P, P, P],
     "omnitok_lm_gemv": [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P],
     "omnitok_lm_gemv_w16": [P, P, c_int, P, P, P, P, P, c_int, c_int, c_int, c_int, P],
+    "omnitok_lm_gemv_fp8": [P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P],
+    "omnitok_lm_quantize_fp8": [P, P, P, c_int, c_int, P, P],
     "omnitok_lm_gemm_streams": [P, P, c_int, P, P, P, P, P, c_int, c_int, c_int, c_int, P],
     "omnitok_lm_gemm_streams16": [P, P, c_int, P, P, P, P, c_int, c_int, c_int, c_int, P, P],
     "omnitok_lm_gemm16": [P, P, c_int, P, P, P, P, I64, c_int, c_int, c_int, P, P],

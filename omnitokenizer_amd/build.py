@@ -22,7 +22,7 @@ OBJ = os.path.join(CSRC, "_obj")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libomnitok.so")
 SOURCES = ["common.cpp", "gemm.hip", "gemm_x3.hip", "gemm_h2.hip", "gemm_pl.hip", "gemm_plt.hip", "norm.hip", "peg.hip", "attn_spatial.hip", "attn_h2.hip", "attn_temporal.hip",
-           "vq.hip", "resample.hip", "frames.hip", "resize_pil.hip", "metrics.hip", "i3d.hip", "inception.hip", "lpips.hip", "losses.hip", "engine.hip", "engine_build.hip", "engine_run.hip", "lm_gemv.hip", "lm_gemv_ks.hip", "lm_gemm_mfma.hip", "lm_gemm_streams16.hip", "lm_gemm16.hip", "lm_attn.hip", "lm_attn_prefill.hip", "lm_engine.hip", "lm_select.hip", "lm_loss.hip", "dit_ops.hip", "dit_attn.hip", "dit_gemm16.hip", "dit_engine.hip", "latte_attn.hip", "latte_ops.hip", "latte_engine.hip", "debug.hip", "comm.hip"]
+           "vq.hip", "resample.hip", "frames.hip", "resize_pil.hip", "metrics.hip", "i3d.hip", "inception.hip", "lpips.hip", "losses.hip", "engine.hip", "engine_build.hip", "engine_run.hip", "lm_gemv.hip", "lm_gemv_ks.hip", "lm_quant.hip", "lm_gemm_mfma.hip", "lm_gemm_streams16.hip", "lm_gemm16.hip", "lm_attn.hip", "lm_attn_prefill.hip", "lm_engine.hip", "lm_select.hip", "lm_loss.hip", "dit_ops.hip", "dit_attn.hip", "dit_gemm16.hip", "dit_engine.hip", "latte_attn.hip", "latte_ops.hip", "latte_engine.hip", "debug.hip", "comm.hip"]
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_common.h"), os.path.join(CSRC, "gemm_x_common.h"), os.path.join(CSRC, "gemm_row_host.h"), os.path.join(CSRC, "attn_host.h"), os.path.join(CSRC, "h2_common.h"), os.path.join(CSRC, "gemm_pl.h"), os.path.join(CSRC, "gemm_plt.h"), os.path.join(CSRC, "engine.h"), os.path.join(CSRC, "planes.h"), os.path.join(CSRC, "peg_wide.h"), os.path.join(CSRC, "convnet_common.h"), os.path.join(CSRC, "lm_common.h"), os.path.join(CSRC, "dit_common.h"), os.path.join(CSRC, "dit_scaffold.h"), os.path.join(CSRC, "latte_common.h"), os.path.join(CSRC, "attn_f32_tiled.h"), os.path.join(CSRC, "attn16_tiled.h"), os.path.join(CSRC, "gemm16_tile.h"),
            os.path.join(os.path.dirname(HERE), "include", "omnitok.h"),
            os.path.join(os.path.dirname(HERE), "include", "omnitok_lm.h"),

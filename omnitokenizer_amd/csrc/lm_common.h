@@ -10,8 +10,9 @@
 // Which unit holds what (every kernel template lives in the one .hip that launches it; this header defines no kernel):
 //   lm_common.h       the constants, the weight / cache element types (LmW, lm_round16, LmKV), LmMerge, the host types LmMat and
 //                     LmLinear, the format dispatches lm_with_wt / lm_with_kt, lm_grow, and the host functions that cross units
-//   lm_gemv.hip       lm_gemv_kernel (the row GEMV), lm_gemv_any (the loop over groups of 8 / 4 / 2 / 1 streams), omnitok_lm_gemv[_w16]
+//   lm_gemv.hip       lm_gemv_kernel (the row GEMV), lm_gemv_any (the loop over groups of 8 / 4 / 2 / 1 streams), omnitok_lm_gemv[_w16|_fp8]
 //   lm_gemv_ks.hip    lm_gemv_ks_kernel (the K-sliced GEMV of K in {1536, 2048, 6144, 8192}) behind lm_gemv_ks_try; LM_TRACE
+//   lm_quant.hip      lm_quantize_fp8_kernel (row amax -> power-of-two scale -> packed e4m3fn image), omnitok_lm_quantize_fp8
 //   lm_gemm_mfma.hip  lm_gemm4_kernel (4 .. 8 streams on the matrix cores, "lm_mfma" 1) behind lm_gemm4_try; lm_gemm_streams_kernel and
 //                     lm_streams_reduce_kernel (17 .. 128 streams, omnitok_lm_set_max_streams), omnitok_lm_gemm_streams
 //   lm_gemm_streams16.hip  lm_gemm_streams16_kernel and lm_streams16_reduce_kernel (17 .. 128 streams on the 16-bit MFMA over packed
@@ -46,11 +47,13 @@ constexpr int LM_MAX_HEADS = 32;   // (bounds the merge-weight table in LDS: B *
 
 // Weight element types of the decode GEMVs (omnitok_lm_set_weight_format).  Both kernels below take the element type WT as a template
 // parameter; a lane's share of a 256-column chunk is always the same 4 consecutive weights -- 16 bytes of fp32, 8 bytes of a 16-bit
-// format -- widened to fp32 in registers (exact) in front of the same fmaf chain.  WT = float compiles to the code it was before.
+// format, 4 bytes of fp8 -- widened to fp32 in registers (exact) in front of the same fmaf chain.  WT = float compiles to the code it
+// was before.
 struct lm_bf16 { unsigned short bits; };
 struct lm_fp16 { unsigned short bits; };
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+struct lm_fp8 { unsigned char bits; };  // OCP e4m3fn, the decode-quant image (omnitok_lm_set_decode_quant): 4 weights are one dword
 template <typename WT> struct LmW;
 template <> struct LmW<float> {
     typedef f32x4 quad;  // 4 consecutive weights as loaded
@@ -80,6 +83,19 @@ template <> struct LmW<lm_fp16> {
     }
     static __device__ __forceinline__ quad load(__amdgpu_buffer_rsrc_t rs, int byte_off) {
         return __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(rs, byte_off, 0, 2));
+    }
+};
+
+template <> struct LmW<lm_fp8> {
+    typedef unsigned quad;
+    // e4m3fn -> fp32 of each byte, subnormals and +-0 included (exact): v_cvt_pk_f32_fp8 on the low and the high half of the dword.  The
+    // row's power-of-two scale is NOT applied here but once per output, in the kernels' epilogue (exact as well)
+    static __device__ __forceinline__ f32x4 widen(const unsigned &q) {
+        const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)q, false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)q, true);
+        return f32x4{lo[0], lo[1], hi[0], hi[1]};
+    }
+    static __device__ __forceinline__ quad load(__amdgpu_buffer_rsrc_t rs, int byte_off) {
+        return (unsigned)__builtin_amdgcn_raw_buffer_load_b32(rs, byte_off, 0, 2);
     }
 };
 
@@ -141,13 +157,22 @@ struct LmMerge {
 // One weight matrix of the decode step.  w32: the fp32 matrix | w16 != nullptr: its packed image in format fmt (OMNITOK_LM_W_BF16 /
 // _FP16), which every group of streams then takes: the 16-bit kernels measured faster than the fp32 ones over the rounded fp32 image
 // at 1, 2, 4 and 8 streams, so no group is routed back.
-struct LmMat { const float *w32; const void *w16; int fmt; };  // w16 == nullptr: fp32
+// w8 != nullptr (omnitok_lm_set_decode_quant, OMNITOK_LM_DQ_FP8): the e4m3fn image of the matrix [N, K] and its per-row scales
+// scale [N] (powers of two).  Only lm_gemv_any reads them -- the decode step of fewer than "lm_streams_min" streams -- and there they
+// take precedence over w32 / w16; every other consumer of an LmMat keeps reading the weight format's images.
+struct LmMat { const float *w32; const void *w16; int fmt; const void *w8 = nullptr; const float *scale = nullptr; };  // w16 == nullptr: fp32
 // the one dispatch on the weight format: f(the matrix as const float * | const lm_bf16 * | const lm_fp16 *)
 template <class F>
 auto lm_with_wt(const LmMat &m, F &&f) {
     if (!m.w16) return f(m.w32);
     if (m.fmt == OMNITOK_LM_W_BF16) return f(static_cast<const lm_bf16 *>(m.w16));
     return f(static_cast<const lm_fp16 *>(m.w16));
+}
+// ... and with the fp8 image in front, for the two VALU GEMV kernels: f(const lm_fp8 *) when the matrix carries one
+template <class F>
+auto lm_with_wt_dq(const LmMat &m, F &&f) {
+    if (m.w8) return f(static_cast<const lm_fp8 *>(m.w8));
+    return lm_with_wt(m, f);
 }
 // the one dispatch on the cache format: f(a value of the cache's element type)
 template <class F>
@@ -249,5 +274,10 @@ int lm_layernorm_rows(const float *x, const float *g, const float *beta, float *
 // contract of omnitok_lm_gemm16, its argument checks included
 int lm_gemm16(const void *a16, const void *w16, int fmt, const float *bias, const float *residual, float *y32, void *y16, int64_t M,
               int N, int K, int act, int *flag, hipStream_t stream);
+// lm_quant.hip.  The fp8 image of w [N, K] (K % 4 == 0): scale[n] = 2^e with e the smallest integer such that amax_n 2^-e <= 448 (1 for
+// a zero row), q8[n, k] = e4m3fn(w[n, k] 2^-e), one round to nearest even.  A row with a NaN or an infinity sets flags[n / seg_rows]
+// (flags may be nullptr); what q8 and scale hold for such a row is not specified.  The contract of omnitok_lm_quantize_fp8 without
+// its argument checks
+int lm_quantize_fp8(const float *w, void *q8, float *scale, int N, int K, int seg_rows, int *flags, hipStream_t stream);
 
 }  // namespace omnitok

@@ -201,6 +201,7 @@ struct omnitok_lm {
     std::vector<LmLayer> layers;
     bool finalized = false;
     int weight_format = OMNITOK_LM_W_FP32;  // of the matrices a decode step streams (omnitok_lm_set_weight_format)
+    int decode_quant = OMNITOK_LM_DQ_NONE;  // the fp8 image a decode step of up to 16 streams reads instead (omnitok_lm_set_decode_quant)
     int prefill_format = OMNITOK_LM_PF_FP32;  // how the batched prefill runs its GEMMs (omnitok_lm_set_prefill_format)
     int prefill_attention = OMNITOK_LM_PA_ROWS;  // how the batched prefill runs its attention (omnitok_lm_set_prefill_attention)
     int prefill_attention_operands = OMNITOK_LM_AOP_FP32;  // operand format of the tiled attention (omnitok_lm_set_prefill_attention_operands)
@@ -337,6 +338,19 @@ extern "C" int omnitok_lm_weight_format(omnitok_lm *lm) {
     return lm->weight_format;
 }
 
+extern "C" int omnitok_lm_set_decode_quant(omnitok_lm *lm, int q) {
+    OT_CHECK_ARG(lm, "lm_set_decode_quant: null engine");
+    OT_CHECK_ARG(q == OMNITOK_LM_DQ_NONE || q == OMNITOK_LM_DQ_FP8, "lm_set_decode_quant: unknown value %d", q);
+    lm->decode_quant = q;
+    lm->finalized = false;  // the images are made (or dropped) by the next finalize, from weights set again
+    return OMNITOK_OK;
+}
+
+extern "C" int omnitok_lm_decode_quant(omnitok_lm *lm) {
+    OT_CHECK_ARG(lm, "lm_decode_quant: null engine");
+    return lm->decode_quant;
+}
+
 extern "C" int omnitok_lm_set_prefill_format(omnitok_lm *lm, int fmt) {
     OT_CHECK_ARG(lm, "lm_set_prefill_format: null engine");
     OT_CHECK_ARG(fmt == OMNITOK_LM_PF_FP32 || fmt == OMNITOK_LM_PF_W16, "lm_set_prefill_format: unknown format %d", fmt);
@@ -418,6 +432,8 @@ extern "C" int omnitok_lm_max_streams(omnitok_lm *lm) {
 extern "C" int64_t omnitok_lm_step_weight_bytes(omnitok_lm *lm) {
     if (!lm) return 0;
     const int64_t C = lm->cfg.n_embd, V = lm->cfg.vocab_size;
+    if (lm->decode_quant == OMNITOK_LM_DQ_FP8)  // one byte per weight and one fp32 scale per output row
+        return (12 * C * C * lm->cfg.n_layer + V * C) + (12 * C * lm->cfg.n_layer + V) * 4;
     return (12 * C * C * lm->cfg.n_layer + V * C) * (lm->weight_format == OMNITOK_LM_W_FP32 ? 4 : 2);
 }
 
@@ -469,11 +485,56 @@ extern "C" int omnitok_lm_finalize(omnitok_lm *lm, omnitok_stream_t stream_) {
         lm->layers.push_back(L);
     }
     lm->head = {LW(lm, "head.weight"), nullptr, OMNITOK_LM_W_FP32};
+    // one flag per source tensor of the five matrix families (6 per layer + the head) -> the tensor's name
+    const int nflags = 6 * lm->cfg.n_layer + 1;
+    auto first_flagged = [&](int *flags, std::string *name) -> int {
+        std::vector<int> hf((size_t)nflags);
+        OT_HIP(hipMemcpyAsync(hf.data(), flags, (size_t)nflags * sizeof(int), hipMemcpyDeviceToHost, stream));
+        OT_HIP(hipStreamSynchronize(stream));
+        for (int f = 0; f < nflags && name->empty(); ++f)
+            if (hf[(size_t)f]) {
+                static const char *const names[6] = {".attn.query.weight", ".attn.key.weight", ".attn.value.weight",
+                                                     ".attn.proj.weight", ".mlp.0.weight", ".mlp.2.weight"};
+                *name = f == nflags - 1 ? std::string("head.weight") : "blocks." + std::to_string(f / 6) + names[f % 6];
+            }
+        return OMNITOK_OK;
+    };
+    std::string nonfinite;  // the first tensor with a NaN or an infinity (only looked for by the fp8 quantiser)
+    if (lm->decode_quant == OMNITOK_LM_DQ_FP8) {
+        // the fp8 image and the row scales of the five matrix families, for the decode step of up to 16 streams -- made BEFORE the
+        // 16-bit rounding below overwrites the fp32 images: always from the fp32 originals, whatever the weight format is
+        const int64_t V = lm->cfg.vocab_size;
+        int *flags = nullptr;
+        OT_HIP(hipMalloc(reinterpret_cast<void **>(&flags), (size_t)nflags * sizeof(int)));
+        lm->owned.push_back(flags);
+        OT_HIP(hipMemsetAsync(flags, 0, (size_t)nflags * sizeof(int), stream));
+        auto quant = [&](LmMat &m, int64_t N, int64_t K, int64_t seg_rows, int *fl) -> int {
+            void *p8 = nullptr, *sc = nullptr;
+            OT_HIP(hipMalloc(&p8, (size_t)(N * K)));
+            lm->owned.push_back(p8);
+            OT_HIP(hipMalloc(&sc, (size_t)N * 4));
+            lm->owned.push_back(sc);
+            if (int rc = lm_quantize_fp8(m.w32, p8, static_cast<float *>(sc), (int)N, (int)K, (int)seg_rows, fl, stream)) return rc;
+            m.w8 = p8;
+            m.scale = static_cast<const float *>(sc);
+            return OMNITOK_OK;
+        };
+        for (int i = 0; i < lm->cfg.n_layer; ++i) {
+            LmLayer &L = lm->layers[i];
+            int *fl = flags + 6 * i;
+            if (int rc = quant(L.wqkv, 3 * C, C, C, fl)) return rc;
+            if (int rc = quant(L.wproj, C, C, C, fl + 3)) return rc;
+            if (int rc = quant(L.w1, 4 * C, C, 4 * C, fl + 4)) return rc;
+            if (int rc = quant(L.w2, C, 4 * C, C, fl + 5)) return rc;
+        }
+        if (int rc = quant(lm->head, V, C, V, flags + 6 * lm->cfg.n_layer)) return rc;
+        if (int rc = first_flagged(flags, &nonfinite)) return rc;
+    }
     std::string overflow;  // the first tensor with an element outside the fp16 range
     if (lm->weight_format != OMNITOK_LM_W_FP32) {
         // 16-bit format: round the five matrix families on the device -- packed image for the decode GEMVs, rounded values back into
         // the fp32 image for the prefill GEMMs.  One overflow flag per source tensor (6 per layer + the head).
-        const int fmt = lm->weight_format, nflags = 6 * lm->cfg.n_layer + 1;
+        const int fmt = lm->weight_format;
         const int64_t V = lm->cfg.vocab_size;
         int *flags = nullptr;
         OT_HIP(hipMalloc(reinterpret_cast<void **>(&flags), (size_t)nflags * sizeof(int)));
@@ -501,15 +562,7 @@ extern "C" int omnitok_lm_finalize(omnitok_lm *lm, omnitok_stream_t stream_) {
             if (int rc = round(L.w2, 4 * C * C, 4 * C * C, fl + 5)) return rc;
         }
         if (int rc = round(lm->head, V * C, V * C, flags + 6 * lm->cfg.n_layer)) return rc;
-        std::vector<int> hf((size_t)nflags);
-        OT_HIP(hipMemcpyAsync(hf.data(), flags, (size_t)nflags * sizeof(int), hipMemcpyDeviceToHost, stream));
-        OT_HIP(hipStreamSynchronize(stream));
-        for (int f = 0; f < nflags && overflow.empty(); ++f)
-            if (hf[(size_t)f]) {
-                static const char *const names[6] = {".attn.query.weight", ".attn.key.weight", ".attn.value.weight",
-                                                     ".attn.proj.weight", ".mlp.0.weight", ".mlp.2.weight"};
-                overflow = f == nflags - 1 ? std::string("head.weight") : "blocks." + std::to_string(f / 6) + names[f % 6];
-            }
+        if (int rc = first_flagged(flags, &overflow)) return rc;
     }
     // the separate q/k/v copies are no longer needed: free them (2.7 GB model -> no duplicate)
     OT_HIP(hipStreamSynchronize(stream));
@@ -523,6 +576,12 @@ extern "C" int omnitok_lm_finalize(omnitok_lm *lm, omnitok_stream_t stream_) {
                     lm->w[k] = nullptr;
                 }
             }
+    if (!nonfinite.empty()) {
+        // as below: the q/k/v sources are gone, so the next finalize wants all weights set again
+        set_error("lm_finalize: %s has a NaN or an infinity: the fp8 decode image (omnitok_lm_set_decode_quant, OMNITOK_LM_DQ_FP8) "
+                  "needs finite weights; set all weights again", nonfinite.c_str());
+        return OMNITOK_ERR_INVALID;
+    }
     if (!overflow.empty()) {
         // the fp32 images already hold the fp16-rounded values (some +-inf).  The q/k/v sources were released above like after any
         // finalize, so a finalize in another format without setting the weights again is refused ("released by a previous finalize")

@@ -1,4 +1,4 @@
-// LM decode: the row GEMV kernel, the loop over groups of streams, omnitok_lm_gemv / omnitok_lm_gemv_w16 (index: lm_common.h)
+// LM decode: the row GEMV kernel, the loop over groups of streams, omnitok_lm_gemv / _gemv_w16 / _gemv_fp8 (index: lm_common.h)
 #include "lm_common.h"
 #include "gemm_x_common.h"  // gelu_erf
 
@@ -18,7 +18,9 @@ template <typename WT, int BQ, int ROWS, int U, int ACT, bool LN, bool XM, int N
 __global__ __launch_bounds__(NW * 64) void lm_gemv_kernel(const float *__restrict__ x, const WT *__restrict__ w,
                                                       const float *__restrict__ bias, const float *residual,
                                                       const float *__restrict__ g, const float *__restrict__ beta,
-                                                      float *y, int N, int K, LmMerge mg) {
+                                                      float *y, int N, int K, LmMerge mg, const float *__restrict__ scale) {
+    // scale [N]: the row scales of an fp8 matrix (WT = lm_fp8, powers of two: an exact multiplication of the finished dot product in
+    // front of the bias); not read by any other instantiation
     extern __shared__ __attribute__((aligned(16))) float xs[];  // [BQ][kp]
     __shared__ float s_mean[BQ], s_rstd[BQ];
     constexpr int NT = NW * 64;  // NW waves per workgroup: the launcher picks NW and ROWS so that the grid is a whole number of
@@ -246,6 +248,7 @@ __global__ __launch_bounds__(NW * 64) void lm_gemv_kernel(const float *__restric
         const int r = lane / BQ, b = lane % BQ, n = row0 + r;
         if (n < N) {
             float v = mine;
+            if constexpr (__is_same(WT, lm_fp8)) v *= scale[n];
             if (bias) v += bias[n];
             if (ACT == 1) v = gelu_erf(v);
             if (residual) v += residual[(int64_t)b * N + n];
@@ -269,13 +272,13 @@ static void launch_gemv_cfg(const WT *w, const LmLinear &c, const LmMerge &mg, h
     const int rows_per_wg = NW * ROWS;
     if (lds > 65536) (void)set_max_dynamic_lds(reinterpret_cast<const void *>(lm_gemv_kernel<WT, BQ, ROWS, U, ACT, LN, XM, NW>), lds);
     hipLaunchKernelGGL((lm_gemv_kernel<WT, BQ, ROWS, U, ACT, LN, XM, NW>), dim3((c.N + rows_per_wg - 1) / rows_per_wg), dim3(NW * 64),
-                       lds, stream, c.x, w, c.bias, c.residual, c.ln_g, c.ln_b, c.y, c.N, c.K, mg);
+                       lds, stream, c.x, w, c.bias, c.residual, c.ln_g, c.ln_b, c.y, c.N, c.K, mg, c.w.scale);
 }
 
 template <int BQ, int ACT, bool LN, bool XM, typename WT>
 static void launch_gemv_rows(const WT *w, const LmLinear &c, const LmMerge &mg, hipStream_t stream) {
     // ROWS weight rows x U chunks (x2 register buffers) per wave = 8 KiB of fp32 weights in flight per wave.  The 16-bit
-    // instantiations keep ROWS and U (4 KiB in flight): the row kernel serves no GEMV of the reference's LM, it was taken as it is
+    // instantiations keep ROWS and U (4 KiB in flight; 2 KiB of fp8): the row kernel serves no GEMV of the reference's LM, it was taken as it is
     // and not A/B'd -- the rows-per-group A/B (lm_gemv_ks.hip) is about the K-sliced kernel only.
     // Narrow outputs (N <= 2048: the C x C and C x 4C projections) take one row per wave so that the
     // launch still covers every CU.  Wide outputs: 2 rows x 2 chunks x 2 buffers per wave, i.e. a whole K = 1536 row pair is
@@ -319,7 +322,7 @@ int lm_gemv_any(const LmLinear &c, const LmMerge *mg, hipStream_t stream) {
             m2.cache_len += b0;
         }
         const bool mfma_k = K == 1536 || K == 2048 || (!c.ln_g && (K == 6144 || K == 8192));
-        if (g_lm_mfma && !c.w.w16 && left >= 4 && mfma_k && N >= 16 && (int64_t)N * K < (1ll << 29) && (!mg || mg->merged)) {
+        if (g_lm_mfma && !c.w.w16 && !c.w.w8 && left >= 4 && mfma_k && N >= 16 && (int64_t)N * K < (1ll << 29) && (!mg || mg->merged)) {
             // 4 .. 8 streams in one pass over the weights on the matrix cores (lm_gemm4_kernel)
             g.B = left > 8 ? 8 : left;
             if (mg) {   // the merged attention output as a tensor first (the VALU path merges inside its prologue)
@@ -336,7 +339,7 @@ int lm_gemv_any(const LmLinear &c, const LmMerge *mg, hipStream_t stream) {
         g.B = left >= 8 ? 8 : (left >= 4 ? 4 : (left >= 2 ? 2 : 1));
         // the K-sliced kernel where it has the shape, the row kernel for every other
         if (!lm_gemv_ks_try(g, m2, mg != nullptr, stream))
-            lm_with_wt(g.w, [&](auto *w) {
+            lm_with_wt_dq(g.w, [&](auto *w) {
                 lm_with_gemv_cfg(g, mg != nullptr, [&](auto bq, auto act, auto ln, auto xm) {
                     launch_gemv_rows<decltype(bq)::value, decltype(act)::value, decltype(ln)::value, decltype(xm)::value>(w, g, m2, stream);
                 });
@@ -353,7 +356,7 @@ int lm_linear_check(const char *who, int bmax, const LmLinear &c, bool y16) {
                  c.K, bmax);
     OT_CHECK_ARG((c.ln_g != nullptr) == (c.ln_b != nullptr), "%s: ln_gamma / ln_beta must come together", who);
     OT_CHECK_ARG(c.act == 0 || c.act == 1, "%s: act %d", who, c.act);
-    OT_CHECK_ARG(aligned16(c.x) && aligned16(c.w.w16 ? c.w.w16 : c.w.w32) && (!y16 || aligned16(c.y)), "%s: unaligned", who);
+    OT_CHECK_ARG(aligned16(c.x) && aligned16(c.w.w8 ? c.w.w8 : c.w.w16 ? c.w.w16 : c.w.w32) && (!y16 || aligned16(c.y)), "%s: unaligned", who);
     return OMNITOK_OK;
 }
 
@@ -379,5 +382,15 @@ extern "C" int omnitok_lm_gemv_w16(const float *x, const void *w16, int fmt, con
     if (B == 0) return OMNITOK_OK;
     const LmLinear c{x, {nullptr, w16, fmt}, bias, residual, ln_gamma, ln_beta, y, B, N, K, act};
     if (int rc = lm_linear_check("lm_gemv_w16", 16, c, false)) return rc;
+    return lm_gemv_any(c, nullptr, static_cast<hipStream_t>(stream_));
+}
+
+extern "C" int omnitok_lm_gemv_fp8(const float *x, const void *q8, const float *scale, const float *bias, const float *residual,
+                                   const float *ln_gamma, const float *ln_beta, float *y, int B, int N, int K, int act,
+                                   omnitok_stream_t stream_) {
+    OT_CHECK_ARG(x && q8 && scale && y, "lm_gemv_fp8: null pointer");
+    if (B == 0) return OMNITOK_OK;
+    const LmLinear c{x, {nullptr, nullptr, OMNITOK_LM_W_FP32, q8, scale}, bias, residual, ln_gamma, ln_beta, y, B, N, K, act};
+    if (int rc = lm_linear_check("lm_gemv_fp8", 16, c, false)) return rc;
     return lm_gemv_any(c, nullptr, static_cast<hipStream_t>(stream_));
 }

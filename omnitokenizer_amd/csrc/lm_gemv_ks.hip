@@ -66,7 +66,11 @@ template <typename WT, int BQ, int CW, int RG, int ACT, bool LN, bool XM, int NW
 __global__ __launch_bounds__(NW * 64) void lm_gemv_ks_kernel(const float *__restrict__ x, const WT *__restrict__ w,
                                                              const float *__restrict__ bias, const float *residual,
                                                              const float *__restrict__ g, const float *__restrict__ beta,
-                                                             float *y, int N, int K, LmMerge mg, long long *trace) {
+                                                             float *y, int N, int K, LmMerge mg, long long *trace,
+                                                             const float *__restrict__ scale) {
+    // scale [N]: the row scales of an fp8 matrix (WT = lm_fp8), multiplied onto the finished dot product in front of the bias (powers
+    // of two: exact); no other instantiation reads it
+    constexpr bool W8 = __is_same(WT, lm_fp8);
     extern __shared__ float ks_part[];  // [rows of this workgroup][BQ][NW]
     auto stamp = [&](int k) {
         if constexpr (LM_TRACE)
@@ -98,7 +102,7 @@ __global__ __launch_bounds__(NW * 64) void lm_gemv_ks_kernel(const float *__rest
     const int fr = tid / BQ < nrows ? tid / BQ : nrows - 1, fb = tid % BQ, fn = r_begin + fr;
     const float *w_any = reinterpret_cast<const float *>(w);  // (a valid address for the loads whose value is not used)
     const float *bias_p = bias ? bias + fn : w_any, *res_p = residual ? residual + (int64_t)fb * N + fn : w_any;
-    float e_bias, e_res;
+    float e_bias, e_res, e_scale = 1.0f;
     // ---- this wave's slice of the activations -> registers, then the weights of the first two row groups ----
     if constexpr (XM) {
         // merged attention partials (see lm_gemv_kernel): every lane merges the head its 4 columns belong to.  The partials of the
@@ -133,6 +137,7 @@ __global__ __launch_bounds__(NW * 64) void lm_gemv_ks_kernel(const float *__rest
         load_w(wb, 1);
         e_bias = *bias_p;
         e_res = *res_p;
+        if constexpr (W8) e_scale = scale[fn];
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int b = 0; b < BQ; ++b) {
@@ -201,6 +206,7 @@ __global__ __launch_bounds__(NW * 64) void lm_gemv_ks_kernel(const float *__rest
         load_w(wb, 1);
         e_bias = *bias_p;
         e_res = *res_p;
+        if constexpr (W8) e_scale = scale[fn];
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (WAVE_LN) {
             // nn.LayerNorm, two-pass like ATen.  Every wave reduces the WHOLE row itself (xf: NW * CW float4 per lane, L2 hits for all but
@@ -308,6 +314,7 @@ __global__ __launch_bounds__(NW * 64) void lm_gemv_ks_kernel(const float *__rest
         float v = 0.0f;
 #pragma unroll
         for (int w8 = 0; w8 < NW; ++w8) v += ks_part[(fr * BQ + fb) * NW + w8];
+        if constexpr (W8) v *= e_scale;
         if (bias) v += e_bias;
         if (ACT == 1) v = gelu_erf(v);
         if (residual) v += e_res;
@@ -349,10 +356,10 @@ static bool launch_gemv_ks(const WT *w, const LmLinear &c, const LmMerge &mg, hi
         const int max_rows = (N + grid - 1) / grid + 1;
         if (N >= grid && max_rows * BQ <= 6 * 64) {
             const int lds = max_rows * BQ * 8 * 4;
-            constexpr bool W16 = sizeof(WT) == 2;
+            constexpr bool W16 = sizeof(WT) < 4;  // a packed format: bf16 / fp16, or the fp8 image (1 KiB per row group and chunk; not A/B'd)
 #define OT_KS1(CW_, RG_, NW_)                                                                                                        \
     hipLaunchKernelGGL((lm_gemv_ks_kernel<WT, BQ, CW_, RG_, ACT, LN, XM, NW_>), dim3(grid), dim3(NW_ * 64), lds, stream, c.x, w, c.bias, c.residual, \
-                       c.ln_g, c.ln_b, c.y, N, K, mg, lm_trace_slot(grid))
+                       c.ln_g, c.ln_b, c.y, N, K, mg, lm_trace_slot(grid), c.w.scale)
 #define OT_KS(CW_, RG_, NW_)                        \
     {                                               \
         if (deep) OT_KS1(CW_, RG_ * DEEP, NW_);     \
@@ -376,7 +383,7 @@ static bool launch_gemv_ks(const WT *w, const LmLinear &c, const LmMerge &mg, hi
 }
 
 bool lm_gemv_ks_try(const LmLinear &c, const LmMerge &mg, bool xm, hipStream_t stream) {
-    return lm_with_wt(c.w, [&](auto *w) {
+    return lm_with_wt_dq(c.w, [&](auto *w) {
         return lm_with_gemv_cfg(c, xm, [&](auto bq, auto act, auto ln, auto xm_) {
             return launch_gemv_ks<decltype(bq)::value, decltype(act)::value, decltype(ln)::value, decltype(xm_)::value>(w, c, mg, stream);
         });

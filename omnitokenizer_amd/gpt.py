@@ -6,7 +6,7 @@ sampling path, plus its sampling loops `sample_with_past` (:327-359) and `sample
 The class owns the parameters under the reference's state_dict key names; all arithmetic of a decode
 step runs in libomnitok.so (include/omnitok_lm.h, csrc/lm_engine.hip and the other csrc/lm_*.hip): a preallocated K/V cache instead of
 the reference's per-step torch.cat of all pasts, GEMV kernels that stream each weight matrix
-once per step (fp32, or bf16 / fp16 at half the bytes: GPT.set_weight_format), flash-decode
+once per step (fp32, or bf16 / fp16 at half the bytes: GPT.set_weight_format; or an fp8 image at a quarter: GPT.set_decode_quant), flash-decode
 attention over an fp32, bf16 or fp16 cache (GPT.set_cache_format), up to 16 streams per engine or, on an fp32-MFMA GEMM that reads
 each matrix once for the whole batch, up to 128 (GPT.set_max_streams), and -- because the step's launch sequence does not depend on the position -- one
 captured HIP graph replayed per token.  Token selection (temperature, the CFG blend,
@@ -28,11 +28,43 @@ from ._lib import OmnitokLmConfig, check
 
 
 WEIGHT_FORMATS = {"fp32": 0, "bf16": 1, "fp16": 2}  # OMNITOK_LM_W_* of include/omnitok_lm.h
+DECODE_QUANTS = {"none": 0, "fp8": 1}               # OMNITOK_LM_DQ_*
 KV_FORMATS = {"fp32": 0, "bf16": 1, "fp16": 2}      # OMNITOK_LM_KV_*
 PREFILL_FORMATS = {"fp32": 0, "w16": 1}             # OMNITOK_LM_PF_*
 PREFILL_ATTENTIONS = {"rows": 0, "tiled": 1}        # OMNITOK_LM_PA_*
 STREAMS_FORMATS = {"fp32": 0, "w16": 1}             # OMNITOK_LM_SF_*
 PREFILL_ATTENTION_OPERANDS = {"fp32": 0, "bf16": 1, "fp16": 2}  # OMNITOK_LM_AOP_*
+
+
+_FP8_MATRICES = (".attn.key.weight", ".attn.query.weight", ".attn.value.weight", ".attn.proj.weight", ".mlp.0.weight", ".mlp.2.weight")
+
+
+def fp8_quantize_rows(w):
+    """(q, s) of a float32 matrix w [N, K] by the rule of omnitok_lm_set_decode_quant, on the CPU with torch: s[n] = 2^e with e the
+    smallest integer such that amax_n 2^-e <= 448 -- with amax_n = m 2^x, m in [0.5, 1) (frexp): e = x - 9 if m <= 0.875 else
+    x - 8; 1 for an all-zero row; e clamped to [-126, 127] -- and q = (w 2^-e).to(torch.float8_e4m3fn): an exact scaling and one
+    round to nearest even.  q is a float8_e4m3fn tensor [N, K], s a float32 tensor [N]."""
+    w = w.detach().to("cpu", torch.float32)
+    m, x = torch.frexp(w.abs().amax(dim=1))
+    e = torch.where(m <= 0.875, x - 9, x - 8).clamp(-126, 127)
+    e = torch.where(m == 0, torch.zeros_like(e), e)
+    q = torch.ldexp(w, -e[:, None]).to(torch.float8_e4m3fn)
+    return q, torch.ldexp(torch.ones_like(m), e)
+
+
+def fp8_dequantized(state_dict):
+    """The state dict a GPT under set_decode_quant("fp8") steps with: the five matrix families of a decode step (q/k/v, proj,
+    mlp.0, mlp.2 of every block and head.weight) replaced by s * q (exact in float32; fp8_quantize_rows), every other tensor as it
+    is.  Loaded into a GPT with the switch off it measures what fp8 costs a checkpoint (validation_step), and it is the
+    restatement the tests hold the fp8 step to."""
+    out = {}
+    for k, v in state_dict.items():
+        if k == "head.weight" or k.endswith(_FP8_MATRICES):
+            q, s = fp8_quantize_rows(v)
+            out[k] = (q.float() * s[:, None]).to(v.device)
+        else:
+            out[k] = v
+    return out
 
 
 class _Holder(nn.Module):
@@ -107,6 +139,7 @@ class GPT(nn.Module):
         self._pos = self._len = None
         self._graphs = {}
         self._weight_format = "fp32"
+        self._decode_quant = "none"
         self._cache_format = "fp32"
         self._prefill_format = "fp32"
         self._prefill_attention = "rows"
@@ -163,6 +196,26 @@ class GPT(nn.Module):
         if fmt not in WEIGHT_FORMATS:
             raise ValueError(f"weight format {fmt!r}: expected one of {sorted(WEIGHT_FORMATS)}")
         self._weight_format = fmt
+        self._engine_sig = None
+        self._graphs = {}
+        return self
+
+    @property
+    def decode_quant(self) -> str:
+        return self._decode_quant
+
+    def set_decode_quant(self, name: str):
+        """Weight-only quantisation of the decode step (include/omnitok_lm.h, omnitok_lm_set_decode_quant): "none" (default) or
+        "fp8": the engine additionally keeps an e4m3fn image of the q/k/v, proj, mlp and head matrices with one power-of-two scale
+        per output row (the rule: fp8_dequantized below), always quantised from the float32 parameters, and a decode step of up to
+        16 streams streams that image -- a quarter of the fp32 bytes -- instead of the weight format's.  Activations,
+        accumulation, LayerNorm, attention and the K/V cache stay as they are.  It is not a weight format: forward, token_losses,
+        prefill (the conditioning prefix of the sampling loops included) and steps of more than 16 streams keep the weight
+        format's arithmetic bit for bit, so prefill and stepping then compute on different weight values.  The module's
+        parameters and state_dict() are unchanged; the captured graphs are dropped.  A non-finite weight raises at the next use."""
+        if name not in DECODE_QUANTS:
+            raise ValueError(f"decode quant {name!r}: expected one of {sorted(DECODE_QUANTS)}")
+        self._decode_quant = name
         self._engine_sig = None
         self._graphs = {}
         return self
@@ -305,8 +358,11 @@ class GPT(nn.Module):
         """Bytes of weight matrices one decode step with logits streams in the current format (needs no GPU)."""
         if self._engine is not None and self._engine_sig is not None:  # a synced engine: its own count
             return int(_lib.load().omnitok_lm_step_weight_bytes(self._engine))
+        C, L, V = self.n_embd, self.n_layer, self.vocab_size
+        if self._decode_quant == "fp8":  # a byte per weight and an fp32 scale per output row
+            return (12 * C * C * L + V * C) + (12 * C * L + V) * 4
         per = 4 if self._weight_format == "fp32" else 2
-        return (12 * self.n_embd * self.n_embd * self.n_layer + self.vocab_size * self.n_embd) * per
+        return (12 * C * C * L + V * C) * per
 
     def _signature(self):
         return tuple((t.data_ptr(), t._version) for t in self.state_dict(keep_vars=True).values())
@@ -330,6 +386,7 @@ class GPT(nn.Module):
             check(lib.omnitok_lm_set_cache_format(self._engine, KV_FORMATS[self._cache_format]), "lm_set_cache_format")
             check(lib.omnitok_lm_set_max_streams(self._engine, self._max_streams), "lm_set_max_streams")
         check(lib.omnitok_lm_set_weight_format(self._engine, WEIGHT_FORMATS[self._weight_format]), "lm_set_weight_format")
+        check(lib.omnitok_lm_set_decode_quant(self._engine, DECODE_QUANTS[self._decode_quant]), "lm_set_decode_quant")
         check(lib.omnitok_lm_set_prefill_format(self._engine, PREFILL_FORMATS[self._prefill_format]), "lm_set_prefill_format")
         check(lib.omnitok_lm_set_streams_format(self._engine, STREAMS_FORMATS[self._streams_format]), "lm_set_streams_format")
         check(lib.omnitok_lm_set_prefill_attention(self._engine, PREFILL_ATTENTIONS[self._prefill_attention]), "lm_set_prefill_attention")

@@ -115,6 +115,8 @@ class Net2NetTransformer(nn.Module):
         # weight format of the decode step ("fp32" | "bf16" | "fp16", GPT.set_weight_format): an option of this port -- the reference
         # trains the model under Lightning's precision="bf16" / 16 and samples in whatever dtype the checkpoint is cast to
         self.transformer.set_weight_format(_get(args, "lm_weight_format", "fp32"))
+        # weight-only quantisation of the decode step of up to 16 streams ("none" | "fp8", GPT.set_decode_quant)
+        self.transformer.set_decode_quant(_get(args, "lm_decode_quant", "none"))
         # attention of the batched prefill ("rows" | "tiled", GPT.set_prefill_attention)
         self.transformer.set_prefill_attention(_get(args, "lm_prefill_attention", "rows"))
         # ... and the operand format of the tiled mode ("fp32" | "bf16" | "fp16", GPT.set_prefill_attention_operands)

@@ -5,7 +5,8 @@ LM shape by default (scripts/lm_train/train_k600.sh: vocab 8192, block 5120, 24 
 sequence, the HBM roofline of a step (weight bytes + K/V bytes read) and a CPU baseline (the oracle's
 KV-cached step on the host, bounded sample).
     python tools/lm_bench.py [--batch 1] [--steps 512] [--ctx 0] [--weights fp32|bf16|fp16] [--kv fp32|bf16|fp16] [--also 8] [--no-cpu-baseline]
-                             [--max-streams 16] [--streams-format fp32|w16]
+                             [--max-streams 16] [--streams-format fp32|w16] [--decode-quant none|fp8]
+--fp8-session OUT.json: the decode-quant record instead (GPT.set_decode_quant; profiles/lm_fp8.json): see fp8_session.
 --streams-session OUT.json: the many-stream record instead (GPT.set_max_streams; profiles/lm_streams_bench.json): the bare decode step
 (graph replay) of B in --session-batches streams at --session-ctx cached tokens, fp32 weights + fp32 cache first, then bf16 + bf16,
 and of 8 and 16 streams once more with "lm_streams_min" 1 (the many-stream kernel below its default threshold).  The cache lengths
@@ -42,6 +43,66 @@ from omnitokenizer_amd.synth import synth_gpt_state  # noqa: E402
 PEAK_HBM_GBS = 8000.0
 PEAK_F32_MFMA_TFLOPS = 157.3
 PEAK_16BIT_MFMA_TFLOPS = 2500.0
+
+
+def fp8_session(a, sd, dims):
+    """The record of GPT.set_decode_quant (profiles/lm_fp8.json): the bare decode step (graph replay) of B in --session-batches
+    streams at --session-ctx cached tokens on four engines over the same weights -- fp32 weights + fp32 cache and bf16 + bf16, each
+    with the switch off and with "fp8" -- ALTERNATED: five rounds, every round times each arm once, the median per arm.  The cache
+    lengths are set on the device, nothing is prefilled."""
+    V, BS, L, H, C = dims
+    hd = C // H
+    batches = [int(b) for b in a.session_batches.split(",")]
+    ctxs = [int(c) for c in a.session_ctx.split(",")]
+    arms = [("fp32", "none"), ("fp32", "fp8"), ("bf16", "none"), ("bf16", "fp8")]
+    models = {}
+    for fmt, dq in arms:
+        m = og.GPT(argparse.Namespace(), V, BS, n_layer=L, n_head=H, n_embd=C)
+        m.load_state_dict(sd, strict=True)
+        models[fmt, dq] = m.cuda().eval().set_weight_format(fmt).set_cache_format(fmt).set_decode_quant(dq)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    cells = []
+    for ctx in ctxs:
+        for m in models.values():
+            m.set_cache_format(m.cache_format)     # drops the cache: reset_streams allocates exactly ctx + 64 positions
+            m.reset_streams(max(batches), ctx + 64)
+        for B in batches:
+            replays = {k: m.graph_step(B)[2] for k, m in models.items()}
+
+            def one_round(k, n):
+                m = models[k]
+                e0.record()
+                for _ in range(n):
+                    m._pos[:B] = ctx
+                    m._len[:B] = ctx
+                    replays[k]()
+                e1.record()
+                torch.cuda.synchronize()
+                return e0.elapsed_time(e1) / n
+            nrep = max(5, min(50, int(100.0 / max(max(one_round(k, 3) for k in arms), 1e-3))))
+            rounds = {k: [] for k in arms}
+            for _ in range(5):
+                for k in arms:
+                    rounds[k].append(one_round(k, nrep))
+            for (fmt, dq), r in rounds.items():
+                r = sorted(r)
+                m = models[fmt, dq]
+                m.check_overflow()
+                weight_bytes = float(m.step_weight_bytes())
+                kv_bytes = 2.0 * L * B * H * (ctx + 1) * hd * (4.0 if fmt == "fp32" else 2.0)
+                cells.append({"weights": fmt, "kv": fmt, "decode_quant": dq, "ctx": ctx, "streams": B, "step_ms": round(r[2], 4),
+                              "step_ms_min_max": [round(r[0], 4), round(r[-1], 4)], "replays_per_round": nrep,
+                              "weight_bytes": weight_bytes, "kv_bytes": kv_bytes,
+                              "hbm_gbs": round((weight_bytes + kv_bytes) / (r[2] * 1e-3) / 1e9, 1),
+                              "hbm_frac": round((weight_bytes + kv_bytes) / (r[2] * 1e-3) / 1e9 / PEAK_HBM_GBS, 4)})
+                print(json.dumps(cells[-1]), flush=True)
+    ms = {(c["weights"], c["decode_quant"], c["ctx"], c["streams"]): c["step_ms"] for c in cells}
+    ratios = [{"ctx": ctx, "streams": B, "fp8_vs_bf16": round(ms["bf16", "none", ctx, B] / ms["bf16", "fp8", ctx, B], 3),
+               "fp8_vs_fp32": round(ms["fp32", "none", ctx, B] / ms["fp32", "fp8", ctx, B], 3)} for ctx in ctxs for B in batches]
+    return {"workload": f"GPT {L}x{C} ({H} heads, head_dim {hd}), vocab {V}, block {BS}: bare decode step (graph replay)",
+            "method": "four engines over the same synthetic weights, arms alternated inside each of 5 rounds, median per arm; "
+                      "speedups are step_ms(switch off) / step_ms(fp8) at the same weight and cache format",
+            "device": torch.cuda.get_device_name(0), "peak_hbm_gbs": PEAK_HBM_GBS, "cells": cells, "fp8_speedup": ratios}
 
 
 def streams_session(a, m, dims):
@@ -401,6 +462,10 @@ def main():
     ap.add_argument("--weights", choices=("fp32", "bf16", "fp16"), default="fp32",
                     help="format of the matrices a decode step streams (GPT.set_weight_format)")
     ap.add_argument("--kv", choices=("fp32", "bf16", "fp16"), default="fp32", help="format of the K/V cache (GPT.set_cache_format)")
+    ap.add_argument("--decode-quant", choices=("none", "fp8"), default="none",
+                    help="weight-only quantisation of the decode step of up to 16 streams (GPT.set_decode_quant)")
+    ap.add_argument("--fp8-session", metavar="OUT.json", help="write the decode-quant record (fp8_session: --session-batches, "
+                                                              "--session-ctx) and exit")
     ap.add_argument("--max-streams", type=int, default=16, help="streams per engine (GPT.set_max_streams, up to 128): the limit of "
                                                                  "--batch and of every --also count")
     ap.add_argument("--streams-format", choices=("fp32", "w16"), default="fp32",
@@ -433,7 +498,15 @@ def main():
     sd = synth_gpt_state(V, BS, L, H, C, seed=0)
     m = og.GPT(argparse.Namespace(), V, BS, n_layer=L, n_head=H, n_embd=C)
     m.load_state_dict(sd, strict=True)
+    if a.fp8_session:
+        rec = fp8_session(a, sd, (V, BS, L, H, C))
+        with open(a.fp8_session, "w") as f:
+            json.dump(rec, f, indent=1)
+            f.write("\n")
+        print(json.dumps({"written": a.fp8_session, "fp8_speedup": rec["fp8_speedup"]}), flush=True)
+        return
     m = m.cuda().eval().set_weight_format(a.weights).set_cache_format(a.kv).set_max_streams(a.max_streams)
+    m.set_decode_quant(a.decode_quant)
     if a.prefill_session:
         rec = prefill_session(a, m, (V, BS, L, H, C))
         with open(a.prefill_session, "w") as f:
@@ -496,7 +569,7 @@ def main():
         "metric": "LM sampled tokens/sec (sample_with_past, top-k 2048 / top-p 0.9)",
         "value": round(B * a.steps / dt_sample, 1), "unit": "tokens/s", "n_gpus": 1, "batch_streams": B,
         "steps": a.steps, "ctx": a.ctx, "ms_per_token_step": round(dt_sample / a.steps * 1e3, 4),
-        "dtype": "f32", "weights": a.weights, "kv": a.kv, "streams_format": a.streams_format, "data": "synthetic",
+        "dtype": "f32", "weights": a.weights, "kv": a.kv, "decode_quant": a.decode_quant, "streams_format": a.streams_format, "data": "synthetic",
         "config": {"workload": f"GPT {L}x{C} ({H} heads, head_dim {hd}), vocab {V}, block {BS}; B={B} streams, "
                                f"{a.ctx} cached tokens + {a.steps} sampled"},
         "roofline": {"kernel": "decode step (graph replay) at the final context", "bound": "hbm",
