@@ -122,6 +122,34 @@ int omnitok_lm_decode_quant(omnitok_lm *lm); /* -1: null engine */
 int omnitok_lm_set_cache_format(omnitok_lm *lm, int fmt);
 int omnitok_lm_cache_format(omnitok_lm *lm); /* -1: null engine */
 
+/* fp8 K/V cache -- per engine, default OMNITOK_LM_KQ_NONE (nothing below applies then: a default engine issues exactly the launches
+ * and bits it did), independent of the weight format, the decode quant, the streams / prefill formats and max_streams.  It is not a
+ * fourth cache format but a quantisation with side data, as omnitok_lm_set_decode_quant is beside the weight format: the cache FORMAT
+ * keeps its value and its getter and decides nothing about storage while the quant is on.  With OMNITOK_LM_KQ_FP8:
+ *   Storage: for every (layer, K | V, stream, head, position) head_dim bytes of OCP e4m3fn, laid out
+ *     [n_layer][2][max_batch][n_head][max_len][head_dim] as before, and one fp32 scale per such row,
+ *     [n_layer][2][max_batch][n_head][max_len].  omnitok_lm_cache_bytes counts both: elements x 1 + rows x 4 -- a quarter of the fp32
+ *     cache plus 4 / head_dim of it.
+ *   Scale rule: omnitok_lm_set_decode_quant's, applied to one head's row of one token: s = 2^e with e the smallest integer such that
+ *     amax 2^-e <= 448 -- with amax = m 2^x, m in [0.5, 1) (frexp): e = x - 9 if m <= 0.875 else x - 8 -- s = 1 for an all-zero row,
+ *     e clamped to [-126, 127]; q = e4m3fn(v 2^-e), one round to nearest even, subnormal results kept.  The cache HOLDS THE VALUES
+ *     s * widen(q), which are exact in fp32, fp32 subnormals included.
+ *   Quantised once, where a row is stored: the decode step's append and the prefill's scatter -- where the 16-bit formats round.  The
+ *     step (or prefill row) that produces a token uses that token's own fp32 row of qkv.  The OMNITOK_LM_PA_ROWS prefill reads
+ *     earlier rows from the cache, so it sees them quantised; the OMNITOK_LM_PA_TILED prefill reads qkv and is unaffected.
+ *   Arithmetic: every cached element enters as widen(q) * s in front of the unchanged fp32 chain, so attention over an fp8 cache is
+ *     the fp32 kernel's arithmetic on a cache that holds s * widen(q), bit for bit: lane mapping, fmaf chains, softmax, chunking and
+ *     merge are those of the fp32 cache.  omnitok_lm_cache_read returns s * widen(q).
+ *   Non-finite rows: a K or V row that holds a NaN or an infinity when it is stored raises bit 32 of the engine's flag word
+ *     (omnitok_lm_overflowed); what the cache holds for that row is unspecified.
+ * omnitok_lm_set_cache_quant: -1 for a null engine or an unknown value (a refused value changes nothing).  Like
+ * omnitok_lm_set_cache_format it frees an allocated cache and its step workspaces -- the next step or prefill returns
+ * OMNITOK_ERR_STATE until omnitok_lm_alloc_cache runs again -- and touches neither `finalized` nor any weight. */
+#define OMNITOK_LM_KQ_NONE 0
+#define OMNITOK_LM_KQ_FP8 1
+int omnitok_lm_set_cache_quant(omnitok_lm *lm, int q);
+int omnitok_lm_cache_quant(omnitok_lm *lm); /* -1: null engine */
+
 /* Streams per engine -- default 16 (nothing below applies then).  omnitok_lm_alloc_cache accepts max_batch <= max_streams; with more
  * than 16 streams one step serves all of them in ONE pass over every weight matrix (the <= 16-stream kernels read each matrix once
  * per group of 8 streams), so tokens per second over all streams keep growing with the batch.  Classifier-free guidance doubles the
@@ -256,12 +284,13 @@ int omnitok_lm_prefill_attention(omnitok_lm *lm); /* -1: null engine */
 int omnitok_lm_set_prefill_attention_operands(omnitok_lm *lm, int fmt);
 int omnitok_lm_prefill_attention_operands(omnitok_lm *lm); /* -1: null engine */
 
-/* K/V cache [n_layer][2][max_batch][n_head][max_len][head_dim] in the engine's cache format + step workspaces;
+/* K/V cache [n_layer][2][max_batch][n_head][max_len][head_dim] in the engine's cache format (or e4m3fn bytes and their row scales,
+ * omnitok_lm_set_cache_quant) + step workspaces;
  * max_batch <= omnitok_lm_max_streams (16 unless raised), otherwise -1 with the limit in force in the message. */
 int omnitok_lm_alloc_cache(omnitok_lm *lm, int max_batch, int max_len);
-int64_t omnitok_lm_cache_bytes(omnitok_lm *lm); /* the bytes allocated: half for a 16-bit cache; 0 without a cache */
+int64_t omnitok_lm_cache_bytes(omnitok_lm *lm); /* the bytes allocated: half for a 16-bit cache, elements + 4 per row for an fp8 cache; 0 without a cache */
 /* Rows t0 .. t0 + n - 1 of stream b of one layer, widened to fp32: k_out / v_out [n_head, n, head_dim] on the device (the
- * counterpart of the reference's `present`).  Every format; fp32 is a plain copy.  Rows beyond cache_len[b] hold whatever the cache
+ * counterpart of the reference's `present`).  Every format; fp32 is a plain copy; an fp8 cache (omnitok_lm_set_cache_quant) returns s * widen(q).  Rows beyond cache_len[b] hold whatever the cache
  * holds.  -1: null pointers, layer outside [0, n_layer), b outside [0, max_batch), t0 < 0, n < 0 or t0 + n > max_len;
  * OMNITOK_ERR_STATE: no cache. */
 int omnitok_lm_cache_read(omnitok_lm *lm, int layer, int b, int t0, int n, float *k_out, float *v_out,
@@ -298,7 +327,9 @@ int omnitok_lm_step_ex(omnitok_lm *lm, const int64_t *idx, const float *emb, con
  *      operands.
  *  16: an activation of an OMNITOK_LM_SF_W16 many-stream step on an fp16 engine (a LayerNorm row, a merged attention row or FC1's GELU
  *      output) left the fp16 range and entered its GEMM as +-inf: the logits from there on are invalid (a non-finite K/V row may sit
- *      in the cache).  Never set by the default streams format or a bf16 engine. */
+ *      in the cache).  Never set by the default streams format or a bf16 engine.
+ *  32: a K or V row stored into an OMNITOK_LM_KQ_FP8 cache (a step's append or a prefill) held a NaN or an infinity: the row's cache
+ *      contents are unspecified and the logits from there on are invalid.  Never set without the cache quant. */
 int omnitok_lm_overflowed(omnitok_lm *lm, omnitok_stream_t stream);
 
 /* Batched prefill of a conditioning prefix into EMPTY streams (GPT.forward / the first
@@ -445,6 +476,15 @@ int omnitok_lm_attn_decode(const float *qkv, float *kc, float *vc, const int32_t
 int omnitok_lm_attn_decode_kv16(const float *qkv, void *kc16, void *vc16, int fmt, const int32_t *cache_len, int B,
                                 int n_head, int head_dim, int max_len, float *scratch, float *out,
                                 omnitok_stream_t stream);
+/* omnitok_lm_attn_decode over fp8 caches (OMNITOK_LM_KQ_FP8): kc8 / vc8 [max_batch][n_head][max_len][head_dim] e4m3fn bytes and
+ * kscale / vscale [max_batch][n_head][max_len] fp32 row scales.  Cached rows enter as widen(q) * s, the new token's rows are appended
+ * quantised by omnitok_lm_set_cache_quant's rule (bytes and scale).  -1 before any HIP call: null pointers (the scales included),
+ * head_dim not 64 | 96 | 128, qkv / kc8 / vc8 not 16-byte aligned ("unaligned"), bad sizes.  Same contract otherwise; out equals
+ * omnitok_lm_attn_decode's on fp32 caches that hold s * widen(q), bit for bit.  (There is no flag word here: a non-finite row is
+ * reported by the engine only.) */
+int omnitok_lm_attn_decode_kv8(const float *qkv, void *kc8, void *vc8, float *kscale, float *vscale,
+                               const int32_t *cache_len, int B, int n_head, int head_dim, int max_len,
+                               float *scratch, float *out, omnitok_stream_t stream);
 /* Causal attention of a batched prefill (the OMNITOK_LM_PA_TILED mode).  qkv [B*T, 3C] fp32 (query | key | value), C = n_head * head_dim,
  * head_dim 64, 96 or 128.  Row b*T + t attends to rows b*T .. b*T + t of its own stream.
  * Exactly one of out32 [B*T, C] fp32 / out16 [B*T, C] packed (fmt = OMNITOK_LM_W_BF16 | _FP16, the value rounded

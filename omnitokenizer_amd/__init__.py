@@ -3,6 +3,7 @@
     from omnitokenizer_amd import OmniTokenizer_VQGAN     # drop-in for the reference class
     from omnitokenizer_amd.gpt import GPT, sample_with_past, sample_with_past_cfg   # LM consumer
     from omnitokenizer_amd import fp8_dequantized         # what GPT.set_decode_quant("fp8") steps with, as a state dict
+    from omnitokenizer_amd import fp8_quantize_rows       # the row rule of both fp8 switches (GPT.set_decode_quant, GPT.set_cache_quant)
     from omnitokenizer_amd import psnr_ssim, calculate_psnr, calculate_ssim          # reconstruction metrics
     from omnitokenizer_amd import InceptionI3d, get_fvd_logits, frechet_distance      # FVD (omnitokenizer_amd.fvd)
     from omnitokenizer_amd import InceptionV3, load_fid_inception, compute_fid       # FID (omnitokenizer_amd.fid)
@@ -27,7 +28,7 @@ __all__ = ["OmniTokenizer_VQGAN", "GPT", "OmniTokConfig", "make_args", "psnr_ssi
                                            "token_cross_entropy", "resize_frames", "images_to_pixels", "center_crop_arr",
                                            "DiT", "DiT_models", "load_dit", "create_diffusion", "generate_images",
                                            "Latte", "Latte_models", "load_latte", "get_1d_sincos_temp_embed", "generate_videos",
-                                           "fp8_dequantized"]
+                                           "fp8_dequantized", "fp8_quantize_rows"]
 
 
 def __getattr__(name):
@@ -37,9 +38,9 @@ def __getattr__(name):
     if name == "GPT":
         from .gpt import GPT
         return GPT
-    if name == "fp8_dequantized":
-        from .gpt import fp8_dequantized
-        return fp8_dequantized
+    if name in ("fp8_dequantized", "fp8_quantize_rows"):
+        from . import gpt
+        return getattr(gpt, name)
     if name in ("psnr_ssim", "calculate_psnr", "calculate_ssim"):
         from . import metrics
         return getattr(metrics, name)

@@ -230,6 +230,8 @@ _PROTOS = {
     "omnitok_lm_decode_quant": [P],
     "omnitok_lm_set_cache_format": [P, c_int],
     "omnitok_lm_cache_format": [P],
+    "omnitok_lm_set_cache_quant": [P, c_int],
+    "omnitok_lm_cache_quant": [P],
     "omnitok_lm_set_streams_format": [P, c_int],
     "omnitok_lm_streams_format": [P],
     "omnitok_lm_set_prefill_format": [P, c_int],
@@ -263,6 +265,7 @@ _PROTOS = {
     "omnitok_lm_layernorm16": [P, P, P, P, c_int, I64, c_int, P, P],
     "omnitok_lm_attn_decode": [P, P, P, P, c_int, c_int, c_int, c_int, P, P, P],
     "omnitok_lm_attn_decode_kv16": [P, P, P, c_int, P, c_int, c_int, c_int, c_int, P, P, P],
+    "omnitok_lm_attn_decode_kv8": [P, P, P, P, P, P, c_int, c_int, c_int, c_int, P, P, P],
     "omnitok_lm_attn_prefill": [P, c_int, c_int, c_int, c_int, P, P, c_int, P, P],
     "omnitok_lm_attn_prefill16": [P, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P, P],
     "omnitok_pl_planes_bytes": [I64, c_int, c_int],

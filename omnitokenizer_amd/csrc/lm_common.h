@@ -18,8 +18,9 @@
 //   lm_gemm_streams16.hip  lm_gemm_streams16_kernel and lm_streams16_reduce_kernel (17 .. 128 streams on the 16-bit MFMA over packed
 //                     activations and weights, omnitok_lm_set_streams_format), omnitok_lm_gemm_streams16
 //   lm_gemm16.hip     lm_gemm16_kernel (the 16-bit MFMA GEMM of a PF_W16 prefill, omnitok_lm_set_prefill_format), omnitok_lm_gemm16
-//   lm_attn.hip       lm_attn_decode_kernel (flash-decode over the fp32 / bf16 / fp16 K/V cache, chunk partials), lm_attn_merge_kernel
-//                     (fp32 or, for a PF_W16 prefill, 16-bit output), lm_kv_scatter_kernel, lm_kv_read_kernel, omnitok_lm_attn_decode[_kv16]
+//   lm_attn.hip       lm_attn_decode_kernel (flash-decode over the fp32 / bf16 / fp16 / fp8 K/V cache, chunk partials), lm_attn_merge_kernel
+//                     (fp32 or, for a PF_W16 prefill, 16-bit output), lm_kv_scatter_kernel, lm_kv_scatter8_kernel (the fp8 cache's),
+//                     lm_kv_read_kernel, omnitok_lm_attn_decode[_kv16|_kv8]
 //   lm_attn_prefill.hip  the tiled causal attention of the prefill, K/V tiles shared by 128 query rows (omnitok_lm_set_prefill_attention):
 //                     lm_attn_prefill_kernel on the fp32-input MFMA (the body it shares with the DiT: attn_f32_tiled.h) and lm_attn_prefill16_kernel on the bf16 / fp16 MFMA (Q / K / V / P
 //                     rounded once to the operand format; omnitok_lm_set_prefill_attention_operands) behind one host side,
@@ -138,11 +139,32 @@ template <> struct LmKV<float> {
     static __device__ __forceinline__ float store(float f, bool &) { return f; }
     static __device__ __forceinline__ f32x4 store4(const f32x4 &v, bool &) { return v; }
 };
+// The power-of-two row scale 2^e of the fp8 images (lm_quantize_fp8_kernel, the K/V cache under omnitok_lm_set_cache_quant) from the row's
+// amax, given as the fp32 pattern without its sign: e is the smallest integer such that amax 2^-e <= 448.  amax = 1.f x 2^(E - 127)
+// = m x 2^(E - 126) with m = 1.f / 2 in [0.5, 1), and m <= 0.875 <=> mantissa field <= 0x600000 (448 = 1.75 x 2^8); a subnormal amax
+// (E = 0) lands below the clamp whatever its mantissa; e = 0 for a zero row; clamped so that the scale is a normal fp32
+__device__ __forceinline__ int lm_fp8_scale_exp(unsigned amax) {
+    int e = 0;
+    if (amax != 0u) {
+        const int E = (int)(amax >> 23), x = E - 126;
+        e = (amax & 0x7FFFFFu) <= 0x600000u ? x - 9 : x - 8;
+        e = e < -126 ? -126 : (e > 127 ? 127 : e);
+    }
+    return e;
+}
+__device__ __forceinline__ float lm_fp8_scale(int e) { return __builtin_bit_cast(float, (unsigned)(e + 127) << 23); }
+// a cached quad as fp32: widened, and for the fp8 cache multiplied by its row's scale s (exact: a power of two times at most 4
+// significant bits, fp32 subnormals kept); every other KT ignores s
+template <typename KT> __device__ __forceinline__ f32x4 lm_kv_widen(const typename LmW<KT>::quad &q, float s) {
+    if constexpr (__is_same(KT, lm_fp8)) return LmW<KT>::widen(q) * s;
+    else return LmW<KT>::widen(q);
+}
 constexpr int LM_FLAG_PAST_CACHE = 1;  // bits of the engine's flag word (omnitok_lm_overflowed)
 constexpr int LM_FLAG_FP16_RANGE = 2;
 constexpr int LM_FLAG_PF16_RANGE = 4;  // an activation of an fp16 PF_W16 prefill rounded to +-inf
 constexpr int LM_FLAG_AOP16_RANGE = 8;  // a Q / K / V element of a prefill attention with fp16 operands rounded to +-inf
 constexpr int LM_FLAG_SF16_RANGE = 16;  // an activation of an fp16 SF_W16 many-stream step rounded to +-inf
+constexpr int LM_FLAG_KV8_NONFINITE = 32;  // a K or V row stored into an fp8 cache (OMNITOK_LM_KQ_FP8) held a NaN or an infinity
 
 struct LmMerge {
     const float *part;         // [B][n_head][nchunk][2 + hd]
@@ -174,12 +196,18 @@ auto lm_with_wt_dq(const LmMat &m, F &&f) {
     if (m.w8) return f(static_cast<const lm_fp8 *>(m.w8));
     return lm_with_wt(m, f);
 }
-// the one dispatch on the cache format: f(a value of the cache's element type)
+// the one dispatch on the cache format: f(a value of the format's element type)
 template <class F>
-auto lm_with_kt(int kvfmt, F &&f) {
+auto lm_with_kfmt(int kvfmt, F &&f) {
     if (kvfmt == OMNITOK_LM_KV_FP32) return f(float{});
     if (kvfmt == OMNITOK_LM_KV_BF16) return f(lm_bf16{});
     return f(lm_fp16{});
+}
+// ... and on the cache's storage: lm_fp8 under OMNITOK_LM_KQ_FP8, whatever the format
+template <class F>
+auto lm_with_kt(int kvfmt, int kq, F &&f) {
+    if (kq == OMNITOK_LM_KQ_FP8) return f(lm_fp8{});
+    return lm_with_kfmt(kvfmt, f);
 }
 
 // One nn.Linear call of the decode step: y = act(LN(x) W^T + bias) (+ residual) for B rows.  bias, residual and the LayerNorm pair
@@ -240,8 +268,10 @@ int64_t lm_streams16_part_floats(int B, int N, int K);
 // prefill_T > 0: B * prefill_T query rows (row = b * T + t, keys 0..t), chunks sized for T keys
 struct LmAttnArgs {
     const float *qkv;
-    void *kc, *vc;             // K / V slabs of one layer, elements of kvfmt
+    void *kc, *vc;             // K / V slabs of one layer, elements of kvfmt (e4m3fn bytes when kq is OMNITOK_LM_KQ_FP8)
     int kvfmt;
+    int kq;                    // OMNITOK_LM_KQ_*
+    float *ksc, *vsc;          // kq == OMNITOK_LM_KQ_FP8: the slabs' row scales [max_batch][n_head][max_len]; otherwise unused
     const int32_t *cache_len;  // [B] (unused when prefill_T > 0)
     int B, n_head, head_dim, max_len;
     float *part;               // [rows][n_head][nchunk][2 + head_dim]
@@ -255,11 +285,12 @@ int lm_attn_partials(const LmAttnArgs &a, hipStream_t stream);
 // flag_bit (LM_FLAG_PF16_RANGE | LM_FLAG_SF16_RANGE) in *flag.  Exactly one of out32 / out16.  The decode step passes cache_len and its chunk, the prefill prefill_T and LM_CHUNK
 void lm_attn_merge(const float *part, const int32_t *cache_len, int n_head, int hd, int nchunk, int prefill_T, float *out32, void *out16,
                    int fmt, int64_t rows, int *flag, int chunk, hipStream_t stream, int flag_bit = LM_FLAG_PF16_RANGE);
-// qkv [B * T, 3C] -> cache rows 0 .. T - 1 of every stream | rows t0 .. t0 + n - 1 of one stream's slabs -> fp32
-int lm_kv_scatter(const float *qkv, void *kc, void *vc, int kvfmt, int64_t rows, int T, int n_head, int hd, int max_len,
-                  int *err_flag, hipStream_t stream);
-int lm_kv_read(const void *kc, const void *vc, int kvfmt, int t0, int n, int n_head, int hd, int max_len, float *k_out,
-               float *v_out, hipStream_t stream);
+// qkv [B * T, 3C] -> cache rows 0 .. T - 1 of every stream | rows t0 .. t0 + n - 1 of one stream's slabs -> fp32.  kq / ksc / vsc as
+// in LmAttnArgs (lm_kv_read: the scales of that stream's rows)
+int lm_kv_scatter(const float *qkv, void *kc, void *vc, int kvfmt, int kq, float *ksc, float *vsc, int64_t rows, int T, int n_head, int hd,
+                  int max_len, int *err_flag, hipStream_t stream);
+int lm_kv_read(const void *kc, const void *vc, int kvfmt, int kq, const float *ksc, const float *vsc, int t0, int n, int n_head, int hd,
+               int max_len, float *k_out, float *v_out, hipStream_t stream);
 // lm_attn_prefill.hip.  Causal attention of B streams x T rows straight from qkv [B * T, 3C] into out32 [B * T, C] or (rounded to out_fmt)
 // out16, with fp32 operands (op_fmt 0) or Q, K, V and P rounded once to op_fmt (OMNITOK_LM_W_BF16 | _FP16) on the 16-bit MFMA: the contract
 // of omnitok_lm_attn_prefill / omnitok_lm_attn_prefill16, their argument checks included (`who` names the entry in the messages); an fp16

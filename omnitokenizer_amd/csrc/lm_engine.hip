@@ -191,7 +191,8 @@ struct LmLayer {
     const float *bproj, *b1, *b2;
 };
 
-static int lm_kv_elem_bytes(int fmt) { return fmt == OMNITOK_LM_KV_FP32 ? 4 : 2; }
+// bytes of one cache element: a byte under OMNITOK_LM_KQ_FP8 (the format then decides nothing about storage), else the format's
+static int lm_kv_elem_bytes(int fmt, int kq) { return kq == OMNITOK_LM_KQ_FP8 ? 1 : fmt == OMNITOK_LM_KV_FP32 ? 4 : 2; }
 
 struct omnitok_lm {
     omnitok_lm_config cfg;
@@ -210,11 +211,14 @@ struct omnitok_lm {
     // cache + workspaces
     void *kv = nullptr;                       // [n_layer][2][max_batch][n_head][max_len][head_dim] elements of cache_format
     int cache_format = OMNITOK_LM_KV_FP32;    // element type of kv (omnitok_lm_set_cache_format; applies at omnitok_lm_alloc_cache)
+    int cache_quant = OMNITOK_LM_KQ_NONE;     // OMNITOK_LM_KQ_FP8: kv holds e4m3fn bytes and kvs their row scales (omnitok_lm_set_cache_quant)
+    float *kvs = nullptr;                     // [n_layer][2][max_batch][n_head][max_len] fp32 row scales (cache_quant only)
     int max_batch = 0, max_len = 0;
     int max_streams = 16;  // what omnitok_lm_alloc_cache accepts as max_batch (omnitok_lm_set_max_streams, up to 128)
     int chunk = LM_CHUNK;  // keys per attention chunk of the decode step (omnitok_lm_alloc_cache)
     int *err_flag = nullptr;  // LM_FLAG_PAST_CACHE: the attention kernel met a stream past max_len | LM_FLAG_FP16_RANGE: a K/V value
-                              // stored into an fp16 cache rounded to +-inf (the append, the prefill's scatter)
+                              // stored into an fp16 cache rounded to +-inf (the append, the prefill's scatter) | LM_FLAG_KV8_NONFINITE: a
+                              // K/V row stored into an fp8 cache held a NaN or an infinity (the same two places)
     float *x = nullptr, *qkv = nullptr, *att = nullptr, *hid = nullptr, *part = nullptr;
     float *gs = nullptr;  // K-split partials of lm_gemm_streams_kernel / lm_gemm_streams16_kernel (the many-stream step)
     unsigned short *x16 = nullptr, *h16 = nullptr;  // packed GEMM operands of an SF_W16 step: [max_batch, C] | [max_batch, 4 C] (one allocation)
@@ -229,9 +233,13 @@ struct omnitok_lm {
     int64_t ce_rows = 0, ce_bytes = 0;
     int head_dim() const { return cfg.n_embd / cfg.n_head; }
     // the K slab of a layer and the V slab that follows it: [max_batch][n_head][max_len][head_dim] elements of cache_format each
-    int64_t slab_bytes() const { return (int64_t)max_batch * cfg.n_head * max_len * head_dim() * lm_kv_elem_bytes(cache_format); }
+    int64_t slab_bytes() const { return (int64_t)max_batch * cfg.n_head * max_len * head_dim() * lm_kv_elem_bytes(cache_format, cache_quant); }
     void *k_slab(int layer) const { return static_cast<char *>(kv) + 2 * layer * slab_bytes(); }
     void *v_slab(int layer) const { return static_cast<char *>(kv) + (2 * layer + 1) * slab_bytes(); }
+    // ... and the scales of their rows: [max_batch][n_head][max_len] floats each (nullptr without a cache quant)
+    int64_t slab_rows() const { return (int64_t)max_batch * cfg.n_head * max_len; }
+    float *k_scales(int layer) const { return kvs ? kvs + 2 * layer * slab_rows() : nullptr; }
+    float *v_scales(int layer) const { return kvs ? kvs + (2 * layer + 1) * slab_rows() : nullptr; }
 };
 
 static const float *LW(omnitok_lm *lm, const std::string &k) {
@@ -288,6 +296,8 @@ static void lm_free_cache(omnitok_lm *lm) {
     lm->x16 = lm->h16 = nullptr;
     if (lm->kv) (void)hipFree(lm->kv);
     lm->kv = nullptr;
+    if (lm->kvs) (void)hipFree(lm->kvs);
+    lm->kvs = nullptr;
     lm->cache_bytes = 0;
 }
 
@@ -413,6 +423,20 @@ extern "C" int omnitok_lm_set_cache_format(omnitok_lm *lm, int fmt) {
 extern "C" int omnitok_lm_cache_format(omnitok_lm *lm) {
     OT_CHECK_ARG(lm, "lm_cache_format: null engine");
     return lm->cache_format;
+}
+
+extern "C" int omnitok_lm_set_cache_quant(omnitok_lm *lm, int q) {
+    OT_CHECK_ARG(lm, "lm_set_cache_quant: null engine");
+    OT_CHECK_ARG(q == OMNITOK_LM_KQ_NONE || q == OMNITOK_LM_KQ_FP8, "lm_set_cache_quant: unknown value %d", q);
+    lm_free_cache(lm);  // the cache and the step workspaces: the next step / prefill asks for omnitok_lm_alloc_cache
+    lm->max_batch = lm->max_len = 0;
+    lm->cache_quant = q;
+    return OMNITOK_OK;
+}
+
+extern "C" int omnitok_lm_cache_quant(omnitok_lm *lm) {
+    OT_CHECK_ARG(lm, "lm_cache_quant: null engine");
+    return lm->cache_quant;
 }
 
 extern "C" int omnitok_lm_set_max_streams(omnitok_lm *lm, int n) {
@@ -606,7 +630,8 @@ extern "C" int omnitok_lm_alloc_cache(omnitok_lm *lm, int max_batch, int max_len
     const int64_t per_layer = (int64_t)max_batch * c.n_head * max_len * hd;  // elements per K (or V)
     lm->chunk = g_lm_attn_short && max_len <= LM_CHUNK_SHORT * LM_MAX_CHUNKS ? LM_CHUNK_SHORT : LM_CHUNK;
     const int nchunk = (max_len + lm->chunk - 1) / lm->chunk;
-    const int64_t kv_bytes = per_layer * 2 * c.n_layer * lm_kv_elem_bytes(lm->cache_format);
+    const int64_t kv_bytes = per_layer * 2 * c.n_layer * lm_kv_elem_bytes(lm->cache_format, lm->cache_quant);
+    const int64_t scale_bytes = lm->cache_quant == OMNITOK_LM_KQ_FP8 ? per_layer / hd * 2 * c.n_layer * 4 : 0;  // one fp32 per cached row
     // split partials of the many-stream GEMMs of a step: the largest of its five shapes
     int64_t gs = 0;
     const int shapes[5][2] = {{(int)(3 * C), (int)C}, {(int)C, (int)C}, {(int)(4 * C), (int)C}, {(int)C, (int)(4 * C)}, {c.vocab_size, (int)C}};
@@ -624,7 +649,7 @@ extern "C" int omnitok_lm_alloc_cache(omnitok_lm *lm, int max_batch, int max_len
         }
         return e == hipSuccess;
     };
-    if (!alloc(&lm->kv, kv_bytes) || !alloc(reinterpret_cast<void **>(&lm->x), max_batch * C * 4) ||
+    if (!alloc(&lm->kv, kv_bytes) || (scale_bytes > 0 && !alloc(reinterpret_cast<void **>(&lm->kvs), scale_bytes)) || !alloc(reinterpret_cast<void **>(&lm->x), max_batch * C * 4) ||
         !alloc(reinterpret_cast<void **>(&lm->qkv), max_batch * 3 * C * 4) ||
         !alloc(reinterpret_cast<void **>(&lm->att), max_batch * C * 4) ||
         !alloc(reinterpret_cast<void **>(&lm->hid), max_batch * 4 * C * 4) ||
@@ -635,7 +660,7 @@ extern "C" int omnitok_lm_alloc_cache(omnitok_lm *lm, int max_batch, int max_len
     lm->h16 = lm->x16 + max_batch * C;
     lm->max_batch = max_batch;
     lm->max_len = max_len;
-    lm->cache_bytes = kv_bytes;
+    lm->cache_bytes = kv_bytes + scale_bytes;
     if (!lm->err_flag) {
         OT_HIP(hipMalloc(reinterpret_cast<void **>(&lm->err_flag), sizeof(int)));
         OT_HIP(hipMemset(lm->err_flag, 0, sizeof(int)));
@@ -652,7 +677,7 @@ extern "C" int omnitok_lm_overflowed(omnitok_lm *lm, omnitok_stream_t stream_) {
     OT_HIP(hipStreamSynchronize(stream));
     if (h)
         if (int rc = device_fill_u32(lm->err_flag, 0u, 1, stream)) return rc;
-    return h & (LM_FLAG_PAST_CACHE | LM_FLAG_FP16_RANGE | LM_FLAG_PF16_RANGE | LM_FLAG_AOP16_RANGE | LM_FLAG_SF16_RANGE);
+    return h & (LM_FLAG_PAST_CACHE | LM_FLAG_FP16_RANGE | LM_FLAG_PF16_RANGE | LM_FLAG_AOP16_RANGE | LM_FLAG_SF16_RANGE | LM_FLAG_KV8_NONFINITE);
 }
 
 extern "C" int omnitok_lm_cache_read(omnitok_lm *lm, int layer, int b, int t0, int n, float *k_out, float *v_out,
@@ -670,9 +695,11 @@ extern "C" int omnitok_lm_cache_read(omnitok_lm *lm, int layer, int b, int t0, i
     if (n == 0) return OMNITOK_OK;
     const omnitok_lm_config &c = lm->cfg;
     const int hd = lm->head_dim();
-    const int64_t off = (int64_t)b * c.n_head * lm->max_len * hd * lm_kv_elem_bytes(lm->cache_format);  // the stream's rows in a slab
+    const int64_t roff = (int64_t)b * c.n_head * lm->max_len;  // the stream's rows in a slab
+    const int64_t off = roff * hd * lm_kv_elem_bytes(lm->cache_format, lm->cache_quant);
     return lm_kv_read(static_cast<const char *>(lm->k_slab(layer)) + off, static_cast<const char *>(lm->v_slab(layer)) + off,
-                      lm->cache_format, t0, n, c.n_head, hd, lm->max_len, k_out, v_out, stream);
+                      lm->cache_format, lm->cache_quant, lm->kvs ? lm->k_scales(layer) + roff : nullptr,
+                      lm->kvs ? lm->v_scales(layer) + roff : nullptr, t0, n, c.n_head, hd, lm->max_len, k_out, v_out, stream);
 }
 
 extern "C" int64_t omnitok_lm_cache_bytes(omnitok_lm *lm) { return lm ? lm->cache_bytes : 0; }
@@ -745,12 +772,13 @@ extern "C" int omnitok_lm_step_ex(omnitok_lm *lm, const int64_t *idx, const floa
     OT_LAUNCH_CHECK("lm_embed");
     const LmMerge mg{lm->part, cache_len, c.n_head, hd, (lm->max_len + lm->chunk - 1) / lm->chunk, lm->chunk, lm->qkv};   // (qkv is free once the partials exist)
     LmAttnArgs at = {};
-    at.qkv = lm->qkv; at.kvfmt = lm->cache_format; at.cache_len = cache_len;
+    at.qkv = lm->qkv; at.kvfmt = lm->cache_format; at.kq = lm->cache_quant; at.cache_len = cache_len;
     at.B = B; at.n_head = c.n_head; at.head_dim = hd; at.max_len = lm->max_len;
     at.part = lm->part; at.err_flag = lm->err_flag; at.chunk = lm->chunk;
     for (int i = 0; i < c.n_layer; ++i) {
         const LmLayer &L = lm->layers[i];
         at.kc = lm->k_slab(i); at.vc = lm->v_slab(i);
+        at.ksc = lm->k_scales(i); at.vsc = lm->v_scales(i);
         // x + proj(attn(ln1(x)))   (reference gpt.py:159-161)
         if (int rc = lm_step_linear(lm, {lm->x, L.wqkv, L.bqkv, nullptr, L.ln1w, L.ln1b, lm->qkv, B, 3 * C, C, 0}, nullptr, stream)) return rc;
         if (int rc = lm_attn_partials(at, stream)) return rc;
@@ -820,8 +848,8 @@ struct LmPrefill {
         return OMNITOK_OK;
     }
     int scatter(int layer) const {
-        return lm_kv_scatter(qkv, lm->k_slab(layer), lm->v_slab(layer), lm->cache_format, M, T, lm->cfg.n_head, lm->head_dim(), lm->max_len,
-                             lm->err_flag, stream);
+        return lm_kv_scatter(qkv, lm->k_slab(layer), lm->v_slab(layer), lm->cache_format, lm->cache_quant, lm->k_scales(layer),
+                             lm->v_scales(layer), M, T, lm->cfg.n_head, lm->head_dim(), lm->max_len, lm->err_flag, stream);
     }
     // att = causal attention of qkv.  rows (OMNITOK_LM_PA_ROWS): the decode kernel per query row over the cache just scattered, chunk
     // partials, a merge | tiled: straight from qkv, K/V tiles shared by 128 query rows on the fp32-input MFMA: no partials, no dependence on
@@ -835,6 +863,7 @@ struct LmPrefill {
                                        lm->err_flag, stream);
         LmAttnArgs a = {};
         a.qkv = qkv; a.kc = lm->k_slab(layer); a.vc = lm->v_slab(layer); a.kvfmt = lm->cache_format;
+        a.kq = lm->cache_quant; a.ksc = lm->k_scales(layer); a.vsc = lm->v_scales(layer);
         a.B = B; a.n_head = n_head; a.head_dim = hd; a.max_len = lm->max_len;
         a.part = part; a.prefill_T = T; a.chunk = LM_CHUNK;
         if (int rc = lm_attn_partials(a, stream)) return rc;

@@ -5,9 +5,8 @@ namespace omnitok {
 
 // One workgroup per row.  Pass 1: the row's amax as the unsigned maximum of the fp32 patterns without their sign -- for finite
 // values that order is the order of |w|, and a NaN or an infinity (pattern >= 0x7F800000) wins it, so the same maximum says whether
-// the row is finite.  The exponent e of the scale comes from that pattern by integer arithmetic: amax = 1.f x 2^(E - 127)
-// = m x 2^(E - 126) with m = 1.f / 2 in [0.5, 1), and m <= 0.875 <=> f <= 0.75 <=> mantissa field <= 0x600000 (448 = 1.75 x 2^8).
-// A subnormal amax (E = 0) lands below the clamp whatever its mantissa.  Pass 2 reads the row again (L2), scales by 2^-e with
+// the row is finite.  The exponent e of the scale comes from that pattern by integer arithmetic (lm_fp8_scale_exp, lm_common.h).
+// Pass 2 reads the row again (L2), scales by 2^-e with
 // v_ldexp_f32 (exact) and converts with v_cvt_pk_fp8_f32: one round to nearest even, subnormal results kept; no value exceeds 448, so
 // the instruction's behaviour out of range never matters.
 __global__ __launch_bounds__(256) void lm_quantize_fp8_kernel(const float *__restrict__ w, unsigned *__restrict__ q8,
@@ -35,14 +34,9 @@ __global__ __launch_bounds__(256) void lm_quantize_fp8_kernel(const float *__res
     __syncthreads();
     const unsigned a01 = s_max[0] > s_max[1] ? s_max[0] : s_max[1], a23 = s_max[2] > s_max[3] ? s_max[2] : s_max[3];
     const unsigned amax = a01 > a23 ? a01 : a23;
-    int e = 0;  // amax == 0: scale 1
-    if (amax != 0u) {
-        const int E = (int)(amax >> 23), x = E - 126;
-        e = (amax & 0x7FFFFFu) <= 0x600000u ? x - 9 : x - 8;
-        e = e < -126 ? -126 : (e > 127 ? 127 : e);  // the scale is a normal fp32
-    }
+    const int e = lm_fp8_scale_exp(amax);  // (lm_common.h: shared with the K/V cache's append and scatter)
     if (tid == 0) {
-        scale[n] = __builtin_bit_cast(float, (unsigned)(e + 127) << 23);
+        scale[n] = lm_fp8_scale(e);
         if (amax >= 0x7F800000u && flags) flags[n / seg_rows] = 1;
     }
     unsigned *out = q8 + (int64_t)n * k4n;

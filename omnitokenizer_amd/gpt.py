@@ -7,7 +7,7 @@ The class owns the parameters under the reference's state_dict key names; all ar
 step runs in libomnitok.so (include/omnitok_lm.h, csrc/lm_engine.hip and the other csrc/lm_*.hip): a preallocated K/V cache instead of
 the reference's per-step torch.cat of all pasts, GEMV kernels that stream each weight matrix
 once per step (fp32, or bf16 / fp16 at half the bytes: GPT.set_weight_format; or an fp8 image at a quarter: GPT.set_decode_quant), flash-decode
-attention over an fp32, bf16 or fp16 cache (GPT.set_cache_format), up to 16 streams per engine or, on an fp32-MFMA GEMM that reads
+attention over an fp32, bf16 or fp16 cache (GPT.set_cache_format) or an fp8 cache with a scale per row (GPT.set_cache_quant), up to 16 streams per engine or, on an fp32-MFMA GEMM that reads
 each matrix once for the whole batch, up to 128 (GPT.set_max_streams), and -- because the step's launch sequence does not depend on the position -- one
 captured HIP graph replayed per token.  Token selection (temperature, the CFG blend,
 top-k / top-p filtering, argmax or one multinomial draw) is one more kernel (csrc/lm_select.hip); the only
@@ -30,6 +30,7 @@ from ._lib import OmnitokLmConfig, check
 WEIGHT_FORMATS = {"fp32": 0, "bf16": 1, "fp16": 2}  # OMNITOK_LM_W_* of include/omnitok_lm.h
 DECODE_QUANTS = {"none": 0, "fp8": 1}               # OMNITOK_LM_DQ_*
 KV_FORMATS = {"fp32": 0, "bf16": 1, "fp16": 2}      # OMNITOK_LM_KV_*
+CACHE_QUANTS = {"none": 0, "fp8": 1}                # OMNITOK_LM_KQ_*
 PREFILL_FORMATS = {"fp32": 0, "w16": 1}             # OMNITOK_LM_PF_*
 PREFILL_ATTENTIONS = {"rows": 0, "tiled": 1}        # OMNITOK_LM_PA_*
 STREAMS_FORMATS = {"fp32": 0, "w16": 1}             # OMNITOK_LM_SF_*
@@ -141,6 +142,7 @@ class GPT(nn.Module):
         self._weight_format = "fp32"
         self._decode_quant = "none"
         self._cache_format = "fp32"
+        self._cache_quant = "none"
         self._prefill_format = "fp32"
         self._prefill_attention = "rows"
         self._streams_format = "fp32"
@@ -242,6 +244,29 @@ class GPT(nn.Module):
         return self
 
     @property
+    def cache_quant(self) -> str:
+        return self._cache_quant
+
+    def set_cache_quant(self, name: str):
+        """Quantisation of the K/V cache (include/omnitok_lm.h, omnitok_lm_set_cache_quant): "none" (default) or "fp8": every cached
+        row of head_dim values is stored as e4m3fn bytes with one power-of-two fp32 scale (the rule of fp8_quantize_rows, applied to
+        one head's row of one token), a quarter of the fp32 cache's bytes plus 4 per row.  A row is quantised once, where it is
+        stored; the step that produces a token uses its fp32 K/V, and all arithmetic stays fp32 on the values s * q.  It is not a
+        cache format: cache_format keeps its value and decides nothing about storage while the quant is on.  Independent of the
+        weight format, decode quant, streams / prefill formats and max_streams.  The cache and the captured graphs are dropped and
+        handles of earlier streams are rejected; the weights and state_dict() are left alone.  check_overflow() raises if a stored
+        row held a NaN or an infinity."""
+        if name not in CACHE_QUANTS:
+            raise ValueError(f"cache quant {name!r}: expected one of {sorted(CACHE_QUANTS)}")
+        self._cache_quant = name
+        self._cache_shape = (0, 0)
+        self._graphs = {}
+        self._generation += 1
+        if self._engine is not None:  # frees the engine's cache; the next reset_streams allocates it in the new layout
+            check(_lib.load().omnitok_lm_set_cache_quant(self._engine, CACHE_QUANTS[name]), "lm_set_cache_quant")
+        return self
+
+    @property
     def prefill_format(self) -> str:
         return self._prefill_format
 
@@ -340,8 +365,8 @@ class GPT(nn.Module):
         return self
 
     def cache_rows(self, layer, stream, start=0, stop=None):
-        """(k, v) of rows start .. stop - 1 of one stream's cache in one layer, widened to fp32: [n_head, n, head_dim] each (the
-        counterpart of the reference's `present`).  stop=None: the stream's current length (one host synchronisation)."""
+        """(k, v) of rows start .. stop - 1 of one stream's cache in one layer, widened to fp32 (an fp8 cache: scale times widened
+        byte): [n_head, n, head_dim] each (the counterpart of the reference's `present`).  stop=None: the stream's current length (one host synchronisation)."""
         if self._engine is None or self._len is None:
             raise RuntimeError("cache_rows: no streams yet (reset_streams / forward_with_past first)")
         if stop is None:
@@ -384,6 +409,7 @@ class GPT(nn.Module):
             self._engine = h
             # before the first alloc_cache (set_cache_format applies later changes to the engine itself)
             check(lib.omnitok_lm_set_cache_format(self._engine, KV_FORMATS[self._cache_format]), "lm_set_cache_format")
+            check(lib.omnitok_lm_set_cache_quant(self._engine, CACHE_QUANTS[self._cache_quant]), "lm_set_cache_quant")
             check(lib.omnitok_lm_set_max_streams(self._engine, self._max_streams), "lm_set_max_streams")
         check(lib.omnitok_lm_set_weight_format(self._engine, WEIGHT_FORMATS[self._weight_format]), "lm_set_weight_format")
         check(lib.omnitok_lm_set_decode_quant(self._engine, DECODE_QUANTS[self._decode_quant]), "lm_set_decode_quant")
@@ -419,6 +445,8 @@ class GPT(nn.Module):
         self._graphs = {}
 
     def cache_bytes(self) -> int:
+        """Bytes of the allocated K/V cache: elements x 4 | 2 by the cache format, or under set_cache_quant("fp8") elements x 1 plus
+        4 per cached row of head_dim elements (its scale); 0 without a cache."""
         return 0 if self._engine is None else int(_lib.load().omnitok_lm_cache_bytes(self._engine))
 
     # ---- native stepping ----------------------------------------------------------------------------
@@ -436,7 +464,7 @@ class GPT(nn.Module):
 
     def check_overflow(self):
         """Raises if a decode step since the last check ran past the allocated K/V cache, or stored a K/V value outside the
-        fp16 range into an fp16 cache, or a "w16" prefill on fp16 weights rounded an activation to inf, or a prefill attention with
+        fp16 range into an fp16 cache, or stored a K/V row with a NaN or an infinity into an fp8 cache, or a "w16" prefill on fp16 weights rounded an activation to inf, or a prefill attention with
         fp16 operands rounded an element of Q, K or V to inf, or a "w16" many-stream step on fp16 weights rounded an activation to inf (the logits are invalid in each case); one host synchronisation -- the sampling loops call it once at their end."""
         if not self._engine:
             return
@@ -457,6 +485,9 @@ class GPT(nn.Module):
         if rc & 16:
             raise RuntimeError("an activation of a 'w16' many-stream step left the fp16 range and entered its GEMM as inf: use "
                                "set_weight_format('bf16') (fp32's range) or set_streams_format('fp32') for this model")
+        if rc & 32:
+            raise RuntimeError("a K/V row stored into the fp8 cache (set_cache_quant('fp8')) held a NaN or an infinity: the logits "
+                               "from there on are invalid")
 
     @staticmethod
     def _fp(t):

@@ -117,6 +117,8 @@ class Net2NetTransformer(nn.Module):
         self.transformer.set_weight_format(_get(args, "lm_weight_format", "fp32"))
         # weight-only quantisation of the decode step of up to 16 streams ("none" | "fp8", GPT.set_decode_quant)
         self.transformer.set_decode_quant(_get(args, "lm_decode_quant", "none"))
+        # fp8 K/V cache with a scale per cached row ("none" | "fp8", GPT.set_cache_quant)
+        self.transformer.set_cache_quant(_get(args, "lm_cache_quant", "none"))
         # attention of the batched prefill ("rows" | "tiled", GPT.set_prefill_attention)
         self.transformer.set_prefill_attention(_get(args, "lm_prefill_attention", "rows"))
         # ... and the operand format of the tiled mode ("fp32" | "bf16" | "fp16", GPT.set_prefill_attention_operands)

@@ -6,6 +6,8 @@ sequence, the HBM roofline of a step (weight bytes + K/V bytes read) and a CPU b
 KV-cached step on the host, bounded sample).
     python tools/lm_bench.py [--batch 1] [--steps 512] [--ctx 0] [--weights fp32|bf16|fp16] [--kv fp32|bf16|fp16] [--also 8] [--no-cpu-baseline]
                              [--max-streams 16] [--streams-format fp32|w16] [--decode-quant none|fp8]
+                             [--cache-quant none|fp8]
+--kv8-session OUT.json: the cache-quant record instead (GPT.set_cache_quant; profiles/lm_kv8_bench.json): see kv8_session.
 --fp8-session OUT.json: the decode-quant record instead (GPT.set_decode_quant; profiles/lm_fp8.json): see fp8_session.
 --streams-session OUT.json: the many-stream record instead (GPT.set_max_streams; profiles/lm_streams_bench.json): the bare decode step
 (graph replay) of B in --session-batches streams at --session-ctx cached tokens, fp32 weights + fp32 cache first, then bf16 + bf16,
@@ -103,6 +105,161 @@ def fp8_session(a, sd, dims):
             "method": "four engines over the same synthetic weights, arms alternated inside each of 5 rounds, median per arm; "
                       "speedups are step_ms(switch off) / step_ms(fp8) at the same weight and cache format",
             "device": torch.cuda.get_device_name(0), "peak_hbm_gbs": PEAK_HBM_GBS, "cells": cells, "fp8_speedup": ratios}
+
+
+def kv8_session(a, sd, dims):
+    """The record of GPT.set_cache_quant (profiles/lm_kv8_bench.json): bf16 weights over three caches -- fp32, bf16 (the yardstick:
+    the code as it was) and fp8 -- as three engines over the same weights.  Per cell the bare decode step (graph replay; the cache
+    lengths are set on the device, nothing is prefilled), arms ALTERNATED inside each of 1 dropped + 5 timed rounds, the median per
+    arm; then the attention launch alone: the exported entry of that cache (partials + merge) at the cell's shape, rotating over
+    four layers' worth of slabs, 1 dropped + 5 timed rounds of 24 launches.  Cells: --session-ctx x --session-batches on 16-stream
+    engines, then --kv8-many streams at the last context on engines of max(--kv8-many) streams, where the fp32 cache is timed on its
+    own first (the three caches do not fit side by side) and bf16 / fp8 alternate.  The first cell is repeated at the end: the
+    session's drift."""
+    import ctypes
+    from omnitokenizer_amd import _lib
+    V, BS, L, H, C = dims
+    hd = C // H
+    batches = [int(b) for b in a.session_batches.split(",")]
+    ctxs = [int(c) for c in a.session_ctx.split(",")]
+    many = [int(b) for b in a.kv8_many.split(",") if b]
+    arms = ["fp32", "bf16", "fp8"]
+    elem = {"fp32": 4.0, "bf16": 2.0, "fp8": 1.0}
+    models = {}
+    for arm in arms:
+        m = og.GPT(argparse.Namespace(), V, BS, n_layer=L, n_head=H, n_embd=C)
+        m.load_state_dict(sd, strict=True)
+        m = m.cuda().eval().set_weight_format("bf16")
+        models[arm] = m.set_cache_quant("fp8") if arm == "fp8" else m.set_cache_format(arm)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    lib = _lib.load()
+    cells = []
+
+    def p(t):
+        return ctypes.c_void_p(t.data_ptr())
+
+    def drop(ms_):
+        for m in ms_:
+            m.set_cache_format(m.cache_format)     # drops the cache: reset_streams allocates exactly ctx + 64 positions
+
+    def attn_ms(arm, B, ctx):
+        """median ms of one attention launch pair of `arm`'s exported entry: B streams, ctx cached tokens, max_len ctx + 64"""
+        ml, NS = ctx + 64, 4
+        dt = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp8": torch.uint8}[arm]
+        kc = [torch.zeros(B, H, ml, hd, dtype=dt, device="cuda") for _ in range(NS)]
+        vc = [torch.zeros(B, H, ml, hd, dtype=dt, device="cuda") for _ in range(NS)]
+        sc = [torch.ones(2, B, H, ml, device="cuda") for _ in range(NS if arm == "fp8" else 0)]
+        qkv = torch.randn(B, 3 * C, device="cuda")
+        cl = torch.full((B,), ctx, dtype=torch.int32, device="cuda")
+        scratch = torch.empty(B * H * ((ml + 255) // 256) * (2 + hd), device="cuda")
+        out = torch.empty(B, C, device="cuda")
+        st = torch.cuda.current_stream().cuda_stream
+
+        def launch(i):
+            if arm == "fp32":
+                rc = lib.omnitok_lm_attn_decode(p(qkv), p(kc[i]), p(vc[i]), p(cl), B, H, hd, ml, p(scratch), p(out), st)
+            elif arm == "bf16":
+                rc = lib.omnitok_lm_attn_decode_kv16(p(qkv), p(kc[i]), p(vc[i]), 1, p(cl), B, H, hd, ml, p(scratch), p(out), st)
+            else:
+                rc = lib.omnitok_lm_attn_decode_kv8(p(qkv), p(kc[i]), p(vc[i]), p(sc[i][0]), p(sc[i][1]), p(cl), B, H, hd, ml,
+                                                    p(scratch), p(out), st)
+            _lib.check(rc, "attention entry")
+        rounds = []
+        for _ in range(6):
+            e0.record()
+            for i in range(24):
+                launch(i % NS)
+            e1.record()
+            torch.cuda.synchronize()
+            rounds.append(e0.elapsed_time(e1) / 24)
+        return sorted(rounds[1:])[2]
+
+    def cell(ctx, B, group, note=None):
+        replays = {k: models[k].graph_step(B)[2] for k in group}
+
+        def one_round(k, n):
+            m = models[k]
+            e0.record()
+            for _ in range(n):
+                m._pos[:B] = ctx
+                m._len[:B] = ctx
+                replays[k]()
+            e1.record()
+            torch.cuda.synchronize()
+            return e0.elapsed_time(e1) / n
+        nrep = max(3, min(50, int(100.0 / max(max(one_round(k, 2) for k in group), 1e-3))))
+        rounds = {k: [] for k in group}
+        for _ in range(6):
+            for k in group:
+                rounds[k].append(one_round(k, nrep))
+        for k in group:
+            r = sorted(rounds[k][1:])
+            m = models[k]
+            m.check_overflow()
+            kv_bytes = 2.0 * L * B * H * (ctx + 1) * (hd * elem[k] + (4.0 if k == "fp8" else 0.0))     # read by one step, scales included
+            cells.append({"weights": "bf16", "cache": k, "ctx": ctx, "streams": B, "max_streams": m.max_streams,
+                          "max_len": m._cache_shape[1], "step_ms": round(r[2], 4), "step_ms_min_max": [round(r[0], 4), round(r[-1], 4)],
+                          "replays_per_round": nrep, "cache_bytes_allocated": m.cache_bytes(), "kv_bytes_read": kv_bytes,
+                          "weight_bytes": float(m.step_weight_bytes()),
+                          "step_hbm_frac": round((m.step_weight_bytes() + kv_bytes) / (r[2] * 1e-3) / 1e9 / PEAK_HBM_GBS, 4),
+                          **({"note": note} if note else {})})
+            print(json.dumps(cells[-1]), flush=True)
+
+    def attn_cells(ctx, B, tag=None):
+        for k in arms:
+            ms = attn_ms(k, B, ctx)
+            byts = 2.0 * B * H * (ctx + 1) * (hd * elem[k] + (4.0 if k == "fp8" else 0.0))
+            for c in cells:
+                if (c["cache"], c["ctx"], c["streams"], c.get("note")) == (k, ctx, B, tag):
+                    c.update({"attn_launch_ms": round(ms, 5), "attn_bytes": byts, "attn_gbs": round(byts / (ms * 1e-3) / 1e9, 1),
+                              "attn_hbm_frac": round(byts / (ms * 1e-3) / 1e9 / PEAK_HBM_GBS, 4)})
+
+    for ctx in ctxs:
+        drop(models.values())
+        for m in models.values():
+            m.reset_streams(max(batches), ctx + 64)
+        for B in batches:
+            cell(ctx, B, arms)
+    if ctxs[-1] != ctxs[0]:      # the first cell again, in a cache of its own size like the first time
+        drop(models.values())
+        for m in models.values():
+            m.reset_streams(max(batches), ctxs[0] + 64)
+    cell(ctxs[0], batches[0], arms, note="first cell again")
+    drop(models.values())
+    if many:
+        ctx, NB = ctxs[-1], max(many)
+        for m in models.values():
+            m.set_max_streams(NB)
+        for group in (["fp32"], ["bf16", "fp8"]):
+            try:
+                for k in group:
+                    models[k].reset_streams(NB, ctx + 64)
+                for B in many:
+                    cell(ctx, B, group)
+            except Exception as exc:     # a cache the device cannot hold: recorded, not fatal
+                cells.append({"weights": "bf16", "cache": "+".join(group), "ctx": ctx, "skipped": f"{NB} streams x {ctx + 64} tokens: {exc}"})
+            drop(models[k] for k in group)
+    for ctx in ctxs:
+        for B in batches:
+            attn_cells(ctx, B)
+    for B in many:
+        attn_cells(ctxs[-1], B)
+    ms = {(c["cache"], c["ctx"], c["streams"]): c for c in cells if "step_ms" in c and "note" not in c}
+    verdict = []
+    for (k, ctx, B), c in ms.items():
+        if k == "fp8" and ("bf16", ctx, B) in ms:
+            y = ms["bf16", ctx, B]
+            verdict.append({"ctx": ctx, "streams": B, "bf16_cache_ms": y["step_ms"], "fp8_cache_ms": c["step_ms"],
+                            "step_speedup": round(y["step_ms"] / c["step_ms"], 3), "fp8_gained": bool(c["step_ms"] < y["step_ms"]),
+                            **({"attn_speedup": round(y["attn_launch_ms"] / c["attn_launch_ms"], 3)} if "attn_launch_ms" in c and "attn_launch_ms" in y else {})})
+    return {"metric": "LM decode step (graph replay) over an fp32 / bf16 / fp8 K/V cache, bf16 weights", "unit": "ms per step",
+            "workload": f"GPT {L}x{C} ({H} heads, head_dim {hd}), vocab {V}, block {BS}",
+            "protocol": "graph replay, pos / cache_len reset before every replay, arms alternated inside each of 1 dropped + 5 timed "
+                        "rounds, median per arm; the yardstick is the bf16 cache (the code as it was); attn_*: the exported attention "
+                        "entry alone (partials + merge launches) at the cell's shape over 4 rotating slab pairs, 1 dropped + 5 timed "
+                        "rounds of 24 launches; cache contents not prefilled",
+            "device": torch.cuda.get_device_name(0), "peak_hbm_gbs": PEAK_HBM_GBS, "cells": cells, "fp8_vs_bf16_cache": verdict,
+            "did_not_gain": [f"ctx {v['ctx']} x {v['streams']} streams" for v in verdict if not v["fp8_gained"]]}
 
 
 def streams_session(a, m, dims):
@@ -464,6 +621,11 @@ def main():
     ap.add_argument("--kv", choices=("fp32", "bf16", "fp16"), default="fp32", help="format of the K/V cache (GPT.set_cache_format)")
     ap.add_argument("--decode-quant", choices=("none", "fp8"), default="none",
                     help="weight-only quantisation of the decode step of up to 16 streams (GPT.set_decode_quant)")
+    ap.add_argument("--cache-quant", choices=("none", "fp8"), default="none",
+                    help="fp8 K/V cache with a scale per cached row (GPT.set_cache_quant)")
+    ap.add_argument("--kv8-session", metavar="OUT.json", help="write the cache-quant record (kv8_session: --session-batches, default "
+                    "1,2,4,8,16, x --session-ctx, then --kv8-many streams) and exit")
+    ap.add_argument("--kv8-many", default="64,128", metavar="B[,B..]", help="stream counts of the many-stream cells of --kv8-session")
     ap.add_argument("--fp8-session", metavar="OUT.json", help="write the decode-quant record (fp8_session: --session-batches, "
                                                               "--session-ctx) and exit")
     ap.add_argument("--max-streams", type=int, default=16, help="streams per engine (GPT.set_max_streams, up to 128): the limit of "
@@ -498,6 +660,15 @@ def main():
     sd = synth_gpt_state(V, BS, L, H, C, seed=0)
     m = og.GPT(argparse.Namespace(), V, BS, n_layer=L, n_head=H, n_embd=C)
     m.load_state_dict(sd, strict=True)
+    if a.kv8_session:
+        if a.session_batches == ap.get_default("session_batches"):
+            a.session_batches = "1,2,4,8,16"
+        rec = kv8_session(a, sd, (V, BS, L, H, C))
+        with open(a.kv8_session, "w") as f:
+            json.dump(rec, f, indent=1)
+            f.write("\n")
+        print(json.dumps({"written": a.kv8_session, "did_not_gain": rec["did_not_gain"]}), flush=True)
+        return
     if a.fp8_session:
         rec = fp8_session(a, sd, (V, BS, L, H, C))
         with open(a.fp8_session, "w") as f:
@@ -506,7 +677,7 @@ def main():
         print(json.dumps({"written": a.fp8_session, "fp8_speedup": rec["fp8_speedup"]}), flush=True)
         return
     m = m.cuda().eval().set_weight_format(a.weights).set_cache_format(a.kv).set_max_streams(a.max_streams)
-    m.set_decode_quant(a.decode_quant)
+    m.set_decode_quant(a.decode_quant).set_cache_quant(a.cache_quant)
     if a.prefill_session:
         rec = prefill_session(a, m, (V, BS, L, H, C))
         with open(a.prefill_session, "w") as f:
@@ -564,12 +735,14 @@ def main():
     hd = C // H
     weight_bytes = float(m.step_weight_bytes())
     kv_elem = 4.0 if a.kv == "fp32" else 2.0  # bytes per cached K/V element
+    if a.cache_quant == "fp8":                # a byte, and its share of the row's fp32 scale
+        kv_elem = 1.0 + 4.0 / hd
     kv_bytes = 2.0 * L * B * H * (a.ctx + a.steps) * hd * kv_elem
     out_json = {
         "metric": "LM sampled tokens/sec (sample_with_past, top-k 2048 / top-p 0.9)",
         "value": round(B * a.steps / dt_sample, 1), "unit": "tokens/s", "n_gpus": 1, "batch_streams": B,
         "steps": a.steps, "ctx": a.ctx, "ms_per_token_step": round(dt_sample / a.steps * 1e3, 4),
-        "dtype": "f32", "weights": a.weights, "kv": a.kv, "decode_quant": a.decode_quant, "streams_format": a.streams_format, "data": "synthetic",
+        "dtype": "f32", "weights": a.weights, "kv": a.kv, "decode_quant": a.decode_quant, "cache_quant": a.cache_quant, "streams_format": a.streams_format, "data": "synthetic",
         "config": {"workload": f"GPT {L}x{C} ({H} heads, head_dim {hd}), vocab {V}, block {BS}; B={B} streams, "
                                f"{a.ctx} cached tokens + {a.steps} sampled"},
         "roofline": {"kernel": "decode step (graph replay) at the final context", "bound": "hbm",
