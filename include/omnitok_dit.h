@@ -183,6 +183,23 @@ int omnitok_dit_unpatchify(const float *lin, int B, int N, int p, int Cout, floa
 int omnitok_dit_p_sample(const float *model_out, const float *x, const float *noise, const float *coef, int n_steps,
                          const int64_t *t, int B, int C, int64_t HW, int learned_range, int clip, float *x_prev,
                          float *pred_xstart, omnitok_stream_t stream);
+/* One DDIM step (gaussian_diffusion.py:513-560) or, with reverse != 0, one step of the reverse ODE (:562-598), epsilon prediction:
+ * model_out, x, t as above, noise [B,C,HW] or NULL, coef [n_steps][8] on the device, the rows of
+ * DDIMDiffusion.ddim_coefficient_table(eta) -- the reference's fp32 scalar chain, done on the host:
+ *   0 sqrt_recip_alphas_cumprod  1 sqrt_recipm1_alphas_cumprod  2 sqrt(abar_prev)  3 sqrt(1 - abar_prev - sigma^2)
+ *   4 sigma * (t != 0)  5 sqrt(abar_next)  6 sqrt(1 - abar_next)  7 unused (0)
+ * Per element, each operation rounded to fp32 (the multiply-adds fused), eps = model_out[:, c]:
+ *   pred_xstart = coef0 * x - coef1 * eps, clamped to [-1, 1] if clip;  e = (coef0 * x - pred_xstart) / coef1 (the reference
+ *   re-derives eps from pred_xstart: under clip it is not the model's);
+ *   forward: x_out = pred_xstart * coef2 + coef3 * e (+ coef4 * noise if noise != NULL);  reverse: x_out = pred_xstart * coef5 + coef6 * e.
+ * DDIM ignores the variance: channels [C, 2C) of a learned_range output are never read.  noise is never read under reverse; pass
+ * NULL for eta == 0 (coef4 == 0), and no draw is needed.  pred_xstart may be NULL.  Four elements per thread where C * HW % 4 == 0
+ * and every pointer is 16-byte aligned, one otherwise: the bits are the same.
+ * -1 before any HIP call, the message naming the argument: model_out, x, coef, t or x_out null; n_steps, B, C or HW below 1; more
+ * elements than a 32-bit grid of 256-thread workgroups covers. */
+int omnitok_dit_ddim_step(const float *model_out, const float *x, const float *noise, const float *coef, int n_steps,
+                          const int64_t *t, int B, int C, int64_t HW, int learned_range, int clip, int reverse, float *x_out,
+                          float *pred_xstart, omnitok_stream_t stream);
 
 #ifdef __cplusplus
 }

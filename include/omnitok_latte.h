@@ -13,7 +13,8 @@
  * batch: sample i of a call with B samples has the bits of a call with that sample alone.
  *
  * Built: extras 1 (unconditional) and 2 (class labels).  Not built: extras 78 (the text embedding of latte_t2v.py's relatives),
- * latte_img.py, latte_t2v.py, fp16, DDIM.
+ * latte_img.py, latte_t2v.py, fp16.  The samplers (ancestral and DDIM) are omnitok_dit.h's: omnitok_dit_p_sample and omnitok_dit_ddim_step
+ * over the B F frames.
  */
 #ifndef OMNITOK_LATTE_H
 #define OMNITOK_LATTE_H

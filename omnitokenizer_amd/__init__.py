@@ -13,6 +13,7 @@
     from omnitokenizer_amd import resize_frames, images_to_pixels, center_crop_arr   # Pillow-exact resize (omnitokenizer_amd.frames)
     from omnitokenizer_amd import DiT, DiT_models, load_dit                           # DiT denoiser (omnitokenizer_amd.dit)
     from omnitokenizer_amd import create_diffusion, generate_images                  # its sampler (omnitokenizer_amd.diffusion)
+    from omnitokenizer_amd import create_ddim_diffusion, DDIMDiffusion, ddim_timesteps   # ... and the DDIM sampler
     from omnitokenizer_amd import Latte, Latte_models, load_latte, generate_videos   # Latte video denoiser (omnitokenizer_amd.latte)
 """
 from .config import OmniTokConfig, make_args  # noqa: F401
@@ -27,6 +28,7 @@ __all__ = ["OmniTokenizer_VQGAN", "GPT", "OmniTokConfig", "make_args", "psnr_ssi
            "InceptionV3"] + list(_FID_NAMES) + ["LPIPS", "load_lpips", "lpips_frames", "reconstruction_losses",
                                            "token_cross_entropy", "resize_frames", "images_to_pixels", "center_crop_arr",
                                            "DiT", "DiT_models", "load_dit", "create_diffusion", "generate_images",
+                                           "create_ddim_diffusion", "DDIMDiffusion", "ddim_timesteps",
                                            "Latte", "Latte_models", "load_latte", "get_1d_sincos_temp_embed", "generate_videos",
                                            "fp8_dequantized", "fp8_quantize_rows"]
 
@@ -74,7 +76,7 @@ def __getattr__(name):
     if name in ("Latte", "Latte_models", "load_latte", "get_1d_sincos_temp_embed"):
         from . import latte
         return getattr(latte, name)
-    if name in ("create_diffusion", "generate_images", "generate_videos"):
+    if name in ("create_diffusion", "generate_images", "generate_videos", "create_ddim_diffusion", "DDIMDiffusion", "ddim_timesteps"):
         from . import diffusion
         return getattr(diffusion, name)
     raise AttributeError(name)

@@ -335,6 +335,7 @@ _DIT_PROTOS = {
     "omnitok_dit_gemm16": [P, P, c_int, P, c_int, P, P, P, I64, c_int, P, I64, c_int, c_int, P, P],
     "omnitok_dit_unpatchify": [P, c_int, c_int, c_int, c_int, P, P],
     "omnitok_dit_p_sample": [P, P, P, P, c_int, P, c_int, c_int, I64, c_int, c_int, P, P, P],
+    "omnitok_dit_ddim_step": [P, P, P, P, c_int, P, c_int, c_int, I64, c_int, c_int, c_int, P, P, P],
 }
 _RESTYPES.update({"omnitok_dit_destroy": None, "omnitok_dit_workspace_bytes": c_int64})
 DIT_EXPORTED_SYMBOLS = tuple(_DIT_PROTOS)

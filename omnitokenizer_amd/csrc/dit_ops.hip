@@ -220,6 +220,63 @@ __global__ void dit_p_sample_kernel(const float *__restrict__ mo, const float *_
     x_prev[id] = mean + k[7] * expf(0.5f * logvar) * noise[id];
 }
 
+// ---- ddim_step -----------------------------------------------------------------------------------------------------------------------------------
+// gaussian_diffusion.py:513-598 behind the model call.  One element: contraction is off and every fused multiply-add is written
+// out, so the scalar and the float4 kernel give the same bits and a row does not depend on which of them its call took.
+// k: the row of DDIMDiffusion.ddim_coefficient_table (omnitok_dit.h).  n is read only where has_noise.
+__device__ __forceinline__ float dit_ddim_elem(const float *__restrict__ k, float xv, float eps, float n, bool has_noise, bool clip,
+                                               bool reverse, float *xs_out) {
+#pragma clang fp contract(off)
+    float xs = fmaf(k[0], xv, -(k[1] * eps));
+    if (clip) xs = fminf(fmaxf(xs, -1.0f), 1.0f);
+    const float e = fmaf(k[0], xv, -xs) / k[1];  // re-derived from pred_xstart: not eps under clip
+    *xs_out = xs;
+    if (reverse) return fmaf(k[6], e, xs * k[5]);
+    const float mean = fmaf(k[3], e, xs * k[2]);
+    return has_noise ? fmaf(k[4], n, mean) : mean;
+}
+
+__device__ __forceinline__ const float *dit_ddim_row(const float *__restrict__ coef, int n_steps, const int64_t *__restrict__ t, int64_t b) {
+    int64_t tv = t[b];
+    tv = tv < 0 ? 0 : (tv >= n_steps ? n_steps - 1 : tv);
+    return coef + tv * 8;
+}
+
+__global__ void dit_ddim_step_kernel(const float *__restrict__ mo, const float *__restrict__ x, const float *__restrict__ noise,
+                                     const float *__restrict__ coef, int n_steps, const int64_t *__restrict__ t, int64_t total, int64_t chw,
+                                     int mo_mul, int clip, int reverse, float *__restrict__ x_out, float *__restrict__ pred_xstart) {
+    const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (id >= total) return;
+    const int64_t b = id / chw, rest = id - b * chw;
+    const float *k = dit_ddim_row(coef, n_steps, t, b);
+    float xs;
+    const float out = dit_ddim_elem(k, x[id], mo[b * mo_mul * chw + rest], noise ? noise[id] : 0.0f, noise != nullptr, clip, reverse, &xs);
+    if (pred_xstart) pred_xstart[id] = xs;
+    x_out[id] = out;
+}
+
+// chw % 4 == 0 and 16-byte aligned pointers: four elements of one sample per thread, total4 = B chw / 4
+__global__ void dit_ddim_step4_kernel(const float *__restrict__ mo, const float *__restrict__ x, const float *__restrict__ noise,
+                                      const float *__restrict__ coef, int n_steps, const int64_t *__restrict__ t, int64_t total4, int64_t chw,
+                                      int mo_mul, int clip, int reverse, float *__restrict__ x_out, float *__restrict__ pred_xstart) {
+    const int64_t id4 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (id4 >= total4) return;
+    const int64_t id = id4 * 4;
+    const int64_t b = id / chw, rest = id - b * chw;
+    const float *k = dit_ddim_row(coef, n_steps, t, b);
+    const float4 xv = *reinterpret_cast<const float4 *>(x + id);
+    const float4 ev = *reinterpret_cast<const float4 *>(mo + b * mo_mul * chw + rest);
+    float4 nv = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (noise) nv = *reinterpret_cast<const float4 *>(noise + id);
+    float4 xs, out;
+    out.x = dit_ddim_elem(k, xv.x, ev.x, nv.x, noise != nullptr, clip, reverse, &xs.x);
+    out.y = dit_ddim_elem(k, xv.y, ev.y, nv.y, noise != nullptr, clip, reverse, &xs.y);
+    out.z = dit_ddim_elem(k, xv.z, ev.z, nv.z, noise != nullptr, clip, reverse, &xs.z);
+    out.w = dit_ddim_elem(k, xv.w, ev.w, nv.w, noise != nullptr, clip, reverse, &xs.w);
+    if (pred_xstart) *reinterpret_cast<float4 *>(pred_xstart + id) = xs;
+    *reinterpret_cast<float4 *>(x_out + id) = out;
+}
+
 static inline unsigned blocks_for(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
 int dit_cond_gather(const float *table, const int64_t *t, int B, float *temb, int *flag, hipStream_t stream) {
@@ -368,5 +425,33 @@ extern "C" int omnitok_dit_p_sample(const float *model_out, const float *x, cons
     hipLaunchKernelGGL(dit_p_sample_kernel, dim3(blocks_for(total, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), model_out, x, noise,
                        coef, n_steps, t, total, C, HW, learned_range != 0, clip != 0, x_prev, pred_xstart);
     OT_LAUNCH_CHECK("dit_p_sample");
+    return OMNITOK_OK;
+}
+
+extern "C" int omnitok_dit_ddim_step(const float *model_out, const float *x, const float *noise, const float *coef, int n_steps,
+                                     const int64_t *t, int B, int C, int64_t HW, int learned_range, int clip, int reverse, float *x_out,
+                                     float *pred_xstart, omnitok_stream_t stream) {
+    OT_CHECK_ARG(model_out, "dit_ddim_step: model_out is null");
+    OT_CHECK_ARG(x, "dit_ddim_step: x is null");
+    OT_CHECK_ARG(coef, "dit_ddim_step: coef is null");
+    OT_CHECK_ARG(t, "dit_ddim_step: t is null");
+    OT_CHECK_ARG(x_out, "dit_ddim_step: x_out is null");
+    OT_CHECK_ARG(n_steps >= 1, "dit_ddim_step: n_steps %d (>= 1)", n_steps);
+    OT_CHECK_ARG(B >= 1, "dit_ddim_step: B %d (>= 1)", B);
+    OT_CHECK_ARG(C >= 1, "dit_ddim_step: C %d (>= 1)", C);
+    OT_CHECK_ARG(HW >= 1, "dit_ddim_step: HW %lld (>= 1)", (long long)HW);
+    OT_CHECK_ARG(HW <= INT64_MAX / C / B, "dit_ddim_step: too many elements (B %d, C %d, HW %lld)", B, C, (long long)HW);
+    const int64_t chw = (int64_t)C * HW, total = (int64_t)B * chw;
+    DIT_CHECK_GRID("dit_ddim_step", total);
+    if (reverse) noise = nullptr;
+    const int mo_mul = learned_range ? 2 : 1;
+    const bool vec = chw % 4 == 0 && aligned16(model_out) && aligned16(x) && aligned16(noise) && aligned16(x_out) && aligned16(pred_xstart);
+    if (vec)
+        hipLaunchKernelGGL(dit_ddim_step4_kernel, dim3(blocks_for(total / 4, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), model_out, x,
+                           noise, coef, n_steps, t, total / 4, chw, mo_mul, clip != 0, reverse != 0, x_out, pred_xstart);
+    else
+        hipLaunchKernelGGL(dit_ddim_step_kernel, dim3(blocks_for(total, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), model_out, x,
+                           noise, coef, n_steps, t, total, chw, mo_mul, clip != 0, reverse != 0, x_out, pred_xstart);
+    OT_LAUNCH_CHECK("dit_ddim_step");
     return OMNITOK_OK;
 }

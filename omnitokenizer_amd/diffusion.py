@@ -11,6 +11,13 @@ Built: epsilon prediction, LEARNED_RANGE or fixed variances, the linear schedule
 ("10,15,20").  The coefficient tables are computed on the host in fp64 exactly as the reference's numpy does (respacing
 included) and rounded to fp32 where _extract_into_tensor rounds them (gaussian_diffusion.py:861-874); one step is one model call
 plus ONE element-wise kernel (omnitok_dit_p_sample).  Everything else raises NotImplementedError with the reference line.
+
+The DDIM sampler (gaussian_diffusion.py:513-680, the Latte scripts' `--sample_method ddim`) and the "ddimN" striding come on an object
+of their own, because create_diffusion("ddimN") and SpacedDiffusion.ddim_* are pinned as refused:
+
+    diffusion = create_ddim_diffusion("ddim50")            # a DDIMDiffusion; the reference: create_diffusion("ddim50")
+    samples = diffusion.ddim_sample_loop(model.forward_with_cfg, z.shape, z, clip_denoised=False,
+                                         model_kwargs=dict(y=y, cfg_scale=4.0), device=z.device, eta=0.0)
 """
 from __future__ import annotations
 
@@ -122,6 +129,35 @@ class SpacedDiffusion:
         if cond_fn is not None:
             _not_built("cond_fn (classifier guidance)", "gaussian_diffusion.py:346-356, 414-415")
 
+    def _model_call(self, model, x, t, model_kwargs):
+        """What p_sample and the DDIM steps share in front of their kernel: the argument checks, the model call with
+        timestep_map[t] (respace.py:124-129) and the check of its output's shape.  Returns x and the model output as contiguous fp32,
+        t as int64 on x's device, and (B, frames, C)."""
+        if x.device.type != "cuda":
+            raise RuntimeError(f"x is on {x.device}: the sampler runs on the GPU only")
+        if x.dim() not in (4, 5):
+            raise ValueError(f"x must be [N,C,H,W] or [N,F,C,H,W], got {tuple(x.shape)}")
+        x = x.float().contiguous()
+        B, frames, C = x.shape[0], (x.shape[1] if x.dim() == 5 else 1), x.shape[-3]
+        t = t.to(device=x.device, dtype=torch.int64).contiguous()
+        if tuple(t.shape) != (B,):
+            raise ValueError(f"t must be [{B}]")
+        model_output = model(x, self._table_on(x.device)[1][t], **(model_kwargs or {}))
+        if isinstance(model_output, tuple):
+            model_output = model_output[0]
+        want = (*x.shape[:-3], C * (2 if self.learn_sigma else 1), *x.shape[-2:])
+        if tuple(model_output.shape) != want:
+            raise ValueError(f"model output {tuple(model_output.shape)}, expected {want}")
+        return x, t, model_output.float().contiguous(), (B, frames, C)
+
+    @staticmethod
+    def _step_noise(noise, x):
+        if noise is None:
+            return torch.randn_like(x)
+        if noise.shape != x.shape or noise.device != x.device:
+            raise ValueError("noise must have x's shape and device")
+        return noise.float().contiguous()
+
     @torch.no_grad()
     def p_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None, noise=None):
         """gaussian_diffusion.py:376-417.  x [N,C,H,W] fp32 on the GPU, t [N] indices of the RESPACED process; the model is called
@@ -130,31 +166,11 @@ class SpacedDiffusion:
         split on dim 2, and the update runs over the N F frames with each sample's t repeated F times.
         Returns {"sample", "pred_xstart"}."""
         self._refuse(denoised_fn, cond_fn)
-        if x.device.type != "cuda":
-            raise RuntimeError(f"x is on {x.device}: the sampler runs on the GPU only")
-        if x.dim() not in (4, 5):
-            raise ValueError(f"x must be [N,C,H,W] or [N,F,C,H,W], got {tuple(x.shape)}")
-        x = x.float().contiguous()
-        video = x.dim() == 5
-        B, frames, C = x.shape[0], (x.shape[1] if video else 1), x.shape[-3]
-        t = t.to(device=x.device, dtype=torch.int64).contiguous()
-        if tuple(t.shape) != (B,):
-            raise ValueError(f"t must be [{B}]")
-        coef, tmap = self._table_on(x.device)
-        model_output = model(x, tmap[t], **(model_kwargs or {}))
-        if isinstance(model_output, tuple):
-            model_output = model_output[0]
-        want = (*x.shape[:-3], C * (2 if self.learn_sigma else 1), *x.shape[-2:])
-        if tuple(model_output.shape) != want:
-            raise ValueError(f"model output {tuple(model_output.shape)}, expected {want}")
-        model_output = model_output.float().contiguous()
-        if noise is None:
-            noise = torch.randn_like(x)
-        elif noise.shape != x.shape or noise.device != x.device:
-            raise ValueError("noise must have x's shape and device")
-        noise = noise.float().contiguous()
+        x, t, model_output, (B, frames, C) = self._model_call(model, x, t, model_kwargs)
+        coef = self._table_on(x.device)[0]
+        noise = self._step_noise(noise, x)
         sample, xstart = torch.empty_like(x), torch.empty_like(x)
-        if video:
+        if x.dim() == 5:
             t = t.repeat_interleave(frames)
         P = ctypes.c_void_p
         check(_lib.load().omnitok_dit_p_sample(P(model_output.data_ptr()), P(x.data_ptr()), P(noise.data_ptr()), P(coef.data_ptr()),
@@ -170,6 +186,14 @@ class SpacedDiffusion:
         """gaussian_diffusion.py:464-511.  step_noise: [num_timesteps, *shape] -- row k is the draw of the k-th step taken
         (timestep num_timesteps - 1 - k) -- or a callable step_noise(k, shape, device); it replaces the per-step torch.randn."""
         self._refuse(denoised_fn, cond_fn)
+
+        def step(img, t, kwargs, eps):
+            return self.p_sample(model, img, t, clip_denoised=clip_denoised, model_kwargs=kwargs, noise=eps)
+
+        yield from self._loop(step, model, shape, noise, model_kwargs, device, progress, step_noise)
+
+    def _loop(self, step, model, shape, noise, model_kwargs, device, progress, step_noise):
+        """The loop of p_sample_loop_progressive and ddim_sample_loop_progressive around step(img, t, model_kwargs, draw)."""
         if device is None:
             owner = getattr(model, "__self__", model)
             device = next(owner.parameters()).device
@@ -195,7 +219,7 @@ class SpacedDiffusion:
                 eps = step_noise(k, tuple(shape), device)
             else:
                 eps = step_noise[k].to(device)
-            out = self.p_sample(model, img, t, clip_denoised=clip_denoised, model_kwargs=kwargs, noise=eps)
+            out = step(img, t, kwargs, eps)
             yield out
             img = out["sample"]
         if fast:
@@ -212,7 +236,7 @@ class SpacedDiffusion:
             final = sample
         return final["sample"]
 
-    # ---- what is not built ----------------------------------------------------------------------------------------------------------
+    # ---- what this class refuses: the DDIM sampler is DDIMDiffusion's (create_ddim_diffusion), the rest is not built ---------------
     def ddim_sample(self, *a, **k):
         _not_built("DDIM sampling", "gaussian_diffusion.py:513-560")
 
@@ -232,9 +256,120 @@ class SpacedDiffusion:
         _not_built("calc_bpd_loop", "gaussian_diffusion.py:805-858")
 
 
-def create_diffusion(timestep_respacing, noise_schedule="linear", use_kl=False, sigma_small=False, predict_xstart=False,
-                     learn_sigma=True, rescale_learned_sigmas=False, diffusion_steps=1000):
-    """diffusion/__init__.py:10-46.  use_kl / rescale_learned_sigmas only choose a training loss there and are accepted."""
+def ddim_timesteps(num_timesteps, count):
+    """respace.py:32-39, the "ddimN" striding: range(0, num_timesteps, i) for the first integer stride i that keeps `count` steps."""
+    for i in range(1, num_timesteps):
+        if len(range(0, num_timesteps, i)) == count:
+            return set(range(0, num_timesteps, i))
+    raise ValueError(f"cannot create exactly {num_timesteps} steps with an integer stride")
+
+
+class DDIMDiffusion(SpacedDiffusion):
+    """A SpacedDiffusion with the DDIM sampler of gaussian_diffusion.py:513-680 next to the ancestral one: ddim_sample,
+    ddim_reverse_sample (DDIM inversion), ddim_sample_loop and ddim_sample_loop_progressive with the reference's signatures plus this
+    package's noise= / step_noise= arguments.  One step is one model call plus ONE element-wise kernel (omnitok_dit_ddim_step)."""
+
+    DDIM_COEF_NAMES = ("sqrt_recip_alphas_cumprod", "sqrt_recipm1_alphas_cumprod", "sqrt_alphas_cumprod_prev", "sqrt_one_minus_prev_sigma2",
+                       "sigma_nonzero", "sqrt_alphas_cumprod_next", "sqrt_one_minus_alphas_cumprod_next", "unused")
+
+    def __init__(self, use_timesteps, betas, learn_sigma=True, sigma_small=False):
+        super().__init__(use_timesteps, betas, learn_sigma=learn_sigma, sigma_small=sigma_small)
+        self.alphas_cumprod_next = np.append(self.alphas_cumprod[1:], 0.0)
+        self._ddim_dev_tables = {}
+
+    @staticmethod
+    def _eta(eta):
+        eta = float(eta)
+        if not np.isfinite(eta) or eta < 0:
+            raise ValueError(f"eta must be finite and >= 0, got {eta}")
+        return eta
+
+    def ddim_coefficient_table(self, eta=0.0) -> np.ndarray:
+        """[num_timesteps, 8] fp32, the columns of DDIM_COEF_NAMES (include/omnitok_dit.h, omnitok_dit_ddim_step).  The reference's
+        _extract_into_tensor returns fp32 whatever x's dtype is, so its per-timestep scalars (gaussian_diffusion.py:543-558, 590-596)
+        are an fp32 chain; it is done here, in numpy float32 from the fp64 tables rounded once, in the reference's operation order.
+        Every operation is correctly rounded (IEEE), which is what torch's CPU tensors give for + - * / and, in all but about one
+        element of a hundred of a long table, for its vectorised sqrt (tests/test_ddim_cpu.py).  A negative radicand in 1 - alpha_bar_prev - sigma^2 (a NaN in the reference) raises ValueError."""
+        f32 = np.float32
+        eta = f32(self._eta(eta))
+        ab, abp, abn = (v.astype(f32) for v in (self.alphas_cumprod, self.alphas_cumprod_prev, self.alphas_cumprod_next))
+        one = f32(1.0)
+        sigma = eta * np.sqrt((one - abp) / (one - ab)) * np.sqrt(one - ab / abp)
+        radicand = one - abp - sigma ** 2
+        if not (radicand >= 0).all():
+            bad = int(np.argmin(radicand >= 0))
+            raise ValueError(f"eta {float(eta)}: 1 - alpha_bar_prev - sigma^2 = {float(radicand[bad])} < 0 at timestep {bad}")
+        cols = [self.sqrt_recip_alphas_cumprod.astype(f32), self.sqrt_recipm1_alphas_cumprod.astype(f32), np.sqrt(abp), np.sqrt(radicand),
+                sigma * (np.arange(self.num_timesteps) != 0).astype(f32), np.sqrt(abn), np.sqrt(one - abn),
+                np.zeros(self.num_timesteps, f32)]
+        table = np.stack(cols, axis=1)
+        assert table.dtype == f32
+        return table
+
+    def _ddim_table_on(self, device, eta):
+        key = (str(device), self._eta(eta))
+        if key not in self._ddim_dev_tables:
+            self._ddim_dev_tables[key] = torch.from_numpy(self.ddim_coefficient_table(eta)).to(device).contiguous()
+        return self._ddim_dev_tables[key]
+
+    def _ddim_step(self, model, x, t, clip_denoised, model_kwargs, eta, noise, reverse):
+        x, t, model_output, (B, frames, C) = self._model_call(model, x, t, model_kwargs)
+        coef = self._ddim_table_on(x.device, eta)
+        # eta == 0 and the reverse step read no noise: none is drawn and none is passed
+        noise = self._step_noise(noise, x) if eta > 0 and not reverse else None
+        sample, xstart = torch.empty_like(x), torch.empty_like(x)
+        if x.dim() == 5:
+            t = t.repeat_interleave(frames)
+        P = ctypes.c_void_p
+        check(_lib.load().omnitok_dit_ddim_step(P(model_output.data_ptr()), P(x.data_ptr()), P(noise.data_ptr()) if noise is not None else None,
+                                                P(coef.data_ptr()), self.num_timesteps, P(t.data_ptr()), B * frames, C,
+                                                x.shape[-2] * x.shape[-1], int(self.learn_sigma), int(bool(clip_denoised)), int(reverse),
+                                                P(sample.data_ptr()), P(xstart.data_ptr()), torch.cuda.current_stream().cuda_stream),
+              "dit_ddim_step")
+        return {"sample": sample, "pred_xstart": xstart}
+
+    @torch.no_grad()
+    def ddim_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None, eta=0.0, noise=None):
+        """gaussian_diffusion.py:513-560: x_{t-1} from x_t.  x, t, the model call and the video form as p_sample.  noise: this step's
+        normal draw, read only when eta > 0 (default torch.randn_like(x)); with eta == 0 nothing is drawn.
+        Returns {"sample", "pred_xstart"}."""
+        self._refuse(denoised_fn, cond_fn)
+        return self._ddim_step(model, x, t, clip_denoised, model_kwargs, self._eta(eta), noise, False)
+
+    @torch.no_grad()
+    def ddim_reverse_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None, eta=0.0):
+        """gaussian_diffusion.py:562-598: x_{t+1} from x_t by the reverse ODE (DDIM inversion); eta must be 0, where the reference
+        asserts."""
+        self._refuse(denoised_fn, cond_fn)
+        if eta != 0.0:
+            raise ValueError("Reverse ODE only for deterministic path (eta must be 0)")
+        return self._ddim_step(model, x, t, clip_denoised, model_kwargs, 0.0, None, True)
+
+    @torch.no_grad()
+    def ddim_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
+                                     model_kwargs=None, device=None, progress=False, eta=0.0, step_noise=None):
+        """gaussian_diffusion.py:633-680.  step_noise as in p_sample_loop_progressive, consulted only when eta > 0."""
+        self._refuse(denoised_fn, cond_fn)
+        eta = self._eta(eta)
+        self.ddim_coefficient_table(eta)  # a refused eta raises before the first model call
+
+        def step(img, t, kwargs, eps):
+            return self.ddim_sample(model, img, t, clip_denoised=clip_denoised, model_kwargs=kwargs, eta=eta, noise=eps)
+
+        yield from self._loop(step, model, shape, noise, model_kwargs, device, progress, step_noise if eta > 0 else None)
+
+    def ddim_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
+                         device=None, progress=False, eta=0.0, step_noise=None):
+        """gaussian_diffusion.py:600-631: all rows of the batch, as p_sample_loop returns them."""
+        final = None
+        for sample in self.ddim_sample_loop_progressive(model, shape, noise=noise, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
+                                                        cond_fn=cond_fn, model_kwargs=model_kwargs, device=device, progress=progress,
+                                                        eta=eta, step_noise=step_noise):
+            final = sample
+        return final["sample"]
+
+
+def _process(cls, stride, timestep_respacing, noise_schedule, sigma_small, predict_xstart, learn_sigma, diffusion_steps):
     if noise_schedule != "linear":
         _not_built(f"the {noise_schedule!r} noise schedule", "gaussian_diffusion.py:116-122")
     if predict_xstart:
@@ -242,18 +377,59 @@ def create_diffusion(timestep_respacing, noise_schedule="linear", use_kl=False, 
     betas = linear_betas(diffusion_steps)
     if timestep_respacing is None or timestep_respacing == "":
         timestep_respacing = [diffusion_steps]
-    return SpacedDiffusion(space_timesteps(diffusion_steps, timestep_respacing), betas, learn_sigma=learn_sigma,
-                           sigma_small=sigma_small)
+    return cls(stride(diffusion_steps, timestep_respacing), betas, learn_sigma=learn_sigma, sigma_small=sigma_small)
+
+
+def create_diffusion(timestep_respacing, noise_schedule="linear", use_kl=False, sigma_small=False, predict_xstart=False,
+                     learn_sigma=True, rescale_learned_sigmas=False, diffusion_steps=1000):
+    """diffusion/__init__.py:10-46.  use_kl / rescale_learned_sigmas only choose a training loss there and are accepted."""
+    return _process(SpacedDiffusion, space_timesteps, timestep_respacing, noise_schedule, sigma_small, predict_xstart, learn_sigma,
+                    diffusion_steps)
+
+
+def create_ddim_diffusion(timestep_respacing, noise_schedule="linear", use_kl=False, sigma_small=False, predict_xstart=False,
+                          learn_sigma=True, rescale_learned_sigmas=False, diffusion_steps=1000):
+    """create_diffusion for the DDIM sampler: the same signature and refusals, "ddimN" (respace.py:32-39) accepted next to "250" and
+    "10,15,20", a DDIMDiffusion returned.  create_diffusion("ddimN") itself stays refused."""
+    def stride(num_timesteps, section_counts):
+        if isinstance(section_counts, str) and section_counts.startswith("ddim"):
+            return ddim_timesteps(num_timesteps, int(section_counts[len("ddim"):]))
+        return space_timesteps(num_timesteps, section_counts)
+
+    return _process(DDIMDiffusion, stride, timestep_respacing, noise_schedule, sigma_small, predict_xstart, learn_sigma, diffusion_steps)
+
+
+def _check_sample_method(diffusion, sample_method):
+    if sample_method not in ("ddpm", "ddim"):
+        raise ValueError(f"sample_method must be 'ddpm' or 'ddim', got {sample_method!r}")
+    if sample_method == "ddim" and not isinstance(diffusion, DDIMDiffusion):
+        raise TypeError("sample_method='ddim' needs a DDIMDiffusion: build it with create_ddim_diffusion")
+
+
+def _run_sampler(diffusion, sample_method, eta, sample_fn, z, model_kwargs, device, gen):
+    """--sample_method of the Latte scripts (sample/sample.py:100-107): "ddpm" is p_sample_loop, "ddim" ddim_sample_loop, both with
+    clip_denoised=False.  The per-step draws come from `gen` in step order; DDIM with eta == 0 draws none."""
+    def draw(k, shape, dev):
+        return torch.randn(*shape, device=dev, generator=gen)
+
+    if sample_method == "ddim":
+        return diffusion.ddim_sample_loop(sample_fn, z.shape, z, clip_denoised=False, model_kwargs=model_kwargs, device=device,
+                                          eta=eta, step_noise=draw)
+    return diffusion.p_sample_loop(sample_fn, z.shape, z, clip_denoised=False, model_kwargs=model_kwargs, device=device,
+                                   step_noise=draw)
 
 
 @torch.no_grad()
-def generate_images(dit, diffusion, vae, labels, cfg_scale=1.5, seed=0):
+def generate_images(dit, diffusion, vae, labels, cfg_scale=1.5, seed=0, sample_method="ddpm", eta=0.0):
     """The body of sample_ddp.py:136-163 in one call: labels [n] int64 on the GPU -> uint8 images [n,H,W,3].
     z ~ N(0, 1) from a generator seeded with `seed` on the model's device; with cfg_scale > 1 the batch is doubled with the null
     class (num_classes) and run through forward_with_cfg; p_sample_loop with clip_denoised=False; the null half is dropped;
     vae.decode(samples / 0.18215, is_image=True); frames.pixels_to_frames, this package's uint8 conversion (the script's own is
-    clamp(255 x + 128, 0, 255) truncated: half a grey level above it)."""
+    clamp(255 x + 128, 0, 255) truncated: half a grey level above it).
+    sample_method="ddim" (with a DDIMDiffusion from create_ddim_diffusion, else TypeError) runs ddim_sample_loop(eta=eta) instead:
+    with eta == 0 the generator is consumed for z only, with eta > 0 for one more normal draw per step, in step order."""
     from .frames import pixels_to_frames
+    _check_sample_method(diffusion, sample_method)
     if cfg_scale < 1.0:
         raise ValueError("In almost all cases, cfg_scale be >= 1.0")
     device = dit.device
@@ -270,11 +446,7 @@ def generate_images(dit, diffusion, vae, labels, cfg_scale=1.5, seed=0):
     else:
         model_kwargs, sample_fn = dict(y=labels), dit.forward
 
-    def draw(k, shape, dev):
-        return torch.randn(*shape, device=dev, generator=gen)
-
-    samples = diffusion.p_sample_loop(sample_fn, z.shape, z, clip_denoised=False, model_kwargs=model_kwargs, device=device,
-                                      step_noise=draw)
+    samples = _run_sampler(diffusion, sample_method, eta, sample_fn, z, model_kwargs, device, gen)
     if using_cfg:
         samples, _ = samples.chunk(2, dim=0)
     pixels = vae.decode((samples / 0.18215).contiguous(), is_image=True)
@@ -282,15 +454,17 @@ def generate_images(dit, diffusion, vae, labels, cfg_scale=1.5, seed=0):
 
 
 @torch.no_grad()
-def generate_videos(latte, diffusion, vae, labels, cfg_scale=7.0, seed=0):
+def generate_videos(latte, diffusion, vae, labels, cfg_scale=7.0, seed=0, sample_method="ddpm", eta=0.0):
     """The loop body of Diffusion/Latte/sample/sample_ddp.py:148-211 in one call: labels [n] int64 on the GPU (an int n, or None
     with n = 1, for a model without labels, extras == 1) -> uint8 videos [n,F_pixels,H,W,3].
     z ~ N(0, 1) of shape [n, latte.num_frames, in_channels, s, s] from a generator seeded with `seed` on the model's device; with
     cfg_scale > 1 the batch is doubled with the null class (num_classes: the script's literal 101 is UCF-101's) and run through
     forward_with_cfg; p_sample_loop with clip_denoised=False; the null half is dropped; the latents go channel-last
     ("b f c h w -> b f h w c", :202) into vae.decode(samples / 0.18215, is_image=False); frames.pixels_to_frames, which is the
-    script's own uint8 conversion (:207)."""
+    script's own uint8 conversion (:207).
+    sample_method="ddim", eta: the scripts' --sample_method ddim (sample/sample.py:100-107), as in generate_images."""
     from .frames import pixels_to_frames
+    _check_sample_method(diffusion, sample_method)
     if cfg_scale < 1.0:
         raise ValueError("In almost all cases, cfg_scale be >= 1.0")
     device = latte.device
@@ -314,11 +488,7 @@ def generate_videos(latte, diffusion, vae, labels, cfg_scale=7.0, seed=0):
     else:
         model_kwargs, sample_fn = dict(y=labels), latte.forward
 
-    def draw(k, shape, dev):
-        return torch.randn(*shape, device=dev, generator=gen)
-
-    samples = diffusion.p_sample_loop(sample_fn, z.shape, z, clip_denoised=False, model_kwargs=model_kwargs, device=device,
-                                      step_noise=draw)
+    samples = _run_sampler(diffusion, sample_method, eta, sample_fn, z, model_kwargs, device, gen)
     if using_cfg:
         samples, _ = samples.chunk(2, dim=0)
     pixels = vae.decode((samples / 0.18215).permute(0, 1, 3, 4, 2).contiguous(), is_image=False)
